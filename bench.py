@@ -3,13 +3,22 @@
 K3 Benjamini-Hochberg) on synthetic human contacts, with the inputs resident in HBM.
 
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full   (the headline plus every check and extra figure listed below)
+    python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR
     python bench.py --gpus N --steps K --warmup W          (no launcher: the script starts its N ranks itself; fewer than N visible
                                                             GPUs -> one JSON diagnostic line with "value": null, exit code 2)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
-One JSON line on stdout (rank 0) with the driver's contract fields plus `roofline` (dominant kernel, HIP-event timed),
-`cpu_baseline` (the oracle timed on this box's host cores on a bounded sample of the same rows, N = 1 only) and
+A plain run sets up, warms up, times `--steps` steps and prints one JSON line on stdout (rank 0): the driver's contract fields
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall milliseconds of one timed step) plus `roofline`
+(dominant kernel, HIP-event timed) and the per-kernel times of the timed steps.  Its `parity_check` says that the check did not run.
+`--dump-outputs DIR` writes what the last timed step computed: p and q of the rows (rank 0's rows at N > 1) as DIR/p.npy and DIR/q.npy
+(float64), all of them up to 2^21 rows, above that a fixed seeded sample of 2^21 row numbers, stored as DIR/rows.npy (float64).
+The inputs are generated from fixed seeds: two runs with the same arguments time and dump the same rows.
+
+`--full` adds everything the headline figure does not need, each leg as before: `cpu_baseline` (the oracle timed on this box's
+host cores on a bounded sample of the same rows, N = 1 only), the `k3_stress` workloads, the weak-scaling figure and
 `parity_check` - the run that is timed is the run that is checked, at every N:
   N = 1: the engine's K1 histogram and its fit (bins, possible pairs, x, y, s, knots, table, N) against what the REAL reference's
          stage functions returned on this workload (fixtures tests/golden/f14_*), the p-values of the CPU sample recomputed by the
@@ -26,11 +35,13 @@ Workloads (`--config`, BASELINE.json configs):
       (`--max-chroms k` takes the first k chromosomes; the trans rows scale with the loci).
 With N > 1 GPUs the headline is STRONG scaling (BASELINE configs[3]: the one genome sharded by chromosome over the ranks,
 distance histogram all-reduced, BH ranking global over RCCL); the weak-scaling figure (genome replicated N times, N x the
-rows) is measured afterwards and reported under `weak_scaling` (`--no-weak` skips it, `--weak` makes it the headline).  The N > 1
-line also carries `per_rank` (rows and kernel times of every rank), `single_gpu_ms_per_step` / `strong_speedup` / `strong_efficiency`
-(against the one-GPU pass rank 0 times in the same run while it verifies) and `predicted_ms` (profiles/scaling_model.json).
-At N = 1 on C3 a second, labelled workload follows the headline: `k3_stress` - the same genome with lognormal rate noise, where
-12 % of the rows fall below the BH cutoff and K3's sort has work to do (`--no-k3-stress` skips it; it never enters `value`).
+rows) is measured afterwards with --full and reported under `weak_scaling` (`--no-weak` skips it, `--weak` makes it the headline).  The
+N > 1 line also carries `per_rank` (rows and kernel times of every rank) and `predicted_ms` (profiles/scaling_model.json); with
+--full also `single_gpu_ms_per_step` / `strong_speedup` / `strong_efficiency` (against the one-GPU pass rank 0 times in the same
+run while it verifies).
+With --full at N = 1 on C3 three labelled workloads follow the headline: `k3_stress` - the same genome with lognormal rate noise
+or hotspots, where 12 % to 55 % of the rows fall below the BH cutoff and K3's sort has work to do (`--no-k3-stress` skips them;
+they never enter `value`).  `--no-cpu-baseline` and `--no-parity-check` drop single legs of a --full run.
 """
 import argparse
 import json
@@ -254,7 +265,19 @@ def main():
                          "function).  The line says which ran: totals_semantics")
     ap.add_argument("--no-bias", action="store_true", help="variant: no bias file (p depends on (distance, count) only: table path)")
     ap.add_argument("--replicas", type=int, default=0, help="debug: replicate the genome R times per run regardless of --gpus (size test)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: parity check, CPU baselines, k3_stress workloads (N = 1, C3), "
+                         "the one-GPU verification and the weak-scaling figure (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write p and q of the last timed step (a fixed seeded sample of 2^21 rows above that size) as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # legs outside the headline: only with --full, each one still switched off by its own --no-* option
+    args.do_parity = args.full and not args.no_parity_check
+    args.do_cpu_baseline = args.full and not args.no_cpu_baseline
+    args.do_k3_stress = args.full and not args.no_k3_stress
+    args.do_weak = args.full and not args.no_weak
 
     # `python bench.py --gpus N` outside a launcher: this process starts the N ranks itself (torch.distributed.run on 127.0.0.1)
     # and passes their one JSON line through; with fewer than N visible GPUs the one line is a diagnostic instead
@@ -272,12 +295,12 @@ def main():
         if args.path == "kr":
             import kr_bench
             out, genome, cols = kr_bench.measure(args.max_chroms)
-            if not args.no_cpu_baseline:
+            if args.do_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline_kr(genome, cols, 0.05)
         else:
             import cni_bench
             out, table = cni_bench.measure()
-            if not args.no_cpu_baseline:
+            if args.do_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline_cni(*table)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
@@ -355,9 +378,10 @@ def main():
         return phi, m
 
     def measure(replicas, with_cpu_leg, solo=False, want_hashes=False, steps=None, warmup=None, overdispersion=None, hotspots=None,
-                sample_budget=3.0e7):
+                sample_budget=3.0e7, dump_dir=None):
         """Generate, load, warm up, time `steps` steps.  Returns the result pieces of this workload.
-        solo: this process alone takes the whole genome through the plain single-GPU path (the verification run of rank 0)."""
+        solo: this process alone takes the whole genome through the plain single-GPU path (the verification run of rank 0).
+        dump_dir: write p and q of the last timed step there (dump_outputs) before anything else runs on the engine."""
         world, rank, comm = (1, 0, None) if solo else (world_all, rank_all, comm_all)
         steps = args.steps if steps is None else steps
         warmup = args.warmup if warmup is None else warmup
@@ -478,6 +502,8 @@ def main():
                 log("[rank 0] host wall per pass of the distributed stages (ms): " + ", ".join("%s %.2f" % kv for kv in stage_ms.items()))
         mine_row = list(kt) + [float(n_local)] + list(heavy)
         k_all = comm.gather_floats(mine_row) if comm else [mine_row]
+        if dump_dir:
+            dump_outputs(torch, eng, n_local, dump_dir)
         hashes = None
         if want_hashes:
             if passes > 1:                                       # the timed steps end with reset_passes(): hash an (untimed) pass 1
@@ -508,10 +534,10 @@ def main():
     # the f14 fixture of this workload (the real reference's fit on it) applies when the run IS that workload
     canonical = (args.keep == 0 and args.max_chroms == 0 and args.shard_of <= 1 and args.overdispersion == 0 and not args.hotspots and replicas == 1)
     fixture_name = args.config if canonical and os.path.exists(os.path.join(ROOT, "tests", "golden", "f14_%s_fit.npz" % args.config)) else None
-    verify_sharded = comm is not None and not args.no_parity_check         # N > 1 (or FHX_FORCE_DIST): compare with one GPU
+    verify_sharded = comm is not None and args.do_parity                   # N > 1 (or FHX_FORCE_DIST): compare with one GPU
     want_digest = bool(os.environ.get("FHX_BENCH_HASH"))          # A/B of kernel variants: a digest of every p and q in the result line
-    M = measure(replicas, with_cpu_leg=(rank == 0 and comm is None and not (args.no_cpu_baseline and args.no_parity_check)),
-                want_hashes=verify_sharded or want_digest)
+    M = measure(replicas, with_cpu_leg=(rank == 0 and comm is None and (args.do_cpu_baseline or args.do_parity)),
+                want_hashes=verify_sharded or want_digest, dump_dir=args.dump_outputs if rank == 0 else None)
     eng, genome = M["eng"], M["genome"]
     passes = cfg["passes"]
 
@@ -625,19 +651,19 @@ def main():
                                    "heavy_ms": 1e3 * r[4], "heavy_rows": int(r[5])} for i, r in enumerate(M["k_all"])]
             if not weak_headline:
                 result["predicted_ms"] = predicted_pass_ms(world, max(int(r[3]) for r in M["k_all"]), args.config)
-        if args.no_parity_check:
-            result["parity_check"] = {"ok": None, "skipped": "--no-parity-check"}
+        if not args.do_parity:
+            result["parity_check"] = {"ok": None, "skipped": "--no-parity-check" if args.full else "runs with --full"}
         if want_digest and M["hashes"] is not None:
             import hashlib
             result["result_digest"] = hashlib.sha256(M["hashes"].cpu().numpy().tobytes()).hexdigest()[:16]
         if M["sample"] is not None:
-            if not args.no_parity_check:
+            if args.do_parity:
                 if passes > 1:                              # the timed steps end with reset_passes(): check an (untimed) pass 1
                     out1 = eng.run_pass(collect=False)
                     M["info"] = (out1.info, out1.stats)
                 result["parity_check"] = checked(eng, genome, M["sample"], M["info"], fixture_name)
                 log("headline checked (%.1f s)" % result["parity_check"].get("seconds", -1))
-            if not args.no_cpu_baseline:
+            if args.do_cpu_baseline:
                 try:
                     result["cpu_baseline"] = cpu_baseline(genome, M["sample"], cfg, not args.no_bias)
                     log("cpu_baseline (one core) done")
@@ -653,7 +679,7 @@ def main():
     eng.close()
     del M
     torch.cuda.empty_cache()
-    if (rank == 0 and comm is None and args.path == "fithic" and args.overdispersion == 0 and not args.hotspots and not args.no_k3_stress
+    if (rank == 0 and comm is None and args.path == "fithic" and args.overdispersion == 0 and not args.hotspots and args.do_k3_stress
             and args.config == "C3"):
         # K3 where it works: on synth-v1 the exact cutoff leaves < 0.1 % of the rows to sort.  Three more, labelled workloads on the
         # same genome put 12 %, 39 % and 55 % of the rows below the BH cutoff - real (over-dispersed, domain-structured) maps sit
@@ -663,7 +689,7 @@ def main():
         for label, od, hot in (("lognormal rate noise s = 1.0", 1.0, None), ("hotspots phi:m = 0.2:4.5", 0.0, (0.2, 4.5)),
                                ("hotspots phi:m = 0.25:3.9", 0.0, (0.25, 3.9))):
             try:
-                S = measure(replicas, with_cpu_leg=not args.no_parity_check, steps=max(2, min(args.steps, 10)), warmup=min(max(args.warmup, 1), 3), overdispersion=od,
+                S = measure(replicas, with_cpu_leg=args.do_parity, steps=max(2, min(args.steps, 10)), warmup=min(max(args.warmup, 1), 3), overdispersion=od,
                             hotspots=hot if hot else (), sample_budget=1.0e7)
                 k3_s = max(r[2] for r in S["k_all"])
                 entry = {
@@ -730,7 +756,7 @@ def main():
                 result["parity_check"] = {"ok": False, "error": repr(e)}
             torch.cuda.empty_cache()
         comm.barrier()
-    if world > 1 and not weak_headline and not args.no_weak and args.replicas == 0:
+    if world > 1 and not weak_headline and args.do_weak and args.replicas == 0:
         W = measure(world, with_cpu_leg=False)                  # the weak-scaling figure: genome replicated per GPU
         if rank == 0:
             result["weak_scaling"] = {"value": W["n_total"] * passes * args.steps / W["elapsed"], "ms_per_step": 1e3 * W["elapsed"] / args.steps,
@@ -798,6 +824,41 @@ def self_launch(args):
     diagnostic(1, args, "the %d rank(s) started by bench.py ended with exit code %d without a result line (see stderr)" % (args.gpus, r.returncode),
                visible_devices=n_vis)
     return r.returncode or 1
+
+
+DUMP_ROWS = 1 << 21            # p, q and the row numbers in float64: 48 MB at most
+DUMP_SEED = 20240611
+
+
+def dump_outputs(torch, eng, n, out_dir, chunk=1 << 27):
+    """p and q of the engine's last pass, as a caller fetching them would receive them, into out_dir/p.npy, q.npy and rows.npy
+    (float64): every row up to DUMP_ROWS rows, above that a fixed seeded sample of DUMP_ROWS row numbers (duplicates of the draw
+    dropped, ascending), the same rows for the same workload in every run.  Read from the device buffers, so that a multi-pass
+    step (which ends with reset_passes()) still gives its last pass; walked in chunks of 2^27 rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    eng.ctx.sync()
+    if n <= DUMP_ROWS:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        rows = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_ROWS, dtype=np.int64))
+    out = {"rows": rows.astype(np.float64)}
+    buf = torch.empty(min(n, chunk), dtype=torch.float64, device=torch.device("cuda", eng.device)) if n else None
+    for which, name in ((0, "p"), (1, "q")):
+        vals = np.empty(len(rows), np.float64)
+        base = eng.ctx.device_ptr(which)
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            a, b = np.searchsorted(rows, [lo, hi])
+            if a == b:
+                continue
+            eng.ctx.memcpy_d2d(buf.data_ptr(), base + 8 * lo, 8 * (hi - lo))          # (returns when the copy is done)
+            idx = torch.from_numpy(rows[a:b] - lo).to(buf.device)
+            vals[a:b] = buf[idx].cpu().numpy()
+        out[name] = vals
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    log("outputs of the last timed step: %d of %d rows -> %s" % (len(rows), n, out_dir))
 
 
 def predicted_pass_ms(world, rows_largest_rank, config):

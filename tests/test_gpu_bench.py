@@ -28,7 +28,7 @@ def _run(extra_env, *flags):
 
 
 def test_single_gpu_line_is_checked_against_the_oracle():
-    out = _run({}, "--max-chroms", "2", "--no-cpu-baseline")
+    out = _run({}, "--max-chroms", "2", "--full", "--no-cpu-baseline")
     pc = out["parity_check"]
     assert pc["ok"] and pc["max_dp"] <= 1e-10 and pc["max_dq"] == 0.0 and pc["rows_q"] == out["config"]["pairs"]
     assert "fit_vs_reference" not in pc                     # two chromosomes are not the workload the f14 fixture was made on
@@ -46,7 +46,7 @@ def test_sharded_schedule_over_rccl_is_verified_against_one_gpu():
     """FHX_FORCE_DIST=1: the library's communicator (real RCCL, one rank) and fhx_run_pass_distributed carry the timed pass; the
     same code then verifies it as an N > 1 run is verified - per-chromosome hashes of (row, p) and (row, q) of the sharded run
     against a plain single-GPU pass over all rows, which in turn is checked against the oracle."""
-    out = _run({"FHX_FORCE_DIST": "1"}, "--max-chroms", "3", "--no-weak")
+    out = _run({"FHX_FORCE_DIST": "1"}, "--max-chroms", "3", "--full", "--no-weak")
     pc = out["parity_check"]
     assert pc["ok"] and pc["sharded_equals_single_gpu"] and pc["ranks"] == 1 and pc["chromosomes_hashed"] == 3
     assert pc["chromosomes_p_differ"] == [] and pc["chromosomes_q_differ"] == [] and pc["global_stats_equal"] and pc["fit_scalars_equal"]
@@ -69,7 +69,7 @@ def _plain(extra_env, *flags, expect_rc=0):
 def test_plain_invocation_starts_its_own_ranks():
     """`python bench.py --gpus N` without torch.distributed.run: the script launches the ranks itself (here N = 1 with the
     sharded schedule forced) and the one line carries everything an N > 1 line must carry."""
-    out = _plain({"FHX_FORCE_DIST": "1"}, "--gpus", "1", "--max-chroms", "3", "--no-weak")
+    out = _plain({"FHX_FORCE_DIST": "1"}, "--gpus", "1", "--max-chroms", "3", "--full", "--no-weak")
     assert out["value"] > 1e8 and out["scaling"] == "strong" and out["n_gpus"] == 1
     assert out["rccl"]["world_in_library"] == 1
     assert len(out["per_rank"]) == 1 and out["per_rank"][0]["rows"] == out["config"]["pairs"]
@@ -91,6 +91,43 @@ def test_single_gpu_line_says_strong_scaling():
     assert out["scaling"] == "strong" and out["n_gpus"] == 1 and out["value"] > 1e8 and "k3_stress" not in out
 
 
+def test_plain_line_runs_the_headline_only():
+    """Without --full the run times the headline and nothing else: no CPU leg, no check, no extra workloads - and says so."""
+    out = _plain({}, "--gpus", "1", "--max-chroms", "2")
+    assert out["value"] > 1e8 and out["ms_per_step"] > 0 and out["steps"] == 2 and out["dtype"] == "f64" and out["higher_is_better"]
+    assert out["parity_check"] == {"ok": None, "skipped": "runs with --full"}
+    assert "cpu_baseline" not in out and "k3_stress" not in out
+
+
+def test_dump_outputs_are_the_last_step_and_repeat_run_to_run(tmp_path):
+    """--dump-outputs: p and q of the timed path's last step - every row of a workload below 2^21 rows, a fixed seeded sample of
+    row numbers above - bit-identical between two runs of the same workload (with a different number of timed steps)."""
+    import numpy as np
+
+    def load(d):
+        return {k: np.load(str(d / (k + ".npy"))) for k in ("rows", "p", "q")}
+
+    small = _plain({}, "--gpus", "1", "--max-chroms", "1", "--keep", "0.05", "--dump-outputs", str(tmp_path / "s"))
+    n = small["config"]["pairs"]
+    assert 0 < n <= 1 << 21
+    got = load(tmp_path / "s")
+    assert all(v.dtype == np.float64 and v.shape == (n,) for v in got.values())
+    assert np.array_equal(got["rows"], np.arange(n, dtype=np.float64))
+    fin = np.isfinite(got["p"])
+    assert fin.sum() > n // 2 and got["p"][fin].min() >= 0 and got["p"][fin].max() <= 1
+
+    big = _plain({}, "--gpus", "1", "--max-chroms", "2", "--dump-outputs", str(tmp_path / "a"))
+    _plain({}, "--gpus", "1", "--max-chroms", "2", "--steps", "3", "--dump-outputs", str(tmp_path / "b"))
+    n = big["config"]["pairs"]
+    a, b = load(tmp_path / "a"), load(tmp_path / "b")
+    rows = a["rows"].astype(np.int64)
+    assert n > 1 << 21 and 0.9 * (1 << 21) < len(rows) <= 1 << 21
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < n
+    assert all(v.dtype == np.float64 and v.shape == rows.shape for v in a.values())
+    for k in ("rows", "p", "q"):
+        assert np.array_equal(a[k].view(np.int64), b[k].view(np.int64)), k
+
+
 def test_shard_of_runs_the_fullest_rank_of_an_n_way_sharding():
     """--shard-of N (profiles/scaling_model.py): the chromosomes the fullest of N ranks would hold, alone on this GPU."""
     import bench
@@ -98,7 +135,7 @@ def test_shard_of_runs_the_fullest_rank_of_an_n_way_sharding():
     g = synth.Genome(5000, synth.HG19_AUTOSOMES[:6])
     owner = synth.assign_chromosomes(g, 3)
     loads = [sum(g.n_loci[c] for c in range(6) if owner[c] == r) for r in range(3)]
-    out = _plain({}, "--max-chroms", "6", "--shard-of", "3", "--no-cpu-baseline", "--no-k3-stress")
+    out = _plain({}, "--max-chroms", "6", "--shard-of", "3", "--full", "--no-cpu-baseline", "--no-k3-stress")
     assert out["parity_check"]["ok"] and "fit_vs_reference" not in out["parity_check"]
     whole = _plain({}, "--max-chroms", "6", "--no-cpu-baseline", "--no-parity-check", "--no-k3-stress")
     frac = out["config"]["pairs"] / whole["config"]["pairs"]
@@ -115,7 +152,7 @@ def test_n_ranks_branch_of_bench_runs_end_to_end_over_the_pipe_transport(world, 
     nothing in it measures xGMI."""
     # (eight ranks: the weak-scaling leg - eight genomes on this one GPU - is left to the 2- and 4-rank cases)
     extra = ("--no-weak",) if world == 8 else ()
-    out = _plain({"FHX_BENCH_TRANSPORT": "pipes"}, "--gpus", str(world), "--max-chroms", str(chroms), *extra)
+    out = _plain({"FHX_BENCH_TRANSPORT": "pipes"}, "--gpus", str(world), "--max-chroms", str(chroms), "--full", *extra)
     assert out["n_gpus"] == world and out["scaling"] == "strong"
     assert out["value"] is None and out["value_over_pipes"] > 1e6 and "pipes" in out["value_note"]
     assert out["rccl"]["transport"] == "pipes" and out["rccl"]["backend"] == "gloo" and out["rccl"]["world"] == world
