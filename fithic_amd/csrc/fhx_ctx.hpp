@@ -109,7 +109,6 @@ struct K2Params {
     // the true totals (observedIntraInRangeSum, observedInterAllSum) for ExpCC = total * prior (fithic.py:1076, 1106): the n
     // of intra / inter above is what bdtrc is given, which differs from these once a total reaches 2^31 (bdtrc_total)
     double total_intra, total_inter;
-    int lean_closed;              // experiment (FHX_LEAN_CLOSED=1): count == 1 rows with prior < 0.01 through a division-free log1p
 };
 
 constexpr int K2_THREADS = 256;
@@ -157,7 +156,7 @@ struct K2Queues {
     unsigned long long* count;         // (K2_QUEUES + 1) x K2_MAX_SHARDS counters: [class * K2_MAX_SHARDS + shard]
     unsigned int* heavy_hist;          // K2H_BUCKETS x K2H_BLOCKS bucket counts of the swapped-fraction queue (zeroed before the
                                        // launch; column = shard % K2H_BLOCKS, the workgroup of k2h_scatter that will move the shard);
-                                       // nullptr = not collected
+                                       // nullptr = not collected (FHX_K2_LEGACY: the heavy class is not count-sorted)
 };
 
 // bucket of a swapped-continued-fraction row in the count sort that feeds k2h_heavy (defined with that sort, below); k2_classify
@@ -477,10 +476,8 @@ __device__ __forceinline__ void publish_ticket(unsigned int* done, volatile unsi
     }
 }
 // Host side: spin until h_flags[word] shows `ticket`.  The stream is asked now and then: an error (or a stream that has drained
-// without the ticket: cannot happen) ends the wait with that answer instead of hanging.  FHX_NO_SPIN=1: hipStreamSynchronize.
+// without the ticket: cannot happen) ends the wait with that answer instead of hanging.
 inline hipError_t wait_ticket(fhx_ctx* ctx, int word, unsigned long long ticket) {
-    static const bool no_spin = std::getenv("FHX_NO_SPIN") != nullptr;
-    if (no_spin) return hipStreamSynchronize(ctx->stream);
     volatile unsigned long long* f = ctx->h_flags + word;
     for (unsigned int spins = 1;; ++spins) {
         if (*f == ticket) {
@@ -579,12 +576,7 @@ inline int grid_for(int64_t n, int threads, int max_blocks = 256 * 8) {
 // k2_classify over n rows: workgroup b of `grid` takes tiles b, b + grid, ... and queues into shard b, so a shard receives at
 // most ceil(tiles / grid) tiles of rows, whatever their classes
 inline int k2_classify_grid(int64_t n) {
-    static const int cap = [] {                      // FHX_CL_SHARDS: measurements (a smaller grid = fewer, longer queue shards)
-        const char* e = std::getenv("FHX_CL_SHARDS");
-        const int v = e ? std::atoi(e) : 0;
-        return v >= 1 && v <= K2_MAX_SHARDS ? v : K2_MAX_SHARDS;
-    }();
-    return grid_for(n, K2_CL_TILE, cap);
+    return grid_for(n, K2_CL_TILE, K2_MAX_SHARDS);
 }
 inline long long k2_shard_capacity(int64_t n) {              // entries per shard region: the rows one workgroup of k2_classify can meet
     const long long tiles = std::max<long long>(1, (n + K2_CL_TILE - 1) / K2_CL_TILE), grid = k2_classify_grid(n);

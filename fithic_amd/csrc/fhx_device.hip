@@ -310,7 +310,7 @@ int fhx_fit(fhx_ctx* ctx, fhx_fit_info* out) {
     // parked side threads while this one bins and fits; small tables (5 kb bins: 700 entries, 10 us) stay inline.
     const int64_t mc = std::max<int64_t>(ctx->stats.max_count, 1);
     std::vector<double> lb_a, ib_a, lb_e, ib_e;
-    const bool tables_aside = ctx->device >= 0 && mc >= 2048 && !std::getenv("FHX_FIT_SERIAL");
+    const bool tables_aside = ctx->device >= 0 && mc >= 2048;
     if (tables_aside) {
         const double n_a = bdtrc_total(ctx->prm, ctx->stats.in_range_sum), n_e = bdtrc_total(ctx->prm, ctx->stats.inter_sum);
         lb_a.assign((size_t)mc + 1, 0.0);

@@ -941,8 +941,7 @@ int fhx::launch_k1(fhx_ctx* ctx) {
     const uint8_t* skip = ctx->skip_active ? ctx->d_skip : (const uint8_t*)nullptr;
     const long long* grow = (ctx->skip_limit != INT64_MAX) ? (const long long*)ctx->d_grow : (const long long*)nullptr;
     const int lo_i = (int)std::min<int64_t>(lo, INT32_MAX);
-    static const bool force_narrow = std::getenv("FHX_K1_NARROW") != nullptr;      // measurements only
-    if (hi - lo + 1 > K1_LDS_BINS && !force_narrow) {                                // more distance values than the 12-B window holds
+    if (hi - lo + 1 > K1_LDS_BINS) {                                                 // more distance values than the 12-B window holds
         const size_t lds = (size_t)K1_WIDE_BINS * 6;
         static bool attr_done = false;
         if (!attr_done) {
@@ -1047,13 +1046,11 @@ int fhx_pass_stats(fhx_ctx* ctx, fhx_stats* out) {
     // behind it, off the host's critical path: what fhx_pvalues would otherwise have to zero before it can classify
     ctx->k2_prezeroed = false;
     if (ctx->d_block_hist && ctx->d_k2_hist) {
-        static const bool prefill = !(std::getenv("FHX_Q_PREFILL") && std::atoi(std::getenv("FHX_Q_PREFILL")) == 0);     // 0: measurements
-        hipLaunchKernelGGL(k1_prezero, dim3(prefill ? 2048 : 1024), dim3(256), 0, ctx->stream, ctx->d_k2_hist, (int64_t)TOP_BINS,
-                           reinterpret_cast<uint4*>(ctx->d_block_hist), (int64_t)K2H_BUCKETS * K2H_BLOCKS / 4, ctx->d_q,
-                           prefill ? ctx->n_rows : (int64_t)0);
+        hipLaunchKernelGGL(k1_prezero, dim3(2048), dim3(256), 0, ctx->stream, ctx->d_k2_hist, (int64_t)TOP_BINS,
+                           reinterpret_cast<uint4*>(ctx->d_block_hist), (int64_t)K2H_BUCKETS * K2H_BLOCKS / 4, ctx->d_q, ctx->n_rows);
         FHX_HIP(hipGetLastError());
         ctx->k2_prezeroed = true;
-        ctx->q_prefilled = prefill;
+        ctx->q_prefilled = true;
     }
     FHX_HIP(wait_ticket(ctx, FLAG_K1, ticket));
     fold_kernel_events(ctx);               // this pass's K1 and, behind it on the stream, the previous pass's K2 and K3

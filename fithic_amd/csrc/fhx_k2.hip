@@ -351,8 +351,7 @@ __global__ __launch_bounds__(K2_THREADS) __attribute__((amdgpu_waves_per_eu(WPE,
             const unsigned int ix = cf_idx[wave][j];
             const double n_total = (ix & 0x8000u) ? P.inter.n : P.intra.n;
             const double pr = cf_prior[wave][j];
-            const double pv = P.lean_closed ? -dev::cephes_expm1(n_total * dev::lean_log1p_neg(pr))
-                                            : -dev::cephes_expm1(n_total * dev::cephes_log1p(-pr));             // bdtrc_closed_form, prior < 0.01
+            const double pv = -dev::cephes_expm1(n_total * dev::cephes_log1p(-pr));         // bdtrc_closed_form, prior < 0.01
             P.p[wave_row0 + (ix & 0x7FFFu)] = pv;
             H.add(pv);
         }
@@ -509,13 +508,12 @@ __global__ __launch_bounds__(K2_THREADS) void k2_queue(K2Params P, QSpan q) {
 // therefore takes a tile of 1024 entries, counting-sorts it by min(count, 31) in LDS (one LDS atomic per entry) and hands
 // every wave 64 neighbours of that order (per-wave maximum 11.4).  Results go to P.p[row], so the order is free.
 // Tiles are pieces of the dense list (QDense): a workgroup's first tile is its own number, the others come from the launch's
-// counter (`quarters` 1..4 fixes the tile at that many times 256 entries: measurements).
+// counter.
 constexpr int K2_SORT_TILE = 1024;
 constexpr int K2_SORT_BUCKETS = 32;
 template <int CLS, bool SMALL_N, int WPE>
 __global__ __launch_bounds__(K2_THREADS) __attribute__((amdgpu_waves_per_eu(WPE))) void k2_queue_by_count(K2Params P, QSpan q,
-                                                                                                         unsigned int* next_tile,
-                                                                                                         int quarters) {
+                                                                                                         unsigned int* next_tile) {
     static_assert(K2_SORT_TILE == 4 * K2_THREADS, "four entries per thread");
     __shared__ QEntry tile[K2_SORT_TILE];
     __shared__ unsigned int bucket_cnt[K2_SORT_BUCKETS], bucket_off[K2_SORT_BUCKETS];
@@ -528,13 +526,9 @@ __global__ __launch_bounds__(K2_THREADS) __attribute__((amdgpu_waves_per_eu(WPE)
     const unsigned int total = D.total();
     // tile: at most 1024 entries, and such that the workgroups' shares are whole tiles - a 1/8 shard of C3 has 2.6 tiles of 1024
     // per workgroup, i.e. three rounds of which the last is 60 % full; three tiles of 896 each fill them all
-    unsigned int tile_n = (unsigned int)quarters * K2_THREADS;
-    if (quarters < 1 || quarters > 4) {
-        const unsigned int share = (total + gridDim.x - 1) / gridDim.x;
-        const unsigned int rounds = max(1u, (share + K2_SORT_TILE - 1) / K2_SORT_TILE);
-        tile_n = min((unsigned int)K2_SORT_TILE, ((share + rounds - 1) / rounds + 63u) & ~63u);
-        tile_n = max(tile_n, 64u);
-    }
+    const unsigned int share = (total + gridDim.x - 1) / gridDim.x;
+    const unsigned int rounds = max(1u, (share + K2_SORT_TILE - 1) / K2_SORT_TILE);
+    const unsigned int tile_n = max(min((unsigned int)K2_SORT_TILE, ((share + rounds - 1) / rounds + 63u) & ~63u), 64u);
     const unsigned int tiles = (total + tile_n - 1) / tile_n;
     unsigned int mine = blockIdx.x;
     for (;;) {
@@ -608,20 +602,6 @@ __device__ __forceinline__ int k2h_bucket(int signed_count) {
     const bool inter = signed_count < 0;
     const int c = inter ? -signed_count : signed_count;
     return c < K2H_KCAP ? (inter ? K2H_KCAP + c : c) : K2H_GENERIC;
-}
-
-// per-workgroup bucket counts of its shards of the queue (digit-major matrix, as rs_count writes it): workgroup b takes the
-// shards b, b + K2H_BLOCKS, ...
-__global__ __launch_bounds__(K2H_THREADS) void k2h_count(QSpan q, unsigned int* __restrict__ block_hist) {
-    __shared__ unsigned int h[K2H_BUCKETS];
-    for (int d = threadIdx.x; d < K2H_BUCKETS; d += K2H_THREADS) h[d] = 0;
-    __syncthreads();
-    for (int sh = blockIdx.x; sh < q.n_shards; sh += K2H_BLOCKS) {
-        const long long n = (long long)q.count[sh];
-        for (long long i = threadIdx.x; i < n; i += K2H_THREADS) atomicAdd(&h[k2h_bucket(qentry(q, sh, i)->count)], 1u);
-    }
-    __syncthreads();
-    for (int d = threadIdx.x; d < K2H_BUCKETS; d += K2H_THREADS) block_hist[(size_t)d * K2H_BLOCKS + blockIdx.x] = h[d];
 }
 
 __global__ __launch_bounds__(K2H_THREADS) void k2h_scatter(QSpan q, const unsigned int* __restrict__ block_hist,
@@ -1016,8 +996,6 @@ K2Params make_k2_params(fhx_ctx* c) {
     P.count = c->d_count;
     P.slot_bias = c->d_slot_bias;
     P.no_bias = !c->have_bias;
-    static const int lean = std::getenv("FHX_LEAN_CLOSED") ? std::atoi(std::getenv("FHX_LEAN_CLOSED")) : 0;
-    P.lean_closed = lean;
     P.prior_lut = c->d_lut;
     P.lut_len = (int)std::min<size_t>(std::max<size_t>(c->fit.prior_lut.size(), 1), (size_t)INT32_MAX);
     // the n of the two binomials: narrowed to a C int as scipy does, unless the caller asked for wide totals (bdtrc_total)
@@ -1108,7 +1086,7 @@ int fhx_pvalues(fhx_ctx* ctx) {
     ctx->k2_prezeroed = false;
     // K3's key histogram rides on K2's stores of p - except on the table path, whose class kernels store table entries
     ctx->k2_hist_valid = false;
-    if (memo_cap < 0 && !getenv("FHX_NO_FUSED_HIST")) {
+    if (memo_cap < 0) {
         if (!ctx->d_k2_hist) FHX_HIP(hipMalloc(&ctx->d_k2_hist, TOP_BINS * sizeof(unsigned long long)));
         if (!prezeroed) FHX_HIP(hipMemsetAsync(ctx->d_k2_hist, 0, TOP_BINS * sizeof(unsigned long long), ctx->stream));
         P.top_hist = ctx->d_k2_hist;
@@ -1148,10 +1126,9 @@ int fhx_pvalues(fhx_ctx* ctx) {
     if ((int64_t)n_shards * cap_s > ctx->queue_cap) return fail(ctx, FHX_ERR_HIP, "internal: queue workspace smaller than the shard layout");
     if (!ctx->d_k2_counts) FHX_HIP(hipMalloc(&ctx->d_k2_counts, (size_t)(K2_QUEUES + 1) * K2_MAX_SHARDS * sizeof(unsigned long long)));
     Q.count = ctx->d_k2_counts;
-    static const bool own_count_pass = std::getenv("FHX_K2H_COUNT") != nullptr;          // measurements: the separate k2h_count launch
-    const bool heavy_sorted = getenv("FHX_K2_LEGACY") == nullptr;
+    const bool legacy_heavy = getenv("FHX_K2_LEGACY") != nullptr;      // A/B and tests: the per-lane kernel of round 1
     Q.heavy_hist = nullptr;
-    if (heavy_sorted && !own_count_pass) {
+    if (!legacy_heavy) {                 // k2_classify counts the heavy class's buckets while it queues
         static_assert((K2H_BLOCKS & (K2H_BLOCKS - 1)) == 0, "shard -> column by masking");
         if (!prezeroed)
             FHX_HIP(hipMemsetAsync(ctx->d_block_hist, 0, (size_t)K2H_BUCKETS * K2H_BLOCKS * sizeof(unsigned int), ctx->stream));
@@ -1173,24 +1150,11 @@ int fhx_pvalues(fhx_ctx* ctx) {
     span(K2_CLOSED, ctx->d_queue_sorted, 1);             // the sorted heavy queue is written after k2_closed has run
     // (no reset of the counters: every workgroup of k2_classify writes its own shard's counts)
     {
-        const dim3 cgrid(k2_classify_grid(k2_n)), cblock(K2_THREADS);
-        // FHX_CL_BASE=1: round 3's kernel (gathers row by row, 24 ballots, the division per row) for A/B runs; FHX_CL_PACK=0 /
-        // FHX_CL_TB=0 switch the two later steps off one at a time
-        static const bool cl_base = std::getenv("FHX_CL_BASE") != nullptr;
-        static const bool cl_pack = !(std::getenv("FHX_CL_PACK") && std::atoi(std::getenv("FHX_CL_PACK")) == 0);
-        static const bool cl_tb = !(std::getenv("FHX_CL_TB") && std::atoi(std::getenv("FHX_CL_TB")) == 0);
+        const dim3 cgrid(n_shards), cblock(K2_THREADS);
         if (P.nonfixed)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<1, 4, 0>), cgrid, cblock, 0, ctx->stream, P, Q);
-        else if (cl_base)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<0, 4, 0>), cgrid, cblock, 0, ctx->stream, P, Q);
-        else if (cl_pack && cl_tb)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<0, 4, 3, true, true>), cgrid, cblock, 0, ctx->stream, P, Q);
-        else if (cl_pack)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<0, 4, 0, true, true>), cgrid, cblock, 0, ctx->stream, P, Q);
-        else if (cl_tb)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<0, 4, 3, true, false>), cgrid, cblock, 0, ctx->stream, P, Q);
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<0, 4, 0, true, false>), cgrid, cblock, 0, ctx->stream, P, Q);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<0, 4, 3, true, true>), cgrid, cblock, 0, ctx->stream, P, Q);
     }
     const dim3 qgrid(256 * 8), qblock(K2_THREADS);
     hipLaunchKernelGGL(k2_closed, qgrid, qblock, 0, ctx->stream, P, Q.q[K2_CLOSED - 1], ctx->d_misc + MISC_K2_REDO, ctx->d_misc + 6);
@@ -1198,18 +1162,16 @@ int fhx_pvalues(fhx_ctx* ctx) {
     // rows - classifies every row as trivial and reaches no class kernel: it does not count)
     const bool small_n = (P.intra.small_n && P.intra.n >= 1.0) || (P.inter.small_n && P.inter.n >= 1.0);
     // one range per wave of TWICE the resident workgroups: the ranges are cut by entries, not by work, and the second half
-    // evens the first one out (C3: 376 us at 1 x, 358 at 2.3 x, 362 at 4.7 x, profiles/history/r04_t_ps.txt); FHX_PS_GRID: measurements
-    static const int ps_grid = std::getenv("FHX_PS_GRID") ? std::atoi(std::getenv("FHX_PS_GRID")) : 0;
+    // evens the first one out (C3: 376 us at 1 x, 358 at 2.3 x, 362 at 4.7 x, profiles/history/r04_t_ps.txt)
 #define FHX_LAUNCH_QUEUE(CLS)                                                                                         \
     do {                                                                                                              \
         if (small_n)                                                                                                  \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue<CLS, true>), dim3(2 * resident_grid(ctx, k2_queue<CLS, true>)), qblock, 0,      \
                                ctx->stream, P, Q.q[(CLS) - 1]);                                                       \
         else                                                                                                          \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue<CLS, false>), dim3(ps_grid > 0 ? ps_grid : 2 * resident_grid(ctx, k2_queue<CLS, false>)), qblock, 0,    \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue<CLS, false>), dim3(2 * resident_grid(ctx, k2_queue<CLS, false>)), qblock, 0,     \
                                ctx->stream, P, Q.q[(CLS) - 1]);                                                       \
     } while (0)
-    const bool legacy_heavy = getenv("FHX_K2_LEGACY") != nullptr;      // A/B and tests: the per-lane kernel of round 1
     // the handed-back rows' counter and the work counters of the class kernels (k2h_heavy's tasks, one per class queue)
     unsigned long long* n_redo = ctx->d_misc + MISC_K2_REDO;
     unsigned long long* k2_next = ctx->d_misc + MISC_K2_NEXT;                 // both zeroed by k2_closed above
@@ -1223,21 +1185,16 @@ int fhx_pvalues(fhx_ctx* ctx) {
         const QSpan hs = Q.q[dev::BC_CF_SWAPPED - 1];
         QEntry* hq = ctx->d_queue[0];                    // the handed-back rows: this buffer is dead once it is scattered and the
                                                          // power-series class (its other tenant) has run
-        if (!Q.heavy_hist)              // otherwise k2_classify has counted while it queued
-            hipLaunchKernelGGL(k2h_count, dim3(K2H_BLOCKS), dim3(K2H_THREADS), 0, ctx->stream, hs, ctx->d_block_hist);
         launch_rs_scan(ctx, (int)SORT_BLOCKS);
-        // rows per lane: 4 at 4 waves/SIMD (7.43 -> 6.66 ms per 2.7e7 rows against one row per lane at 8 waves/SIMD; 2 x 8, 2 x 6,
-        // 3 x 5, 4 x 3 are within 3 % of each other, profiles/history/r03_c_heavy_variants.txt); FHX_K2H_ROWS / FHX_K2H_WAVES: measurements
         // rows per lane: 4 at 4 waves/SIMD - C3 (2.7e7 rows in the class) 7.43 -> 6.66 ms, a 1/18 shard (1.5e6 rows) 0.87 -> 0.78 ms of
-        // K2 against one row per lane at 8 waves/SIMD; 2 x 8, 3 x 5 and 4 x 3 are within 3 % (profiles/history/r03_c_*heavy_variants.txt).
-        // FHX_K2H_ROWS (1, 2) / FHX_K2H_WAVES (3) select the instantiations kept for measurements.
-        const char* heavy_rows_env = std::getenv("FHX_K2H_ROWS");                 // read per call: the tests run every instantiation
+        // K2 against one row per lane at 8 waves/SIMD; 2 x 8, 2 x 6, 3 x 5 and 4 x 3 are within 3 % of each other
+        // (profiles/history/r03_c_*heavy_variants.txt).  A small input (a shard of a strong-scaling run) has a handful of 256-entry
+        // tasks per wave and ends with most waves idle: two rows per lane at eight waves per SIMD halves the task (a 1/8 shard of
+        // C3: 876 -> 829 us, profiles/history/r04_t_rows.txt).  FHX_K2H_ROWS (2 or 4), read per call, forces one of the two for tests.
+        const char* heavy_rows_env = std::getenv("FHX_K2H_ROWS");
         const int heavy_rows = heavy_rows_env ? std::atoi(heavy_rows_env) : 0;
-        static const int heavy_wpe = std::getenv("FHX_K2H_WAVES") ? std::atoi(std::getenv("FHX_K2H_WAVES")) : 0;
-        // a small input (a shard of a strong-scaling run) has a handful of 256-entry tasks per wave and ends with most waves idle:
-        // two rows per lane at eight waves per SIMD halves the task (a 1/8 shard of C3: 876 -> 829 us, profiles/history/r04_t_rows.txt)
-        const int hr = (heavy_rows == 1 || heavy_rows == 2) ? heavy_rows       // the instantiations below: 1, 2 or 4 rows per lane - the
-                       : (heavy_rows == 0 && k2_n < 32000000) ? 2 : 4;         // bucket granule must be the launched kernel's task size
+        const int hr = (heavy_rows == 2 || heavy_rows == 4) ? heavy_rows      // the bucket granule must be the launched kernel's task size
+                       : k2_n < 32000000 ? 2 : 4;
         hipLaunchKernelGGL(k2h_offsets_and_tables, dim3(K2H_GENERIC + 1), dim3(1024), 0, ctx->stream, (const unsigned int*)ctx->d_digit_total,
                            ctx->d_k2h_off, 64u * (unsigned int)hr, P.intra.n, P.inter.n, ctx->d_cf_tab);
         hipLaunchKernelGGL(k2h_scatter, dim3(K2H_BLOCKS), dim3(K2H_THREADS), 0, ctx->stream, hs,
@@ -1256,9 +1213,7 @@ int fhx_pvalues(fhx_ctx* ctx) {
         else                      \
             FHX_HEAVY_N(R, W, false); \
     } while (0)
-        if (hr == 1) FHX_HEAVY(1, 8);
-        else if (hr == 2) FHX_HEAVY(2, 8);
-        else if (heavy_wpe == 3) FHX_HEAVY(4, 3);
+        if (hr == 2) FHX_HEAVY(2, 8);
         else FHX_HEAVY(4, 4);
 #undef FHX_HEAVY
 #undef FHX_HEAVY_N
@@ -1268,22 +1223,14 @@ int fhx_pvalues(fhx_ctx* ctx) {
                            (const unsigned int*)ctx->d_k2h_off, (const unsigned int*)ctx->d_digit_total, (const QEntry*)hq,
                            (const unsigned long long*)n_redo);
     }
-    static const int cf_wpe = std::getenv("FHX_CF_WAVES") ? std::atoi(std::getenv("FHX_CF_WAVES")) : 0;              // measurements
-    static const int cf_quarters = std::getenv("FHX_CF_QUARTERS") ? std::atoi(std::getenv("FHX_CF_QUARTERS")) : 0;   // 1..4: measurements
 #define FHX_LAUNCH_QUEUE_BY_COUNT(CLS)                                                                                                \
     do {                                                                                                                              \
         if (small_n)                                                                                                                  \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue_by_count<CLS, true, 4>), dim3(resident_grid(ctx, k2_queue_by_count<CLS, true, 4>)), \
-                               qblock, 0, ctx->stream, P, Q.q[(CLS) - 1],          \
-                               (unsigned int*)(k2_next + (CLS)), cf_quarters);     \
-        else if (cf_wpe == 4)                                                                                                         \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue_by_count<CLS, false, 4>), dim3(resident_grid(ctx, k2_queue_by_count<CLS, false, 4>)), \
-                               qblock, 0, ctx->stream, P, Q.q[(CLS) - 1],          \
-                               (unsigned int*)(k2_next + (CLS)), cf_quarters);     \
+                               qblock, 0, ctx->stream, P, Q.q[(CLS) - 1], (unsigned int*)(k2_next + (CLS)));                          \
         else                                                                                                                          \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue_by_count<CLS, false, 5>), dim3(resident_grid(ctx, k2_queue_by_count<CLS, false, 5>)), \
-                               qblock, 0, ctx->stream, P, Q.q[(CLS) - 1],          \
-                               (unsigned int*)(k2_next + (CLS)), cf_quarters);     \
+                               qblock, 0, ctx->stream, P, Q.q[(CLS) - 1], (unsigned int*)(k2_next + (CLS)));                          \
     } while (0)
     FHX_LAUNCH_QUEUE_BY_COUNT(dev::BC_CF_BD);
     FHX_LAUNCH_QUEUE_BY_COUNT(dev::BC_CF_BCF);

@@ -847,8 +847,8 @@ int sort_blocks_for(int64_t n_hint) {
     return (int)std::max<int64_t>(64, std::min<int64_t>(SORT_BLOCKS, (want + 63) / 64 * 64));
 }
 
-// LSD radix passes over the low `key_bits` bits of the keys, `bits` bits per pass (8..11), starting in buffer pair `src`;
-// *result_buf = the pair that holds the sorted keys and payloads
+// LSD radix passes over the low `key_bits` bits of the keys, `bits` bits per pass (SORT_BITS_LARGE or RADIX_BITS), starting in
+// buffer pair `src`; *result_buf = the pair that holds the sorted keys and payloads
 static int radix_passes(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int* vals[2], const unsigned long long* counter, int nblk,
                         int key_bits, int bits, int src, int* result_buf) {
     const int passes = (key_bits + bits - 1) / bits;
@@ -865,10 +865,8 @@ static int radix_passes(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int*
                            keys[1 - src], vals[1 - src], counter, shift, (const unsigned int*)ctx->d_block_hist,                      \
                            (const unsigned int*)ctx->d_digit_total);                                                                 \
     } while (0)
-        if (bits == 8) FHX_RS_PASS(8);
-        else if (bits == 9) FHX_RS_PASS(9);
-        else if (bits == 10) FHX_RS_PASS(10);
-        else FHX_RS_PASS(11);
+        if (bits == SORT_BITS_LARGE) FHX_RS_PASS(SORT_BITS_LARGE);
+        else FHX_RS_PASS(RADIX_BITS);
 #undef FHX_RS_PASS
         src = 1 - src;
     }
@@ -921,23 +919,11 @@ static int os_run_passes(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int
 #undef FHX_OS_HIST
     }
     int src = *src_io;
-    const char* we = std::getenv("FHX_OS_WPE");            // waves per SIMD the scatter is compiled for (measurements): 4 or 6
-    const int wpe = we ? std::atoi(we) : 4;
-    const char* le = std::getenv("FHX_OS_LB");             // descriptors per look-back step: 8 (default), 16, 32
-    const int lb = le ? std::atoi(le) : 8;
-    const bool persist = std::getenv("FHX_OS_PERSIST") != nullptr;      // resident workgroups taking tiles in a loop (measured slower)
     for (int p = 0; p < plan.passes; ++p) {
-#define FHX_OS_SCATTER(W, P, L)                                                                                                       \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(os_scatter<W, P, L>), dim3(P ? std::min(tiles, 256 * (W / 2)) : tiles), dim3(OS_THREADS), 0, ctx->stream, (const unsigned long long*)keys[src], \
-                       (const unsigned int*)vals[src], keys[1 - src], vals[1 - src], counter, plan.lo + p * OS_BITS,                \
-                       (const unsigned int*)(ctrl + OSC_HIST + p * OS_RADIX), ctrl + OSC_DESC + (size_t)p * tiles * OS_RADIX,        \
-                       ctrl + OSC_TICKET + p, ctrl + OSC_COPY_PASSES)
-        if (wpe == 6) FHX_OS_SCATTER(6, false, 8);
-        else if (persist) FHX_OS_SCATTER(4, true, 8);
-        else if (lb == 8) FHX_OS_SCATTER(4, false, 8);
-        else if (lb == 32) FHX_OS_SCATTER(4, false, 32);
-        else FHX_OS_SCATTER(4, false, 16);
-#undef FHX_OS_SCATTER
+        hipLaunchKernelGGL(os_scatter, dim3(tiles), dim3(OS_THREADS), 0, ctx->stream, (const unsigned long long*)keys[src],
+                           (const unsigned int*)vals[src], keys[1 - src], vals[1 - src], counter, plan.lo + p * OS_BITS,
+                           (const unsigned int*)(ctrl + OSC_HIST + p * OS_RADIX), ctrl + OSC_DESC + (size_t)p * tiles * OS_RADIX,
+                           ctrl + OSC_TICKET + p, ctrl + OSC_COPY_PASSES);
         src = 1 - src;
     }
     FHX_HIP(hipGetLastError());
@@ -1199,20 +1185,18 @@ static int compact_pvalues(fhx_ctx* ctx, const double* d_p, int64_t n, unsigned 
     ctx->k3_counter_zeroed = false;                   // (auto_cutoff had k3_cutoff zero it)
     // one workgroup per tile, not a resident grid walking the column: 0.507 -> 0.451 ms on C3 (profiles/history/r03_x_k3_grid.txt); the
     // plain copy kernel of profiles/hbm_rate.hip shows the same (4.9 TB/s with 2048 grid-striding workgroups, 5.6 with one per
-    // chunk).  FHX_K3_GRID caps the grid for measurements.
-    static const int k3_cap = std::getenv("FHX_K3_GRID") ? std::atoi(std::getenv("FHX_K3_GRID")) : (1 << 30);
+    // chunk).  The grids of k3_compact and k3_fill_q are therefore not capped.
     if (dq)
-        hipLaunchKernelGGL(k3_compact<true>, dim3(grid_for(n, CP_TILE, k3_cap)), dim3(CP_THREADS), 0, ctx->stream, d_p, n,
+        hipLaunchKernelGGL(k3_compact<true>, dim3(grid_for(n, CP_TILE, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, d_p, n,
                            keys[0], vals[0], d_q, counter, d_cutoff, *dq, false, 1);
     if (!dq || dq->flag) {                           // (with a flag the device picks one of the two; the other returns at once)
         DenseQ off;
         if (dq) off.flag = dq->flag;
         const bool ones = ctx->q_prefilled && d_q == ctx->d_q && d_p == ctx->d_p;
         // tiles per workgroup: as many as leave every CU its two workgroups several times over (a shard keeps one tile per workgroup)
-        static const int per_env = std::getenv("FHX_K3_TILES_PER_WG") ? std::atoi(std::getenv("FHX_K3_TILES_PER_WG")) : 0;
         const int64_t n_tiles = (n + CP_TILE - 1) / CP_TILE;
-        const int per = per_env > 0 ? per_env : (int)std::max<int64_t>(1, std::min<int64_t>(4, n_tiles / 2048));
-        hipLaunchKernelGGL(k3_compact<false>, dim3(grid_for((n_tiles + per - 1) / per, 1, k3_cap)), dim3(CP_THREADS), 0, ctx->stream, d_p, n,
+        const int per = (int)std::max<int64_t>(1, std::min<int64_t>(4, n_tiles / 2048));
+        hipLaunchKernelGGL(k3_compact<false>, dim3(grid_for((n_tiles + per - 1) / per, 1, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, d_p, n,
                            keys[0], vals[0], d_q, counter, d_cutoff, off, ones, per);
     }
     if (d_q == ctx->d_q) ctx->q_prefilled = false;      // from here on the column holds this pass's q
@@ -1271,10 +1255,7 @@ static int sort_kept(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int* va
         bool moved = false;
         return onesweep_finish(ctx, pend, &moved);
     }
-    // FHX_RS_BITS: digit width of these passes (measurements)
-    const char* be = std::getenv("FHX_RS_BITS");
-    const int bits = (be && std::atoi(be) >= 8 && std::atoi(be) <= 11) ? std::atoi(be) : SORT_BITS_LARGE;
-    return radix_passes(ctx, keys, vals, counter, sort_blocks_for(n_kept), key_hi, bits, 0, sorted_buf);
+    return radix_passes(ctx, keys, vals, counter, sort_blocks_for(n_kept), key_hi, SORT_BITS_LARGE, 0, sorted_buf);
 }
 
 static int sort_pvalues(fhx_ctx* ctx, const double* d_p, int64_t n, unsigned long long* keys[2], unsigned int* vals[2],
@@ -1332,8 +1313,7 @@ static int bh_from_sorted(fhx_ctx* ctx, const unsigned long long* keys, const un
                        n_total_tests, 0.0, tile_max, (const double*)nullptr, d_q, dq ? dq->dense : (double*)nullptr,
                        dq ? dq->flag : (const unsigned long long*)nullptr);
     if (dq) {
-        static const int fill_cap = std::getenv("FHX_K3_GRID") ? std::atoi(std::getenv("FHX_K3_GRID")) : (1 << 30);
-        hipLaunchKernelGGL(k3_fill_q, dim3(grid_for(n_rows, CP_TILE, fill_cap)), dim3(CP_THREADS), 0, ctx->stream, p_rows, n_rows, *dq,
+        hipLaunchKernelGGL(k3_fill_q, dim3(grid_for(n_rows, CP_TILE, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, p_rows, n_rows, *dq,
                            d_q);
     }
     FHX_HIP(hipGetLastError());
@@ -1495,17 +1475,15 @@ int fhx_bh(fhx_ctx* ctx, double n_total_tests) {
     // q of the survivors through a dense array + one fill of the q column (k3_compact<true>) when at least K3_DENSE_PERCENT of the
     // rows survive the cutoff - the device decides, from the count k3_cutoff takes off the histogram, while the host goes on
     // enqueueing: below that the two extra passes over the rows cost more than the scattered stores into the q column
-    // (profiles/r06_k3_dense_q.txt).  FHX_K3_DENSE: 1 = always, 0 = never, otherwise the percentage (measurements, tests).
-    static const int dense_env = std::getenv("FHX_K3_DENSE") ? std::atoi(std::getenv("FHX_K3_DENSE")) : K3_DENSE_PERCENT;
+    // (profiles/r06_k3_dense_q.txt).
     DenseQ dq;
     // (a row set whose last pass left under a tenth of its rows below the cutoff will not leave 35 % now: the dense variant's two
     // launches - which would return at once - are not even enqueued then; the decision itself stays the device's whenever they are)
-    const bool far_below = dense_env != 1 && ctx->k3_last_rows == ctx->n_rows && ctx->k3_last_kept >= 0 &&
-                           ctx->k3_last_kept * 10 < ctx->n_rows;
-    const bool dense = dense_env != 0 && !far_below && engine_dense_q(ctx, &dq);
+    const bool far_below = ctx->k3_last_rows == ctx->n_rows && ctx->k3_last_kept >= 0 && ctx->k3_last_kept * 10 < ctx->n_rows;
+    const bool dense = !far_below && engine_dense_q(ctx, &dq);
     unsigned long long dense_min = ~0ull;
     if (dense) {
-        dense_min = dense_env == 1 ? 0ull : (unsigned long long)(((long double)ctx->n_rows * dense_env + 99) / 100);
+        dense_min = (unsigned long long)(((long double)ctx->n_rows * K3_DENSE_PERCENT + 99) / 100);
         dq.flag = ctx->d_misc + MISC_K3_DENSE;
     }
     int rc = auto_cutoff(ctx, ctx->d_p, ctx->n_rows, n_total_tests, ctx->d_misc + 6, dense_min, ctx->d_misc, ctx->ev[4]);

@@ -103,11 +103,11 @@ __device__ __forceinline__ void os_desc_store(unsigned int* p, unsigned int v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// PERSIST = false (what runs): one workgroup per tile.  PERSIST = true (FHX_OS_PERSIST, measured slower and kept for that
-// measurement): resident workgroups take tiles by ticket until none is left, holding the next ticket and the next tile's keys
-// while the current tile looks back - a ticket reserved a tile-time ahead makes every later tile wait for it.
-template <int WPE, bool PERSIST, int LB>       // LB: descriptors read per look-back step
-__global__ __launch_bounds__(OS_THREADS) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void os_scatter(
+// One workgroup per tile.  (Resident workgroups taking tiles by ticket until none is left, holding the next ticket and the next
+// tile's keys while the current tile looks back, were measured slower: a ticket reserved a tile-time ahead makes every later tile
+// wait for it.)
+constexpr int OS_LOOKBACK = 8;                 // descriptors read per look-back step
+__global__ __launch_bounds__(OS_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void os_scatter(
     const unsigned long long* __restrict__ keys_in, const unsigned int* __restrict__ vals_in, unsigned long long* __restrict__ keys_out,
     unsigned int* __restrict__ vals_out, const unsigned long long* __restrict__ n_ptr, int shift, const unsigned int* __restrict__ hist,
     unsigned int* __restrict__ desc, unsigned int* __restrict__ ticket, unsigned int* __restrict__ copy_passes) {
@@ -173,136 +173,120 @@ __global__ __launch_bounds__(OS_THREADS) __attribute__((amdgpu_waves_per_eu(WPE,
         __syncthreads();
         scan_radix(digit_start);
     }
+    const int64_t beg = tile_id * TILE;
+    const int64_t end = min(n, beg + (int64_t)TILE);
+    const int64_t wave_base = beg + (int64_t)wave * (64 * OS_ITEMS);
     unsigned long long key[OS_ITEMS];
     unsigned int val[OS_ITEMS];
-    auto load_tile = [&](int64_t t) {
-        const int64_t wb = t * TILE + (int64_t)wave * (64 * OS_ITEMS);
 #pragma unroll
-        for (int r = 0; r < OS_ITEMS; ++r) {
-            const int64_t i = wb + r * 64 + lane;
-            const bool live = i < n;
-            key[r] = live ? keys_in[i] : ~0ull;
-            val[r] = live ? vals_in[i] : 0u;
+    for (int r = 0; r < OS_ITEMS; ++r) {
+        const int64_t i = wave_base + r * 64 + lane;
+        const bool live = i < n;
+        key[r] = live ? keys_in[i] : ~0ull;
+        val[r] = live ? vals_in[i] : 0u;
+    }
+    for (int i = threadIdx.x; i < OS_WAVES * RADIX / 2; i += OS_THREADS) reinterpret_cast<unsigned int*>(stage_raw)[i] = 0u;
+    unsigned int slot[OS_ITEMS];
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < OS_ITEMS; ++r) {
+        const bool live = (wave_base + r * 64 + lane) < end;
+        const unsigned int digit = (unsigned int)(os_spread(key[r]) >> shift) & (RADIX - 1);
+        unsigned long long same = ~0ull;                   // lanes holding the same digit (dead lanes: a group of their own)
+        const unsigned int tag = digit | (live ? 0u : RADIX);
+#pragma unroll
+        for (int b = 0; b <= RADIX_BITS; ++b) {
+            const unsigned long long m = __ballot((tag >> b) & 1u);
+            same &= ((tag >> b) & 1u) ? m : ~m;
         }
-    };
-    load_tile(tile_id);
-    int slot_i = 0;
-    while (true) {
-        const int64_t beg = tile_id * TILE;
-        const int64_t end = min(n, beg + (int64_t)TILE);
-        const int64_t wave_base = beg + (int64_t)wave * (64 * OS_ITEMS);
-        if (PERSIST && threadIdx.x == 0) s_tile[slot_i ^ 1] = atomicAdd(ticket, 1u);      // the next tile's ticket: needed only after the staging below
-        for (int i = threadIdx.x; i < OS_WAVES * RADIX / 2; i += OS_THREADS) reinterpret_cast<unsigned int*>(stage_raw)[i] = 0u;
-        unsigned int slot[OS_ITEMS];
-        __syncthreads();
+        const unsigned int before = __popcll(same & lane_lt);
+        unsigned int old = 0;
+        if (live) old = wave_digit[wave][digit];
+        slot[r] = old + before;
+        __builtin_amdgcn_wave_barrier();
+        if (live && before == 0) wave_digit[wave][digit] = (unsigned short)(old + __popcll(same));
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    unsigned int my_count = 0;
+    unsigned int lbv[OS_LOOKBACK];
+    if ((int)threadIdx.x < RADIX) {                        // per digit: exclusive offsets over the waves, the tile's total
+        const int d = threadIdx.x;
+        unsigned int acc = 0;
 #pragma unroll
-        for (int r = 0; r < OS_ITEMS; ++r) {
-            const bool live = (wave_base + r * 64 + lane) < end;
-            const unsigned int digit = (unsigned int)(os_spread(key[r]) >> shift) & (RADIX - 1);
-            unsigned long long same = ~0ull;                   // lanes holding the same digit (dead lanes: a group of their own)
-            const unsigned int tag = digit | (live ? 0u : RADIX);
-#pragma unroll
-            for (int b = 0; b <= RADIX_BITS; ++b) {
-                const unsigned long long m = __ballot((tag >> b) & 1u);
-                same &= ((tag >> b) & 1u) ? m : ~m;
-            }
-            const unsigned int before = __popcll(same & lane_lt);
-            unsigned int old = 0;
-            if (live) old = wave_digit[wave][digit];
-            slot[r] = old + before;
-            __builtin_amdgcn_wave_barrier();
-            if (live && before == 0) wave_digit[wave][digit] = (unsigned short)(old + __popcll(same));
-            __builtin_amdgcn_wave_barrier();
+        for (int w = 0; w < OS_WAVES; ++w) {
+            const unsigned int c = wave_digit[w][d];
+            wave_digit[w][d] = (unsigned short)acc;
+            acc += c;
         }
-        __syncthreads();
-        unsigned int my_count = 0;
-        unsigned int lbv[LB];
-        if ((int)threadIdx.x < RADIX) {                        // per digit: exclusive offsets over the waves, the tile's total
-            const int d = threadIdx.x;
-            unsigned int acc = 0;
+        tile_start[d] = acc;
+        my_count = acc;
+        // the tile's count goes out at once: the tiles behind this one look back at it while this one is still busy
+        os_desc_store(desc + (size_t)tile_id * RADIX + d, tile_id == 0 ? (OS_PREFIX | (digit_start[d] + acc)) : (OS_AGG | acc));
+        // ... and the first eight descriptors behind this tile are asked for now; they are looked at after the staging
 #pragma unroll
-            for (int w = 0; w < OS_WAVES; ++w) {
-                const unsigned int c = wave_digit[w][d];
-                wave_digit[w][d] = (unsigned short)acc;
-                acc += c;
-            }
-            tile_start[d] = acc;
-            my_count = acc;
-            // the tile's count goes out at once: the tiles behind this one look back at it while this one is still busy
-            os_desc_store(desc + (size_t)tile_id * RADIX + d, tile_id == 0 ? (OS_PREFIX | (digit_start[d] + acc)) : (OS_AGG | acc));
-            // ... and the first eight descriptors behind this tile are asked for now; they are looked at after the staging
+        for (int u = 0; u < OS_LOOKBACK; ++u)
+            lbv[u] = (tile_id - 1 - u >= 0) ? os_desc_load(desc + (size_t)(tile_id - 1 - u) * RADIX + d) : OS_PREFIX;
+    }
+    __syncthreads();
+    scan_radix(tile_start);
+    const int live_in_tile = (int)(end - beg);
 #pragma unroll
-            for (int u = 0; u < LB; ++u)
-                lbv[u] = (tile_id - 1 - u >= 0) ? os_desc_load(desc + (size_t)(tile_id - 1 - u) * RADIX + d) : OS_PREFIX;
+    for (int r = 0; r < OS_ITEMS; ++r) {
+        const unsigned int digit = (unsigned int)(os_spread(key[r]) >> shift) & (RADIX - 1);
+        if (wave_base + r * 64 + lane < end) slot[r] += tile_start[digit] + wave_digit[wave][digit];
+    }
+    __syncthreads();                                       // the counters are dead: their block now stages the keys
+#pragma unroll
+    for (int r = 0; r < OS_ITEMS; ++r)
+        if (wave_base + r * 64 + lane < end) {
+            s_keys[slot[r]] = key[r];
+            s_vals[slot[r]] = val[r];
         }
-        __syncthreads();
-        scan_radix(tile_start);
-        const int live_in_tile = (int)(end - beg);
+    if ((int)threadIdx.x < RADIX) {                        // decoupled look-back, one digit per thread
+        const int d = threadIdx.x;
+        unsigned int excl = 0;
+        if (tile_id == 0) excl = digit_start[d];
+        else {
+            // Eight predecessors are read per step (independent loads in flight together) and taken in order up to the first
+            // that holds a prefix; one that has not published yet is polled.  At the start of a launch some five hundred tiles
+            // begin together and the nearest prefix is hundreds of tiles back.
+            int64_t j = tile_id - 1;
+            bool done = false, have = true;                // the first step's loads were issued before the staging
+            while (!done) {
+                if (!have) {
 #pragma unroll
-        for (int r = 0; r < OS_ITEMS; ++r) {
-            const unsigned int digit = (unsigned int)(os_spread(key[r]) >> shift) & (RADIX - 1);
-            if (wave_base + r * 64 + lane < end) slot[r] += tile_start[digit] + wave_digit[wave][digit];
-        }
-        __syncthreads();                                       // the counters are dead: their block now stages the keys
-#pragma unroll
-        for (int r = 0; r < OS_ITEMS; ++r)
-            if (wave_base + r * 64 + lane < end) {
-                s_keys[slot[r]] = key[r];
-                s_vals[slot[r]] = val[r];
-            }
-        const int64_t next_tile = PERSIST ? (int64_t)s_tile[slot_i ^ 1] : tiles;
-        if ((int)threadIdx.x < RADIX) {                        // decoupled look-back, one digit per thread
-            const int d = threadIdx.x;
-            unsigned int excl = 0;
-            if (tile_id == 0) excl = digit_start[d];
-            else {
-                // Eight predecessors are read per step (independent loads in flight together) and taken in order up to the first
-                // that holds a prefix; one that has not published yet is polled.  At the start of a launch some five hundred tiles
-                // begin together and the nearest prefix is hundreds of tiles back.
-                int64_t j = tile_id - 1;
-                bool done = false, have = true;                // the first step's loads were issued before the staging
-                while (!done) {
-                    if (!have) {
-#pragma unroll
-                        for (int u = 0; u < LB; ++u) lbv[u] = (j - u >= 0) ? os_desc_load(desc + (size_t)(j - u) * RADIX + d) : OS_PREFIX;
-                    }
-                    have = false;
-#pragma unroll
-                    for (int u = 0; u < LB; ++u) {
-                        if (done) break;
-                        unsigned int w = lbv[u];
-                        while ((w >> 30) == 0u) {
-                            __builtin_amdgcn_s_sleep(1);
-                            w = os_desc_load(desc + (size_t)(j - u) * RADIX + d);
-                        }
-                        excl += w & OS_VALUE;
-                        done = (w >> 30) == 2u;
-                    }
-                    j -= LB;
+                    for (int u = 0; u < OS_LOOKBACK; ++u) lbv[u] = (j - u >= 0) ? os_desc_load(desc + (size_t)(j - u) * RADIX + d) : OS_PREFIX;
                 }
-                os_desc_store(desc + (size_t)tile_id * RADIX + d, OS_PREFIX | (excl + my_count));
-            }
-            global_base[d] = excl;
-        }
-        // the registers are free and the look-back is through (its loads must not queue behind these): the next tile's keys start
-        // their way in while this tile is written out (its ticket was asked for a whole ranking ago)
-        if (next_tile < tiles) load_tile(next_tile);
-        __syncthreads();
+                have = false;
 #pragma unroll
-        for (int j = 0; j < OS_ITEMS; ++j) {
-            const int s = threadIdx.x + j * OS_THREADS;
-            if (s < live_in_tile) {
-                const unsigned long long k = s_keys[s];
-                const unsigned int digit = (unsigned int)(os_spread(k) >> shift) & (RADIX - 1);
-                const unsigned int dst = global_base[digit] + (s - tile_start[digit]);
-                keys_out[dst] = k;
-                vals_out[dst] = s_vals[s];
+                for (int u = 0; u < OS_LOOKBACK; ++u) {
+                    if (done) break;
+                    unsigned int w = lbv[u];
+                    while ((w >> 30) == 0u) {
+                        __builtin_amdgcn_s_sleep(1);
+                        w = os_desc_load(desc + (size_t)(j - u) * RADIX + d);
+                    }
+                    excl += w & OS_VALUE;
+                    done = (w >> 30) == 2u;
+                }
+                j -= OS_LOOKBACK;
             }
+            os_desc_store(desc + (size_t)tile_id * RADIX + d, OS_PREFIX | (excl + my_count));
         }
-        if (next_tile >= tiles) return;
-        __syncthreads();                                       // LDS is read out: the next tile may zero its counters
-        tile_id = next_tile;
-        slot_i ^= 1;
+        global_base[d] = excl;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < OS_ITEMS; ++j) {
+        const int s = threadIdx.x + j * OS_THREADS;
+        if (s < live_in_tile) {
+            const unsigned long long k = s_keys[s];
+            const unsigned int digit = (unsigned int)(os_spread(k) >> shift) & (RADIX - 1);
+            const unsigned int dst = global_base[digit] + (s - tile_start[digit]);
+            keys_out[dst] = k;
+            vals_out[dst] = s_vals[s];
+        }
     }
 }
 
