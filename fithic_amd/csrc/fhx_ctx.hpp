@@ -23,6 +23,7 @@
 #include <condition_variable>
 #include <algorithm>
 #include <climits>
+#include <cstddef>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -165,12 +166,54 @@ constexpr int K2H_BUCKETS = 2048;                       // == RADIX: the radix s
 constexpr int K2H_BLOCKS = 1024;                        // == SORT_BLOCKS
 __device__ __forceinline__ int k2h_bucket(int signed_count);
 
-// words of fhx_ctx::d_misc that K2's class kernels use, zeroed together before they are launched
-constexpr int MISC_K2_REDO = 64;                         // rows k2h_heavy handed back
-constexpr int MISC_K2_NEXT = 65;                         // + 0: k2h_heavy's next task; + class (1..K2_QUEUES): that kernel's next piece
-constexpr int MISC_K2_WORDS = 8;
-constexpr int MISC_K3_DENSE = 80;                        // k3_cutoff's decision: this pass takes q through the dense array (fhx_k3.hip: DenseQ)
-constexpr int K3_DENSE_PERCENT = 35;                     // ... when at least this share of the rows survives the BH cutoff
+constexpr int K3_DENSE_PERCENT = 35;                     // share of the rows that must survive the BH cutoff for q to go through the dense array
+constexpr int K2_COUNTER_WORDS = 8;                      // k2_redo + k2_next below: the words k2_closed zeroes for the class kernels
+constexpr int FDR_BUCKETS = 51;                          // plot_qvalues' buckets: floor(q / 0.001) = 0 .. 50 (k_fdr_hist, fhx_k3.hip)
+
+// Every small device value of a pass: counters, cutoff keys, flags (fhx_ctx::d_words; allocated in fhx_create, freed in fhx_destroy,
+// never initialised - each word is written before it is read, as its line says).  Kernels take pointers to single words, not this
+// struct.  The words that several workgroups add to (k2_*, k3_dense) keep a cache line of their own.
+struct DeviceWords {
+    // ---- K3, the engine's own pass: the first two cross call boundaries
+    // survivors of the BH sort.  zeroed: k3_cutoff (fhx_bh) or compact_pvalues; written: k3_compact; read: the sort and the scan of
+    // that call, later fhx_n_sorted, fhx_bh_scatter and fhx_bh_distributed (its d_n)
+    unsigned long long bh_kept;
+    // the BH cutoff key.  k2_closed sets "keep every p" in every fhx_pvalues; written: k3_cutoff, fhx_bh_set_cutoff(_device);
+    // read: k3_compact (fhx_bh, fhx_bh_local_sort)
+    unsigned long long bh_cutoff;
+    // survivors by the key histogram.  written: k3_cutoff (auto_cutoff), which also stores the number into h_flags - the copy the
+    // host reads; nothing reads this one.  It stays because k3_cutoff takes the pointer: dropping it would change the kernel
+    unsigned long long bh_below;
+    // ---- fhx_bh_array sorts a caller's p-values and must leave bh_kept / bh_cutoff as the last pass left them
+    unsigned long long array_kept;     // its bh_kept: zeroed by k3_cutoff, dead at return
+    unsigned long long array_cutoff;   // its bh_cutoff: written by k3_cutoff, dead at return
+    // ---- K1 and the sorts of host-sized arrays: each is written and read inside one call
+    // key count of a radix sort whose size the host knows.  SHARED by ingest_device_rows_nonfixed and fhx_sort_u64: each copies n
+    // in, radix_passes reads it
+    unsigned long long sort_n;
+    unsigned long long run_total;      // run_ids: number of runs.  written: seg_scan_tiles; read: the host, in run_ids
+    // pass_stats_nonfixed: in-range rows.  zeroed there; written: nf_k1_classify; read: radix_sort_pairs and the host
+    unsigned long long nf_keys;
+    // ---- K2's bookkeeping around the class kernels
+    // fhx_next_pass: outliers of the pass.  zeroed there; written: k_fold_outliers / nf_fold_outliers; read: the host
+    unsigned long long outliers_added;
+    unsigned long long first_dup;      // fhx_next_pass: first row that is an outlier twice.  set to ~0 there; otherwise as outliers_added
+    // no-bias table path: rows the table does not cover.  zeroed in finish_k2; written: k2_memo_gather; read: the host
+    unsigned long long memo_overflow;
+    // ---- K2's class kernels: one contiguous run of K2_COUNTER_WORDS words, zeroed by k2_closed in every fhx_pvalues
+    alignas(128) unsigned long long k2_redo;             // rows k2h_heavy handed back.  read: k2h_generic, fhx_k2_heavy_launch (FHX_DEBUG_HEAVY)
+    // [0]: k2h_heavy's next task; [class] (1..K2_QUEUES): the next piece of k2_queue_by_count<class>; the rest is spare
+    unsigned long long k2_next[K2_COUNTER_WORDS - 1];
+    // k3_cutoff's decision: this pass takes q through the dense array (fhx_k3.hip: DenseQ).  written and read inside fhx_bh
+    alignas(128) unsigned long long k3_dense;
+    // fhx_get_array(FHX_A_FDR_COUNTS): zeroed there, filled by launch_fdr_hist, copied to the host, all in that call
+    alignas(128) unsigned long long fdr_buckets[FDR_BUCKETS];
+};
+static_assert(offsetof(DeviceWords, k2_next) == offsetof(DeviceWords, k2_redo) + sizeof(unsigned long long) &&
+                  sizeof(DeviceWords::k2_next) == (K2_COUNTER_WORDS - 1) * sizeof(unsigned long long),
+              "k2_closed zeroes K2_COUNTER_WORDS words starting at k2_redo");
+static_assert(K2_COUNTER_WORDS >= 2 + K2_QUEUES, "k2_next holds k2h_heavy's word and one per class queue");
+static_assert(sizeof(DeviceWords::fdr_buckets) == FDR_BUCKETS * sizeof(unsigned long long), "one word per FDR bucket");
 
 constexpr int K2_CL_ITEMS = 4;
 constexpr int K2_CL_TILE = K2_THREADS * K2_CL_ITEMS;     // 1024 rows per workgroup step: four waves of 256 consecutive rows
@@ -340,7 +383,8 @@ struct fhx_ctx {
     int pass_no = 0;                  // passes completed so far
     uint8_t *d_skip = nullptr, *d_outlier = nullptr, *d_seen_twice = nullptr;
     bool skip_active = false;
-    unsigned long long *d_hist_cc = nullptr, *d_hist_np = nullptr, *d_out_hist = nullptr, *d_misc = nullptr;
+    unsigned long long *d_hist_cc = nullptr, *d_hist_np = nullptr, *d_out_hist = nullptr;
+    DeviceWords* d_words = nullptr;   // the small device values of a pass, by name
     K1Sums* d_sums = nullptr;
     fhx_stats stats{};
     bool have_stats = false;

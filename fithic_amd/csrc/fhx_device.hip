@@ -32,9 +32,13 @@ int fhx_create(int device, fhx_ctx** out) {
         }
         for (auto& e : ctx->ev)
             if (hipEventCreate(&e) != hipSuccess) {
-                delete ctx;
+                fhx_destroy(ctx);                // (the stream and the events made so far go with it)
                 return FHX_ERR_HIP;
             }
+        if (hipMalloc(&ctx->d_words, sizeof(DeviceWords)) != hipSuccess) {
+            fhx_destroy(ctx);
+            return FHX_ERR_HIP;
+        }
     }
     *out = ctx;
     return FHX_OK;
@@ -68,7 +72,7 @@ void fhx_destroy(fhx_ctx* ctx) {
         dev_free(ctx->d_hist_cc);
         dev_free(ctx->d_hist_np);
         dev_free(ctx->d_out_hist);
-        dev_free(ctx->d_misc);
+        dev_free(ctx->d_words);
         dev_free(ctx->d_sums);
         dev_free(ctx->d_fit_tables);            // d_lut, d_lbeta_*, d_invb_*, d_table_x / y point into it
         if (ctx->h_fit_stage) (void)hipHostFree(ctx->h_fit_stage);
@@ -561,14 +565,14 @@ int fhx_get_array(fhx_ctx* ctx, int which, void* dst, int64_t cap, int64_t* n_ou
         if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
         if (!ctx->have_q) return fail(ctx, FHX_ERR_ARG, "no q-values yet");
         FHX_HIP(hipSetDevice(ctx->device));
-        unsigned long long* buckets = ctx->d_misc + 8;
-        FHX_HIP(hipMemsetAsync(buckets, 0, 51 * sizeof(unsigned long long), ctx->stream));
+        unsigned long long* buckets = ctx->d_words->fdr_buckets;
+        FHX_HIP(hipMemsetAsync(buckets, 0, sizeof(ctx->d_words->fdr_buckets), ctx->stream));
         launch_fdr_hist(ctx, ctx->d_q, ctx->n_rows, buckets);
-        std::vector<int64_t> c(51, 0);
-        FHX_HIP(hipMemcpyAsync(c.data(), buckets, 51 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        std::vector<int64_t> c(FDR_BUCKETS, 0);
+        FHX_HIP(hipMemcpyAsync(c.data(), buckets, sizeof(ctx->d_words->fdr_buckets), hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipStreamSynchronize(ctx->stream));
-        for (int i = 1; i < 51; ++i) c[i] += c[i - 1];       // cumulative ...
-        for (int i = 50; i >= 1; --i) c[i] = c[i - 1];       // ... shifted by one (fithic.py:1249-1254)
+        for (int i = 1; i < FDR_BUCKETS; ++i) c[i] += c[i - 1];       // cumulative ...
+        for (int i = FDR_BUCKETS - 1; i >= 1; --i) c[i] = c[i - 1];       // ... shifted by one (fithic.py:1249-1254)
         c[0] = 0;
         return put(c.data(), c.size(), sizeof(int64_t));
     }
@@ -615,7 +619,7 @@ int64_t fhx_n_sorted(fhx_ctx* ctx) {
     if (ctx->n_sorted == -2) {
         unsigned long long n = 0;
         if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-        if (hipMemcpyAsync(&n, ctx->d_misc, sizeof(n), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return -1;
+        if (hipMemcpyAsync(&n, &ctx->d_words->bh_kept, sizeof(n), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return -1;
         if (hipStreamSynchronize(ctx->stream) != hipSuccess) return -1;
         ctx->n_sorted = (int64_t)n;
     }

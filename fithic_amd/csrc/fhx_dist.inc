@@ -827,10 +827,10 @@ int fhx_bh_distributed(fhx_ctx* ctx, double n_tests) {
     if (rc != FHX_OK) return rc;
     rc = dist_all_reduce_i64(ctx, fhx::DS_TOP_HIST, ctx->d_top_hist, TOP_BINS, 0);
     if (rc != FHX_OK) return rc;
-    launch_k3_cutoff(ctx, n_tests, ctx->d_misc + 6);
-    rc = fhx_bh_local_sort(ctx);                                   // survivors of this rank, sorted: keys + rows; count in d_misc[0]
+    launch_k3_cutoff(ctx, n_tests, &ctx->d_words->bh_cutoff);
+    rc = fhx_bh_local_sort(ctx);                                   // survivors of this rank, sorted: keys + rows; count in bh_kept
     if (rc != FHX_OK) return rc;
-    const unsigned long long* d_n = ctx->d_misc;
+    const unsigned long long* d_n = &ctx->d_words->bh_kept;
     const unsigned long long* keys = ctx->d_keys[ctx->sorted_buf];
     // regular samples per rank: 128 cut every slice to within 1/128 of its even share, and the one-workgroup sort of all
     // ranks' samples is 8x shorter than with 1024 (it was 0.1 ms of every pass)

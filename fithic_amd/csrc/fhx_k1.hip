@@ -584,7 +584,7 @@ int run_ids(fhx_ctx* ctx, const unsigned long long* keys, int64_t n, unsigned in
     *n_runs = 0;
     if (n == 0) return FHX_OK;
     const int tiles = (int)((n + SEG_TILE - 1) / SEG_TILE);
-    unsigned long long* total = ctx->d_misc + 9;
+    unsigned long long* total = &ctx->d_words->run_total;
     hipLaunchKernelGGL(seg_count_heads, dim3(tiles), dim3(SEG_THREADS), 0, ctx->stream, keys, n, tile_scratch);
     hipLaunchKernelGGL(seg_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tile_scratch, (int64_t)tiles, total);
     hipLaunchKernelGGL(seg_ids, dim3(tiles), dim3(SEG_THREADS), 0, ctx->stream, keys, n, (const unsigned int*)tile_scratch, ids);
@@ -626,7 +626,7 @@ int ingest_device_rows_nonfixed(fhx_ctx* ctx, const int32_t* c1, const int32_t* 
     FHX_HIP(tmp.get(&bad, sizeof(int)));
     FHX_HIP(hipMemsetAsync(bad, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(nf_locus_keys, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, c1, m1, c2, m2, n, keys[0], vals[0], bad);
-    unsigned long long* counter = ctx->d_misc + 3;
+    unsigned long long* counter = &ctx->d_words->sort_n;
     const unsigned long long n2u = (unsigned long long)n2;
     FHX_HIP(hipMemcpyAsync(counter, &n2u, sizeof(n2u), hipMemcpyHostToDevice, ctx->stream));
     int buf = 0;
@@ -802,7 +802,6 @@ int alloc_row_arrays(fhx_ctx* ctx, int64_t n, int64_t n_dist) {
     FHX_HIP(hipMalloc(&ctx->d_out_hist, hist_len * sizeof(unsigned long long)));
     FHX_HIP(hipMemsetAsync(ctx->d_out_hist, 0, hist_len * sizeof(unsigned long long), ctx->stream));
     if (!ctx->d_sums) FHX_HIP(hipMalloc(&ctx->d_sums, sizeof(K1Sums)));
-    if (!ctx->d_misc) FHX_HIP(hipMalloc(&ctx->d_misc, 192 * sizeof(unsigned long long)));
     // One workspace, two views that are never live together (K2 and K3 run back to back on one stream):
     //   K2: queue[0] (16 B/row) | queue[1] (16 B/row) | the bucketed 300-iteration queue (16 B/row + bucket padding)
     //   K3: keys[0], keys[1] (8 B/row each)            | vals[0], vals[1] (4 B/row each)
@@ -854,7 +853,7 @@ int alloc_row_arrays(fhx_ctx* ctx, int64_t n, int64_t n_dist) {
 // -r 0: classification + sums as K1, then the in-range (distance, count) pairs are radix-sorted by distance and the runs
 // are reduced to (distinct distance, sum of counts, rows): the reference's mainDic for arbitrary distances
 int fhx::pass_stats_nonfixed(fhx_ctx* ctx, fhx_stats* out) {
-    unsigned long long* counter = ctx->d_misc + 10;
+    unsigned long long* counter = &ctx->d_words->nf_keys;
     FHX_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
     FHX_HIP(hipMemsetAsync(ctx->d_sums, 0, sizeof(K1Sums), ctx->stream));
     before_rerecord(ctx, 0);

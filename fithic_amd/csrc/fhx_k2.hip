@@ -372,8 +372,8 @@ __global__ __launch_bounds__(K2_THREADS) __attribute__((amdgpu_waves_per_eu(WPE,
 __global__ __launch_bounds__(K2_THREADS) void k2_closed(K2Params P, QSpan q, unsigned long long* __restrict__ zero_words,
                                                         unsigned long long* __restrict__ cutoff_word) {
     __shared__ unsigned int hist_lds[K2_HIST_BINS];
-    if (blockIdx.x == 0 && threadIdx.x < MISC_K2_WORDS) zero_words[threadIdx.x] = 0ull;
-    if (blockIdx.x == 0 && threadIdx.x == MISC_K2_WORDS) *cutoff_word = KEY_KEEP_ALL;
+    if (blockIdx.x == 0 && threadIdx.x < K2_COUNTER_WORDS) zero_words[threadIdx.x] = 0ull;
+    if (blockIdx.x == 0 && threadIdx.x == K2_COUNTER_WORDS) *cutoff_word = KEY_KEEP_ALL;
     FusedHist H;
     H.init(hist_lds, P.top_hist);
     for (int sh = blockIdx.x; sh < q.n_shards; sh += gridDim.x) {
@@ -1052,205 +1052,179 @@ static int resident_grid(fhx_ctx* ctx, K kernel) {
     return cache[key] = per_cu * cus;
 }
 
-int fhx_pvalues(fhx_ctx* ctx) {
-    if (!ctx) return FHX_ERR_ARG;
-    if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
-    if (!ctx->have_fit) return fail(ctx, FHX_ERR_ARG, "fhx_fit must run first");
-    FHX_HIP(hipSetDevice(ctx->device));
-    if (ctx->tables_dirty) {               // e.g. the bias table arrived after the fit (the reference's call order)
-        const int r2 = build_slot_tables(ctx);
-        if (r2 != FHX_OK) return r2;
-    }
-    K2Params P = make_k2_params(ctx);
-    before_rerecord(ctx, 1);
-    FHX_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+// ---- fhx_pvalues: what a pass decides on the host (K2Plan), its two layouts, its launches in their two forms, its tail ---------------
+struct K2Plan {
+    int memo_cap = -1, memo_nd = 0;     // the table path (k2_memo_rows): largest count and number of distances tabulated; cap < 0: off
+    bool memo_intra = false, memo_inter = false, small_n = false, legacy_heavy = false;
+    int64_t k2_n = 0, cap_s = 0;        // rows K2 classifies (the context's, or the table's virtual ones); entries per queue shard
+    int heavy_rows = 4, n_shards = 0;   // rows per lane of k2h_heavy (not used under legacy_heavy); queue shards for k2_n rows
+};
+static K2Plan plan_k2(const fhx_ctx* ctx, const K2Params& P) {
+    K2Plan plan;
     // no bias table, fixed-size loci: evaluate a (distance, count) table instead of every row (see k2_memo_rows)
-    int32_t *v_loc1 = nullptr, *v_loc2 = nullptr, *v_count = nullptr;
-    double* v_table = nullptr;
-    unsigned int* over_rows = nullptr;
-    unsigned long long over_cap = 0;
-    int memo_cap = -1, memo_nd = 0;
-    const bool memo_intra = ctx->prm.mode != FHX_MODE_INTER_ONLY, memo_inter = ctx->prm.mode != FHX_MODE_INTRA_ONLY;
+    plan.memo_intra = ctx->prm.mode != FHX_MODE_INTER_ONLY;
+    plan.memo_inter = ctx->prm.mode != FHX_MODE_INTRA_ONLY;
     if (!ctx->have_bias && !ctx->nonfixed && !getenv("FHX_NO_MEMO")) {
-        memo_nd = memo_intra ? (int)(P.hi_idx - P.lo_idx + 1) : 0;
+        plan.memo_nd = plan.memo_intra ? (int)(P.hi_idx - P.lo_idx + 1) : 0;
         const int64_t budget = std::min<int64_t>(1ll << 24, ctx->n_rows / 4);
-        const int64_t per_count = (int64_t)memo_nd + (memo_inter ? 1 : 0);
-        if (per_count > 0 && memo_nd >= 0) {
+        const int64_t per_count = (int64_t)plan.memo_nd + (plan.memo_inter ? 1 : 0);
+        if (per_count > 0 && plan.memo_nd >= 0) {
             const int64_t cap = std::min<int64_t>(ctx->stats.max_count, budget / per_count - 1);
-            if (cap >= 8) memo_cap = (int)cap;
+            if (cap >= 8) plan.memo_cap = (int)cap;
         }
     }
-    // fhx_pass_stats zeroes the two histograms of this call behind K1, while the host fits (k1_prezero); any other caller - and
-    // anything that used the count matrix in between (radix_passes clears the mark) - gets them zeroed here
-    const bool prezeroed = ctx->k2_prezeroed;
-    ctx->k2_prezeroed = false;
-    // K3's key histogram rides on K2's stores of p - except on the table path, whose class kernels store table entries
-    ctx->k2_hist_valid = false;
-    if (memo_cap < 0) {
-        if (!ctx->d_k2_hist) FHX_HIP(hipMalloc(&ctx->d_k2_hist, TOP_BINS * sizeof(unsigned long long)));
-        if (!prezeroed) FHX_HIP(hipMemsetAsync(ctx->d_k2_hist, 0, TOP_BINS * sizeof(unsigned long long), ctx->stream));
-        P.top_hist = ctx->d_k2_hist;
-        ctx->k2_hist_valid = true;
+    plan.k2_n = plan.memo_cap < 0 ? ctx->n_rows : (int64_t)plan.memo_nd * (plan.memo_cap + 1) + (plan.memo_inter ? (plan.memo_cap + 1) : 0);
+    // totals below 171: the kernels that carry Cephes' pow branch (a binomial without a single contact - no inter-chromosomal
+    // rows - classifies every row as trivial and reaches no class kernel: it does not count)
+    plan.small_n = (P.intra.small_n && P.intra.n >= 1.0) || (P.inter.small_n && P.inter.n >= 1.0);
+    plan.legacy_heavy = getenv("FHX_K2_LEGACY") != nullptr;      // A/B and tests: the per-lane kernel of round 1
+    // rows per lane: 4 at 4 waves/SIMD - C3 (2.7e7 rows in the class) 7.43 -> 6.66 ms, a 1/18 shard (1.5e6 rows) 0.87 -> 0.78 ms of
+    // K2 against one row per lane at 8 waves/SIMD; 2 x 8, 2 x 6, 3 x 5 and 4 x 3 are within 3 % of each other
+    // (profiles/history/r03_c_*heavy_variants.txt).  A small input (a shard of a strong-scaling run) has a handful of 256-entry
+    // tasks per wave and ends with most waves idle: two rows per lane at eight waves per SIMD halves the task (a 1/8 shard of
+    // C3: 876 -> 829 us, profiles/history/r04_t_rows.txt).  FHX_K2H_ROWS (2 or 4), read per call, forces one of the two for tests.
+    const char* heavy_rows_env = plan.legacy_heavy ? nullptr : std::getenv("FHX_K2H_ROWS");
+    const int heavy_rows = heavy_rows_env ? std::atoi(heavy_rows_env) : 0;
+    plan.heavy_rows = (heavy_rows == 2 || heavy_rows == 4) ? heavy_rows      // the bucket granule must be the launched kernel's task size
+                      : plan.k2_n < 32000000 ? 2 : 4;
+    plan.cap_s = k2_shard_capacity(plan.k2_n);
+    plan.n_shards = k2_classify_grid(plan.k2_n);
+    return plan;
+}
+
+struct K2Memo {                         // the table path's views into fhx_ctx::d_memo (kept across passes)
+    int32_t *loc1 = nullptr, *loc2 = nullptr, *count = nullptr;   // the table's virtual rows ...
+    double* table = nullptr;                                      // ... and their p
+    unsigned int* over_rows = nullptr;                            // real rows the table does not cover, at most over_cap listed
+    unsigned long long over_cap = 0;
+};
+// grows d_memo, carves it, writes the virtual rows and points K2 at them: P describes the table from here on
+static int k2_table_rows(fhx_ctx* ctx, const K2Plan& plan, K2Memo* M, K2Params* P) {
+    M->over_cap = (unsigned long long)std::max<int64_t>(ctx->n_rows / 16, 1024);
+    const size_t col = ((size_t)plan.k2_n + 3) / 4 * 4;                               // the three columns are read 16 bytes at a time
+    const size_t need = col * (4 + 4 + 4 + 8) + (size_t)M->over_cap * 4 + 64;
+    if (need > ctx->memo_bytes) {
+        dev_free(ctx->d_memo);
+        ctx->memo_bytes = 0;
+        FHX_HIP(hipMalloc(&ctx->d_memo, need));
+        ctx->memo_bytes = need;
     }
-    const K2Params P_rows = P;
-    int64_t k2_n = ctx->n_rows;
-    if (memo_cap >= 0) {
-        k2_n = (int64_t)memo_nd * (memo_cap + 1) + (memo_inter ? (memo_cap + 1) : 0);
-        over_cap = (unsigned long long)std::max<int64_t>(ctx->n_rows / 16, 1024);
-        const size_t col = ((size_t)k2_n + 3) / 4 * 4;                               // the three columns are read 16 bytes at a time
-        const size_t need = col * (4 + 4 + 4 + 8) + (size_t)over_cap * 4 + 64;
-        if (need > ctx->memo_bytes) {
-            dev_free(ctx->d_memo);
-            ctx->memo_bytes = 0;
-            FHX_HIP(hipMalloc(&ctx->d_memo, need));
-            ctx->memo_bytes = need;
-        }
-        v_loc1 = reinterpret_cast<int32_t*>(ctx->d_memo);
-        v_loc2 = v_loc1 + col;
-        v_count = v_loc2 + col;
-        v_table = reinterpret_cast<double*>(v_count + col);
-        over_rows = reinterpret_cast<unsigned int*>(v_table + col);
-        hipLaunchKernelGGL(k2_memo_rows, dim3(grid_for(k2_n, 256)), dim3(256), 0, ctx->stream, memo_nd, P.lo_idx, memo_cap, (int)memo_inter,
-                           v_loc1, v_loc2, v_count, k2_n);
-        P.loc1 = v_loc1;
-        P.loc2 = v_loc2;
-        P.count = v_count;
-        P.p = v_table;
-        P.n = k2_n;
-    }
-    // queues live in the sort workspace, which is idle until K3: 2 x u32[n] + 2 x u64[n]
-    // two entry buffers of n_rows each: [swapped CF up | power series down] and [incbcf up | incbd down]
-    K2Queues Q;
-    const long long cap_s = k2_shard_capacity(k2_n);
-    const int n_shards = k2_classify_grid(k2_n);
-    if ((int64_t)n_shards * cap_s > ctx->queue_cap) return fail(ctx, FHX_ERR_HIP, "internal: queue workspace smaller than the shard layout");
+    M->loc1 = reinterpret_cast<int32_t*>(ctx->d_memo);
+    M->loc2 = M->loc1 + col;
+    M->count = M->loc2 + col;
+    M->table = reinterpret_cast<double*>(M->count + col);
+    M->over_rows = reinterpret_cast<unsigned int*>(M->table + col);
+    hipLaunchKernelGGL(k2_memo_rows, dim3(grid_for(plan.k2_n, 256)), dim3(256), 0, ctx->stream, plan.memo_nd, P->lo_idx, plan.memo_cap,
+                       (int)plan.memo_inter, M->loc1, M->loc2, M->count, plan.k2_n);
+    P->loc1 = M->loc1;
+    P->loc2 = M->loc2;
+    P->count = M->count;
+    P->p = M->table;
+    P->n = plan.k2_n;
+    return FHX_OK;
+}
+
+// queues live in the sort workspace, which is idle until K3: 2 x u32[n] + 2 x u64[n]
+// two entry buffers of n_rows each: [swapped CF up | power series down] and [incbcf up | incbd down]
+static int k2_queue_layout(fhx_ctx* ctx, const K2Plan& plan, bool prezeroed, K2Queues* Q) {
+    if ((int64_t)plan.n_shards * plan.cap_s > ctx->queue_cap) return fail(ctx, FHX_ERR_HIP, "internal: queue workspace smaller than the shard layout");
     if (!ctx->d_k2_counts) FHX_HIP(hipMalloc(&ctx->d_k2_counts, (size_t)(K2_QUEUES + 1) * K2_MAX_SHARDS * sizeof(unsigned long long)));
-    Q.count = ctx->d_k2_counts;
-    const bool legacy_heavy = getenv("FHX_K2_LEGACY") != nullptr;      // A/B and tests: the per-lane kernel of round 1
-    Q.heavy_hist = nullptr;
-    if (!legacy_heavy) {                 // k2_classify counts the heavy class's buckets while it queues
-        static_assert((K2H_BLOCKS & (K2H_BLOCKS - 1)) == 0, "shard -> column by masking");
-        if (!prezeroed)
-            FHX_HIP(hipMemsetAsync(ctx->d_block_hist, 0, (size_t)K2H_BUCKETS * K2H_BLOCKS * sizeof(unsigned int), ctx->stream));
-        Q.heavy_hist = ctx->d_block_hist;
-    }
-    ctx->k2_shards = n_shards;
+    Q->count = ctx->d_k2_counts;
+    static_assert((K2H_BLOCKS & (K2H_BLOCKS - 1)) == 0, "shard -> column by masking");
+    Q->heavy_hist = plan.legacy_heavy ? nullptr : ctx->d_block_hist;   // k2_classify counts the heavy class's buckets while it queues
+    if (Q->heavy_hist && !prezeroed)
+        FHX_HIP(hipMemsetAsync(ctx->d_block_hist, 0, (size_t)K2H_BUCKETS * K2H_BLOCKS * sizeof(unsigned int), ctx->stream));
+    ctx->k2_shards = plan.n_shards;
     auto span = [&](int cls, QEntry* buf, int dir) {
-        QSpan& q = Q.q[cls - 1];
-        q.base = dir > 0 ? buf : buf + cap_s - 1;
-        q.cap_s = cap_s;
-        q.dir = dir;
-        q.n_shards = n_shards;
-        q.count = Q.count + (size_t)(cls - 1) * K2_MAX_SHARDS;
+        Q->q[cls - 1] = QSpan{dir > 0 ? buf : buf + plan.cap_s - 1, plan.cap_s, dir, plan.n_shards, Q->count + (size_t)(cls - 1) * K2_MAX_SHARDS};
     };
     span(dev::BC_CF_SWAPPED, ctx->d_queue[0], 1);
     span(dev::BC_PSERIES, ctx->d_queue[0], -1);
     span(dev::BC_CF_BCF, ctx->d_queue[1], 1);
     span(dev::BC_CF_BD, ctx->d_queue[1], -1);
     span(K2_CLOSED, ctx->d_queue_sorted, 1);             // the sorted heavy queue is written after k2_closed has run
-    // (no reset of the counters: every workgroup of k2_classify writes its own shard's counts)
-    {
-        const dim3 cgrid(n_shards), cblock(K2_THREADS);
-        if (P.nonfixed)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<1, 4, 0>), cgrid, cblock, 0, ctx->stream, P, Q);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<0, 4, 3, true, true>), cgrid, cblock, 0, ctx->stream, P, Q);
-    }
-    const dim3 qgrid(256 * 8), qblock(K2_THREADS);
-    hipLaunchKernelGGL(k2_closed, qgrid, qblock, 0, ctx->stream, P, Q.q[K2_CLOSED - 1], ctx->d_misc + MISC_K2_REDO, ctx->d_misc + 6);
-    // totals below 171: the kernels that carry Cephes' pow branch (a binomial without a single contact - no inter-chromosomal
-    // rows - classifies every row as trivial and reaches no class kernel: it does not count)
-    const bool small_n = (P.intra.small_n && P.intra.n >= 1.0) || (P.inter.small_n && P.inter.n >= 1.0);
-    // one range per wave of TWICE the resident workgroups: the ranges are cut by entries, not by work, and the second half
-    // evens the first one out (C3: 376 us at 1 x, 358 at 2.3 x, 362 at 4.7 x, profiles/history/r04_t_ps.txt)
-#define FHX_LAUNCH_QUEUE(CLS)                                                                                         \
-    do {                                                                                                              \
-        if (small_n)                                                                                                  \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue<CLS, true>), dim3(2 * resident_grid(ctx, k2_queue<CLS, true>)), qblock, 0,      \
-                               ctx->stream, P, Q.q[(CLS) - 1]);                                                       \
-        else                                                                                                          \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue<CLS, false>), dim3(2 * resident_grid(ctx, k2_queue<CLS, false>)), qblock, 0,     \
-                               ctx->stream, P, Q.q[(CLS) - 1]);                                                       \
-    } while (0)
-    // the handed-back rows' counter and the work counters of the class kernels (k2h_heavy's tasks, one per class queue)
-    unsigned long long* n_redo = ctx->d_misc + MISC_K2_REDO;
-    unsigned long long* k2_next = ctx->d_misc + MISC_K2_NEXT;                 // both zeroed by k2_closed above
-    if (legacy_heavy) {
+    return FHX_OK;                                       // (no reset of the counters: every workgroup of k2_classify writes its own shard's counts)
+}
+
+// k2_queue: one range per wave of TWICE the resident workgroups: the ranges are cut by entries, not by work, and the second half
+// evens the first one out (C3: 376 us at 1 x, 358 at 2.3 x, 362 at 4.7 x, profiles/history/r04_t_ps.txt)
+template <int CLS, bool SMALL_N>
+static void launch_k2_queue(fhx_ctx* ctx, const K2Params& P, const K2Queues& Q) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue<CLS, SMALL_N>), dim3(2 * resident_grid(ctx, k2_queue<CLS, SMALL_N>)), dim3(K2_THREADS), 0,
+                       ctx->stream, P, Q.q[CLS - 1]);
+}
+template <int CLS, bool SMALL_N>
+static void launch_k2_queue_by_count(fhx_ctx* ctx, const K2Params& P, const K2Queues& Q) {
+    constexpr int PIECE = SMALL_N ? 4 : 5;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue_by_count<CLS, SMALL_N, PIECE>), dim3(resident_grid(ctx, k2_queue_by_count<CLS, SMALL_N, PIECE>)),
+                       dim3(K2_THREADS), 0, ctx->stream, P, Q.q[CLS - 1], (unsigned int*)(ctx->d_words->k2_next + CLS));
+}
+template <int ROWS, int WAVES, bool SMALL_N>
+static void launch_k2h_heavy(fhx_ctx* ctx, const K2Params& P, QEntry* redo) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k2h_heavy<ROWS, WAVES, SMALL_N>), dim3(256 * WAVES), dim3(K2H_THREADS), 0, ctx->stream,
+                       K2HeavyParams{P.intra, P.inter, P.p, P.top_hist}, (const QEntry*)ctx->d_queue_sorted, (const unsigned int*)ctx->d_k2h_off,
+                       (const unsigned int*)ctx->d_digit_total, (const dev::CfRow*)ctx->d_cf_tab, redo, &ctx->d_words->k2_redo,
+                       (unsigned int*)ctx->d_words->k2_next);
+}
+
+// The launches of a pass: classification, the closed form, the class kernels.  FHX_K2_LEGACY: the heavy class as it was queued, one row
+// per lane.  Otherwise: the swapped-fraction queue is bucketed by (binomial, count) and run in uniform waves, which hand back what does not fit
+template <bool SMALL_N>
+static int launch_k2(fhx_ctx* ctx, const K2Plan& plan, const K2Params& P, const K2Queues& Q) {
+    const dim3 cgrid(plan.n_shards), block(K2_THREADS);
+    if (P.nonfixed)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<1, 4, 0>), cgrid, block, 0, ctx->stream, P, Q);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_classify<0, 4, 3, true, true>), cgrid, block, 0, ctx->stream, P, Q);
+    hipLaunchKernelGGL(k2_closed, dim3(256 * 8), block, 0, ctx->stream, P, Q.q[K2_CLOSED - 1], &ctx->d_words->k2_redo, &ctx->d_words->bh_cutoff);
+    if (plan.legacy_heavy) {
         FHX_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
-        FHX_LAUNCH_QUEUE(dev::BC_CF_SWAPPED);            // longest-running class first
+        launch_k2_queue<dev::BC_CF_SWAPPED, SMALL_N>(ctx, P, Q);     // longest-running class first
         FHX_HIP(hipEventRecord(ctx->ev[7], ctx->stream));
         ctx->ev_folded[3] = false;
-    } else {
-        static_assert(K2H_BUCKETS == RADIX && K2H_BLOCKS == SORT_BLOCKS, "the radix sort's count matrix and scan are reused");
-        const QSpan hs = Q.q[dev::BC_CF_SWAPPED - 1];
-        QEntry* hq = ctx->d_queue[0];                    // the handed-back rows: this buffer is dead once it is scattered and the
-                                                         // power-series class (its other tenant) has run
-        launch_rs_scan(ctx, (int)SORT_BLOCKS);
-        // rows per lane: 4 at 4 waves/SIMD - C3 (2.7e7 rows in the class) 7.43 -> 6.66 ms, a 1/18 shard (1.5e6 rows) 0.87 -> 0.78 ms of
-        // K2 against one row per lane at 8 waves/SIMD; 2 x 8, 2 x 6, 3 x 5 and 4 x 3 are within 3 % of each other
-        // (profiles/history/r03_c_*heavy_variants.txt).  A small input (a shard of a strong-scaling run) has a handful of 256-entry
-        // tasks per wave and ends with most waves idle: two rows per lane at eight waves per SIMD halves the task (a 1/8 shard of
-        // C3: 876 -> 829 us, profiles/history/r04_t_rows.txt).  FHX_K2H_ROWS (2 or 4), read per call, forces one of the two for tests.
-        const char* heavy_rows_env = std::getenv("FHX_K2H_ROWS");
-        const int heavy_rows = heavy_rows_env ? std::atoi(heavy_rows_env) : 0;
-        const int hr = (heavy_rows == 2 || heavy_rows == 4) ? heavy_rows      // the bucket granule must be the launched kernel's task size
-                       : k2_n < 32000000 ? 2 : 4;
-        hipLaunchKernelGGL(k2h_offsets_and_tables, dim3(K2H_GENERIC + 1), dim3(1024), 0, ctx->stream, (const unsigned int*)ctx->d_digit_total,
-                           ctx->d_k2h_off, 64u * (unsigned int)hr, P.intra.n, P.inter.n, ctx->d_cf_tab);
-        hipLaunchKernelGGL(k2h_scatter, dim3(K2H_BLOCKS), dim3(K2H_THREADS), 0, ctx->stream, hs,
-                           (const unsigned int*)ctx->d_block_hist, (const unsigned int*)ctx->d_k2h_off, ctx->d_queue_sorted);
-        FHX_LAUNCH_QUEUE(dev::BC_PSERIES);               // before the redo list reuses the buffer it shares with the heavy queue
-        FHX_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
-        const K2HeavyParams HP{P.intra, P.inter, P.p, P.top_hist};
-#define FHX_HEAVY_N(R, W, S)                                                                                                        \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k2h_heavy<R, W, S>), dim3(256 * W), dim3(K2H_THREADS), 0, ctx->stream, HP,                     \
-                       (const QEntry*)ctx->d_queue_sorted, (const unsigned int*)ctx->d_k2h_off, (const unsigned int*)ctx->d_digit_total, \
-                       (const dev::CfRow*)ctx->d_cf_tab, hq, n_redo, (unsigned int*)k2_next)
-#define FHX_HEAVY(R, W)           \
-    do {                          \
-        if (small_n)              \
-            FHX_HEAVY_N(R, W, true);  \
-        else                      \
-            FHX_HEAVY_N(R, W, false); \
-    } while (0)
-        if (hr == 2) FHX_HEAVY(2, 8);
-        else FHX_HEAVY(4, 4);
-#undef FHX_HEAVY
-#undef FHX_HEAVY_N
-        FHX_HIP(hipEventRecord(ctx->ev[7], ctx->stream));
-        ctx->ev_folded[3] = false;
-        hipLaunchKernelGGL(k2h_generic, dim3(256 * 4), dim3(K2_THREADS), 0, ctx->stream, P, (const QEntry*)ctx->d_queue_sorted,
-                           (const unsigned int*)ctx->d_k2h_off, (const unsigned int*)ctx->d_digit_total, (const QEntry*)hq,
-                           (const unsigned long long*)n_redo);
+        launch_k2_queue_by_count<dev::BC_CF_BD, SMALL_N>(ctx, P, Q);
+        launch_k2_queue_by_count<dev::BC_CF_BCF, SMALL_N>(ctx, P, Q);
+        launch_k2_queue<dev::BC_PSERIES, SMALL_N>(ctx, P, Q);
+        return FHX_OK;
     }
-#define FHX_LAUNCH_QUEUE_BY_COUNT(CLS)                                                                                                \
-    do {                                                                                                                              \
-        if (small_n)                                                                                                                  \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue_by_count<CLS, true, 4>), dim3(resident_grid(ctx, k2_queue_by_count<CLS, true, 4>)), \
-                               qblock, 0, ctx->stream, P, Q.q[(CLS) - 1], (unsigned int*)(k2_next + (CLS)));                          \
-        else                                                                                                                          \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue_by_count<CLS, false, 5>), dim3(resident_grid(ctx, k2_queue_by_count<CLS, false, 5>)), \
-                               qblock, 0, ctx->stream, P, Q.q[(CLS) - 1], (unsigned int*)(k2_next + (CLS)));                          \
-    } while (0)
-    FHX_LAUNCH_QUEUE_BY_COUNT(dev::BC_CF_BD);
-    FHX_LAUNCH_QUEUE_BY_COUNT(dev::BC_CF_BCF);
-    if (legacy_heavy) FHX_LAUNCH_QUEUE(dev::BC_PSERIES);
-#undef FHX_LAUNCH_QUEUE_BY_COUNT
-#undef FHX_LAUNCH_QUEUE
-    if (memo_cap >= 0) {
-        unsigned long long* n_over = ctx->d_misc + 5;
+    static_assert(K2H_BUCKETS == RADIX && K2H_BLOCKS == SORT_BLOCKS, "the radix sort's count matrix and scan are reused");
+    QEntry* hq = ctx->d_queue[0];                    // the handed-back rows: this buffer is dead once it is scattered and the
+                                                     // power-series class (its other tenant) has run
+    launch_rs_scan(ctx, (int)SORT_BLOCKS);
+    hipLaunchKernelGGL(k2h_offsets_and_tables, dim3(K2H_GENERIC + 1), dim3(1024), 0, ctx->stream, (const unsigned int*)ctx->d_digit_total,
+                       ctx->d_k2h_off, 64u * (unsigned int)plan.heavy_rows, P.intra.n, P.inter.n, ctx->d_cf_tab);
+    hipLaunchKernelGGL(k2h_scatter, dim3(K2H_BLOCKS), dim3(K2H_THREADS), 0, ctx->stream, Q.q[dev::BC_CF_SWAPPED - 1],
+                       (const unsigned int*)ctx->d_block_hist, (const unsigned int*)ctx->d_k2h_off, ctx->d_queue_sorted);
+    launch_k2_queue<dev::BC_PSERIES, SMALL_N>(ctx, P, Q);        // before the redo list reuses the buffer it shares with the heavy queue
+    FHX_HIP(hipEventRecord(ctx->ev[6], ctx->stream));
+    if (plan.heavy_rows == 2) launch_k2h_heavy<2, 8, SMALL_N>(ctx, P, hq);
+    else launch_k2h_heavy<4, 4, SMALL_N>(ctx, P, hq);
+    FHX_HIP(hipEventRecord(ctx->ev[7], ctx->stream));
+    ctx->ev_folded[3] = false;
+    hipLaunchKernelGGL(k2h_generic, dim3(256 * 4), dim3(K2_THREADS), 0, ctx->stream, P, (const QEntry*)ctx->d_queue_sorted,
+                       (const unsigned int*)ctx->d_k2h_off, (const unsigned int*)ctx->d_digit_total, (const QEntry*)hq,
+                       (const unsigned long long*)&ctx->d_words->k2_redo);
+    launch_k2_queue_by_count<dev::BC_CF_BD, SMALL_N>(ctx, P, Q);
+    launch_k2_queue_by_count<dev::BC_CF_BCF, SMALL_N>(ctx, P, Q);
+    return FHX_OK;
+}
+
+// the table path hands the table's p to the real rows (P_rows) and evaluates what the table does not cover; then the pass is closed
+static int finish_k2(fhx_ctx* ctx, const K2Plan& plan, const K2Params& P_rows, const K2Memo& M) {
+    if (plan.memo_cap >= 0) {
+        unsigned long long* n_over = &ctx->d_words->memo_overflow;
         FHX_HIP(hipMemsetAsync(n_over, 0, sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(k2_memo_gather, dim3(grid_for(ctx->n_rows, 256, 256 * 16)), dim3(256), 0, ctx->stream, P_rows,
-                           (const double*)v_table, memo_nd, memo_cap, (int)memo_intra, (int)memo_inter, over_rows, n_over, over_cap);
+        hipLaunchKernelGGL(k2_memo_gather, dim3(grid_for(ctx->n_rows, 256, 256 * 16)), dim3(256), 0, ctx->stream, P_rows, (const double*)M.table,
+                           plan.memo_nd, plan.memo_cap, (int)plan.memo_intra, (int)plan.memo_inter, M.over_rows, n_over, M.over_cap);
         FHX_HIP(hipGetLastError());
         unsigned long long h_over = 0;
         FHX_HIP(hipMemcpyAsync(&h_over, n_over, sizeof(h_over), hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipStreamSynchronize(ctx->stream));
         if (h_over > 0) {
-            const bool listed = h_over <= over_cap;
+            const bool listed = h_over <= M.over_cap;
             const int64_t work = listed ? (int64_t)h_over : ctx->n_rows;
             hipLaunchKernelGGL(k2_memo_overflow, dim3(grid_for(work, 256, 256 * 16)), dim3(256), 0, ctx->stream, P_rows,
-                               (const unsigned int*)over_rows, (int64_t)h_over, listed ? 1 : 0);
+                               (const unsigned int*)M.over_rows, (int64_t)h_over, listed ? 1 : 0);
             FHX_HIP(hipGetLastError());
             FHX_HIP(hipStreamSynchronize(ctx->stream));
         }
@@ -1263,6 +1237,40 @@ int fhx_pvalues(fhx_ctx* ctx) {
     ctx->have_q = false;
     ctx->n_sorted = -1;
     return FHX_OK;                                                 // (K3's cutoff word says "keep every p": k2_closed)
+}
+
+int fhx_pvalues(fhx_ctx* ctx) {
+    if (!ctx) return FHX_ERR_ARG;
+    if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
+    if (!ctx->have_fit) return fail(ctx, FHX_ERR_ARG, "fhx_fit must run first");
+    FHX_HIP(hipSetDevice(ctx->device));
+    if (ctx->tables_dirty) {               // e.g. the bias table arrived after the fit (the reference's call order)
+        const int r2 = build_slot_tables(ctx);
+        if (r2 != FHX_OK) return r2;
+    }
+    K2Params P = make_k2_params(ctx);
+    before_rerecord(ctx, 1);
+    FHX_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
+    const K2Plan plan = plan_k2(ctx, P);
+    // fhx_pass_stats zeroes the two histograms of this call behind K1, while the host fits (k1_prezero); any other caller - and
+    // anything that used the count matrix in between (radix_passes clears the mark) - gets them zeroed here
+    const bool prezeroed = ctx->k2_prezeroed;
+    ctx->k2_prezeroed = false;
+    // K3's key histogram rides on K2's stores of p - except on the table path, whose class kernels store table entries
+    ctx->k2_hist_valid = false;
+    if (plan.memo_cap < 0) {
+        if (!ctx->d_k2_hist) FHX_HIP(hipMalloc(&ctx->d_k2_hist, TOP_BINS * sizeof(unsigned long long)));
+        if (!prezeroed) FHX_HIP(hipMemsetAsync(ctx->d_k2_hist, 0, TOP_BINS * sizeof(unsigned long long), ctx->stream));
+        P.top_hist = ctx->d_k2_hist;
+        ctx->k2_hist_valid = true;
+    }
+    const K2Params P_rows = P;             // the context's rows, whatever K2 classifies
+    K2Memo M;
+    K2Queues Q;
+    int rc = plan.memo_cap >= 0 ? k2_table_rows(ctx, plan, &M, &P) : FHX_OK;
+    if (rc == FHX_OK) rc = k2_queue_layout(ctx, plan, prezeroed, &Q);
+    if (rc == FHX_OK) rc = plan.small_n ? launch_k2<true>(ctx, plan, P, Q) : launch_k2<false>(ctx, plan, P, Q);
+    return rc == FHX_OK ? finish_k2(ctx, plan, P_rows, M) : rc;
 }
 
 int fhx_bdtrc_array(fhx_ctx* ctx, double n_total, const int32_t* count, const double* prior, int64_t n, double* out) {
@@ -1373,8 +1381,8 @@ int fhx_next_pass(fhx_ctx* ctx, int64_t* n_outliers_total) {
     if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
     if (!ctx->have_p) return fail(ctx, FHX_ERR_ARG, "fhx_pvalues must run first");
     FHX_HIP(hipSetDevice(ctx->device));
-    unsigned long long* n_out = ctx->d_misc + 1;
-    unsigned long long* first_dup = ctx->d_misc + 4;
+    unsigned long long* n_out = &ctx->d_words->outliers_added;
+    unsigned long long* first_dup = &ctx->d_words->first_dup;
     FHX_HIP(hipMemsetAsync(n_out, 0, sizeof(unsigned long long), ctx->stream));
     FHX_HIP(hipMemsetAsync(first_dup, 0xFF, sizeof(unsigned long long), ctx->stream));
     if (ctx->nonfixed) {
@@ -1533,7 +1541,7 @@ int fhx_k2_heavy_launch(fhx_ctx* ctx, double* seconds, int64_t* rows) {
     for (unsigned long long v : part) n += v;
     if (std::getenv("FHX_DEBUG_HEAVY")) {                  // how many rows the uniform kernel handed back to the per-lane loop
         unsigned long long redo = 0;
-        FHX_HIP(hipMemcpy(&redo, ctx->d_misc + MISC_K2_REDO, sizeof(redo), hipMemcpyDeviceToHost));
+        FHX_HIP(hipMemcpy(&redo, &ctx->d_words->k2_redo, sizeof(redo), hipMemcpyDeviceToHost));
         std::fprintf(stderr, "k2h_heavy: %.3f ms, %llu rows in the class, %llu handed back\n", ms, n, redo);
     }
     if (seconds) *seconds = ms * 1e-3;

@@ -1149,7 +1149,7 @@ static int auto_cutoff(fhx_ctx* ctx, const double* d_p, int64_t n, double n_tota
         FHX_HIP(hipMemsetAsync(ctx->d_top_hist, 0, TOP_BINS * sizeof(unsigned long long), ctx->stream));
         hipLaunchKernelGGL(k3_top_hist, dim3(grid_for((n + 1) / 2, 512, 256 * 4)), dim3(512), 0, ctx->stream, d_p, n, ctx->d_top_hist);
     }
-    // the survivors' number by the histogram (d_misc[8]) goes to pinned memory right behind the cutoff: compact_pvalues waits for
+    // the survivors' number by the histogram (DeviceWords::bh_below) goes to pinned memory right behind the cutoff: compact_pvalues waits for
     // that copy alone, while the compaction it has already enqueued runs
     {
         int rc = ensure_k3_host(ctx);
@@ -1167,8 +1167,8 @@ static int auto_cutoff(fhx_ctx* ctx, const double* d_p, int64_t n, double n_tota
     host.ticket = ++ctx->ticket;
     host.done = ctx->d_done + 1;
     host.zero_me = counter_to_zero;
-    hipLaunchKernelGGL(k3_cutoff, dim3(1), dim3(1024), 0, ctx->stream, hist, n_total_tests, d_cutoff, ctx->d_misc + 8, dense_min,
-                       ctx->d_misc + MISC_K3_DENSE, host);
+    hipLaunchKernelGGL(k3_cutoff, dim3(1), dim3(1024), 0, ctx->stream, hist, n_total_tests, d_cutoff, &ctx->d_words->bh_below, dense_min,
+                       &ctx->d_words->k3_dense, host);
     FHX_HIP(hipGetLastError());
     ctx->k3_ticket = host.ticket;
     ctx->k3_kept_by_hist = true;
@@ -1343,7 +1343,6 @@ static int rank_and_adjust(fhx_ctx* ctx, const double* d_p, int64_t n, unsigned 
 int fhx::ensure_sort_scratch(fhx_ctx* ctx) {
     if (!ctx->d_block_hist) FHX_HIP(hipMalloc(&ctx->d_block_hist, (size_t)RADIX * SORT_BLOCKS * sizeof(unsigned int)));
     if (!ctx->d_digit_total) FHX_HIP(hipMalloc(&ctx->d_digit_total, RADIX * sizeof(unsigned int)));
-    if (!ctx->d_misc) FHX_HIP(hipMalloc(&ctx->d_misc, 192 * sizeof(unsigned long long)));
     if (!ctx->d_top_hist) FHX_HIP(hipMalloc(&ctx->d_top_hist, TOP_BINS * sizeof(unsigned long long)));
     return FHX_OK;
 }
@@ -1382,7 +1381,7 @@ int fhx_bh_set_cutoff_device(fhx_ctx* ctx, double n_total_tests) {
     if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
     FHX_HIP(hipSetDevice(ctx->device));
     hipLaunchKernelGGL(k3_cutoff, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long*)ctx->d_top_hist, n_total_tests,
-                       ctx->d_misc + 6, (unsigned long long*)nullptr);
+                       &ctx->d_words->bh_cutoff, (unsigned long long*)nullptr);
     FHX_HIP(hipGetLastError());
     return FHX_OK;
 }
@@ -1399,7 +1398,7 @@ int fhx_bh_set_cutoff(fhx_ctx* ctx, const int64_t* global_hist, int64_t n_bins, 
             break;
         }
     }
-    FHX_HIP(hipMemcpyAsync(ctx->d_misc + 6, &cutoff, sizeof(cutoff), hipMemcpyHostToDevice, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(&ctx->d_words->bh_cutoff, &cutoff, sizeof(cutoff), hipMemcpyHostToDevice, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
     return FHX_OK;
 }
@@ -1418,8 +1417,8 @@ int fhx_bh_local_sort(fhx_ctx* ctx) {
     if (!ctx->have_p) return fail(ctx, FHX_ERR_ARG, "fhx_pvalues must run first");
     FHX_HIP(hipSetDevice(ctx->device));
     int64_t kept = 0;
-    const int rc = sort_pvalues(ctx, ctx->d_p, ctx->n_rows, ctx->d_keys, ctx->d_vals, ctx->d_q, ctx->d_misc, ctx->d_misc + 6,
-                                &ctx->sorted_buf, &kept, 62, engine_sort_ctrl(ctx));
+    const int rc = sort_pvalues(ctx, ctx->d_p, ctx->n_rows, ctx->d_keys, ctx->d_vals, ctx->d_q, &ctx->d_words->bh_kept,
+                                &ctx->d_words->bh_cutoff, &ctx->sorted_buf, &kept, 62, engine_sort_ctrl(ctx));
     if (rc != FHX_OK) return rc;
     ctx->n_sorted = kept;
     return FHX_OK;
@@ -1453,8 +1452,8 @@ int fhx_bh_array(fhx_ctx* ctx, const double* p, int64_t n, double n_total_tests,
     if (n > KS_MAX_KEYS && n <= OS_MAX_KEYS) FHX_HIP(tmp.get(&ctrl, os_scratch_bytes(n)));
     FHX_HIP(hipMemcpyAsync(d_p, p, cap * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     int buf = 0;
-    unsigned long long* counter = ctx->d_misc + 2;
-    unsigned long long* cutoff = ctx->d_misc + 7;
+    unsigned long long* counter = &ctx->d_words->array_kept;
+    unsigned long long* cutoff = &ctx->d_words->array_cutoff;
     rc = auto_cutoff(ctx, d_p, n, n_total_tests, cutoff, ~0ull, counter);
     if (rc == FHX_OK) rc = rank_and_adjust(ctx, d_p, n, keys, vals, d_q, counter, cutoff, n_total_tests, tile_max, &buf, nullptr, 64, ctrl);
     if (rc == FHX_OK) {
@@ -1484,12 +1483,12 @@ int fhx_bh(fhx_ctx* ctx, double n_total_tests) {
     unsigned long long dense_min = ~0ull;
     if (dense) {
         dense_min = (unsigned long long)(((long double)ctx->n_rows * K3_DENSE_PERCENT + 99) / 100);
-        dq.flag = ctx->d_misc + MISC_K3_DENSE;
+        dq.flag = &ctx->d_words->k3_dense;
     }
-    int rc = auto_cutoff(ctx, ctx->d_p, ctx->n_rows, n_total_tests, ctx->d_misc + 6, dense_min, ctx->d_misc, ctx->ev[4]);
+    int rc = auto_cutoff(ctx, ctx->d_p, ctx->n_rows, n_total_tests, &ctx->d_words->bh_cutoff, dense_min, &ctx->d_words->bh_kept, ctx->ev[4]);
     if (rc != FHX_OK) return rc;
     int64_t kept = 0;
-    rc = rank_and_adjust(ctx, ctx->d_p, ctx->n_rows, ctx->d_keys, ctx->d_vals, ctx->d_q, ctx->d_misc, ctx->d_misc + 6, n_total_tests,
+    rc = rank_and_adjust(ctx, ctx->d_p, ctx->n_rows, ctx->d_keys, ctx->d_vals, ctx->d_q, &ctx->d_words->bh_kept, &ctx->d_words->bh_cutoff, n_total_tests,
                          ctx->d_tile_max, &ctx->sorted_buf, &kept, 62, engine_sort_ctrl(ctx), dense ? &dq : nullptr);
     if (rc != FHX_OK) return rc;
     ctx->n_sorted = ctx->k3_n_is_bound ? -2 : kept;      // -2: fhx_n_sorted reads the device counter when somebody asks
@@ -1544,7 +1543,7 @@ int fhx_sort_u64(fhx_ctx* ctx, const void* d_keys_in, int64_t n, void* d_keys_ou
     DeviceScratch tmp;                               // freed on every return path
     FHX_HIP(tmp.get(&keys[0], (size_t)n * sizeof(unsigned long long)));
     FHX_HIP(tmp.get(&vals[0], (size_t)n * sizeof(unsigned int)));
-    unsigned long long* counter = ctx->d_misc + 3;
+    unsigned long long* counter = &ctx->d_words->sort_n;
     const unsigned long long n_host = (unsigned long long)n;
     FHX_HIP(hipMemcpyAsync(counter, &n_host, sizeof(n_host), hipMemcpyHostToDevice, ctx->stream));
     // an even number of ping-pong passes: start in the caller's output pair so that the result lands there
@@ -1564,7 +1563,7 @@ int fhx_bh_scatter(fhx_ctx* ctx, const void* d_q_sorted_local) {
     FHX_HIP(hipSetDevice(ctx->device));
     if (d_q_sorted_local)                       // NULL is legal when this rank holds no p < 1 at all
         hipLaunchKernelGGL(k_scatter_q, dim3(grid_for(ctx->n_rows, 256)), dim3(256), 0, ctx->stream, ctx->d_vals[ctx->sorted_buf],
-                       (const double*)d_q_sorted_local, ctx->d_misc, ctx->d_q);
+                       (const double*)d_q_sorted_local, &ctx->d_words->bh_kept, ctx->d_q);
     FHX_HIP(hipGetLastError());
     FHX_HIP(hipStreamSynchronize(ctx->stream));
     ctx->have_q = true;
