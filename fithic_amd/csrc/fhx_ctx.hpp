@@ -166,6 +166,14 @@ constexpr int K2H_BUCKETS = 2048;                       // == RADIX: the radix s
 constexpr int K2H_BLOCKS = 1024;                        // == SORT_BLOCKS
 __device__ __forceinline__ int k2h_bucket(int signed_count);
 
+// what k3_cutoff hands the host in the engine's own pass (auto_cutoff, fhx_k3.hip); all null: nothing
+struct CutoffToHost {
+    volatile unsigned long long* words = nullptr;    // [0] the ticket, [1] the number of values below the cutoff
+    unsigned long long ticket = 0;
+    unsigned int* done = nullptr;
+    unsigned long long* zero_me = nullptr;
+};
+
 constexpr int K3_DENSE_PERCENT = 35;                     // share of the rows that must survive the BH cutoff for q to go through the dense array
 constexpr int K2_COUNTER_WORDS = 8;                      // k2_redo + k2_next below: the words k2_closed zeroes for the class kernels
 constexpr int FDR_BUCKETS = 51;                          // plot_qvalues' buckets: floor(q / 0.001) = 0 .. 50 (k_fdr_hist, fhx_k3.hip)
@@ -282,6 +290,7 @@ using namespace fhx;
 
 namespace fhx {
 struct DistState;
+struct K3Host;                                   // fhx_k3.hip: what the one-sweep sort's repair copies back for the host
 }
 
 struct FhxPinnedPair;                            // fhx_emit.inc: two pinned 64 MB buffers + events, kept for the context's life
@@ -427,7 +436,7 @@ struct fhx_ctx {
     // Results the host waits for in the middle of a pass leave the device by the kernel's own stores into coherent pinned memory,
     // followed by a ticket in h_flags (system-scope release); the host spins on the ticket (wait_ticket) instead of sleeping in
     // hipStreamSynchronize: no copy dispatch behind the kernel, no interrupt + wake-up in front of the host fit.
-    //   h_flags[0]  k1_pack_window's ticket (fhx_pass_stats)      h_flags[8]  k3_cutoff's ticket (auto_cutoff)
+    //   h_flags[0]  k1_pack_window's ticket (fhx_pass_stats)      h_flags[8]  k3_cutoff's ticket, [9] its survivor count (auto_cutoff)
     //   h_flags[16] K3's fault word (check_fault)
     volatile unsigned long long* h_flags = nullptr;
     unsigned int* d_done = nullptr;                   // [0]: workgroups of k1_pack_window that have stored their part
@@ -455,14 +464,9 @@ struct fhx_ctx {
     double* d_tile_max = nullptr;
     int sorted_buf = 0;
     int64_t n_sorted = -1;
-    unsigned int* h_k3 = nullptr;                     // pinned: [0..1] survivors by the histogram, [8..15] the sort repair's verdict
-    hipEvent_t ev_k3 = nullptr;                       // the copy into h_k3
-    bool k3_n_is_bound = false;                       // the survivors' number compact_pvalues returned is an upper bound
+    fhx::K3Host* h_k3 = nullptr;                      // pinned: the sort repair's verdict, the exact key count, the long runs' bounds
+    hipEvent_t ev_k3 = nullptr;                       // the copy into h_k3; auto_cutoff's mark behind K2 when its caller recorded none
     int64_t k3_last_kept = -1, k3_last_rows = -1;     // survivors and rows of the last fhx_bh: whether the dense-q launches are worth enqueueing
-    hipEvent_t k3_wait_ev = nullptr;                  // the event recorded in front of k3_cutoff (K2's end) the host sleeps on
-    unsigned long long k3_ticket = 0;                 // the ticket k3_cutoff publishes behind the survivors' number (h_flags[FLAG_K3 + 1])
-    bool k3_counter_zeroed = false;                   // k3_cutoff zeroes the compaction's counter (auto_cutoff), no fill in front of k3_compact
-    bool k3_kept_by_hist = false;                     // auto_cutoff has put the survivors' number on its way into h_k3[0..1]
     int64_t sort_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the last large sort of K3 (fhx_bh_sort_stats)
     std::vector<int64_t> fdr_counts;
     fhx::DistState* dist = nullptr;                 // communicator + exchange buffers of sharded runs (fhx_dist.inc)
@@ -651,13 +655,16 @@ int radix_sort_pairs(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int* va
                      int* result_buf, int64_t n_hint = -1);
 void launch_rs_scan(fhx_ctx* ctx, int nblk);                     // exclusive scan of d_block_hist along the workgroup axis + digit totals
 int fill_top_hist(fhx_ctx* ctx);
-void launch_k3_cutoff(fhx_ctx* ctx, double n_tests, unsigned long long* d_cutoff);
+// the one launch site of each of these kernels; what a caller does not use is spelled out: null pointers, dense_min ~0, n_bound -1
+void launch_k3_cutoff(fhx_ctx* ctx, const unsigned long long* hist, double n_tests, unsigned long long* d_cutoff,
+                      unsigned long long* n_below, unsigned long long dense_min, unsigned long long* dense_flag, const CutoffToHost& host);
 void launch_bh_tile_max(fhx_ctx* ctx, int tiles, const unsigned long long* keys, const unsigned long long* n_ptr, int64_t n_fixed,
                         double n_tests, double rank0, double* tile_max);
 void launch_bh_scan_tiles(fhx_ctx* ctx, double* tile_max, const unsigned long long* n_ptr, int64_t n_fixed, double carry_in,
-                          double* total_max);
+                          double* total_max, int64_t n_bound, unsigned long long* fault);
 void launch_bh_apply(fhx_ctx* ctx, int tiles, const unsigned long long* keys, const unsigned int* vals, const unsigned long long* n_ptr,
-                     int64_t n_fixed, double n_tests, double rank0, const double* tile_carry, const double* extra_carry, double* q_out);
+                     int64_t n_fixed, double n_tests, double rank0, const double* tile_carry, const double* extra_carry, double* q_out,
+                     double* dense, const unsigned long long* dense_flag);
 void launch_scatter_q(fhx_ctx* ctx, int64_t n_rows, const unsigned int* rows, const double* q_sorted, const unsigned long long* n_ptr,
                       double* q);
 void launch_fdr_hist(fhx_ctx* ctx, const double* q, int64_t n, unsigned long long* buckets);

@@ -827,7 +827,7 @@ int fhx_bh_distributed(fhx_ctx* ctx, double n_tests) {
     if (rc != FHX_OK) return rc;
     rc = dist_all_reduce_i64(ctx, fhx::DS_TOP_HIST, ctx->d_top_hist, TOP_BINS, 0);
     if (rc != FHX_OK) return rc;
-    launch_k3_cutoff(ctx, n_tests, &ctx->d_words->bh_cutoff);
+    launch_k3_cutoff(ctx, ctx->d_top_hist, n_tests, &ctx->d_words->bh_cutoff, nullptr, ~0ull, nullptr, CutoffToHost{});
     rc = fhx_bh_local_sort(ctx);                                   // survivors of this rank, sorted: keys + rows; count in bh_kept
     if (rc != FHX_OK) return rc;
     const unsigned long long* d_n = &ctx->d_words->bh_kept;
@@ -899,7 +899,7 @@ int fhx_bh_distributed(fhx_ctx* ctx, double n_tests) {
         buf = 1;
         launch_bh_tile_max(ctx, tiles, (const unsigned long long*)D->xkeys[buf].p, (const unsigned long long*)nullptr, m, n_tests, (double)rank0,
                            D->tile_max.p);
-        launch_bh_scan_tiles(ctx, D->tile_max.p, (const unsigned long long*)nullptr, m, 0.0, D->slice_max.p);
+        launch_bh_scan_tiles(ctx, D->tile_max.p, (const unsigned long long*)nullptr, m, 0.0, D->slice_max.p, -1, nullptr);
     } else {
         FHX_HIP(hipMemsetAsync(D->slice_max.p, 0, sizeof(double), ctx->stream));
     }
@@ -910,7 +910,7 @@ int fhx_bh_distributed(fhx_ctx* ctx, double n_tests) {
     if (m > 0)                                                     // q in ARRIVAL order: the sort's payload is the arrival index
         launch_bh_apply(ctx, tiles, (const unsigned long long*)D->xkeys[buf].p, (const unsigned int*)D->xvals[buf].p,
                         (const unsigned long long*)nullptr, m, n_tests, (double)rank0, (const double*)D->tile_max.p, (const double*)D->carry.p,
-                        D->q_arrival.p);
+                        D->q_arrival.p, nullptr, nullptr);
     FHX_HIP(hipGetLastError());
     rc = dist_all_to_all_v(ctx, fhx::DS_Q_BACK, D->q_arrival.p, rcnt.data(), ro.data(), D->q_back.p, sc.data(), so.data());
     if (rc != FHX_OK) return rc;

@@ -58,17 +58,12 @@ __host__ __device__ inline bool bin_saturates(int b, unsigned long long cum_incl
 
 // (dense_flag: 1 when at least dense_min values lie below the cutoff - the pass then takes q through the dense array, k3_compact<true>)
 // (host: the engine's own pass - the survivors' number goes straight to the host's pinned words, followed by the ticket the host
-// waits for (fhx_ctx::h_flags: no copy dispatched behind this kernel), and the compaction's counter is zeroed here (no fill before it))
-struct CutoffToHost {
-    volatile unsigned long long* words = nullptr;    // [0] the ticket, [1] the number of values below the cutoff
-    unsigned long long ticket = 0;
-    unsigned int* done = nullptr;
-    unsigned long long* zero_me = nullptr;
-};
+// waits for (fhx_ctx::h_flags: no copy dispatched behind this kernel), and the compaction's counter is zeroed here (no fill before it):
+// CutoffToHost, fhx_ctx.hpp)
 __global__ __launch_bounds__(1024) void k3_cutoff(const unsigned long long* __restrict__ hist, double n_tests,
                                                   unsigned long long* __restrict__ cutoff_key, unsigned long long* __restrict__ n_below,
-                                                  unsigned long long dense_min = ~0ull, unsigned long long* __restrict__ dense_flag = nullptr,
-                                                  CutoffToHost host = CutoffToHost{}) {
+                                                  unsigned long long dense_min, unsigned long long* __restrict__ dense_flag,
+                                                  CutoffToHost host) {
     __shared__ unsigned long long part[1024];
     __shared__ unsigned long long below;
     __shared__ unsigned int best;
@@ -722,8 +717,8 @@ __global__ __launch_bounds__(BH_THREADS) void bh_tile_max(const unsigned long lo
 // the context's fault word - pinned memory, read by every call that hands results to the host: check_fault)
 __global__ __launch_bounds__(1024) void bh_scan_tiles(double* __restrict__ tile_max,
                                                       const unsigned long long* __restrict__ n_ptr, int64_t n_fixed,
-                                                      double carry_in, double* __restrict__ total_max, int64_t n_bound = -1,
-                                                      unsigned long long* __restrict__ fault = nullptr) {
+                                                      double carry_in, double* __restrict__ total_max, int64_t n_bound,
+                                                      unsigned long long* __restrict__ fault) {
     __shared__ double part[1024];
     const int64_t n = n_ptr ? (int64_t)*n_ptr : n_fixed;
     if (fault && threadIdx.x == 0 && n > n_bound)
@@ -757,8 +752,8 @@ __global__ __launch_bounds__(BH_THREADS) void bh_apply(const unsigned long long*
                                                        const unsigned long long* __restrict__ n_ptr, int64_t n_fixed,
                                                        double n_tests, double rank0, const double* __restrict__ tile_carry,
                                                        const double* __restrict__ extra_carry, double* __restrict__ q_out,
-                                                       double* __restrict__ dense = nullptr,
-                                                       const unsigned long long* __restrict__ dense_flag = nullptr) {
+                                                       double* __restrict__ dense,
+                                                       const unsigned long long* __restrict__ dense_flag) {
     __shared__ double wtot[BH_THREADS / 64];
     const bool into_dense = dense && (!dense_flag || *dense_flag != 0ull);    // the values are compact indices: q goes to the dense array
     if (into_dense) q_out = dense;
@@ -847,6 +842,17 @@ int sort_blocks_for(int64_t n_hint) {
     return (int)std::max<int64_t>(64, std::min<int64_t>(SORT_BLOCKS, (want + 63) / 64 * 64));
 }
 
+// one count / scan / scatter pass over BITS bits from `shift`, out of buffer pair `src` into the other
+template <int BITS>
+static void rs_pass(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int* vals[2], const unsigned long long* counter, int nblk, int shift,
+                    int src) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rs_count<BITS>), dim3(nblk), dim3(SORT_THREADS), 0, ctx->stream, keys[src], counter, shift,
+                       ctx->d_block_hist);
+    hipLaunchKernelGGL(rs_scan, dim3(1 << BITS), dim3((nblk + 63) / 64 * 64), 0, ctx->stream, ctx->d_block_hist, ctx->d_digit_total, nblk);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(rs_scatter<512, 4, BITS>), dim3(nblk), dim3(512), 0, ctx->stream, keys[src], vals[src], keys[1 - src],
+                       vals[1 - src], counter, shift, (const unsigned int*)ctx->d_block_hist, (const unsigned int*)ctx->d_digit_total);
+}
+
 // LSD radix passes over the low `key_bits` bits of the keys, `bits` bits per pass (SORT_BITS_LARGE or RADIX_BITS), starting in
 // buffer pair `src`; *result_buf = the pair that holds the sorted keys and payloads
 static int radix_passes(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int* vals[2], const unsigned long long* counter, int nblk,
@@ -855,19 +861,8 @@ static int radix_passes(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int*
     ctx->k2_prezeroed = false;                        // the count matrix is K2's heavy-class histogram too (fhx_pass_stats zeroes it ahead)
     for (int pass = 0; pass < passes; ++pass) {
         const int shift = pass * bits;
-#define FHX_RS_PASS(B)                                                                                                               \
-    do {                                                                                                                             \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(rs_count<B>), dim3(nblk), dim3(SORT_THREADS), 0, ctx->stream, keys[src], counter, shift,    \
-                           ctx->d_block_hist);                                                                                       \
-        hipLaunchKernelGGL(rs_scan, dim3(1 << B), dim3((nblk + 63) / 64 * 64), 0, ctx->stream, ctx->d_block_hist, ctx->d_digit_total, \
-                           nblk);                                                                                                    \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(rs_scatter<512, 4, B>), dim3(nblk), dim3(512), 0, ctx->stream, keys[src], vals[src],        \
-                           keys[1 - src], vals[1 - src], counter, shift, (const unsigned int*)ctx->d_block_hist,                      \
-                           (const unsigned int*)ctx->d_digit_total);                                                                 \
-    } while (0)
-        if (bits == SORT_BITS_LARGE) FHX_RS_PASS(SORT_BITS_LARGE);
-        else FHX_RS_PASS(RADIX_BITS);
-#undef FHX_RS_PASS
+        if (bits == SORT_BITS_LARGE) rs_pass<SORT_BITS_LARGE>(ctx, keys, vals, counter, nblk, shift, src);
+        else rs_pass<RADIX_BITS>(ctx, keys, vals, counter, nblk, shift, src);
         src = 1 - src;
     }
     FHX_HIP(hipGetLastError());
@@ -909,15 +904,11 @@ static int os_run_passes(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int
         counter = slot;
     }
     const int hgrid = std::max(1, std::min(tiles / 2, 1024));
-    switch (plan.passes) {
-#define FHX_OS_HIST(P)                                                                                                             \
-    case P:                                                                                                                        \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(os_hist<P>), dim3(hgrid), dim3(OS_HIST_THREADS), 0, ctx->stream, (const unsigned long long*)keys[*src_io], \
-                           counter, plan.lo, ctrl + OSC_HIST);                                                                     \
-        break
-        FHX_OS_HIST(1); FHX_OS_HIST(2); FHX_OS_HIST(3); FHX_OS_HIST(4); FHX_OS_HIST(5); FHX_OS_HIST(6); FHX_OS_HIST(7); FHX_OS_HIST(8);
-#undef FHX_OS_HIST
-    }
+    using OsHist = decltype(&os_hist<1>);
+    static const OsHist os_hist_for[OS_MAX_PASSES] = {os_hist<1>, os_hist<2>, os_hist<3>, os_hist<4>, os_hist<5>, os_hist<6>, os_hist<7>, os_hist<8>};
+    if (plan.passes >= 1 && plan.passes <= OS_MAX_PASSES)
+        hipLaunchKernelGGL(os_hist_for[plan.passes - 1], dim3(hgrid), dim3(OS_HIST_THREADS), 0, ctx->stream,
+                           (const unsigned long long*)keys[*src_io], counter, plan.lo, ctrl + OSC_HIST);
     int src = *src_io;
     for (int p = 0; p < plan.passes; ++p) {
         hipLaunchKernelGGL(os_scatter, dim3(tiles), dim3(OS_THREADS), 0, ctx->stream, (const unsigned long long*)keys[src],
@@ -931,6 +922,18 @@ static int os_run_passes(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int
     return FHX_OK;
 }
 
+// Up to KS_MAX_KEYS keys (n > 0 of them sizes the grids, the kernels read *counter): tiles sorted in LDS out of pair [0] into pair
+// [1], then - more than one tile - merged by rank back into pair [0].  Returns the pair that holds the result.
+static int small_sort(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int* vals[2], const unsigned long long* counter, int64_t n) {
+    const int tiles = (int)((n + KS_TILE - 1) / KS_TILE);
+    hipLaunchKernelGGL(ks_tile_sort, dim3(tiles), dim3(KS_THREADS), 0, ctx->stream, (const unsigned long long*)keys[0],
+                       (const unsigned int*)vals[0], counter, keys[1], vals[1]);
+    if (tiles == 1) return 1;
+    hipLaunchKernelGGL(ks_merge_tiles, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys[1],
+                       (const unsigned int*)vals[1], counter, keys[0], vals[0]);
+    return 0;
+}
+
 // One-sweep passes + repair, in two halves: onesweep_launch enqueues the passes, the repair and a copy of the repair's verdict
 // into pinned memory; onesweep_finish waits for that copy alone (an event, not the stream) and - rarely - sorts what the repair
 // could not reach.  Between the two a caller may enqueue whatever only READS the sorted keys (the BH scan): it runs while the
@@ -940,14 +943,21 @@ struct OsPending {
     OsPlan plan{0, 0};
     int src = 0, key_hi = 62;
     int64_t n = 0;
-    unsigned long long* keys[2] = {nullptr, nullptr};
-    unsigned int* vals[2] = {nullptr, nullptr};
+    unsigned long long** keys = nullptr;               // the two buffer pairs the passes go between
+    unsigned int** vals = nullptr;
     const unsigned long long* counter = nullptr;
     unsigned int* ctrl = nullptr;
 };
 
+// what onesweep_launch copies back behind the repair and onesweep_finish reads behind ev_k3 (fhx_ctx::h_k3, pinned)
+struct K3Host {
+    unsigned int verdict[8];                 // ctrl[OSC_FALLBACK ..]: the fallback bits and the repair's statistics
+    unsigned long long n_keys;               // the device counter: the exact key count where the launch was sized for a bound
+    long long seg[RP_SEG_CAP * 2];           // [begin, end) of the long runs os_long_runs left to the host
+};
+
 static int ensure_k3_host(fhx_ctx* ctx) {
-    if (!ctx->h_k3) FHX_HIP(hipHostMalloc((void**)&ctx->h_k3, (20 + RP_SEG_CAP * 4 + 4) * sizeof(unsigned int), hipHostMallocDefault));
+    if (!ctx->h_k3) FHX_HIP(hipHostMalloc((void**)&ctx->h_k3, sizeof(K3Host), hipHostMallocDefault));
     if (!ctx->ev_k3) FHX_HIP(hipEventCreateWithFlags(&ctx->ev_k3, hipEventDisableTiming));
     return FHX_OK;
 }
@@ -963,13 +973,11 @@ static int onesweep_launch(fhx_ctx* ctx, unsigned long long* keys[2], unsigned i
     pend->n = n;
     pend->counter = counter;
     pend->ctrl = ctrl;
-    for (int b = 0; b < 2; ++b) {
-        pend->keys[b] = keys[b];
-        pend->vals[b] = vals[b];
-    }
+    pend->keys = keys;
+    pend->vals = vals;
     rc = os_run_passes(ctx, keys, vals, counter, n, pend->plan, ctrl, &pend->src);
     if (rc != FHX_OK) return rc;
-    for (int k = 0; k < 8; ++k) ctx->h_k3[8 + k] = 0u;
+    for (int k = 0; k < 8; ++k) ctx->h_k3->verdict[k] = 0u;
     if (pend->plan.lo > 0) {
         unsigned int* rp = ctrl + os_repair_offset(n);
         const unsigned int region_cap = (unsigned int)os_region_cap(n);
@@ -989,10 +997,10 @@ static int onesweep_launch(fhx_ctx* ctx, unsigned long long* keys[2], unsigned i
                            (const unsigned int*)d_longs, d_segs);
         hipLaunchKernelGGL(os_fix_long, dim3(64), dim3(512), 0, ctx->stream, k, v, (const unsigned int*)ctrl, (const long long*)d_segs);
         FHX_HIP(hipGetLastError());
-        FHX_HIP(hipMemcpyAsync(ctx->h_k3 + 8, ctrl + OSC_FALLBACK, 8 * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipMemcpyAsync(ctx->h_k3->verdict, ctrl + OSC_FALLBACK, sizeof(K3Host::verdict), hipMemcpyDeviceToHost, ctx->stream));
         // (n may be the histogram's upper bound, see compact_pvalues: the exact count comes back with the verdict)
-        FHX_HIP(hipMemcpyAsync(ctx->h_k3 + 16, counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        FHX_HIP(hipMemcpyAsync(ctx->h_k3 + 20, d_segs, RP_SEG_CAP * 2 * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipMemcpyAsync(&ctx->h_k3->n_keys, counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipMemcpyAsync(ctx->h_k3->seg, d_segs, sizeof(K3Host::seg), hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipEventRecord(ctx->ev_k3, ctx->stream));
     }
     pend->active = true;
@@ -1014,8 +1022,8 @@ static int onesweep_finish(fhx_ctx* ctx, OsPending* pend, bool* moved) {
     int rc = FHX_OK;
     if (plan.lo > 0) {
         FHX_HIP(hipEventSynchronize(ctx->ev_k3));
-        for (int k = 0; k < 8; ++k) st[k] = ctx->h_k3[8 + k];
-        const int64_t n_exact = (int64_t)*reinterpret_cast<volatile unsigned long long*>(ctx->h_k3 + 16);
+        for (int k = 0; k < 8; ++k) st[k] = ctx->h_k3->verdict[k];
+        const int64_t n_exact = (int64_t)*const_cast<volatile unsigned long long*>(&ctx->h_k3->n_keys);
         if (n_exact > n) return fail(ctx, FHX_ERR_HIP, "internal: more keys were compacted than the histogram counted");
         n = n_exact;
         if (std::getenv("FHX_OS_FORCE_FALLBACK")) st[0] |= 4u;      // tests
@@ -1026,7 +1034,7 @@ static int onesweep_finish(fhx_ctx* ctx, OsPending* pend, bool* moved) {
                 int64_t s, e;
             };
             std::vector<OsSegment> segs;
-            const long long* hs = reinterpret_cast<const long long*>(ctx->h_k3 + 20);
+            const long long* hs = ctx->h_k3->seg;
             for (unsigned int k = 0; k < n_segs && k < (unsigned int)RP_SEG_CAP; ++k) {
                 const OsSegment g{hs[2 * k], hs[2 * k + 1]};
                 if (g.s < 0 || g.e > n || g.e <= g.s) return fail(ctx, FHX_ERR_HIP, "internal: a long run's bounds are off");
@@ -1046,14 +1054,8 @@ static int onesweep_finish(fhx_ctx* ctx, OsPending* pend, bool* moved) {
                 if (m <= KS_MAX_KEYS) {                    // tiles sorted in LDS + merge by rank (whole keys: the run's top bits are equal anyway)
                     unsigned long long* slot = reinterpret_cast<unsigned long long*>(ctrl + OSC_SEG_N);
                     hipLaunchKernelGGL(os_set_n, dim3(1), dim3(1), 0, ctx->stream, slot, (unsigned long long)m);
-                    const int tiles = (int)((m + KS_TILE - 1) / KS_TILE);
-                    hipLaunchKernelGGL(ks_tile_sort, dim3(tiles), dim3(KS_THREADS), 0, ctx->stream, (const unsigned long long*)kk[0],
-                                       (const unsigned int*)vv[0], (const unsigned long long*)slot, kk[1], vv[1]);
-                    if (tiles > 1)
-                        hipLaunchKernelGGL(ks_merge_tiles, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, (const unsigned long long*)kk[1],
-                                           (const unsigned int*)vv[1], (const unsigned long long*)slot, kk[0], vv[0]);
+                    where = small_sort(ctx, kk, vv, slot, m);
                     FHX_HIP(hipGetLastError());
-                    where = tiles > 1 ? 0 : 1;
                 } else {
                     rc = os_run_passes(ctx, kk, vv, nullptr, m, OsPlan{(bits + OS_BITS - 1) / OS_BITS, 0}, ctrl, &where, true);
                     if (rc != FHX_OK) return rc;
@@ -1088,26 +1090,28 @@ static int onesweep_finish(fhx_ctx* ctx, OsPending* pend, bool* moved) {
     return FHX_OK;
 }
 
-// launches for the other translation units (the sharded schedule, the heavy class's bucket sort, the FDR counts)
+// launches shared with the other translation units (the sharded schedule, the heavy class's bucket sort, the FDR counts); k3_cutoff
+// and the three BH kernels are launched here and nowhere else
 void launch_rs_scan(fhx_ctx* ctx, int nblk) {
     hipLaunchKernelGGL(rs_scan, dim3(RADIX), dim3((nblk + 63) / 64 * 64), 0, ctx->stream, ctx->d_block_hist, ctx->d_digit_total, nblk);
 }
-void launch_k3_cutoff(fhx_ctx* ctx, double n_tests, unsigned long long* d_cutoff) {
-    hipLaunchKernelGGL(k3_cutoff, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long*)ctx->d_top_hist, n_tests, d_cutoff,
-                       (unsigned long long*)nullptr);
+void launch_k3_cutoff(fhx_ctx* ctx, const unsigned long long* hist, double n_tests, unsigned long long* d_cutoff,
+                      unsigned long long* n_below, unsigned long long dense_min, unsigned long long* dense_flag, const CutoffToHost& host) {
+    hipLaunchKernelGGL(k3_cutoff, dim3(1), dim3(1024), 0, ctx->stream, hist, n_tests, d_cutoff, n_below, dense_min, dense_flag, host);
 }
 void launch_bh_tile_max(fhx_ctx* ctx, int tiles, const unsigned long long* keys, const unsigned long long* n_ptr, int64_t n_fixed,
                         double n_tests, double rank0, double* tile_max) {
     hipLaunchKernelGGL(bh_tile_max, dim3(tiles), dim3(BH_THREADS), 0, ctx->stream, keys, n_ptr, n_fixed, n_tests, rank0, tile_max);
 }
 void launch_bh_scan_tiles(fhx_ctx* ctx, double* tile_max, const unsigned long long* n_ptr, int64_t n_fixed, double carry_in,
-                          double* total_max) {
-    hipLaunchKernelGGL(bh_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tile_max, n_ptr, n_fixed, carry_in, total_max);
+                          double* total_max, int64_t n_bound, unsigned long long* fault) {
+    hipLaunchKernelGGL(bh_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tile_max, n_ptr, n_fixed, carry_in, total_max, n_bound, fault);
 }
 void launch_bh_apply(fhx_ctx* ctx, int tiles, const unsigned long long* keys, const unsigned int* vals, const unsigned long long* n_ptr,
-                     int64_t n_fixed, double n_tests, double rank0, const double* tile_carry, const double* extra_carry, double* q_out) {
+                     int64_t n_fixed, double n_tests, double rank0, const double* tile_carry, const double* extra_carry, double* q_out,
+                     double* dense, const unsigned long long* dense_flag) {
     hipLaunchKernelGGL(bh_apply, dim3(tiles), dim3(BH_THREADS), 0, ctx->stream, keys, vals, n_ptr, n_fixed, n_tests, rank0, tile_carry,
-                       extra_carry, q_out);
+                       extra_carry, q_out, dense, dense_flag);
 }
 void launch_scatter_q(fhx_ctx* ctx, int64_t n_rows, const unsigned int* rows, const double* q_sorted, const unsigned long long* n_ptr,
                       double* q) {
@@ -1120,8 +1124,6 @@ void launch_fdr_hist(fhx_ctx* ctx, const double* q, int64_t n, unsigned long lon
 }  // namespace fhx
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------
-// compact p < 1 and LSD-radix-sort (key, row); returns the index (0/1) of the buffer pair holding the result
-// cutoff key from a device-local histogram of the p-values (single-GPU path; sharded runs all-reduce the histogram)
 // d_top_hist <- key histogram of the context's p: what K2 gathered while storing them, else one more read of p
 int fhx::fill_top_hist(fhx_ctx* ctx) {
     if (ctx->k2_hist_valid) {
@@ -1135,22 +1137,51 @@ int fhx::fill_top_hist(fhx_ctx* ctx) {
     return FHX_OK;
 }
 
-// (k2_done: an event the caller has just recorded on the stream - the host sleeps on it before it spins for k3_cutoff's ticket;
-// nullptr: one is recorded here)
-static int auto_cutoff(fhx_ctx* ctx, const double* d_p, int64_t n, double n_total_tests, unsigned long long* d_cutoff,
-                       unsigned long long dense_min = ~0ull, unsigned long long* counter_to_zero = nullptr, hipEvent_t k2_done = nullptr) {
+// One compaction, sort and BH of a p column (host only, on the entry point's stack): what the entry point asks for - it fills
+// these in order - and below that what the steps hand to each other.  A pass that never went through auto_cutoff counts its
+// survivors with the device counter and zeroes that counter itself: nothing of an earlier call is there to be inherited.
+struct K3Pass {
+    const double* p = nullptr;                    // the p column: n rows
+    int64_t n = 0;
+    unsigned long long** keys = nullptr;          // two buffers each: the compaction fills [0]
+    unsigned int** vals = nullptr;
+    double* q = nullptr;                          // the q column, row order
+    unsigned long long* counter = nullptr;        // device: the survivors' number
+    unsigned long long* cutoff = nullptr;         // device: the cutoff key
+    double n_total_tests = 0.0;
+    double* tile_max = nullptr;                   // BH scan scratch (not needed by sort_pvalues)
+    int key_hi = 62;                              // the key bits that can be set (62 / 64, see onesweep_launch)
+    unsigned int* ctrl = nullptr;                 // os_scratch_bytes(n) of device scratch, or nullptr (then the three-launch passes run)
+    const DenseQ* dq = nullptr;                   // q of the survivors through the dense array (k3_compact<true>, k3_fill_q)
+    // auto_cutoff -> compact_pvalues
+    bool kept_by_hist = false;                    // the survivors' number comes with k3_cutoff's ticket (h_flags[FLAG_K3 + 1]) ...
+    hipEvent_t wait_ev = nullptr;                 // ... behind this event, recorded in front of k3_cutoff (K2's end): the host sleeps on it
+    unsigned long long ticket = 0;
+    bool counter_zeroed = false;                  // k3_cutoff zeroes the counter: no fill in front of k3_compact
+    // compact_pvalues -> sort_kept -> bh_from_sorted, the entry point
+    int64_t n_kept = 0;
+    bool n_is_bound = false;                      // n_kept is the histogram's upper bound: the exact number is in *counter
+    int sorted_buf = 0;                           // the pair of keys / vals that holds the sorted survivors
+    OsPending pend;                               // the one-sweep sort's second half, when sort_kept left it to its caller
+};
+
+// the cutoff key from this GPU's own histogram of pass.p, and the survivors' number on its way to the host
+// (dense_min: k3_cutoff sets DeviceWords::k3_dense from that many survivors on, ~0: never.  k2_done: an event the caller has just
+// recorded on the stream - the host sleeps on it before it spins for k3_cutoff's ticket; nullptr: one is recorded here)
+static int auto_cutoff(fhx_ctx* ctx, K3Pass& pass, unsigned long long dense_min, hipEvent_t k2_done) {
     const unsigned long long* hist = ctx->d_top_hist;
-    if (d_p == ctx->d_p && ctx->k2_hist_valid) {
+    if (pass.p == ctx->d_p && ctx->k2_hist_valid) {
         hist = ctx->d_k2_hist;                          // what K2 counted while it stored p: read where it lies (no copy into d_top_hist)
-    } else if (d_p == ctx->d_p) {
+    } else if (pass.p == ctx->d_p) {
         const int rc = fill_top_hist(ctx);
         if (rc != FHX_OK) return rc;
     } else {
         FHX_HIP(hipMemsetAsync(ctx->d_top_hist, 0, TOP_BINS * sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(k3_top_hist, dim3(grid_for((n + 1) / 2, 512, 256 * 4)), dim3(512), 0, ctx->stream, d_p, n, ctx->d_top_hist);
+        hipLaunchKernelGGL(k3_top_hist, dim3(grid_for((pass.n + 1) / 2, 512, 256 * 4)), dim3(512), 0, ctx->stream, pass.p, pass.n,
+                           ctx->d_top_hist);
     }
-    // the survivors' number by the histogram (DeviceWords::bh_below) goes to pinned memory right behind the cutoff: compact_pvalues waits for
-    // that copy alone, while the compaction it has already enqueued runs
+    // the survivors' number by the histogram goes to pinned memory right behind the cutoff (CutoffToHost): compact_pvalues waits for
+    // that store alone, while the compaction it has already enqueued runs
     {
         int rc = ensure_k3_host(ctx);
         if (rc == FHX_OK) rc = ensure_flags(ctx);
@@ -1161,111 +1192,86 @@ static int auto_cutoff(fhx_ctx* ctx, const double* d_p, int64_t n, double n_tota
         FHX_HIP(hipEventRecord(ctx->ev_k3, ctx->stream));
         k2_done = ctx->ev_k3;
     }
-    ctx->k3_wait_ev = k2_done;
-    CutoffToHost host;
-    host.words = ctx->h_flags + FLAG_K3;
-    host.ticket = ++ctx->ticket;
-    host.done = ctx->d_done + 1;
-    host.zero_me = counter_to_zero;
-    hipLaunchKernelGGL(k3_cutoff, dim3(1), dim3(1024), 0, ctx->stream, hist, n_total_tests, d_cutoff, &ctx->d_words->bh_below, dense_min,
-                       &ctx->d_words->k3_dense, host);
+    const CutoffToHost host{ctx->h_flags + FLAG_K3, ++ctx->ticket, ctx->d_done + 1, pass.counter};      // (zero_me: the compaction's counter)
+    launch_k3_cutoff(ctx, hist, pass.n_total_tests, pass.cutoff, &ctx->d_words->bh_below, dense_min, &ctx->d_words->k3_dense, host);
     FHX_HIP(hipGetLastError());
-    ctx->k3_ticket = host.ticket;
-    ctx->k3_kept_by_hist = true;
-    ctx->k3_counter_zeroed = counter_to_zero != nullptr;
+    pass.wait_ev = k2_done;
+    pass.ticket = host.ticket;
+    pass.kept_by_hist = true;
+    pass.counter_zeroed = true;
     return FHX_OK;
 }
 
-// rows below the cutoff -> keys[0] / vals[0] (their number in *counter and, read back, in *n_kept); every other row gets its q here
-// (dq: k3_compact<true> - no q here, compact indices as values, masks for k3_fill_q)
-static int compact_pvalues(fhx_ctx* ctx, const double* d_p, int64_t n, unsigned long long* keys[2], unsigned int* vals[2], double* d_q,
-                           unsigned long long* counter, const unsigned long long* d_cutoff, int64_t* n_kept_out,
-                           const DenseQ* dq = nullptr) {
-    if (!ctx->k3_counter_zeroed) FHX_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
-    ctx->k3_counter_zeroed = false;                   // (auto_cutoff had k3_cutoff zero it)
+// rows below the cutoff -> keys[0] / vals[0] (their number in *counter and, read back or bounded, in n_kept); every other row gets
+// its q here (pass.dq: k3_compact<true> - no q here, compact indices as values, masks for k3_fill_q)
+static int compact_pvalues(fhx_ctx* ctx, K3Pass& pass) {
+    const DenseQ* dq = pass.dq;
+    if (!pass.counter_zeroed) FHX_HIP(hipMemsetAsync(pass.counter, 0, sizeof(unsigned long long), ctx->stream));
     // one workgroup per tile, not a resident grid walking the column: 0.507 -> 0.451 ms on C3 (profiles/history/r03_x_k3_grid.txt); the
     // plain copy kernel of profiles/hbm_rate.hip shows the same (4.9 TB/s with 2048 grid-striding workgroups, 5.6 with one per
     // chunk).  The grids of k3_compact and k3_fill_q are therefore not capped.
     if (dq)
-        hipLaunchKernelGGL(k3_compact<true>, dim3(grid_for(n, CP_TILE, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, d_p, n,
-                           keys[0], vals[0], d_q, counter, d_cutoff, *dq, false, 1);
+        hipLaunchKernelGGL(k3_compact<true>, dim3(grid_for(pass.n, CP_TILE, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, pass.p, pass.n,
+                           pass.keys[0], pass.vals[0], pass.q, pass.counter, pass.cutoff, *dq, false, 1);
     if (!dq || dq->flag) {                           // (with a flag the device picks one of the two; the other returns at once)
         DenseQ off;
         if (dq) off.flag = dq->flag;
-        const bool ones = ctx->q_prefilled && d_q == ctx->d_q && d_p == ctx->d_p;
+        const bool ones = ctx->q_prefilled && pass.q == ctx->d_q && pass.p == ctx->d_p;
         // tiles per workgroup: as many as leave every CU its two workgroups several times over (a shard keeps one tile per workgroup)
-        const int64_t n_tiles = (n + CP_TILE - 1) / CP_TILE;
+        const int64_t n_tiles = (pass.n + CP_TILE - 1) / CP_TILE;
         const int per = (int)std::max<int64_t>(1, std::min<int64_t>(4, n_tiles / 2048));
-        hipLaunchKernelGGL(k3_compact<false>, dim3(grid_for((n_tiles + per - 1) / per, 1, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, d_p, n,
-                           keys[0], vals[0], d_q, counter, d_cutoff, off, ones, per);
+        hipLaunchKernelGGL(k3_compact<false>, dim3(grid_for((n_tiles + per - 1) / per, 1, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, pass.p,
+                           pass.n, pass.keys[0], pass.vals[0], pass.q, pass.counter, pass.cutoff, off, ones, per);
     }
-    if (d_q == ctx->d_q) ctx->q_prefilled = false;      // from here on the column holds this pass's q
+    if (pass.q == ctx->d_q) ctx->q_prefilled = false;      // from here on the column holds this pass's q
     // how many keys survived decides the shape of the sort.  When the cutoff came from this GPU's own histogram (auto_cutoff) the
     // number is already on its way - the histogram's bins below the cutoff bin hold exactly the rows kept here - and the host goes
     // on to enqueue the sort while the compaction runs; otherwise (sharded runs: the histogram is the all-reduced one) the counter
     // is read back behind the compaction.
     unsigned long long n_kept = 0;
-    ctx->k3_n_is_bound = false;
-    if (ctx->k3_kept_by_hist) {
+    if (pass.kept_by_hist) {
         // (an UPPER BOUND when the histogram is K2's: it counts a wave's values in the bin of the smallest, fhx_k2.hip FusedHist -
         // every launch below takes its true count from the device counter and sizes its grid for the bound)
-        ctx->k3_kept_by_hist = false;
-        FHX_HIP(hipEventSynchronize(ctx->k3_wait_ev));     // K2 is through (the host sleeps: milliseconds) ...
-        FHX_HIP(wait_ticket(ctx, FLAG_K3, ctx->k3_ticket));   // ... and k3_cutoff's one workgroup (microseconds: spin)
+        FHX_HIP(hipEventSynchronize(pass.wait_ev));          // K2 is through (the host sleeps: milliseconds) ...
+        FHX_HIP(wait_ticket(ctx, FLAG_K3, pass.ticket));     // ... and k3_cutoff's one workgroup (microseconds: spin)
         const unsigned long long by_hist = ctx->h_flags[FLAG_K3 + 1];
-        n_kept = std::min<unsigned long long>(by_hist, (unsigned long long)n);
-        ctx->k3_n_is_bound = true;
+        n_kept = std::min<unsigned long long>(by_hist, (unsigned long long)pass.n);
     } else {
-        FHX_HIP(hipMemcpyAsync(&n_kept, counter, sizeof(n_kept), hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipMemcpyAsync(&n_kept, pass.counter, sizeof(n_kept), hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipStreamSynchronize(ctx->stream));
     }
-    *n_kept_out = (int64_t)n_kept;
+    pass.n_kept = (int64_t)n_kept;
+    pass.n_is_bound = pass.kept_by_hist;
     return FHX_OK;
 }
 
-// sort of the n_kept compacted keys; the result is in buffer pair *sorted_buf.  key_hi: the bits that can be set (62 / 64, see
-// onesweep_sort); ctrl: device scratch of os_ctrl_words(n_kept, 8) words, or nullptr (then the three-launch passes run)
-static int sort_kept(fhx_ctx* ctx, unsigned long long* keys[2], unsigned int* vals[2], const unsigned long long* counter, int64_t n_kept,
-                     int* sorted_buf, int key_hi, unsigned int* ctrl, OsPending* defer = nullptr) {
+// sort of the n_kept compacted keys; the result is in buffer pair pass.sorted_buf.  defer: the one-sweep sort's second half
+// (onesweep_finish on pass.pend) is left to the caller, who first enqueues what only reads the keys
+static int sort_kept(fhx_ctx* ctx, K3Pass& pass, bool defer) {
     const char* small_env = std::getenv("FHX_K3_SMALL");          // "0": the radix passes whatever the size (A/B runs, tests)
     const bool small_off = small_env && std::atoi(small_env) == 0;
     for (int k = 0; k < 8; ++k) ctx->sort_stats[k] = 0;
-    if (n_kept <= KS_MAX_KEYS && !small_off) {                     // tile sort in LDS + merge by rank: two launches (see ks_tile_sort)
-        const int tiles = (int)std::max<int64_t>(1, (n_kept + KS_TILE - 1) / KS_TILE);
-        if (n_kept > 0) {
-            hipLaunchKernelGGL(ks_tile_sort, dim3(tiles), dim3(KS_THREADS), 0, ctx->stream, (const unsigned long long*)keys[0],
-                               (const unsigned int*)vals[0], counter, keys[1], vals[1]);
-            if (tiles > 1)
-                hipLaunchKernelGGL(ks_merge_tiles, dim3(grid_for(n_kept, 256)), dim3(256), 0, ctx->stream, (const unsigned long long*)keys[1],
-                                   (const unsigned int*)vals[1], counter, keys[0], vals[0]);
-        }
+    if (pass.n_kept <= KS_MAX_KEYS && !small_off) {                // tile sort in LDS + merge by rank: two launches (see ks_tile_sort)
+        pass.sorted_buf = pass.n_kept > 0 ? small_sort(ctx, pass.keys, pass.vals, pass.counter, pass.n_kept) : 0;
         FHX_HIP(hipGetLastError());
-        *sorted_buf = (n_kept > 0 && tiles == 1) ? 1 : 0;
         return FHX_OK;
     }
     const char* se = std::getenv("FHX_K3_SORT");                  // "legacy": round 4's count / scan / scatter passes (A/B runs)
     const bool legacy = se && std::strcmp(se, "legacy") == 0;
-    if (ctrl && !legacy && n_kept <= OS_MAX_KEYS) {
-        OsPending mine;
-        OsPending* pend = defer ? defer : &mine;
-        int rc = onesweep_launch(ctx, keys, vals, counter, n_kept, key_hi, ctrl, pend);
+    if (pass.ctrl && !legacy && pass.n_kept <= OS_MAX_KEYS) {
+        const int rc = onesweep_launch(ctx, pass.keys, pass.vals, pass.counter, pass.n_kept, pass.key_hi, pass.ctrl, &pass.pend);
         if (rc != FHX_OK) return rc;
-        *sorted_buf = pend->src;                          // (the finish never changes the buffer pair)
-        if (defer) return FHX_OK;                          // the caller finishes, after enqueueing what only reads the keys
+        pass.sorted_buf = pass.pend.src;                   // (the finish never changes the buffer pair)
+        if (defer) return FHX_OK;
         bool moved = false;
-        return onesweep_finish(ctx, pend, &moved);
+        return onesweep_finish(ctx, &pass.pend, &moved);
     }
-    return radix_passes(ctx, keys, vals, counter, sort_blocks_for(n_kept), key_hi, SORT_BITS_LARGE, 0, sorted_buf);
+    return radix_passes(ctx, pass.keys, pass.vals, pass.counter, sort_blocks_for(pass.n_kept), pass.key_hi, SORT_BITS_LARGE, 0, &pass.sorted_buf);
 }
 
-static int sort_pvalues(fhx_ctx* ctx, const double* d_p, int64_t n, unsigned long long* keys[2], unsigned int* vals[2],
-                        double* d_q, unsigned long long* counter, const unsigned long long* d_cutoff, int* sorted_buf,
-                        int64_t* n_sorted_out, int key_hi, unsigned int* ctrl) {
-    int64_t n_kept = 0;
-    const int rc = compact_pvalues(ctx, d_p, n, keys, vals, d_q, counter, d_cutoff, &n_kept);
-    if (rc != FHX_OK) return rc;
-    if (n_sorted_out) *n_sorted_out = n_kept;
-    return sort_kept(ctx, keys, vals, counter, n_kept, sorted_buf, key_hi, ctrl);
+static int sort_pvalues(fhx_ctx* ctx, K3Pass& pass) {
+    const int rc = compact_pvalues(ctx, pass);
+    return rc != FHX_OK ? rc : sort_kept(ctx, pass, false);
 }
 
 // The engine's own sort scratch: the workspace behind the K3 view (alloc_row_arrays: K3 uses 24 of its >= 48 bytes per row; the
@@ -1292,51 +1298,46 @@ static bool engine_dense_q(fhx_ctx* ctx, DenseQ* dq) {
     dq->wave_slot = reinterpret_cast<unsigned long long*>(ctx->d_work + at);
     return true;
 }
+// the engine's own p column, its sort buffers and its words (bdtrc returns values in [0, 1]: 62 key bits)
+static K3Pass engine_pass(fhx_ctx* ctx, double n_total_tests) {
+    return K3Pass{ctx->d_p, ctx->n_rows, ctx->d_keys, ctx->d_vals, ctx->d_q, &ctx->d_words->bh_kept, &ctx->d_words->bh_cutoff, n_total_tests,
+                  ctx->d_tile_max, 62, engine_sort_ctrl(ctx)};
+}
 
-// n_keys: the number of sorted keys when the host knows it (the grids then cover the keys, not the rows), else an upper bound
-// (dq: the values are compact indices - q goes to the dense array and k3_fill_q writes the column: p_rows / n_rows name it)
-static int bh_from_sorted(fhx_ctx* ctx, const unsigned long long* keys, const unsigned int* vals, int64_t n_keys,
-                          const unsigned long long* counter, double n_total_tests, double* tile_max, double* d_q,
-                          const DenseQ* dq = nullptr, const double* p_rows = nullptr, int64_t n_rows = 0) {
-    const int tiles = (int)std::max<int64_t>(1, (n_keys + BH_TILE - 1) / BH_TILE);
+// BH over the sorted survivors -> q in row order.  n_kept sizes the grids: the number of sorted keys when the host knows it, else
+// an upper bound (pass.dq: the values are compact indices - q goes to the dense array and k3_fill_q writes the column)
+static int bh_from_sorted(fhx_ctx* ctx, const K3Pass& pass) {
+    const unsigned long long* keys = pass.keys[pass.sorted_buf];
+    const DenseQ* dq = pass.dq;
+    const int tiles = (int)std::max<int64_t>(1, (pass.n_kept + BH_TILE - 1) / BH_TILE);
     unsigned long long* fault = nullptr;
-    if (ctx->k3_n_is_bound) {                           // n_keys came from the histogram: the device checks it against its counter
+    if (pass.n_is_bound) {                              // n_kept came from the histogram: the device checks it against its counter
         const int rc = ensure_flags(ctx);
         if (rc != FHX_OK) return rc;
         fault = const_cast<unsigned long long*>(ctx->h_flags + FLAG_FAULT);
     }
-    hipLaunchKernelGGL(bh_tile_max, dim3(tiles), dim3(BH_THREADS), 0, ctx->stream, keys, counter, (int64_t)0, n_total_tests,
-                       0.0, tile_max);
-    hipLaunchKernelGGL(bh_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tile_max, counter, (int64_t)0, 0.0,
-                       (double*)nullptr, n_keys, fault);
-    hipLaunchKernelGGL(bh_apply, dim3(tiles), dim3(BH_THREADS), 0, ctx->stream, keys, vals, counter, (int64_t)0,
-                       n_total_tests, 0.0, tile_max, (const double*)nullptr, d_q, dq ? dq->dense : (double*)nullptr,
-                       dq ? dq->flag : (const unsigned long long*)nullptr);
-    if (dq) {
-        hipLaunchKernelGGL(k3_fill_q, dim3(grid_for(n_rows, CP_TILE, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, p_rows, n_rows, *dq,
-                           d_q);
-    }
+    launch_bh_tile_max(ctx, tiles, keys, pass.counter, 0, pass.n_total_tests, 0.0, pass.tile_max);
+    launch_bh_scan_tiles(ctx, pass.tile_max, pass.counter, 0, 0.0, nullptr, pass.n_kept, fault);
+    launch_bh_apply(ctx, tiles, keys, pass.vals[pass.sorted_buf], pass.counter, 0, pass.n_total_tests, 0.0, pass.tile_max, nullptr, pass.q,
+                    dq ? dq->dense : nullptr, dq ? dq->flag : nullptr);
+    if (dq)
+        hipLaunchKernelGGL(k3_fill_q, dim3(grid_for(pass.n, CP_TILE, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, pass.p, pass.n, *dq, pass.q);
     FHX_HIP(hipGetLastError());
     return FHX_OK;
 }
 
 // compaction, sort and BH of one p column -> q in row order
-static int rank_and_adjust(fhx_ctx* ctx, const double* d_p, int64_t n, unsigned long long* keys[2], unsigned int* vals[2], double* d_q,
-                           unsigned long long* counter, const unsigned long long* d_cutoff, double n_total_tests, double* tile_max,
-                           int* sorted_buf, int64_t* n_sorted_out, int key_hi, unsigned int* ctrl, const DenseQ* dq = nullptr) {
-    int64_t n_kept = 0;
-    int rc = compact_pvalues(ctx, d_p, n, keys, vals, d_q, counter, d_cutoff, &n_kept, dq);
+static int rank_and_adjust(fhx_ctx* ctx, K3Pass& pass) {
+    int rc = compact_pvalues(ctx, pass);
     if (rc != FHX_OK) return rc;
-    if (n_sorted_out) *n_sorted_out = n_kept;
-    OsPending pend;
-    rc = sort_kept(ctx, keys, vals, counter, n_kept, sorted_buf, key_hi, ctrl, &pend);
+    rc = sort_kept(ctx, pass, true);
     if (rc != FHX_OK) return rc;
-    rc = bh_from_sorted(ctx, keys[*sorted_buf], vals[*sorted_buf], n_kept, counter, n_total_tests, tile_max, d_q, dq, d_p, n);
+    rc = bh_from_sorted(ctx, pass);
     if (rc != FHX_OK) return rc;
     bool moved = false;
-    rc = onesweep_finish(ctx, &pend, &moved);          // the BH scan above runs while the host reads the repair's verdict
+    rc = onesweep_finish(ctx, &pass.pend, &moved);     // the BH scan above runs while the host reads the repair's verdict
     if (rc != FHX_OK) return rc;
-    if (moved) rc = bh_from_sorted(ctx, keys[*sorted_buf], vals[*sorted_buf], n_kept, counter, n_total_tests, tile_max, d_q, dq, d_p, n);
+    if (moved) rc = bh_from_sorted(ctx, pass);
     return rc;
 }
 
@@ -1380,8 +1381,7 @@ int fhx_bh_set_cutoff_device(fhx_ctx* ctx, double n_total_tests) {
     if (!ctx || !(n_total_tests > 0)) return FHX_ERR_ARG;
     if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
     FHX_HIP(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k3_cutoff, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long*)ctx->d_top_hist, n_total_tests,
-                       &ctx->d_words->bh_cutoff, (unsigned long long*)nullptr);
+    launch_k3_cutoff(ctx, ctx->d_top_hist, n_total_tests, &ctx->d_words->bh_cutoff, nullptr, ~0ull, nullptr, CutoffToHost{});
     FHX_HIP(hipGetLastError());
     return FHX_OK;
 }
@@ -1411,16 +1411,15 @@ int fhx_bh_sort_stats(fhx_ctx* ctx, int64_t* out8) {
 
 int fhx_bh_local_sort(fhx_ctx* ctx) {
     if (!ctx) return FHX_ERR_ARG;
-    ctx->k3_kept_by_hist = false;            // (sharded runs: the cutoff comes from the all-reduced histogram, the count from the counter)
-    ctx->k3_counter_zeroed = false;          // (... and nothing has zeroed the counter ahead of the compaction)
     if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
     if (!ctx->have_p) return fail(ctx, FHX_ERR_ARG, "fhx_pvalues must run first");
     FHX_HIP(hipSetDevice(ctx->device));
-    int64_t kept = 0;
-    const int rc = sort_pvalues(ctx, ctx->d_p, ctx->n_rows, ctx->d_keys, ctx->d_vals, ctx->d_q, &ctx->d_words->bh_kept,
-                                &ctx->d_words->bh_cutoff, &ctx->sorted_buf, &kept, 62, engine_sort_ctrl(ctx));
+    // (sharded runs: the cutoff is the all-reduced histogram's, so the survivors are counted by the device counter)
+    K3Pass pass = engine_pass(ctx, 0.0);
+    const int rc = sort_pvalues(ctx, pass);
     if (rc != FHX_OK) return rc;
-    ctx->n_sorted = kept;
+    ctx->sorted_buf = pass.sorted_buf;
+    ctx->n_sorted = pass.n_kept;
     return FHX_OK;
 }
 
@@ -1451,11 +1450,9 @@ int fhx_bh_array(fhx_ctx* ctx, const double* p, int64_t n, double n_total_tests,
     unsigned int* ctrl = nullptr;
     if (n > KS_MAX_KEYS && n <= OS_MAX_KEYS) FHX_HIP(tmp.get(&ctrl, os_scratch_bytes(n)));
     FHX_HIP(hipMemcpyAsync(d_p, p, cap * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    int buf = 0;
-    unsigned long long* counter = &ctx->d_words->array_kept;
-    unsigned long long* cutoff = &ctx->d_words->array_cutoff;
-    rc = auto_cutoff(ctx, d_p, n, n_total_tests, cutoff, ~0ull, counter);
-    if (rc == FHX_OK) rc = rank_and_adjust(ctx, d_p, n, keys, vals, d_q, counter, cutoff, n_total_tests, tile_max, &buf, nullptr, 64, ctrl);
+    K3Pass pass{d_p, n, keys, vals, d_q, &ctx->d_words->array_kept, &ctx->d_words->array_cutoff, n_total_tests, tile_max, 64, ctrl};
+    rc = auto_cutoff(ctx, pass, ~0ull, nullptr);
+    if (rc == FHX_OK) rc = rank_and_adjust(ctx, pass);
     if (rc == FHX_OK) {
         FHX_HIP(hipMemcpyAsync(q, d_q, cap * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipStreamSynchronize(ctx->stream));
@@ -1485,14 +1482,15 @@ int fhx_bh(fhx_ctx* ctx, double n_total_tests) {
         dense_min = (unsigned long long)(((long double)ctx->n_rows * K3_DENSE_PERCENT + 99) / 100);
         dq.flag = &ctx->d_words->k3_dense;
     }
-    int rc = auto_cutoff(ctx, ctx->d_p, ctx->n_rows, n_total_tests, &ctx->d_words->bh_cutoff, dense_min, &ctx->d_words->bh_kept, ctx->ev[4]);
+    K3Pass pass = engine_pass(ctx, n_total_tests);
+    pass.dq = dense ? &dq : nullptr;
+    int rc = auto_cutoff(ctx, pass, dense_min, ctx->ev[4]);
     if (rc != FHX_OK) return rc;
-    int64_t kept = 0;
-    rc = rank_and_adjust(ctx, ctx->d_p, ctx->n_rows, ctx->d_keys, ctx->d_vals, ctx->d_q, &ctx->d_words->bh_kept, &ctx->d_words->bh_cutoff, n_total_tests,
-                         ctx->d_tile_max, &ctx->sorted_buf, &kept, 62, engine_sort_ctrl(ctx), dense ? &dq : nullptr);
+    rc = rank_and_adjust(ctx, pass);
     if (rc != FHX_OK) return rc;
-    ctx->n_sorted = ctx->k3_n_is_bound ? -2 : kept;      // -2: fhx_n_sorted reads the device counter when somebody asks
-    ctx->k3_last_kept = kept;                            // (the histogram's bound or the exact number: either serves the guess above)
+    ctx->sorted_buf = pass.sorted_buf;
+    ctx->n_sorted = pass.n_is_bound ? -2 : pass.n_kept;  // -2: fhx_n_sorted reads the device counter when somebody asks
+    ctx->k3_last_kept = pass.n_kept;                     // (the histogram's bound or the exact number: either serves the guess above)
     ctx->k3_last_rows = ctx->n_rows;
     FHX_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
     ctx->ev_valid[2] = true;
@@ -1514,14 +1512,11 @@ int fhx_bh_apply_sorted(fhx_ctx* ctx, const void* d_sorted_keys, int64_t n, int6
     double* tile_max = nullptr;
     FHX_HIP(hipMalloc(&tile_max, ((size_t)tiles + 1) * sizeof(double)));
     const unsigned long long* keys = (const unsigned long long*)d_sorted_keys;
-    hipLaunchKernelGGL(bh_tile_max, dim3(tiles), dim3(BH_THREADS), 0, ctx->stream, keys, (const unsigned long long*)nullptr, n,
-                       n_total_tests, (double)global_rank0, tile_max);
-    hipLaunchKernelGGL(bh_scan_tiles, dim3(1), dim3(1024), 0, ctx->stream, tile_max, (const unsigned long long*)nullptr, n,
-                       carry_in, tile_max + tiles);
+    launch_bh_tile_max(ctx, tiles, keys, nullptr, n, n_total_tests, (double)global_rank0, tile_max);
+    launch_bh_scan_tiles(ctx, tile_max, nullptr, n, carry_in, tile_max + tiles, -1, nullptr);
     if (d_q_sorted)
-        hipLaunchKernelGGL(bh_apply, dim3(tiles), dim3(BH_THREADS), 0, ctx->stream, keys, (const unsigned int*)nullptr,
-                           (const unsigned long long*)nullptr, n, n_total_tests, (double)global_rank0, tile_max,
-                           (const double*)nullptr, (double*)d_q_sorted);
+        launch_bh_apply(ctx, tiles, keys, nullptr, nullptr, n, n_total_tests, (double)global_rank0, tile_max, nullptr, (double*)d_q_sorted,
+                        nullptr, nullptr);
     double total = 0.0;
     FHX_HIP(hipMemcpyAsync(&total, tile_max + tiles, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
