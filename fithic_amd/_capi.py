@@ -124,6 +124,8 @@ SYMBOLS = {
     "fhx_debug_contfrac": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _F64P, _F64P, _F64P, ctypes.c_int64, _F64P]),
     "fhx_debug_lean_div": (ctypes.c_int, [_P, _F64P, _F64P, ctypes.c_int64, _F64P]),
     "fhx_debug_classify": (ctypes.c_int, [_P, ctypes.c_double, _I32P, _F64P, ctypes.c_int64, _I32P, _I32P, _F64P]),
+    "fhx_debug_k2_rows": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_double, _I32P, _F64P, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64,
+                                         ctypes.c_int32, _F64P, _I64P, _I64P, _I64P, ctypes.c_int64]),
     "fhx_bh_array": (ctypes.c_int, [_P, _F64P, ctypes.c_int64, ctypes.c_double, _F64P]),
     "fhx_bh_top_hist": (ctypes.c_int, [_P, _I64P, ctypes.c_int64]),
     "fhx_bh_set_cutoff": (ctypes.c_int, [_P, _I64P, ctypes.c_int64, ctypes.c_double]),
@@ -733,6 +735,24 @@ class Context:
                                                _ptr(t, ctypes.c_int32), _ptr(a, ctypes.c_int32),
                                                _ptr(thr, ctypes.c_double) if thresholds else None))
         return (t, a, thr) if thresholds else (t, a)
+
+    def debug_k2_rows(self, n_intra, n_inter, count, prior, is_inter, nonfixed=False):
+        """The K2 launches of a pass on chosen rows (fhx_debug_k2_rows; the context's contact rows are discarded): returns
+        (p, rows per class as k2_class_rows, rows the heavy kernel handed back, the fused key histogram of 4096 bins)."""
+        c = _i32(count)
+        pr = np.ascontiguousarray(prior, np.float64)
+        it = np.ascontiguousarray(is_inter, np.uint8)
+        if not (len(c) == len(pr) == len(it)):
+            raise ValueError("count, prior and is_inter must have one entry per row")
+        p = np.empty(len(c), np.float64)
+        cls = (ctypes.c_int64 * 5)()
+        redo = ctypes.c_int64(0)
+        hist = np.zeros(4096, np.int64)
+        self._check(self._L.fhx_debug_k2_rows(self._h, float(n_intra), float(n_inter), _ptr(c, ctypes.c_int32), _ptr(pr, ctypes.c_double),
+                                              _ptr(it, ctypes.c_uint8), len(c), int(bool(nonfixed)), _ptr(p, ctypes.c_double), cls,
+                                              ctypes.byref(redo), _ptr(hist, ctypes.c_int64), len(hist)))
+        by_class = dict(zip(("pseries", "cf_bcf", "cf_bd", "cf_swapped", "closed_pow"), [int(v) for v in cls]))
+        return p, by_class, redo.value, hist
 
     def debug_contfrac(self, kind, lazy, a, b, x):
         a, b, x = (np.ascontiguousarray(v, np.float64) for v in (a, b, x))

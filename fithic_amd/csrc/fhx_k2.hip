@@ -1059,12 +1059,13 @@ struct K2Plan {
     int64_t k2_n = 0, cap_s = 0;        // rows K2 classifies (the context's, or the table's virtual ones); entries per queue shard
     int heavy_rows = 4, n_shards = 0;   // rows per lane of k2h_heavy (not used under legacy_heavy); queue shards for k2_n rows
 };
-static K2Plan plan_k2(const fhx_ctx* ctx, const K2Params& P) {
+// allow_memo = false: the caller's rows are not a pass's (fhx_debug_k2_rows) - every row is classified, whatever the context holds
+static K2Plan plan_k2(const fhx_ctx* ctx, const K2Params& P, bool allow_memo = true) {
     K2Plan plan;
     // no bias table, fixed-size loci: evaluate a (distance, count) table instead of every row (see k2_memo_rows)
     plan.memo_intra = ctx->prm.mode != FHX_MODE_INTER_ONLY;
     plan.memo_inter = ctx->prm.mode != FHX_MODE_INTRA_ONLY;
-    if (!ctx->have_bias && !ctx->nonfixed && !getenv("FHX_NO_MEMO")) {
+    if (allow_memo && !ctx->have_bias && !ctx->nonfixed && !getenv("FHX_NO_MEMO")) {
         plan.memo_nd = plan.memo_intra ? (int)(P.hi_idx - P.lo_idx + 1) : 0;
         const int64_t budget = std::min<int64_t>(1ll << 24, ctx->n_rows / 4);
         const int64_t per_count = (int64_t)plan.memo_nd + (plan.memo_inter ? 1 : 0);
@@ -1209,6 +1210,22 @@ static int launch_k2(fhx_ctx* ctx, const K2Plan& plan, const K2Params& P, const 
     return FHX_OK;
 }
 
+// K2 collects K3's key histogram while it stores p: the context's table, zeroed unless fhx_pass_stats already did
+static int k2_fused_hist(fhx_ctx* ctx, bool prezeroed, K2Params* P) {
+    if (!ctx->d_k2_hist) FHX_HIP(hipMalloc(&ctx->d_k2_hist, TOP_BINS * sizeof(unsigned long long)));
+    if (!prezeroed) FHX_HIP(hipMemsetAsync(ctx->d_k2_hist, 0, TOP_BINS * sizeof(unsigned long long), ctx->stream));
+    P->top_hist = ctx->d_k2_hist;
+    return FHX_OK;
+}
+
+// queue layout and launches over the rows P describes: the one place both fhx_pvalues and the fhx_debug_k2_rows test hook go through
+static int run_k2(fhx_ctx* ctx, const K2Plan& plan, const K2Params& P, bool prezeroed) {
+    K2Queues Q;
+    const int rc = k2_queue_layout(ctx, plan, prezeroed, &Q);
+    if (rc != FHX_OK) return rc;
+    return plan.small_n ? launch_k2<true>(ctx, plan, P, Q) : launch_k2<false>(ctx, plan, P, Q);
+}
+
 // the table path hands the table's p to the real rows (P_rows) and evaluates what the table does not cover; then the pass is closed
 static int finish_k2(fhx_ctx* ctx, const K2Plan& plan, const K2Params& P_rows, const K2Memo& M) {
     if (plan.memo_cap >= 0) {
@@ -1259,17 +1276,14 @@ int fhx_pvalues(fhx_ctx* ctx) {
     // K3's key histogram rides on K2's stores of p - except on the table path, whose class kernels store table entries
     ctx->k2_hist_valid = false;
     if (plan.memo_cap < 0) {
-        if (!ctx->d_k2_hist) FHX_HIP(hipMalloc(&ctx->d_k2_hist, TOP_BINS * sizeof(unsigned long long)));
-        if (!prezeroed) FHX_HIP(hipMemsetAsync(ctx->d_k2_hist, 0, TOP_BINS * sizeof(unsigned long long), ctx->stream));
-        P.top_hist = ctx->d_k2_hist;
+        const int rh = k2_fused_hist(ctx, prezeroed, &P);
+        if (rh != FHX_OK) return rh;
         ctx->k2_hist_valid = true;
     }
     const K2Params P_rows = P;             // the context's rows, whatever K2 classifies
     K2Memo M;
-    K2Queues Q;
     int rc = plan.memo_cap >= 0 ? k2_table_rows(ctx, plan, &M, &P) : FHX_OK;
-    if (rc == FHX_OK) rc = k2_queue_layout(ctx, plan, prezeroed, &Q);
-    if (rc == FHX_OK) rc = plan.small_n ? launch_k2<true>(ctx, plan, P, Q) : launch_k2<false>(ctx, plan, P, Q);
+    if (rc == FHX_OK) rc = run_k2(ctx, plan, P, prezeroed);
     return rc == FHX_OK ? finish_k2(ctx, plan, P_rows, M) : rc;
 }
 
@@ -1306,6 +1320,136 @@ int fhx_bdtrc_array(fhx_ctx* ctx, double n_total, const int32_t* count, const do
     dev_free(d_prior);
     dev_free(d_out);
     dev_free(d_count);
+    return FHX_OK;
+}
+
+// Test hook: the launches of a pass (plan_k2's rules, k2_queue_layout, launch_k2 - through run_k2, as fhx_pvalues) on rows the caller
+// chose.  How a supplied prior reaches the kernels bit for bit: the bias table is on with slot_bias[0] = 1.0 and slot_bias[i + 1] =
+// prior[i]; row i is (l1 = i + 1, l2 = 0), or l2 = ~0 for the inter-chromosomal binomial; prior_lut is the single entry 1.0 (-r 0: the
+// spline table is the single point (0, 1.0) and every slot_mid is 0), inter_chr_prob is 1.0 and the distance window is everything.
+// row_prior / rows_prior_fixed then form 1.0 * (prior * 1.0), and a multiplication by 1.0 returns its other operand unchanged - NaN
+// and -0.0 included.  A negative prior would read as a discarded bias (p = 1): refused.
+int fhx_debug_k2_rows(fhx_ctx* ctx, double n_intra, double n_inter, const int32_t* count, const double* prior, const uint8_t* is_inter,
+                      int64_t n, int32_t nonfixed, double* p_out, int64_t* class_rows5, int64_t* n_redo, int64_t* top_hist,
+                      int64_t hist_cap) {
+    if (!ctx || n < 0 || n > (1ll << 22) || (n > 0 && (!count || !prior || !is_inter || !p_out))) return FHX_ERR_ARG;
+    if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
+    if (!std::isfinite(n_intra) || !std::isfinite(n_inter) || n_intra < 0.0 || n_inter < 0.0)
+        return fail(ctx, FHX_ERR_ARG, "fhx_debug_k2_rows: totals must be finite and >= 0");
+    if (top_hist && hist_cap < K2_HIST_BINS) return fail(ctx, FHX_ERR_ARG, "fhx_debug_k2_rows: the key histogram has 4096 bins");
+    int64_t mc = 1;
+    for (int64_t i = 0; i < n; ++i) {
+        if (count[i] < 0 || count[i] > (1 << 20)) return fail(ctx, FHX_ERR_ARG, "fhx_debug_k2_rows: counts must be in [0, 2^20]");
+        if (prior[i] < 0.0) return fail(ctx, FHX_ERR_ARG, "fhx_debug_k2_rows: a negative prior would read as a discarded bias");
+        mc = std::max<int64_t>(mc, count[i]);
+    }
+    if (class_rows5) std::fill(class_rows5, class_rows5 + K2_QUEUES + 1, (int64_t)0);
+    if (n_redo) *n_redo = 0;
+    if (top_hist) std::fill(top_hist, top_hist + hist_cap, (int64_t)0);
+    if (n == 0) return FHX_OK;
+    FHX_HIP(hipSetDevice(ctx->device));
+    // integral totals are narrowed as fhx_bdtrc_array narrows them (bdtrc_total)
+    if (std::fabs(n_intra) < 9.2e18 && n_intra == std::floor(n_intra)) n_intra = bdtrc_total(ctx->prm, (long long)n_intra);
+    if (std::fabs(n_inter) < 9.2e18 && n_inter == std::floor(n_inter)) n_inter = bdtrc_total(ctx->prm, (long long)n_inter);
+    // The context's contacts go: row arrays and workspace are sized anew for n rows, every have_* mark is cleared (alloc_row_arrays),
+    // and at the end the rows are dropped again - until the next load every stage call refuses ("no contact rows loaded")
+    FHX_HIP(hipStreamSynchronize(ctx->stream));
+    before_rerecord(ctx, 1);
+    int rc = alloc_row_arrays(ctx, n, 1);
+    if (rc != FHX_OK) return rc;
+    auto drop_rows = [&]() {
+        dev_free(ctx->d_loc1);
+        dev_free(ctx->d_loc2);
+        dev_free(ctx->d_count);
+        ctx->n_rows = 0;
+        ctx->k2_prezeroed = false;
+        ctx->k2_hist_valid = false;
+        ctx->ev_valid[1] = false;                     // the K2 event pairs describe no pass
+        ctx->ev_folded[1] = ctx->ev_folded[3] = true;
+    };
+    struct DropAtExit {
+        std::function<void()> f;
+        ~DropAtExit() { f(); }
+    } at_exit{drop_rows};
+    const size_t cap = std::max<size_t>(4, ((size_t)n + 3) / 4 * 4);
+    std::vector<int32_t> l1(cap, 0), l2(cap, 0), cnt(cap, 0);
+    std::vector<double> bias((size_t)n + 1, 1.0);
+    for (int64_t i = 0; i < n; ++i) {
+        l1[(size_t)i] = (int32_t)(i + 1);
+        l2[(size_t)i] = is_inter[i] ? ~0 : 0;
+        cnt[(size_t)i] = count[i];
+        bias[(size_t)i + 1] = prior[i];
+    }
+    std::vector<double> lb[2], ib[2];
+    build_lbeta_table(n_intra, mc, lb[0], ib[0]);
+    build_lbeta_table(n_inter, mc, lb[1], ib[1]);
+    DeviceScratch G;
+    double *d_bias = nullptr, *d_one = nullptr, *d_zero = nullptr, *d_lb[2] = {nullptr, nullptr}, *d_ib[2] = {nullptr, nullptr};
+    int32_t* d_mid = nullptr;
+    FHX_HIP(G.get(&d_bias, bias.size() * sizeof(double)));
+    FHX_HIP(G.get(&d_one, sizeof(double)));
+    FHX_HIP(G.get(&d_zero, sizeof(double)));
+    FHX_HIP(G.get(&d_mid, bias.size() * sizeof(int32_t)));
+    const double one = 1.0;
+    FHX_HIP(hipMemcpyAsync(d_bias, bias.data(), bias.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(d_one, &one, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    FHX_HIP(hipMemsetAsync(d_zero, 0, sizeof(double), ctx->stream));
+    FHX_HIP(hipMemsetAsync(d_mid, 0, bias.size() * sizeof(int32_t), ctx->stream));
+    for (int b = 0; b < 2; ++b) {
+        FHX_HIP(G.get(&d_lb[b], lb[b].size() * sizeof(double)));
+        FHX_HIP(G.get(&d_ib[b], ib[b].size() * sizeof(double)));
+        FHX_HIP(hipMemcpyAsync(d_lb[b], lb[b].data(), lb[b].size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        FHX_HIP(hipMemcpyAsync(d_ib[b], ib[b].data(), ib[b].size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    FHX_HIP(hipMemcpyAsync(ctx->d_loc1, l1.data(), cap * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(ctx->d_loc2, l2.data(), cap * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(ctx->d_count, cnt.data(), cap * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    K2Params P{};
+    P.loc1 = ctx->d_loc1;
+    P.loc2 = ctx->d_loc2;
+    P.count = ctx->d_count;
+    P.slot_bias = d_bias;
+    P.no_bias = false;
+    P.prior_lut = d_one;
+    P.lut_len = 1;
+    P.intra = dev::BinomTables{d_lb[0], d_ib[0], n_intra, (n_intra + 1.0) < dev::kMaxGam};
+    P.inter = dev::BinomTables{d_lb[1], d_ib[1], n_inter, (n_inter + 1.0) < dev::kMaxGam};
+    P.total_intra = n_intra;
+    P.total_inter = n_inter;
+    P.inter_chr_prob = 1.0;
+    P.outlier_thres = 0.0;
+    P.lo_idx = 0;
+    P.hi_idx = INT32_MAX;
+    P.mode = FHX_MODE_ALL;
+    P.n = n;
+    P.p = ctx->d_p;
+    P.outlier = ctx->d_outlier;
+    P.nonfixed = nonfixed ? 1 : 0;
+    P.slot_mid = d_mid;
+    P.table_x = d_zero;
+    P.table_y = d_one;
+    P.n_table = 1;
+    P.min_x = P.max_x = 0.0;
+    P.dist_low = 0;
+    P.dist_up = LLONG_MAX;
+    const K2Plan plan = plan_k2(ctx, P, false);
+    rc = k2_fused_hist(ctx, false, &P);
+    if (rc == FHX_OK) rc = run_k2(ctx, plan, P, false);
+    if (rc != FHX_OK) return rc;
+    FHX_HIP(hipGetLastError());
+    FHX_HIP(hipMemcpyAsync(p_out, ctx->d_p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<unsigned long long> part((size_t)(K2_QUEUES + 1) * K2_MAX_SHARDS), hist((size_t)TOP_BINS);
+    unsigned long long redo = 0;
+    FHX_HIP(hipMemcpyAsync(part.data(), ctx->d_k2_counts, part.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(hist.data(), ctx->d_k2_hist, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(&redo, &ctx->d_words->k2_redo, sizeof(redo), hipMemcpyDeviceToHost, ctx->stream));
+    FHX_HIP(hipStreamSynchronize(ctx->stream));
+    if (class_rows5)
+        for (int k = 0; k <= K2_QUEUES; ++k)
+            for (int sh = 0; sh < plan.n_shards; ++sh) class_rows5[k] += (int64_t)part[(size_t)k * K2_MAX_SHARDS + sh];
+    if (n_redo) *n_redo = plan.legacy_heavy ? 0 : (int64_t)redo;       // the per-lane kernel hands nothing back
+    if (top_hist)
+        for (int64_t b = 0; b < std::min<int64_t>(hist_cap, TOP_BINS); ++b) top_hist[b] = (int64_t)hist[(size_t)b];
     return FHX_OK;
 }
 

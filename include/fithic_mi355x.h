@@ -330,6 +330,22 @@ int fhx_bh_array(fhx_ctx* ctx, const double* p, int64_t n, double n_total_tests,
  * context's parameters say FHX_TOTALS_WIDE. */
 int fhx_bdtrc_array(fhx_ctx* ctx, double n_total, const int32_t* count, const double* prior, int64_t n, double* out);
 
+/* Test hook: the K2 launches of a pass - the classification kernel, the closed form, the class kernels, the count-sorted
+ * 300-iteration class with its hand-back - on n rows the caller chose: row i has contact count count[i], prior prior[i] and uses
+ * the inter-chromosomal binomial (total n_inter) where is_inter[i] != 0, else the intra one (total n_intra).  The launches are the
+ * ones fhx_pvalues makes, planned by the same rules (kernels with Cephes' pow branch when a total is below 171, rows per lane of the
+ * heavy kernel by row count or FHX_K2H_ROWS, FHX_K2_LEGACY), without the no-bias table path and with the fused key histogram on;
+ * nonfixed = 0: the fixed-size classification kernel, 1: the -r 0 one.  Every prior reaches the kernels bit for bit (the .hip file
+ * says how).  Totals are narrowed like fhx_bdtrc_array's.  p_out (n): the p-values, which must equal fhx_bdtrc_array's bit for bit;
+ * class_rows5 (optional): as fhx_k2_class_rows; n_redo (optional): rows the uniform heavy kernel handed back to the per-lane loop;
+ * top_hist (optional, hist_cap >= 4096 entries): the histogram of key(p) >> 50 that K2 gathered for K3 (p = 1.0 is bin 4092;
+ * values the heavy kernel stored may be counted in a lower bin than their own, never a higher one).
+ * FHX_ERR_ARG for n > 2^22, a count outside [0, 2^20], a negative prior (NaN is accepted), a total that is negative or not finite.
+ * The call DISCARDS the contact rows of the context: afterwards every stage call refuses until rows are loaded again. */
+int fhx_debug_k2_rows(fhx_ctx* ctx, double n_intra, double n_inter, const int32_t* count, const double* prior, const uint8_t* is_inter,
+                      int64_t n, int32_t nonfixed, double* p_out, int64_t* class_rows5, int64_t* n_redo, int64_t* top_hist,
+                      int64_t hist_cap);
+
 /* Test hook: the raw Cephes continued fraction (kind 0 = incbcf, 1 = incbd) of K2 evaluated element-wise on the GPU,
  * either with Cephes' literal convergence test (lazy = 0) or with the division-free test K2 uses (lazy = 1); the two
  * must agree bit for bit.  Host arrays in and out. */

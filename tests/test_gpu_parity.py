@@ -139,7 +139,10 @@ def test_class_threshold_table_equals_incbet_predicates(ctx):
     """k2_classify reads bdtrc_class as five thresholds on the prior per count (dev::cls_row, bisected on the device with the
     predicates of Cephes' incbet).  Table and arithmetic must agree on EVERY double: random priors over twelve decades, the
     domain edges, and - where a wrong threshold would show - each threshold itself with its 3 neighbours on both sides, for
-    Hi-C-sized and small binomials (the small ones exercise the direct orientation and both power-series tests)."""
+    Hi-C-sized and small binomials (the small ones exercise the direct orientation and both power-series tests).
+    What this covers is cls_row / cls_lookup against bdtrc_class, through the k_debug_classify kernel.  k2_classify itself runs
+    bdtrc_class_tb with the orientation threshold from its per-workgroup LDS table (counts < K2_TB_COUNTS, intra and inter halves):
+    that is tested, on the same thresholds and neighbours, by test_gpu_k2_pass.py::test_class_boundaries."""
     rng = np.random.default_rng(21)
     for n_total in (645040870.0, 7150761687.0, 1.0e6, 5000.0, 170.0, 3.0):
         counts = np.unique(np.concatenate([np.arange(0, 40), rng.integers(1, 5000, 300), [int(min(n_total, 2e9)) - 1, int(min(n_total, 2e9)),
