@@ -210,12 +210,22 @@ SYMBOLS = {
     "fhx_cni_load": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I64P, _I64P, _I64P, _F64P, _F64P, ctypes.c_int64, ctypes.c_int64, _I64P]),
     "fhx_cni_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "fhx_cni_get_records": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _I64P]),
+    # HiC-Pro matrix -> contact columns and per-bin totals (fithic/utils/HiCPro2FitHiC.py)
+    "fhx_hp_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "fhx_hp_destroy": (None, [ctypes.c_void_p]),
+    "fhx_hp_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
+    "fhx_hp_load_bins": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _I32P, _I32P, ctypes.c_int64]),
+    "fhx_hp_parse_matrix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, _I64P, _I32P, _I64P, _I64P]),
+    "fhx_hp_totals": (ctypes.c_int, [ctypes.c_void_p, _I64P]),
+    "fhx_hp_fetch_rows": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
+    "fhx_hp_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
+    "fhx_hp_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
 }
 
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
 # not recompile K1, K3, the Knight-Ruiz path or the host stages.  Flags are the same for every unit - -ffp-contract=off matters
 # for bit-exactness on the host (FITPACK, lgamma tables) as much as on the device (fhx_bdtrc.hpp).
-SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
+SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
 COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread"]
 LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-lz", "-ldl"]
 OBJ_DIR = os.path.join(CSRC, "_obj")
@@ -239,7 +249,7 @@ def build(force=False):
     newest_shared = max(os.path.getmtime(p) for p in shared)
     compiles, link = build_commands()
     # a library newer than every source and header is current whatever csrc/_obj holds: the objects are git- and gpurun-ignored,
-    # so a fresh checkout or the GPU box has the .so without them and must not recompile nine units to find that out
+    # so a fresh checkout or the GPU box has the .so without them and must not recompile ten units to find that out
     newest_src = max([newest_shared] + [os.path.getmtime(os.path.join(CSRC, f)) for f in SOURCES])
     if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= newest_src:
         return LIB_PATH
@@ -1218,3 +1228,76 @@ class CniContext:
         if info.selected:
             self._chk(self.L.fhx_cni_get_records(self.h, out.ctypes.data_as(ctypes.c_void_p), len(out), None))
         return out, info
+
+
+# ---- HiC-Pro matrix -> contact columns and per-bin totals (fhx_hp_*) ------------------------------------------------------
+(HP_OK, HP_TOKENS, HP_INDEX, HP_COUNT, HP_FRACTION, HP_ABSENT, HP_BYTES, HP_LONG_LINE, HP_TOTAL, HP_INTERNAL) = range(10)
+
+
+class HpRefused(FhxError):
+    """fhx_hp_parse_matrix refused the file: why = one of HP_*, line = the smallest offending 1-based line (0: none), index = the
+    absent index for HP_ABSENT"""
+
+    def __init__(self, code, message, why, line, index):
+        super().__init__(code, message)
+        self.why, self.line, self.index = int(why), int(line), int(index)
+
+
+class HpContext:
+    """A HiC-Pro matrix parsed and accumulated on one GPU (fhx_hp_*).  Raises without the library or a GPU."""
+
+    def __init__(self, device=0):
+        self.L = lib()
+        self.h = ctypes.c_void_p()
+        self.n_slots = self.n_rows = 0
+        rc = self.L.fhx_hp_create(int(device), ctypes.byref(self.h))
+        if rc != FHX_OK:
+            self.h = None
+            raise FhxError(rc, "fhx_hp_create(device=%d) failed: no usable MI355X / HIP runtime" % device)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fhx_hp_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _chk(self, rc):
+        if rc != FHX_OK:
+            raise FhxError(rc, (self.L.fhx_hp_last_error(self.h) or b"").decode())
+
+    def load_bins(self, index_base, chr_ids, mids):
+        """dense table over [index_base, index_base + len(chr_ids)); chr id -1 = index absent from the bed"""
+        c, m = _i32(chr_ids), _i32(mids)
+        if len(c) != len(m):
+            raise ValueError("chr_ids and mids differ in length")
+        self._chk(self.L.fhx_hp_load_bins(self.h, int(index_base), _ptr(c, ctypes.c_int32), _ptr(m, ctypes.c_int32), len(c)))
+        self.n_slots, self.n_rows = len(c), 0
+
+    def parse_matrix(self, path):
+        """-> number of rows; HpRefused for a file outside the device grammar or with an index the bed does not list"""
+        n, why, line, index = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self.n_rows = 0
+        rc = self.L.fhx_hp_parse_matrix(self.h, os.fsencode(path), ctypes.byref(n), ctypes.byref(why), ctypes.byref(line), ctypes.byref(index))
+        if rc != FHX_OK and why.value != HP_OK:
+            raise HpRefused(rc, (self.L.fhx_hp_last_error(self.h) or b"").decode(), why.value, line.value, index.value)
+        self._chk(rc)
+        self.n_rows = n.value
+        return self.n_rows
+
+    def totals(self):
+        out = np.zeros(self.n_slots, np.int64)
+        self._chk(self.L.fhx_hp_totals(self.h, _ptr(out, ctypes.c_int64)))
+        return out
+
+    def fetch_rows(self):
+        """(chr1, mid1, chr2, mid2, count), int32, file order"""
+        cols = [np.zeros(self.n_rows, np.int32) for _ in range(5)]
+        self._chk(self.L.fhx_hp_fetch_rows(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
+        return cols
+
+    def device_ptrs(self):
+        return [self.L.fhx_hp_device_ptr(self.h, k) or 0 for k in range(5)]
+
+    def stream(self):
+        return self.L.fhx_hp_stream(self.h) or 0

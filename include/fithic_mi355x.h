@@ -583,6 +583,39 @@ int fhx_cni_run(fhx_cni* cn, int32_t connectivity, int32_t top_percent, int32_t 
                 fhx_cni_info* info);
 int fhx_cni_get_records(const fhx_cni* cn, fhx_cni_record* out, int64_t capacity, int64_t* n_out);
 
+/* ---- HiC-Pro matrix -> Fit-Hi-C contact columns and per-bin totals (fithic/utils/HiCPro2FitHiC.py:33-53; csrc/fhx_hicpro.hip).
+ * One handle per GPU, independent of fhx_ctx.  The caller reads the bed file (one line per bin) and passes the bins as a dense
+ * table over [index_base, index_base + n_slots): chr_id = -1 marks an index the bed does not list.  The matrix file (plain text,
+ * `i j count` per line) is uploaded as it is and parsed by kernels; the five contact columns (chr1, mid1, chr2, mid2, count: int32,
+ * file order) and the totals (every line adds its count to bin i and to bin j, exact 64-bit integers) stay in HBM.
+ * Only the regular file is taken: ASCII, exactly three tokens per line, i and j = [+-]digits (10 digits at most, within int32), count
+ * = digits[.digits] (15 digits at most, integer part within int32, every fraction digit 0); \r\n and a last line without newline
+ * are fine.  Anything else is refused with nothing left loaded: *why = one of FHX_HP_*, *bad_line = the smallest offending 1-based
+ * line number.  Return value: FHX_ERR_REFERENCE_EXIT for FHX_HP_ABSENT (the reference raises KeyError(*bad_index) there),
+ * FHX_ERR_UNSUPPORTED for the other reasons. */
+#define FHX_HP_OK 0
+#define FHX_HP_TOKENS 1            /* not exactly three tokens (an empty line included) */
+#define FHX_HP_INDEX 2             /* i or j is not [+-]digits of at most 10 digits within int32 */
+#define FHX_HP_COUNT 3             /* the count is not digits[.digits] of at most 15 digits with the integer part within int32 */
+#define FHX_HP_FRACTION 4          /* a count with a fraction digit other than 0 */
+#define FHX_HP_ABSENT 5            /* an index outside the table or absent from the bed */
+#define FHX_HP_BYTES 6             /* a NUL, a non-ASCII byte, a \r that is not followed by \n */
+#define FHX_HP_LONG_LINE 7         /* a line of more than 4096 bytes */
+#define FHX_HP_TOTAL 8             /* a bin total of 2^53 or more: the reference's float sum would have rounded (no line number) */
+#define FHX_HP_INTERNAL 9          /* a device-side consistency check failed */
+typedef struct fhx_hp fhx_hp;
+int fhx_hp_create(int device, fhx_hp** out);
+void fhx_hp_destroy(fhx_hp* hp);
+const char* fhx_hp_last_error(const fhx_hp* hp);
+int fhx_hp_load_bins(fhx_hp* hp, int64_t index_base, const int32_t* chr_id, const int32_t* mid, int64_t n_slots);
+int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* why, int64_t* bad_line, int64_t* bad_index);
+int fhx_hp_totals(fhx_hp* hp, int64_t* tcc);                       /* n_slots values */
+int fhx_hp_fetch_rows(fhx_hp* hp, int32_t* chr1, int32_t* mid1, int32_t* chr2, int32_t* mid2, int32_t* count);   /* n_rows each */
+/* the columns in HBM (which 0..4 = chr1, mid1, chr2, mid2, count) and the stream they were written on, for fhx_load_pairs_device;
+ * valid until the next fhx_hp_parse_matrix / fhx_hp_load_bins / fhx_hp_destroy */
+void* fhx_hp_device_ptr(fhx_hp* hp, int32_t which);
+void* fhx_hp_stream(fhx_hp* hp);
+
 #ifdef __cplusplus
 }
 #endif
