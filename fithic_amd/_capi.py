@@ -220,12 +220,25 @@ SYMBOLS = {
     "fhx_hp_fetch_rows": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
     "fhx_hp_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
     "fhx_hp_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    # HiC-Pro allValidPairs -> contact counts (fithic/utils/validPairs2FitHiC-fixedSize.sh)
+    "fhx_vp_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "fhx_vp_destroy": (None, [ctypes.c_void_p]),
+    "fhx_vp_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
+    "fhx_vp_bin_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64, _I64P, _I32P, _I64P]),
+    "fhx_vp_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P, _I32P]),
+    "fhx_vp_name": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_int32]),
+    "fhx_vp_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
+    "fhx_vp_fetch_cells": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
+    "fhx_vp_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
+    "fhx_vp_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "fhx_vp_write_contacts": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, _I32P, _I32P, _I32P, _I32P,
+                                             _I32P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
 }
 
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
 # not recompile K1, K3, the Knight-Ruiz path or the host stages.  Flags are the same for every unit - -ffp-contract=off matters
 # for bit-exactness on the host (FITPACK, lgamma tables) as much as on the device (fhx_bdtrc.hpp).
-SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
+SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
 COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread"]
 LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-lz", "-ldl"]
 OBJ_DIR = os.path.join(CSRC, "_obj")
@@ -1301,3 +1314,88 @@ class HpContext:
 
     def stream(self):
         return self.L.fhx_hp_stream(self.h) or 0
+
+
+(VP_OK, VP_TOKENS, VP_NAME, VP_POSITION, VP_RANGE, VP_BYTES, VP_LONG_LINE, VP_NAMES, VP_COUNT, VP_RES, VP_INTERNAL, VP_PAIRS) = range(12)
+VP_STAGE_NAMES = ("read_upload", "newline_scan", "parse", "names_keys", "sort", "cells")
+
+
+class VpRefused(FhxError):
+    """fhx_vp_bin_file refused the file: why = one of VP_*, line = the smallest offending 1-based line (0: the reason belongs to
+    no line)"""
+
+    def __init__(self, code, message, why, line):
+        super().__init__(code, message)
+        self.why, self.line = int(why), int(line)
+
+
+class VpContext:
+    """A validPairs file binned, sorted and counted on one GPU (fhx_vp_*).  Raises without the library or a GPU."""
+
+    def __init__(self, device=0):
+        self.L = lib()
+        self.h = ctypes.c_void_p()
+        self.n_cells = 0
+        rc = self.L.fhx_vp_create(int(device), ctypes.byref(self.h))
+        if rc != FHX_OK:
+            self.h = None
+            raise FhxError(rc, "fhx_vp_create(device=%d) failed: no usable MI355X / HIP runtime" % device)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fhx_vp_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _chk(self, rc):
+        if rc != FHX_OK:
+            raise FhxError(rc, (self.L.fhx_vp_last_error(self.h) or b"").decode())
+
+    def bin_file(self, path, res):
+        """-> number of cells; VpRefused for a file outside the device grammar"""
+        n, why, line = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        self.n_cells = 0
+        rc = self.L.fhx_vp_bin_file(self.h, os.fsencode(path), int(res), ctypes.byref(n), ctypes.byref(why), ctypes.byref(line))
+        if rc != FHX_OK and why.value != VP_OK:
+            raise VpRefused(rc, (self.L.fhx_vp_last_error(self.h) or b"").decode(), why.value, line.value)
+        self._chk(rc)
+        self.n_cells = n.value
+        return self.n_cells
+
+    def counts(self):
+        """lines read, pairs kept by the filters, cells, distinct names"""
+        a, b, c, d = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        self._chk(self.L.fhx_vp_counts(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+        return dict(lines=a.value, pairs=b.value, cells=c.value, names=d.value)
+
+    def names(self):
+        """the chromosome names in bytewise order: the chr columns index this list"""
+        return [self.L.fhx_vp_name(self.h, k).decode() for k in range(self.counts()["names"])]
+
+    def stage_seconds(self):
+        out = np.zeros(len(VP_STAGE_NAMES), np.float64)
+        self._chk(self.L.fhx_vp_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
+        return dict(zip(VP_STAGE_NAMES, out.tolist()))
+
+    def fetch_cells(self):
+        """(chr1, mid1, chr2, mid2, count), int32, in the script's text order"""
+        cols = [np.zeros(self.n_cells, np.int32) for _ in range(5)]
+        self._chk(self.L.fhx_vp_fetch_cells(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
+        return cols
+
+    def device_ptrs(self):
+        return [self.L.fhx_vp_device_ptr(self.h, k) or 0 for k in range(5)]
+
+    def stream(self):
+        return self.L.fhx_vp_stream(self.h) or 0
+
+
+def vp_write_contacts(path, names, chr1, mid1, chr2, mid2, count, gzip_level=1, threads=0):
+    """the cells as validPairs2FitHiC-fixedSize.sh writes them (the count right-justified to width 7), size-tagged gzip members"""
+    arr_names = (ctypes.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    i32 = [_i32(v) for v in (chr1, mid1, chr2, mid2, count)]
+    rc = lib().fhx_vp_write_contacts(os.fsencode(path), arr_names, len(names), *[_ptr(v, ctypes.c_int32) for v in i32], len(i32[0]),
+                                     int(gzip_level), int(threads))
+    if rc != FHX_OK:
+        raise FhxError(rc, "fhx_vp_write_contacts(%s)" % path)

@@ -12,7 +12,7 @@
 
 extern "C" {
 
-const char* fhx_version(void) { return "fithic-mi355x 0.1.0 (gfx950)"; }
+const char* fhx_version(void) { return "fithic-mi355x 0.2.0 (gfx950)"; }
 
 int fhx_create(int device, fhx_ctx** out) {
     if (!out) return FHX_ERR_ARG;

@@ -1028,6 +1028,58 @@ int fhx_host_write_contacts(const char* path, const char* const* chr_names, int3
     return ok ? FHX_OK : FHX_ERR_ARG;
 }
 
+// The same table as validPairs2FitHiC-fixedSize.sh:38-39 writes it: the count is uniq -c's field, "%7d" - the leading blanks are
+// part of the reference's file and the readers split them away.
+int fhx_vp_write_contacts(const char* path, const char* const* chr_names, int32_t n_names, const int32_t* chr1, const int32_t* mid1,
+                          const int32_t* chr2, const int32_t* mid2, const int32_t* count, int64_t n_rows, int32_t gzip_level,
+                          int32_t n_threads) {
+    if (!path || n_names < 0 || n_rows < 0 || (n_names > 0 && !chr_names)) return FHX_ERR_ARG;
+    if (n_rows > 0 && (!chr1 || !mid1 || !chr2 || !mid2 || !count)) return FHX_ERR_ARG;
+    if (gzip_level < 0 || gzip_level > 9) gzip_level = 6;
+    if (n_threads <= 0) n_threads = fhx::usable_cpus();
+    std::vector<size_t> name_len((size_t)n_names);
+    for (int i = 0; i < n_names; ++i) {
+        name_len[i] = std::strlen(chr_names[i]);
+        if (name_len[i] > 256) return FHX_ERR_ARG;
+    }
+    std::FILE* f = std::fopen(path, "wb");
+    if (!f) return FHX_ERR_ARG;
+    const int64_t block = 1 << 18;
+    const int64_t n_blocks = std::max<int64_t>(1, (n_rows + block - 1) / block);      // no rows: one member that holds nothing
+    auto produce = [&](int64_t blk, std::string& text, std::string& zipped) -> bool {
+        const int64_t lo = blk * block, hi = std::min(n_rows, lo + block);
+        text.clear();
+        zipped.clear();
+        if (text.capacity() < (size_t)(hi - lo) * 40) text.reserve((size_t)(hi - lo) * 40);
+        char buf[600];
+        for (int64_t i = lo; i < hi; ++i) {
+            if (chr1[i] < 0 || chr1[i] >= n_names || chr2[i] < 0 || chr2[i] >= n_names) return false;
+            int n = 0;
+            std::memcpy(buf + n, chr_names[chr1[i]], name_len[chr1[i]]);
+            n += (int)name_len[chr1[i]];
+            buf[n++] = '\t';
+            n += put_int(buf + n, mid1[i]);
+            buf[n++] = '\t';
+            std::memcpy(buf + n, chr_names[chr2[i]], name_len[chr2[i]]);
+            n += (int)name_len[chr2[i]];
+            buf[n++] = '\t';
+            n += put_int(buf + n, mid2[i]);
+            buf[n++] = '\t';
+            char digits[24];
+            const int nd = put_int(digits, count[i]);
+            for (int pad = nd; pad < 7; ++pad) buf[n++] = ' ';
+            std::memcpy(buf + n, digits, (size_t)nd);
+            n += nd;
+            buf[n++] = '\n';
+            text.append(buf, (size_t)n);
+        }
+        return deflate_member(text, gzip_level, zipped);
+    };
+    bool ok = ordered_parallel_write(f, n_blocks, n_threads, produce);
+    if (std::fclose(f) != 0) ok = false;
+    return ok ? FHX_OK : FHX_ERR_ARG;
+}
+
 int64_t fhx_table_rows(const fhx_table* t) { return t ? (t->row0.empty() ? 0 : (int64_t)t->row0.back()) : -1; }
 int32_t fhx_table_n_names(const fhx_table* t) { return t ? (int32_t)t->names.size() : -1; }
 const char* fhx_table_name(const fhx_table* t, int32_t i) {

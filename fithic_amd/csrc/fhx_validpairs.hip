@@ -1,0 +1,820 @@
+// fhx_validpairs.hip - HiC-Pro's allValidPairs (one line per read pair) binned into Fit-Hi-C's contact counts on MI355X (gfx950)
+// (reference: fithic/utils/validPairs2FitHiC-fixedSize.sh:33-40, the pipeline of five awk, grep, sort, uniq -c and sed).
+//
+// The text goes through HBM in BATCHES cut at the last newline (two pinned buffers filled by pread, drained by the copy engine),
+// so a 100 GB file never has to be resident: only 16 bytes per kept pair accumulate.  Per batch:
+//
+//   vp_scan_text   16 KB of text per workgroup, 64 B per lane as 16-byte loads: newlines per block
+//   scan_tiles     exclusive scan of the block counts = the line number of every block's first line             (fhx_scan.hpp)
+//   vp_parse       the lines that begin in a block, one per lane.  One walk along the line splits it on blanks, keeps where
+//                  tokens 2, 3, 5, 6 lie and looks for `chrM` anywhere (grep -v chrM, :34); then the name-length filter (:34),
+//                  the distance filter (pos1-pos2)^2 > 2*res (:35 - the comparison sits INSIDE the sqrt), the bins
+//                  int(pos/res) (:36) and the order of the two ends (:37).  A name of <= 5 bytes is 40 bits, big-endian and
+//                  zero-padded: its integer order is its byte order.  The distinct names go into a 2048-slot table in HBM
+//                  (one load per name once it is there, a compare-and-swap only for a new one); a kept pair becomes the record
+//                  (slot1 << 32 | bin1, slot2 << 32 | bin2), stored compacted: a block scan of the keep flags and ONE atomicAdd
+//                  per 256 lines (r04_w_atomic_rate: same-address atomics run at 0.09e9/s - never one per line).
+//
+// After the last batch the host ranks the names bytewise (sort runs under LC_ALL=C, :38) and
+//
+//   vp_text_keys   for every bin index k up to the largest seen: the decimal string of k*res as a sortable word
+//                  (digits left-aligned, then the length: "100000" < "20000", and "1000" < "10000" because the tab after the
+//                  shorter one is smaller than '0'); fhx_sort_u64 + vp_invert give t[k] = the TEXT rank of bin k
+//   vp_keys        record -> one 64-bit key  rank1 | t[bin1] | rank2 | t[bin2], bit widths fitted to the data
+//   fhx_sort_u64   the stable radix sort; equal keys are the duplicates uniq -c counts
+//   count_heads / scan_tiles / vp_heads / vp_cells    run heads -> cells (chr1, mid1, chr2, mid2, count) in the script's text
+//                  order; a count is the distance between two heads (64-bit), never a walk along the run
+//
+// ONLY THE REGULAR FILE IS TAKEN (the header lists the grammar); anything else is REFUSED with the smallest offending line number
+// (one 64-bit word, atomicMin over line << 8 | reason: the same answer whatever the launch order) and nothing stays loaded.
+#include <hip/hip_runtime.h>
+
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cerrno>
+#include <chrono>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/fithic_mi355x.h"
+#include "fhx_cpus.hpp"
+#include "fhx_scan.hpp"
+
+namespace vpd {
+
+constexpr int WG = 256;
+constexpr int BLOCK_BYTES = 16384;             // text per workgroup
+constexpr int SEG = BLOCK_BYTES / WG;          // 64 bytes per lane in the newline passes
+constexpr int MAX_LINE = 4096;                 // a longer line is not a regular one
+constexpr int NAME_SLOTS = 2048;               // the device name table (open addressing, at most half full)
+constexpr int MAX_NAMES = 1024;
+constexpr unsigned long long NO_ERROR = ~0ull;
+
+// the words the kernels of one call share
+struct Words {
+    unsigned long long newlines;               // scan_tiles' total of the current batch
+    unsigned long long first_error;            // smallest (line << 8 | reason)
+    unsigned long long n_records;              // kept pairs so far
+    unsigned long long max_bin;                // largest bin index among them
+    unsigned long long n_names;                // distinct names in the table
+    unsigned long long n_cells;                // scan_tiles' total of the heads
+    unsigned long long max_count;              // largest cell count
+    unsigned long long names_overflow;         // 1: a pair named a name the full table could not take
+};
+
+// ---- pass 1 over a batch: newlines per block -----------------------------------------------------------------------------
+__global__ __launch_bounds__(WG) void vp_scan_text(const unsigned char* __restrict__ text, int64_t T, unsigned int* __restrict__ block_nl) {
+    const int64_t p0 = (int64_t)blockIdx.x * BLOCK_BYTES + (int64_t)threadIdx.x * SEG;
+    unsigned int nl = 0;
+    if (p0 < T) {
+        const uint4* src = reinterpret_cast<const uint4*>(text + p0);        // the allocation is padded to whole blocks
+        for (int v = 0; v < SEG / 16; ++v) {
+            const uint4 w = src[v];
+            const unsigned int word[4] = {w.x, w.y, w.z, w.w};
+            for (int k = 0; k < 16; ++k) {
+                const unsigned int c = (word[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+                nl += (c == '\n' && p0 + v * 16 + k < T) ? 1u : 0u;
+            }
+        }
+    }
+    unsigned int total;
+    fhxscan::block_exclusive_scan(nl, &total);
+    if (threadIdx.x == 0) block_nl[blockIdx.x] = total;
+}
+
+// The lines that BEGIN after a newline of this block (and line 0 in block 0): their start offsets relative to the block, in
+// order, in LDS.  Line number of entry e within the batch: e in block 0, block_off[block] + 1 + e elsewhere.
+__device__ inline int block_lines(const unsigned char* __restrict__ text, int64_t T, unsigned short* lstart) {
+    const int64_t p0 = (int64_t)blockIdx.x * BLOCK_BYTES + (int64_t)threadIdx.x * SEG;
+    unsigned long long mask = 0;                                              // bit k: byte k of the segment is a newline
+    if (p0 < T) {
+        const uint4* src = reinterpret_cast<const uint4*>(text + p0);
+        for (int v = 0; v < SEG / 16; ++v) {
+            const uint4 w = src[v];
+            const unsigned int word[4] = {w.x, w.y, w.z, w.w};
+            for (int k = 0; k < 16; ++k) {
+                const unsigned int c = (word[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+                if (c == '\n' && p0 + v * 16 + k + 1 < T) mask |= 1ull << (v * 16 + k);        // a newline that ends the text starts no line
+            }
+        }
+    }
+    const unsigned int first = (blockIdx.x == 0 && T > 0) ? 1u : 0u;
+    unsigned int total;
+    unsigned int rank = fhxscan::block_exclusive_scan((unsigned int)__popcll(mask), &total) + first;
+    if (first && threadIdx.x == 0) lstart[0] = 0;
+    while (mask) {
+        const int k = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        lstart[rank++] = (unsigned short)(threadIdx.x * SEG + k + 1);
+    }
+    __syncthreads();
+    return (int)(total + first);
+}
+
+__device__ inline bool is_digit(int c) { return c >= '0' && c <= '9'; }
+__device__ inline bool is_alpha(int c) { return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); }
+
+// A name of 1..5 bytes at text[b, b + len) -> its 40-bit word, or 0 for a name awk would compare as a number (or might): the
+// grammar takes a name that starts with a letter or `_` (but not with inf / nan in any case), and a plain digit string without
+// a leading zero.
+__device__ inline unsigned long long pack_name(const unsigned char* __restrict__ text, int64_t b, int len) {
+    unsigned long long w = 0;
+    bool all_digits = true;
+    int c[5] = {0, 0, 0, 0, 0};
+    for (int k = 0; k < 5; ++k) {
+        if (k < len) {
+            c[k] = text[b + k];
+            all_digits &= is_digit(c[k]);
+        }
+        w = (w << 8) | (unsigned long long)c[k];
+    }
+    if (is_digit(c[0])) return (all_digits && (len == 1 || c[0] != '0')) ? w : 0ull;
+    if (!is_alpha(c[0]) && c[0] != '_') return 0ull;
+    if (len >= 3) {
+        const int l0 = c[0] | 0x20, l1 = c[1] | 0x20, l2 = c[2] | 0x20;
+        if ((l0 == 'i' && l1 == 'n' && l2 == 'f') || (l0 == 'n' && l1 == 'a' && l2 == 'n')) return 0ull;
+    }
+    return w;
+}
+
+// awk's `a < b` for two names of the grammar (:37): numeric when both are digit strings (no leading zeros: the longer one is the
+// larger, equal lengths compare as bytes), bytewise otherwise - the packed words compare as the bytes do.
+__device__ inline bool name_less(unsigned long long a, int la, unsigned long long b, int lb) {
+    const bool da = is_digit((int)(a >> 32)), db = is_digit((int)(b >> 32));
+    if (da && db && la != lb) return la < lb;
+    return a < b;
+}
+
+// digits (1..10 of them) at text[b, b + len) -> the value; false for anything else
+__device__ inline bool position(const unsigned char* __restrict__ text, int64_t b, int len, long long* out) {
+    if (len < 1 || len > 10) return false;
+    long long v = 0;
+    for (int k = 0; k < len; ++k) {
+        const int c = text[b + k];
+        if (!is_digit(c)) return false;
+        v = v * 10 + (c - '0');
+    }
+    *out = v;
+    return true;
+}
+
+// the slot of `name` in the table, inserting it when it is new; -1 when the table holds MAX_NAMES other names already
+__device__ inline int intern_name(unsigned long long* __restrict__ table, unsigned long long* __restrict__ n_names, unsigned long long name) {
+    unsigned int h = (unsigned int)((name * 0x9E3779B97F4A7C15ull) >> 53);    // 11 bits
+    for (int probe = 0; probe < NAME_SLOTS; ++probe, h = (h + 1) & (NAME_SLOTS - 1)) {
+        unsigned long long v = __atomic_load_n(table + h, __ATOMIC_RELAXED);
+        if (v == name) return (int)h;
+        if (v != 0) continue;
+        if (__atomic_load_n(n_names, __ATOMIC_RELAXED) >= (unsigned long long)MAX_NAMES) return -1;
+        v = atomicCAS(table + h, 0ull, name);
+        if (v == 0) {
+            atomicAdd(n_names, 1ull);
+            return (int)h;
+        }
+        if (v == name) return (int)h;
+    }
+    return -1;
+}
+
+__global__ __launch_bounds__(WG) void vp_parse(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ block_off,
+                                               int64_t n_lines_batch, int64_t line_base, long long res, unsigned long long* __restrict__ names,
+                                               ulonglong2* __restrict__ records, unsigned long long capacity, Words* __restrict__ words) {
+    __shared__ unsigned short lstart[BLOCK_BYTES + 2];      // block 0: the implicit first line + one per newline byte = BLOCK_BYTES + 1 entries
+    __shared__ unsigned long long out_base;
+    const int n_lines = block_lines(text, T, lstart);
+    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
+    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    unsigned long long max_bin = 0;
+    for (int base = 0; base < n_lines; base += WG) {        // n_lines is the same for every lane: the scans below see whole blocks
+        const int e = base + threadIdx.x;
+        bool keep = false;
+        ulonglong2 rec = make_ulonglong2(0ull, 0ull);
+        if (e < n_lines) {
+            const int64_t r = row0 + e;
+            const int64_t start = b0 + lstart[e];
+            int why = 0, tok = 0, m = 0;
+            bool in_tok = false, has_chrM = false;
+            int64_t tb[4] = {0, 0, 0, 0}, te[4] = {0, 0, 0, 0};              // tokens 2, 3, 5, 6
+            int64_t p = start;
+            for (;; ++p) {
+                const int c = p < T ? (int)text[p] : '\n';                    // the end of the text ends the line
+                if (c == '\n') break;
+                if (p - start >= MAX_LINE) {
+                    why = FHX_VP_LONG_LINE;
+                    break;
+                }
+                if (c == '\r' && p + 1 < T && text[p + 1] == '\n') break;     // \r\n
+                if (c < 0x20 ? c != '\t' : c >= 0x7f) {                       // NUL, controls (a lone \r among them), DEL, non-ASCII
+                    why = FHX_VP_BYTES;
+                    break;
+                }
+                m = c == "chrM"[m] ? m + 1 : (c == 'c' ? 1 : 0);
+                if (m == 4) {
+                    has_chrM = true;
+                    m = 0;
+                }
+                const bool blank = c == ' ' || c == '\t';
+                if (!blank && !in_tok) {
+                    in_tok = true;
+                    ++tok;
+                    if (tok == 2) tb[0] = p;
+                    if (tok == 3) tb[1] = p;
+                    if (tok == 5) tb[2] = p;
+                    if (tok == 6) tb[3] = p;
+                } else if (blank && in_tok) {
+                    in_tok = false;
+                    if (tok == 2) te[0] = p;
+                    if (tok == 3) te[1] = p;
+                    if (tok == 5) te[2] = p;
+                    if (tok == 6) te[3] = p;
+                }
+            }
+            if (in_tok) {
+                if (tok == 2) te[0] = p;
+                if (tok == 3) te[1] = p;
+                if (tok == 5) te[2] = p;
+                if (tok == 6) te[3] = p;
+            }
+            if (!why && tok < 6) why = FHX_VP_TOKENS;
+            if (!why && r >= n_lines_batch) why = FHX_VP_INTERNAL;           // the scan and this kernel disagree about the lines
+            const int l1 = (int)(te[0] - tb[0]), l2 = (int)(te[2] - tb[2]);
+            // :34 - a line with a longer name, or with chrM anywhere, is dropped whatever else it holds
+            if (!why && l1 <= 5 && l2 <= 5 && !has_chrM) {
+                unsigned long long n1 = pack_name(text, tb[0], l1), n2 = pack_name(text, tb[2], l2);
+                long long p1 = 0, p2 = 0;
+                if (n1 == 0 || n2 == 0) why = FHX_VP_NAME;
+                else if (!position(text, tb[1], (int)(te[1] - tb[1]), &p1) || !position(text, tb[3], (int)(te[3] - tb[3]), &p2)) why = FHX_VP_POSITION;
+                else {
+                    long long k1 = p1 / res, k2 = p2 / res;                   // :36
+                    if (k1 * res + res / 2 > 2147483647ll || k2 * res + res / 2 > 2147483647ll) why = FHX_VP_RANGE;
+                    else {
+                        const long long d = p1 - p2;                          // below 2^31: d * d is exact
+                        if (n1 != n2 || d * d > 2 * res) {                    // :35
+                            const bool as_is = n1 == n2 ? k1 <= k2 : name_less(n1, l1, n2, l2);        // :37
+                            if (!as_is) {
+                                const unsigned long long tn = n1;
+                                n1 = n2;
+                                n2 = tn;
+                                const long long tk = k1;
+                                k1 = k2;
+                                k2 = tk;
+                            }
+                            const int s1 = intern_name(names, &words->n_names, n1);
+                            const int s2 = n2 == n1 ? s1 : intern_name(names, &words->n_names, n2);
+                            // which line meets the full table depends on the launch order: no line is reported for it
+                            if (s1 < 0 || s2 < 0) __atomic_store_n(&words->names_overflow, 1ull, __ATOMIC_RELAXED);
+                            else {
+                                keep = true;
+                                rec = make_ulonglong2(((unsigned long long)s1 << 32) | (unsigned long long)k1,
+                                                      ((unsigned long long)s2 << 32) | (unsigned long long)k2);
+                                max_bin = max(max_bin, (unsigned long long)max(k1, k2));
+                            }
+                        }
+                    }
+                }
+            }
+            if (why) atomicMin(&words->first_error, ((unsigned long long)(line_base + r + 1) << 8) | (unsigned long long)why);
+        }
+        unsigned int total;
+        const unsigned int at = fhxscan::block_exclusive_scan(keep ? 1u : 0u, &total);
+        if (threadIdx.x == 0) out_base = total ? atomicAdd(&words->n_records, (unsigned long long)total) : 0ull;
+        __syncthreads();
+        if (keep) {
+            const unsigned long long pos = out_base + at;
+            if (pos < capacity) records[pos] = rec;
+            else atomicMin(&words->first_error, ((unsigned long long)(line_base + row0 + e + 1) << 8) | (unsigned long long)FHX_VP_INTERNAL);
+        }
+        __syncthreads();                                    // out_base is written again in the next round
+    }
+    for (int s = 32; s >= 1; s >>= 1) max_bin = max(max_bin, (unsigned long long)__shfl_down(max_bin, s, 64));
+    if ((threadIdx.x & 63) == 0 && max_bin) atomicMax(&words->max_bin, max_bin);
+}
+
+// ---- the text order of the bin starts ------------------------------------------------------------------------------------
+// keys[k] = the decimal string of k*res (below 2^31: at most 10 digits) as a word that sorts like the string followed by a tab
+__global__ __launch_bounds__(WG) void vp_text_keys(long long res, int64_t n_bins, unsigned long long* __restrict__ keys) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_bins; k += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned long long v = (unsigned long long)(k * res);
+        int len = 1;
+        unsigned long long aligned = v;
+        for (unsigned long long t = 10; t <= v; t *= 10) ++len;
+        for (int d = len; d < 10; ++d) aligned *= 10;
+        keys[k] = (aligned << 4) | (unsigned long long)len;
+    }
+}
+
+// perm[i] = the bin at text rank i  ->  text_rank[bin] = i
+__global__ __launch_bounds__(WG) void vp_invert(const unsigned int* __restrict__ perm, int64_t n_bins, unsigned int* __restrict__ text_rank) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_bins; i += (int64_t)gridDim.x * blockDim.x) text_rank[perm[i]] = (unsigned int)i;
+}
+
+__global__ __launch_bounds__(WG) void vp_keys(const ulonglong2* __restrict__ records, int64_t n, const int* __restrict__ slot_rank,
+                                              const unsigned int* __restrict__ text_rank, int bin_bits, int name_bits,
+                                              unsigned long long* __restrict__ keys) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const ulonglong2 r = records[i];
+        const unsigned long long e1 = ((unsigned long long)slot_rank[r.x >> 32] << bin_bits) | text_rank[r.x & 0xFFFFFFFFull];
+        const unsigned long long e2 = ((unsigned long long)slot_rank[r.y >> 32] << bin_bits) | text_rank[r.y & 0xFFFFFFFFull];
+        keys[i] = (e1 << (bin_bits + name_bits)) | e2;
+    }
+}
+
+// the run heads of the sorted keys, in order: where each run starts
+__global__ __launch_bounds__(fhxscan::THREADS) void vp_heads(const unsigned long long* __restrict__ keys, int64_t n,
+                                                             const unsigned long long* __restrict__ tile_offsets, int64_t n_cells,
+                                                             unsigned long long* __restrict__ head_at) {
+    const int64_t base = (int64_t)blockIdx.x * fhxscan::TILE + (int64_t)threadIdx.x * fhxscan::SCAN_ITEMS;
+    unsigned int c = 0;
+    bool head[fhxscan::SCAN_ITEMS];
+    for (int k = 0; k < fhxscan::SCAN_ITEMS; ++k) {
+        head[k] = base + k < n && fhxscan::is_head(keys, base + k);
+        c += head[k] ? 1u : 0u;
+    }
+    unsigned int total;
+    unsigned long long pos = tile_offsets[blockIdx.x] + fhxscan::block_exclusive_scan(c, &total);
+    for (int k = 0; k < fhxscan::SCAN_ITEMS; ++k)
+        if (head[k] && (int64_t)pos < n_cells) head_at[pos++] = (unsigned long long)(base + k);
+}
+
+// cell c = the run that starts at head_at[c]: its key decoded, its count = the distance to the next head
+__global__ __launch_bounds__(WG) void vp_cells(const unsigned long long* __restrict__ keys, int64_t n, const unsigned long long* __restrict__ head_at,
+                                               int64_t n_cells, const unsigned int* __restrict__ bin_at_rank, int bin_bits, int name_bits,
+                                               long long res, int32_t* __restrict__ chr1, int32_t* __restrict__ mid1, int32_t* __restrict__ chr2,
+                                               int32_t* __restrict__ mid2, int32_t* __restrict__ count, unsigned long long* __restrict__ max_count) {
+    unsigned long long biggest = 0;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_cells; c += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned long long at = head_at[c];
+        const unsigned long long cnt = (c + 1 < n_cells ? head_at[c + 1] : (unsigned long long)n) - at;
+        const unsigned long long key = keys[at];
+        const unsigned long long bin_mask = (1ull << bin_bits) - 1, name_mask = (1ull << name_bits) - 1;
+        const unsigned long long e1 = key >> (bin_bits + name_bits), e2 = key & ((1ull << (bin_bits + name_bits)) - 1);
+        chr1[c] = (int32_t)((e1 >> bin_bits) & name_mask);
+        mid1[c] = (int32_t)((long long)bin_at_rank[e1 & bin_mask] * res + res / 2);
+        chr2[c] = (int32_t)((e2 >> bin_bits) & name_mask);
+        mid2[c] = (int32_t)((long long)bin_at_rank[e2 & bin_mask] * res + res / 2);
+        count[c] = (int32_t)min(cnt, 0x7fffffffull);
+        biggest = max(biggest, cnt);
+    }
+    for (int s = 32; s >= 1; s >>= 1) biggest = max(biggest, (unsigned long long)__shfl_down(biggest, s, 64));
+    if ((threadIdx.x & 63) == 0 && biggest) atomicMax(max_count, biggest);
+}
+
+}  // namespace vpd
+
+// ===================================================================================================================
+struct fhx_vp {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    fhx_ctx* sorter = nullptr;
+    std::string err;
+    // the last binned file
+    std::vector<std::string> names;               // bytewise order: a cell's chr column is an index into it
+    int64_t n_lines = 0, n_pairs = 0, n_cells = 0;
+    int32_t* d_cols = nullptr;                    // five columns of col_stride elements
+    int64_t col_stride = 0;
+    double seconds[FHX_VP_STAGES] = {0, 0, 0, 0, 0, 0};
+    // the upload path
+    static constexpr size_t kChunk = (size_t)32 << 20;
+    void* pinned[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+namespace {
+
+int vfail(fhx_vp* vp, int code, const std::string& msg) {
+    if (vp) vp->err = msg;
+    return code;
+}
+
+#define VP_HIP(call)                                                                                      \
+    do {                                                                                                  \
+        hipError_t e_ = (call);                                                                           \
+        if (e_ != hipSuccess) return vfail(vp, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// device temporaries of one call
+struct Scratch {
+    std::vector<void*> ptrs;
+    ~Scratch() {
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+    template <typename T>
+    hipError_t get(T** p, size_t count) {
+        hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) ptrs.push_back(*p);
+        return e;
+    }
+    void drop(void* p) {
+        auto it = std::find(ptrs.begin(), ptrs.end(), p);
+        if (it != ptrs.end()) {
+            (void)hipFree(p);
+            ptrs.erase(it);
+        }
+    }
+};
+
+// the text: a file read with pread, or the inflated bytes of a gzip file
+struct Source {
+    int fd = -1;
+    std::vector<char> inflated;
+    int64_t size = 0;
+    ~Source() {
+        if (fd >= 0) ::close(fd);
+    }
+};
+
+void drop_cells(fhx_vp* vp) {
+    if (vp->d_cols) (void)hipFree(vp->d_cols);
+    vp->d_cols = nullptr;
+    vp->names.clear();
+    vp->n_lines = vp->n_pairs = vp->n_cells = 0;
+    vp->col_stride = 0;
+}
+
+// bytes [off, off + len) of the source -> d_text[0, len): host threads fill one of two pinned buffers while the copy engine
+// drains the other.  *last_newline = the offset (within the range) of the range's last newline, -1 without one.
+int upload_range(fhx_vp* vp, Source& src, int64_t off, int64_t len, unsigned char* d_text, int64_t* last_newline) {
+    for (int k = 0; k < 2; ++k) {
+        if (!vp->pinned[k]) VP_HIP(hipHostMalloc(&vp->pinned[k], fhx_vp::kChunk, hipHostMallocDefault));
+        if (!vp->ev[k]) VP_HIP(hipEventCreateWithFlags(&vp->ev[k], hipEventDisableTiming));
+    }
+    const int n_threads = std::min(fhx::usable_cpus(), 8);
+    bool used[2] = {false, false};
+    int turn = 0;
+    *last_newline = -1;
+    for (int64_t done = 0; done < len; done += (int64_t)fhx_vp::kChunk, turn ^= 1) {
+        const int64_t now = std::min<int64_t>((int64_t)fhx_vp::kChunk, len - done);
+        if (used[turn]) VP_HIP(hipEventSynchronize(vp->ev[turn]));
+        char* dst = (char*)vp->pinned[turn];
+        if (src.fd < 0) {
+            std::memcpy(dst, src.inflated.data() + off + done, (size_t)now);
+        } else {
+            const int64_t slice = (int64_t)4 << 20;
+            const int64_t n_slices = (now + slice - 1) / slice;
+            std::atomic<int64_t> next{0};
+            std::atomic<int> io_errno{0};
+            auto work = [&]() {
+                for (;;) {
+                    const int64_t s = next.fetch_add(1);
+                    if (s >= n_slices) return;
+                    int64_t at = s * slice;
+                    const int64_t stop = std::min(now, at + slice);
+                    while (at < stop) {
+                        const ssize_t got = ::pread(src.fd, dst + at, (size_t)(stop - at), (off_t)(off + done + at));
+                        if (got < 0 && errno == EINTR) continue;
+                        if (got <= 0) {                                       // an error, or the file shrank under us
+                            io_errno = got < 0 ? errno : EIO;
+                            return;
+                        }
+                        at += got;
+                    }
+                }
+            };
+            const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, n_slices));
+            std::vector<std::thread> pool;
+            for (int k = 1; k < nt; ++k) pool.emplace_back(work);
+            work();
+            for (auto& th : pool) th.join();
+            if (io_errno) {
+                (void)hipStreamSynchronize(vp->stream);
+                return vfail(vp, FHX_ERR_ARG, std::string("reading the validPairs file: ") + std::strerror(io_errno));
+            }
+        }
+        if (const void* nl = ::memrchr(dst, '\n', (size_t)now)) *last_newline = done + ((const char*)nl - dst);
+        VP_HIP(hipMemcpyAsync(d_text + done, dst, (size_t)now, hipMemcpyHostToDevice, vp->stream));
+        VP_HIP(hipEventRecord(vp->ev[turn], vp->stream));
+        used[turn] = true;
+    }
+    return FHX_OK;
+}
+
+int bits_for(unsigned long long largest) {                                    // bits that hold 0..largest, at least 1
+    int b = 1;
+    while (b < 64 && (largest >> b)) ++b;
+    return b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhx_vp_create(int device, fhx_vp** out) {
+    if (!out) return FHX_ERR_ARG;
+    *out = nullptr;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return FHX_ERR_NO_DEVICE;
+    fhx_vp* vp = new fhx_vp();
+    vp->device = device;
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&vp->stream, hipStreamNonBlocking) != hipSuccess ||
+        fhx_create(device, &vp->sorter) != FHX_OK) {
+        if (vp->stream) (void)hipStreamDestroy(vp->stream);
+        delete vp;
+        return FHX_ERR_HIP;
+    }
+    *out = vp;
+    return FHX_OK;
+}
+
+void fhx_vp_destroy(fhx_vp* vp) {
+    if (!vp) return;
+    (void)hipSetDevice(vp->device);
+    if (vp->stream) (void)hipStreamSynchronize(vp->stream);
+    drop_cells(vp);
+    for (int k = 0; k < 2; ++k) {
+        if (vp->pinned[k]) (void)hipHostFree(vp->pinned[k]);
+        if (vp->ev[k]) (void)hipEventDestroy(vp->ev[k]);
+    }
+    if (vp->sorter) fhx_destroy(vp->sorter);
+    if (vp->stream) (void)hipStreamDestroy(vp->stream);
+    delete vp;
+}
+
+const char* fhx_vp_last_error(const fhx_vp* vp) { return vp ? vp->err.c_str() : "null context"; }
+
+int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_t* why, int64_t* bad_line) {
+    using namespace vpd;
+    if (!vp || !path || !n_cells || !why || !bad_line) return FHX_ERR_ARG;
+    *n_cells = 0;
+    *why = FHX_VP_OK;
+    *bad_line = 0;
+    VP_HIP(hipSetDevice(vp->device));
+    VP_HIP(hipStreamSynchronize(vp->stream));
+    drop_cells(vp);
+    for (double& s : vp->seconds) s = 0;
+    if (res < 2 || (res & 1) || res > 0x7fffffffll) {
+        *why = FHX_VP_RES;
+        return vfail(vp, FHX_ERR_UNSUPPORTED, "the resolution must be an even number from 2 to 2^31 - 2");
+    }
+    auto t_last = std::chrono::steady_clock::now();
+    auto mark = [&](int k) {                                                  // the stream is idle at every call
+        const auto now = std::chrono::steady_clock::now();
+        vp->seconds[k] += std::chrono::duration<double>(now - t_last).count();
+        t_last = now;
+    };
+    // ---- the source: the file itself, or its inflated bytes when it starts with the gzip magic (zcat -f, :33) ----------------
+    Source src;
+    src.fd = ::open(path, O_RDONLY | O_CLOEXEC);
+    if (src.fd < 0) return vfail(vp, FHX_ERR_ARG, std::string(path) + ": " + std::strerror(errno));
+    struct stat sb;
+    if (::fstat(src.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return vfail(vp, FHX_ERR_ARG, std::string(path) + ": not a regular file");
+    src.size = (int64_t)sb.st_size;
+    unsigned char magic[2] = {0, 0};
+    if (src.size >= 2 && ::pread(src.fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
+        fhx_text* x = nullptr;
+        int rc = fhx_host_inflate(path, 0, &x);
+        if (rc != FHX_OK) {
+            const std::string msg = x ? fhx_text_error(x) : "fhx_host_inflate";
+            fhx_text_free(x);
+            return vfail(vp, rc, msg);
+        }
+        src.inflated.resize((size_t)fhx_text_bytes(x));
+        rc = fhx_text_copy(x, src.inflated.data(), (int64_t)src.inflated.size());
+        fhx_text_free(x);
+        if (rc != FHX_OK) return vfail(vp, rc, "fhx_text_copy");
+        ::close(src.fd);
+        src.fd = -1;
+        src.size = (int64_t)src.inflated.size();
+    }
+    // ---- the batches ---------------------------------------------------------------------------------------------------------
+    int64_t batch_bytes = (int64_t)256 << 20;                                 // FHX_VP_BATCH_BYTES overrides (tests put a batch edge inside a small file)
+    if (const char* e = std::getenv("FHX_VP_BATCH_BYTES")) batch_bytes = std::atoll(e);
+    batch_bytes = std::max<int64_t>(2 * MAX_LINE, std::min<int64_t>(batch_bytes, (int64_t)1 << 32));
+    batch_bytes = std::min(batch_bytes, std::max<int64_t>(src.size, 2 * MAX_LINE));
+    const int64_t max_blocks = (batch_bytes + BLOCK_BYTES - 1) / BLOCK_BYTES;
+    Scratch tmp;
+    unsigned char* d_text = nullptr;
+    unsigned int* d_block_nl = nullptr;
+    unsigned long long *d_block_off = nullptr, *d_names = nullptr;
+    Words* d_words = nullptr;
+    ulonglong2* d_records = nullptr;
+    int64_t capacity = 0;
+    VP_HIP(tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
+    VP_HIP(tmp.get(&d_block_nl, (size_t)max_blocks));
+    VP_HIP(tmp.get(&d_block_off, (size_t)max_blocks));
+    VP_HIP(tmp.get(&d_names, (size_t)NAME_SLOTS));
+    VP_HIP(tmp.get(&d_words, 1));
+    VP_HIP(hipMemsetAsync(d_names, 0, NAME_SLOTS * sizeof(unsigned long long), vp->stream));
+    Words words;
+    std::memset(&words, 0, sizeof(words));
+    words.first_error = NO_ERROR;
+    VP_HIP(hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, vp->stream));
+    VP_HIP(hipStreamSynchronize(vp->stream));
+    auto refuse = [&](int rc, int32_t w, int64_t line, const std::string& msg) {
+        drop_cells(vp);
+        *why = w;
+        *bad_line = line;
+        return vfail(vp, rc, msg);
+    };
+    auto refuse_line = [&](unsigned long long word) {
+        const int32_t w = (int32_t)(word & 0xFFu);
+        const int64_t line = (int64_t)(word >> 8);
+        if (w == FHX_VP_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, "the line count of the scan and the parse kernel disagree");
+        return refuse(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
+    };
+    int64_t lines = 0, pairs = 0;
+    for (int64_t off = 0; off < src.size;) {
+        int64_t len = std::min(batch_bytes, src.size - off), last_nl = -1;
+        {
+            const int rc = upload_range(vp, src, off, len, d_text, &last_nl);
+            if (rc != FHX_OK) return rc;
+        }
+        // a batch that does not reach the end of the text ends after its last newline; without one its single line is longer than
+        // MAX_LINE and the parse kernel says so
+        if (off + len < src.size && last_nl >= 0) len = last_nl + 1;
+        const int64_t n_blocks = (len + BLOCK_BYTES - 1) / BLOCK_BYTES;
+        VP_HIP(hipMemsetAsync(d_text + len, ' ', (size_t)(n_blocks * BLOCK_BYTES + 64 - len), vp->stream));
+        VP_HIP(hipStreamSynchronize(vp->stream));                             // the pinned buffers are free again
+        mark(0);
+        hipLaunchKernelGGL(vp_scan_text, dim3((unsigned)n_blocks), dim3(WG), 0, vp->stream, (const unsigned char*)d_text, len, d_block_nl);
+        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
+                           &d_words->newlines);
+        VP_HIP(hipGetLastError());
+        unsigned long long n_newlines = 0;
+        VP_HIP(hipMemcpyAsync(&n_newlines, &d_words->newlines, sizeof(n_newlines), hipMemcpyDeviceToHost, vp->stream));
+        VP_HIP(hipStreamSynchronize(vp->stream));
+        mark(1);
+        const int64_t n = (int64_t)n_newlines + (last_nl == len - 1 ? 0 : 1);
+        if (pairs + n >= ((int64_t)1 << 32)) return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_PAIRS, 0, "2^32 or more pairs may be kept: the sort does not take them");
+        if (pairs + n > capacity) {                                           // room for every line of the batch to be kept
+            const int64_t want = std::max<int64_t>(pairs + n, capacity * 2);
+            ulonglong2* bigger = nullptr;
+            VP_HIP(tmp.get(&bigger, (size_t)want));
+            if (pairs) VP_HIP(hipMemcpyAsync(bigger, d_records, (size_t)pairs * sizeof(ulonglong2), hipMemcpyDeviceToDevice, vp->stream));
+            VP_HIP(hipStreamSynchronize(vp->stream));
+            tmp.drop(d_records);
+            d_records = bigger;
+            capacity = want;
+        }
+        hipLaunchKernelGGL(vp_parse, dim3((unsigned)n_blocks), dim3(WG), 0, vp->stream, (const unsigned char*)d_text, len,
+                           (const unsigned long long*)d_block_off, n, lines, (long long)res, d_names, d_records, (unsigned long long)capacity, d_words);
+        VP_HIP(hipGetLastError());
+        VP_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, vp->stream));
+        VP_HIP(hipStreamSynchronize(vp->stream));
+        mark(2);
+        if (words.first_error != NO_ERROR) return refuse_line(words.first_error);   // earlier batches hold the smaller line numbers
+        lines += n;
+        pairs = (int64_t)words.n_records;
+        if (pairs > capacity) return refuse(FHX_ERR_INTERNAL, FHX_VP_INTERNAL, 0, "more records than lines");
+        off += len;
+    }
+    tmp.drop(d_text);
+    d_text = nullptr;
+    std::vector<char>().swap(src.inflated);
+    if (words.names_overflow || words.n_names > (unsigned long long)MAX_NAMES)       // after every line has been checked: a line error wins
+        return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_NAMES, 0, "more than " + std::to_string(MAX_NAMES) + " distinct chromosome names among the kept pairs");
+    vp->n_lines = lines;
+    vp->n_pairs = pairs;
+    if (pairs == 0) {
+        mark(3);
+        return FHX_OK;
+    }
+    // ---- names: ranked bytewise on the host (the packed words compare as the bytes do) --------------------------------------
+    std::vector<unsigned long long> table((size_t)NAME_SLOTS);
+    VP_HIP(hipMemcpy(table.data(), d_names, NAME_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::vector<std::pair<unsigned long long, int>> present;
+    for (int s = 0; s < NAME_SLOTS; ++s)
+        if (table[(size_t)s]) present.emplace_back(table[(size_t)s], s);
+    std::sort(present.begin(), present.end());
+    std::vector<int> slot_rank((size_t)NAME_SLOTS, 0);
+    for (size_t k = 0; k < present.size(); ++k) {
+        slot_rank[(size_t)present[k].second] = (int)k;
+        std::string name;
+        for (int b = 4; b >= 0; --b)
+            if (const char c = (char)((present[k].first >> (8 * b)) & 0xFF)) name.push_back(c);
+        vp->names.push_back(name);
+    }
+    const int64_t n_bins = (int64_t)words.max_bin + 1;
+    const int bin_bits = bits_for(words.max_bin), name_bits = bits_for(present.size() - 1);
+    if (2 * (bin_bits + name_bits) > 64)
+        return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_NAMES, 0,
+                      std::to_string(present.size()) + " distinct names and bin indices up to " + std::to_string(words.max_bin) + " need " +
+                          std::to_string(2 * (bin_bits + name_bits)) + " key bits, the sort key has 64");
+    int* d_slot_rank = nullptr;
+    unsigned int *d_text_rank = nullptr, *d_bin_at_rank = nullptr, *d_perm = nullptr;
+    unsigned long long *d_keys = nullptr, *d_sorted = nullptr;
+    VP_HIP(tmp.get(&d_slot_rank, (size_t)NAME_SLOTS));
+    VP_HIP(hipMemcpyAsync(d_slot_rank, slot_rank.data(), NAME_SLOTS * sizeof(int), hipMemcpyHostToDevice, vp->stream));
+    VP_HIP(tmp.get(&d_text_rank, (size_t)n_bins));
+    VP_HIP(tmp.get(&d_bin_at_rank, (size_t)n_bins));
+    {
+        unsigned long long *d_bin_keys = nullptr, *d_bin_sorted = nullptr;
+        VP_HIP(tmp.get(&d_bin_keys, (size_t)n_bins));
+        VP_HIP(tmp.get(&d_bin_sorted, (size_t)n_bins));
+        const unsigned grid = (unsigned)std::min<int64_t>((n_bins + WG - 1) / WG, 4096);
+        hipLaunchKernelGGL(vp_text_keys, dim3(grid), dim3(WG), 0, vp->stream, (long long)res, n_bins, d_bin_keys);
+        VP_HIP(hipGetLastError());
+        VP_HIP(hipStreamSynchronize(vp->stream));                             // the sorter has a stream of its own
+        const int rc = fhx_sort_u64(vp->sorter, d_bin_keys, n_bins, d_bin_sorted, d_bin_at_rank);
+        if (rc != FHX_OK) return vfail(vp, rc, std::string("sort of the bin starts: ") + fhx_last_error(vp->sorter));
+        hipLaunchKernelGGL(vp_invert, dim3(grid), dim3(WG), 0, vp->stream, (const unsigned int*)d_bin_at_rank, n_bins, d_text_rank);
+        VP_HIP(hipGetLastError());
+        VP_HIP(hipStreamSynchronize(vp->stream));
+        tmp.drop(d_bin_keys);
+        tmp.drop(d_bin_sorted);
+    }
+    VP_HIP(tmp.get(&d_keys, (size_t)pairs));
+    {
+        const unsigned grid = (unsigned)std::min<int64_t>((pairs + WG - 1) / WG, 8192);
+        hipLaunchKernelGGL(vp_keys, dim3(grid), dim3(WG), 0, vp->stream, (const ulonglong2*)d_records, pairs, (const int*)d_slot_rank,
+                           (const unsigned int*)d_text_rank, bin_bits, name_bits, d_keys);
+        VP_HIP(hipGetLastError());
+        VP_HIP(hipStreamSynchronize(vp->stream));
+    }
+    tmp.drop(d_records);
+    d_records = nullptr;
+    mark(3);
+    VP_HIP(tmp.get(&d_sorted, (size_t)pairs));
+    VP_HIP(tmp.get(&d_perm, (size_t)pairs));
+    {
+        const int rc = fhx_sort_u64(vp->sorter, d_keys, pairs, d_sorted, d_perm);
+        if (rc != FHX_OK) return vfail(vp, rc, std::string("sort: ") + fhx_last_error(vp->sorter));
+    }
+    tmp.drop(d_keys);
+    tmp.drop(d_perm);
+    mark(4);
+    // ---- run heads -> cells --------------------------------------------------------------------------------------------------
+    const int64_t tiles = (pairs + fhxscan::TILE - 1) / fhxscan::TILE;
+    unsigned int* d_tile_cnt = nullptr;
+    unsigned long long *d_tile_off = nullptr, *d_head_at = nullptr;
+    VP_HIP(tmp.get(&d_tile_cnt, (size_t)tiles));
+    VP_HIP(tmp.get(&d_tile_off, (size_t)tiles));
+    hipLaunchKernelGGL(fhxscan::count_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned long long*)d_sorted, pairs,
+                       d_tile_cnt);
+    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned int*)d_tile_cnt, tiles, d_tile_off,
+                       &d_words->n_cells);
+    VP_HIP(hipGetLastError());
+    unsigned long long cells = 0;
+    VP_HIP(hipMemcpyAsync(&cells, &d_words->n_cells, sizeof(cells), hipMemcpyDeviceToHost, vp->stream));
+    VP_HIP(hipStreamSynchronize(vp->stream));
+    if (cells == 0 || cells > (unsigned long long)pairs) return refuse(FHX_ERR_INTERNAL, FHX_VP_INTERNAL, 0, "the run heads do not match the keys");
+    const int64_t stride = ((int64_t)cells + 63) / 64 * 64;                   // every column starts on a 256-byte boundary
+    VP_HIP(tmp.get(&d_head_at, (size_t)cells));
+    VP_HIP(hipMalloc((void**)&vp->d_cols, (size_t)stride * 5 * sizeof(int32_t)));
+    vp->col_stride = stride;
+    int32_t* c = vp->d_cols;
+    hipLaunchKernelGGL(vp_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned long long*)d_sorted, pairs,
+                       (const unsigned long long*)d_tile_off, (int64_t)cells, d_head_at);
+    hipLaunchKernelGGL(vp_cells, dim3((unsigned)std::min<int64_t>(((int64_t)cells + WG - 1) / WG, 8192)), dim3(WG), 0, vp->stream,
+                       (const unsigned long long*)d_sorted, pairs, (const unsigned long long*)d_head_at, (int64_t)cells,
+                       (const unsigned int*)d_bin_at_rank, bin_bits, name_bits, (long long)res, c, c + stride, c + 2 * stride, c + 3 * stride,
+                       c + 4 * stride, &d_words->max_count);
+    VP_HIP(hipGetLastError());
+    unsigned long long max_count = 0;
+    VP_HIP(hipMemcpyAsync(&max_count, &d_words->max_count, sizeof(max_count), hipMemcpyDeviceToHost, vp->stream));
+    VP_HIP(hipStreamSynchronize(vp->stream));
+    mark(5);
+    if (max_count > 0x7fffffffull) return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_COUNT, 0, "a cell is hit by more than 2^31 - 1 pairs: the count column is int32");
+    vp->n_cells = (int64_t)cells;
+    *n_cells = vp->n_cells;
+    if (std::getenv("FHX_TIMING"))
+        std::fprintf(stderr, "validPairs on the device (%s): %lld lines, %lld kept pairs, %lld cells: read + upload %.6f s; scan %.6f s; parse %.6f s; "
+                     "names + keys %.6f s; sort %.6f s; cells %.6f s\n", path, (long long)lines, (long long)pairs, (long long)cells, vp->seconds[0],
+                     vp->seconds[1], vp->seconds[2], vp->seconds[3], vp->seconds[4], vp->seconds[5]);
+    return FHX_OK;
+}
+
+int fhx_vp_counts(const fhx_vp* vp, int64_t* n_lines, int64_t* n_pairs, int64_t* n_cells, int32_t* n_names) {
+    if (!vp) return FHX_ERR_ARG;
+    if (n_lines) *n_lines = vp->n_lines;
+    if (n_pairs) *n_pairs = vp->n_pairs;
+    if (n_cells) *n_cells = vp->n_cells;
+    if (n_names) *n_names = (int32_t)vp->names.size();
+    return FHX_OK;
+}
+
+const char* fhx_vp_name(const fhx_vp* vp, int32_t i) { return (vp && i >= 0 && i < (int32_t)vp->names.size()) ? vp->names[(size_t)i].c_str() : nullptr; }
+
+int fhx_vp_stage_seconds(const fhx_vp* vp, double* seconds) {
+    if (!vp || !seconds) return FHX_ERR_ARG;
+    for (int k = 0; k < FHX_VP_STAGES; ++k) seconds[k] = vp->seconds[k];
+    return FHX_OK;
+}
+
+int fhx_vp_fetch_cells(fhx_vp* vp, int32_t* chr1, int32_t* mid1, int32_t* chr2, int32_t* mid2, int32_t* count) {
+    if (!vp) return FHX_ERR_ARG;
+    if (vp->n_cells > 0 && (!chr1 || !mid1 || !chr2 || !mid2 || !count)) return FHX_ERR_ARG;
+    VP_HIP(hipSetDevice(vp->device));
+    int32_t* out[5] = {chr1, mid1, chr2, mid2, count};
+    for (int k = 0; k < 5 && vp->n_cells > 0; ++k)
+        VP_HIP(hipMemcpyAsync(out[k], vp->d_cols + k * vp->col_stride, (size_t)vp->n_cells * sizeof(int32_t), hipMemcpyDeviceToHost, vp->stream));
+    VP_HIP(hipStreamSynchronize(vp->stream));
+    return FHX_OK;
+}
+
+void* fhx_vp_device_ptr(fhx_vp* vp, int32_t which) {
+    if (!vp || which < 0 || which > 4 || !vp->d_cols) return nullptr;
+    return vp->d_cols + which * vp->col_stride;
+}
+
+void* fhx_vp_stream(fhx_vp* vp) { return vp ? (void*)vp->stream : nullptr; }
+
+}  // extern "C"

@@ -616,6 +616,52 @@ int fhx_hp_fetch_rows(fhx_hp* hp, int32_t* chr1, int32_t* mid1, int32_t* chr2, i
 void* fhx_hp_device_ptr(fhx_hp* hp, int32_t which);
 void* fhx_hp_stream(fhx_hp* hp);
 
+/* ---- HiC-Pro allValidPairs -> Fit-Hi-C contact counts (fithic/utils/validPairs2FitHiC-fixedSize.sh:33-40; csrc/fhx_validpairs.hip).
+ * One handle per GPU, independent of fhx_ctx.  The file (plain text, or gzip: it is inflated on the host first, as zcat -f does)
+ * goes through HBM in batches cut at the last newline (FHX_VP_BATCH_BYTES overrides the batch size of 256 MB; 8192 at least);
+ * kernels split every line on blanks, apply the script's filters - both names of at most 5 bytes, no `chrM` anywhere in the
+ * line, different names or (pos1 - pos2)^2 > 2 * res - bin both ends (pos / res), order them as the script's awk does, sort and
+ * count.  The cells (chr1, mid1, chr2, mid2, count: int32; mid = bin start + res / 2; chr = index into the names, which are in
+ * bytewise order) stay in HBM in the order of the script's `sort` under LC_ALL=C: the lines name1 TAB bin1 TAB name2 TAB bin2
+ * compared as text.
+ * Taken: printable ASCII and tabs, lines of at most 4096 bytes ending in \n or \r\n (the last one may end with the file), at
+ * least 6 tokens per line; on a line the first two filters keep: names that start with a letter or `_` (not with inf / nan in
+ * any case) or are decimal digits without a leading zero, positions of 1..10 digits with bin start + res / 2 < 2^31.  res is even
+ * and >= 2.  At most 1024 distinct names, and 2 * (bits of the largest bin index + bits of the largest name rank) <= 64.
+ * Anything else is refused with nothing left loaded: *why = one of FHX_VP_*, *bad_line = the smallest offending 1-based line
+ * number (0 for the reasons that belong to no line).  Return value: FHX_ERR_UNSUPPORTED. */
+#define FHX_VP_OK 0
+#define FHX_VP_TOKENS 1            /* fewer than six tokens (an empty line included) */
+#define FHX_VP_NAME 2              /* a name awk would, or might, compare as a number */
+#define FHX_VP_POSITION 3          /* a position that is not 1..10 digits */
+#define FHX_VP_RANGE 4             /* bin start + res / 2 >= 2^31: awk prints such a number in %.6g form */
+#define FHX_VP_BYTES 5             /* a NUL, another control byte than tab, DEL, a non-ASCII byte, a \r that is not followed by \n */
+#define FHX_VP_LONG_LINE 6         /* a line of more than 4096 bytes */
+#define FHX_VP_NAMES 7             /* more distinct names, or larger bin indices, than the 64-bit sort key holds (no line number) */
+#define FHX_VP_COUNT 8             /* a cell hit by more than 2^31 - 1 pairs (no line number) */
+#define FHX_VP_RES 9               /* res is odd or below 2 (no line number) */
+#define FHX_VP_INTERNAL 10         /* a device-side consistency check failed */
+#define FHX_VP_PAIRS 11            /* 2^32 or more pairs could be kept: the sort does not take them (no line number) */
+#define FHX_VP_STAGES 6            /* read + upload, newline scan, parse, names + keys, sort, cells */
+typedef struct fhx_vp fhx_vp;
+int fhx_vp_create(int device, fhx_vp** out);
+void fhx_vp_destroy(fhx_vp* vp);
+const char* fhx_vp_last_error(const fhx_vp* vp);
+int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_t* why, int64_t* bad_line);
+int fhx_vp_counts(const fhx_vp* vp, int64_t* n_lines, int64_t* n_pairs, int64_t* n_cells, int32_t* n_names);
+const char* fhx_vp_name(const fhx_vp* vp, int32_t i);
+int fhx_vp_stage_seconds(const fhx_vp* vp, double* seconds);       /* FHX_VP_STAGES host clocks of the last call */
+int fhx_vp_fetch_cells(fhx_vp* vp, int32_t* chr1, int32_t* mid1, int32_t* chr2, int32_t* mid2, int32_t* count);   /* n_cells each */
+/* the columns in HBM (which 0..4 = chr1, mid1, chr2, mid2, count) and the stream they were written on, for fhx_load_pairs_device;
+ * valid until the next fhx_vp_bin_file / fhx_vp_destroy */
+void* fhx_vp_device_ptr(fhx_vp* vp, int32_t which);
+void* fhx_vp_stream(fhx_vp* vp);
+/* The cells as the script writes them: name1 TAB mid1 TAB name2 TAB mid2 TAB count, the count right-justified to width 7 as
+ * uniq -c prints it (:38-39); size-tagged gzip members through the pool of the host writer.  Host only: needs no GPU. */
+int fhx_vp_write_contacts(const char* path, const char* const* chr_names, int32_t n_names, const int32_t* chr1,
+                          const int32_t* mid1, const int32_t* chr2, const int32_t* mid2, const int32_t* count, int64_t n_rows,
+                          int32_t gzip_level, int32_t n_threads);
+
 #ifdef __cplusplus
 }
 #endif
