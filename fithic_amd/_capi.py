@@ -233,12 +233,21 @@ SYMBOLS = {
     "fhx_vp_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     "fhx_vp_write_contacts": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, _I32P, _I32P, _I32P, _I32P,
                                              _I32P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    # the FDR subset of a significances file (fithic/utils/merge-filter.sh)
+    "fhx_ms_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "fhx_ms_destroy": (None, [ctypes.c_void_p]),
+    "fhx_ms_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
+    "fhx_ms_select_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.c_int32, _I64P, _I32P, _I64P]),
+    "fhx_ms_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P]),
+    "fhx_ms_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
+    "fhx_ms_copy_subset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
 }
 
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
 # not recompile K1, K3, the Knight-Ruiz path or the host stages.  Flags are the same for every unit - -ffp-contract=off matters
 # for bit-exactness on the host (FITPACK, lgamma tables) as much as on the device (fhx_bdtrc.hpp).
-SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
+SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
 COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread"]
 LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-lz", "-ldl"]
 OBJ_DIR = os.path.join(CSRC, "_obj")
@@ -1399,3 +1408,67 @@ def vp_write_contacts(path, names, chr1, mid1, chr2, mid2, count, gzip_level=1, 
                                      int(gzip_level), int(threads))
     if rc != FHX_OK:
         raise FhxError(rc, "fhx_vp_write_contacts(%s)" % path)
+
+
+(MS_OK, MS_TOKENS, MS_FIELD, MS_BYTES, MS_LONG_LINE, MS_FDR, MS_INTERNAL) = range(7)
+MS_FDR_BYTES = 32
+MS_STAGE_NAMES = ("read_upload", "newline_scan", "select", "gather", "copy_out")
+
+
+class MsRefused(FhxError):
+    """fhx_ms_select_file refused the file: why = one of MS_*, line = the smallest offending 1-based line (0: the reason belongs
+    to no line)"""
+
+    def __init__(self, code, message, why, line):
+        super().__init__(code, message)
+        self.why, self.line = int(why), int(line)
+
+
+class MsContext:
+    """The FDR subset of a significances file made on one GPU (fhx_ms_*).  Raises without the library or a GPU."""
+
+    def __init__(self, device=0):
+        self.L = lib()
+        self.h = ctypes.c_void_p()
+        rc = self.L.fhx_ms_create(int(device), ctypes.byref(self.h))
+        if rc != FHX_OK:
+            self.h = None
+            raise FhxError(rc, "fhx_ms_create(device=%d) failed: no usable MI355X / HIP runtime" % device)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.fhx_ms_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _chk(self, rc):
+        if rc != FHX_OK:
+            raise FhxError(rc, (self.L.fhx_ms_last_error(self.h) or b"").decode())
+
+    def select_file(self, path, fdr_text, key_bound, zero_kept, strict=False, skip_first_line=True):
+        """-> bytes of the subset; MsRefused for a file outside the device grammar"""
+        n, why, line = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self.L.fhx_ms_select_file(self.h, os.fsencode(path), fdr_text, len(fdr_text), int(key_bound), int(bool(zero_kept)),
+                                       int(bool(strict)), int(bool(skip_first_line)), ctypes.byref(n), ctypes.byref(why), ctypes.byref(line))
+        if rc != FHX_OK and why.value != MS_OK:
+            raise MsRefused(rc, (self.L.fhx_ms_last_error(self.h) or b"").decode(), why.value, line.value)
+        self._chk(rc)
+        return n.value
+
+    def counts(self):
+        """lines read, lines kept, bytes of the subset"""
+        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self.L.fhx_ms_counts(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return dict(lines=a.value, kept=b.value, bytes=c.value)
+
+    def stage_seconds(self):
+        out = np.zeros(len(MS_STAGE_NAMES), np.float64)
+        self._chk(self.L.fhx_ms_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
+        return dict(zip(MS_STAGE_NAMES, out.tolist()))
+
+    def subset(self):
+        """the kept lines, verbatim and in file order, each ending in a newline"""
+        buf = np.empty(self.counts()["bytes"], np.uint8)
+        self._chk(self.L.fhx_ms_copy_subset(self.h, buf.ctypes.data_as(ctypes.c_void_p), len(buf)))
+        return buf.tobytes()

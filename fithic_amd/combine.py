@@ -48,8 +48,15 @@ def read_significances(path, header=1):
     return df
 
 
-def combine_records(df, bin_size, conn=8, pct=100, neigh=2, order=0):
-    """-> (sorted chromosome names, record array in output order, info)."""
+def frame_of_text(data):
+    """read_significances(path, header=0) for rows held in memory as bytes (fithic_amd.mergefilter's subset)"""
+    import io
+    import pandas as pd
+    return pd.read_csv(io.BytesIO(data), sep=r"\s+", header=None, usecols=range(7), dtype=str, engine="c", keep_default_na=False)
+
+
+def combine_records(df, bin_size, conn=8, pct=100, neigh=2, order=0, device=None):
+    """-> (sorted chromosome names, record array in output order, info); on GPU `device` (None: the module's)."""
     intra = (df[0] == df[2]).to_numpy()
     names = sorted(set(df[0]))                                   # `sort -k1,1 | uniq` in the C locale (:204-212)
     ids = {name: i for i, name in enumerate(names)}
@@ -61,7 +68,7 @@ def combine_records(df, bin_size, conn=8, pct=100, neigh=2, order=0):
     cc = sub[4].to_numpy().astype(np.int64)                      # int(text): ValueError on "12.0", like the reference (:312)
     p = sub[5].to_numpy().astype(np.float64)                     # float(text), correctly rounded
     q = sub[6].to_numpy().astype(np.float64)
-    cn = _capi.CniContext(device)
+    cn = _capi.CniContext(globals()["device"] if device is None else device)
     try:
         cn.load(chr_ids, n1, n2, cc, p, q, bin_size)
         rec, info = cn.run(conn, pct, neigh, order)
@@ -87,6 +94,14 @@ def format_lines(names, rec, bin_size):
     return out
 
 
+def write_merged(path, names, rec, bin_size):
+    """the output file: the header line, then one line per record, no newline at the end (:565-600)"""
+    with gzip.open(path, "wt") as f:
+        f.write(HEADER)
+        for ln in format_lines(names, rec, bin_size):
+            f.write("\n" + ln)
+
+
 def main():
     options = parse_args(sys.argv[1:])
     bin_size = int(options.resolution)
@@ -107,10 +122,7 @@ def main():
     names, rec, info = combine_records(df, bin_size, conn, pct, neigh, order)
     print("List of chromosomes considered: ", str(names))
     print("No of nodes: ", info.nodes, " connected components: ", info.components, " selected loops: ", info.selected)
-    with gzip.open(options.OutFile, "wt") as f:
-        f.write(HEADER)
-        for ln in format_lines(names, rec, bin_size):
-            f.write("\n" + ln)
+    write_merged(options.OutFile, names, rec, bin_size)
     print("End of merging filtering loops !!! ")
 
 

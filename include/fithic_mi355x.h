@@ -662,6 +662,42 @@ int fhx_vp_write_contacts(const char* path, const char* const* chr_names, int32_
                           const int32_t* mid1, const int32_t* chr2, const int32_t* mid2, const int32_t* count, int64_t n_rows,
                           int32_t gzip_level, int32_t n_threads);
 
+/* ---- the FDR subset of a significances file (fithic/utils/merge-filter.sh:22; csrc/fhx_sigselect.hip).
+ * One handle per GPU, independent of fhx_ctx.  The file (plain text, or gzip: it is inflated on the host first) goes through HBM
+ * in batches cut at the last newline (FHX_MS_BATCH_BYTES overrides the batch size of 256 MB; 8192 at least); kernels split every
+ * line on blanks, find field 7 and decide `$7 <= fdr` (`$7 < fdr` when strict) as mawk 1.3.4 decides it on the TEXT of the
+ * field, and gather the kept lines verbatim, in file order, each ending in a newline.  The subset stays in host memory.
+ * Taken: printable ASCII and tabs, lines of at most 4096 bytes ending in \n (the last one may end with the file), at least 7
+ * tokens per line, field 7 written as C's %e writes a non-negative finite double: D.DDDDDDe[+-]XX or e[+-]XXX.  Such a field is
+ *   zero     every digit 0: kept when zero_kept is set (the caller knows whether 0 <= fdr, or 0 < fdr);
+ *   numeric  first digit 1-9 and a value in [2.225074e-308, 9.999999e+307]: kept when its key
+ *            (exponent + 308) * 10^7 + the seven digits as one integer  is <= key_bound (0 keeps none): strtod is monotone in
+ *            the key, so the caller finds the bound by bisection with its own strtod;
+ *   string   a non-zero value below 2.225074e-308, or an exponent of 309 and more (mawk's strtod flags ERANGE there and awk
+ *            compares strings): kept when the field's bytes compare <= (< when strict) with fdr_text, memcmp then length.
+ * An exponent of exactly 308 is refused: mawk compares numbers up to 1.797693e+308 and strings above.
+ * With skip_first_line set, line 1 of the file is dropped without being parsed (the byte and length rules still hold for it).
+ * Anything else is refused and no subset is kept: *why = one of FHX_MS_*, *bad_line = the smallest offending 1-based line number
+ * (0 for FHX_MS_FDR).  Return value: FHX_ERR_UNSUPPORTED. */
+#define FHX_MS_OK 0
+#define FHX_MS_TOKENS 1            /* fewer than seven tokens (an empty line included) */
+#define FHX_MS_FIELD 2             /* field 7 is not in the %e shape, starts with 0 without being zero, or has exponent 308 */
+#define FHX_MS_BYTES 3             /* a NUL, another control byte than tab (\r included), DEL, a non-ASCII byte */
+#define FHX_MS_LONG_LINE 4         /* a line of more than 4096 bytes */
+#define FHX_MS_FDR 5               /* the text of fdr is empty or longer than FHX_MS_FDR_BYTES (no line number) */
+#define FHX_MS_INTERNAL 6          /* a device-side consistency check failed */
+#define FHX_MS_FDR_BYTES 32
+#define FHX_MS_STAGES 5            /* read + upload, newline scan, select, gather, copy out */
+typedef struct fhx_ms fhx_ms;
+int fhx_ms_create(int device, fhx_ms** out);
+void fhx_ms_destroy(fhx_ms* ms);
+const char* fhx_ms_last_error(const fhx_ms* ms);
+int fhx_ms_select_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept,
+                       int32_t strict, int32_t skip_first_line, int64_t* n_bytes, int32_t* why, int64_t* bad_line);
+int fhx_ms_counts(const fhx_ms* ms, int64_t* n_lines, int64_t* n_kept, int64_t* n_bytes);
+int fhx_ms_stage_seconds(const fhx_ms* ms, double* seconds);       /* FHX_MS_STAGES host clocks of the last call */
+int fhx_ms_copy_subset(const fhx_ms* ms, void* dst, int64_t capacity);   /* the n_bytes of the last selection */
+
 #ifdef __cplusplus
 }
 #endif
