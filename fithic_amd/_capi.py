@@ -1094,6 +1094,41 @@ def host_lbeta_table(n_total, max_count):
     return lb, ib
 
 
+# ---- the contexts beside Context: one native handle each, made by fhx_<prefix>_create -------------------------------------
+class _Handle:
+    """A native context on one GPU: fhx_<PREFIX>_create / _destroy / _last_error.  Raises without the built library or a GPU."""
+    PREFIX = None
+    REFUSED = None                   # the text paths: what _chk raises when the call named a reason
+
+    def __init__(self, device=0):
+        self.L = lib()
+        self.h = ctypes.c_void_p()
+        rc = self._fn("create")(int(device), ctypes.byref(self.h))
+        if rc != FHX_OK:
+            self.h = None
+            raise FhxError(rc, "fhx_%s_create(device=%d) failed: no usable MI355X / HIP runtime" % (self.PREFIX, device))
+
+    def _fn(self, name):
+        return getattr(self.L, "fhx_%s_%s" % (self.PREFIX, name))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _last_error(self):
+        return (self._fn("last_error")(self.h) or b"").decode()
+
+    def _chk(self, rc, why=0, *where):
+        """why, where: the reason (not 0: the file was refused) and the line (and index) a text path's call reported"""
+        if rc != FHX_OK and why:
+            raise self.REFUSED(rc, self._last_error(), why, *where)
+        if rc != FHX_OK:
+            raise FhxError(rc, self._last_error())
+
+
 # ---- Knight-Ruiz (fhx_kr_*) ------------------------------------------------------------------------------------------
 class KrInfo(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int64), ("nnz", ctypes.c_int64), ("outer_iterations", ctypes.c_int32),
@@ -1105,27 +1140,9 @@ class KrInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
-class KrContext:
+class KrContext(_Handle):
     """One Knight-Ruiz balancing context on one GPU (fhx_kr_*).  Raises without the built library or without a GPU."""
-
-    def __init__(self, device=0):
-        self.L = lib()
-        self.h = ctypes.c_void_p()
-        rc = self.L.fhx_kr_create(int(device), ctypes.byref(self.h))
-        if rc != FHX_OK:
-            self.h = None
-            raise FhxError(rc, "fhx_kr_create(device=%d) failed: no usable MI355X / HIP runtime" % device)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fhx_kr_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def _chk(self, rc):
-        if rc != FHX_OK:
-            raise FhxError(rc, (self.L.fhx_kr_last_error(self.h) or b"").decode())
+    PREFIX = "kr"
 
     def load_loci(self, chr_ids, mids):
         c, m = _i32(chr_ids), _i32(mids)
@@ -1161,7 +1178,7 @@ class KrContext:
         nrem, val, rem = ctypes.c_int64(), ctypes.c_double(), ctypes.c_int64()
         rc = self.L.fhx_kr_remove_sparse(self.h, float(perc), ctypes.byref(nrem), ctypes.byref(val), ctypes.byref(rem))
         if rc == FHX_ERR_REFERENCE_EXIT:
-            raise IndexError((self.L.fhx_kr_last_error(self.h) or b"").decode())
+            raise IndexError(self._last_error())
         self._chk(rc)
         idx = np.zeros(nrem.value, np.int64)
         self._chk(self.L.fhx_kr_get_removed(self.h, _ptr(idx, ctypes.c_int64), len(idx), None))
@@ -1171,7 +1188,7 @@ class KrContext:
         info = KrInfo()
         rc = self.L.fhx_kr_balance(self.h, float(tol), ctypes.byref(info))
         if rc == FHX_ERR_REFERENCE_EXIT:
-            raise ValueError((self.L.fhx_kr_last_error(self.h) or b"").decode())
+            raise ValueError(self._last_error())
         self._chk(rc)
         x = np.zeros(info.n, np.float64)
         if info.n:
@@ -1212,27 +1229,9 @@ CNI_RECORD = np.dtype([("chr", np.int32), ("reserved", np.int32), ("n_lo", np.in
                        ("component_size", np.int64), ("first_row", np.int64)])
 
 
-class CniContext:
+class CniContext(_Handle):
     """Connected-component merging of significant contacts on one GPU (fhx_cni_*).  Raises without the library or a GPU."""
-
-    def __init__(self, device=0):
-        self.L = lib()
-        self.h = ctypes.c_void_p()
-        rc = self.L.fhx_cni_create(int(device), ctypes.byref(self.h))
-        if rc != FHX_OK:
-            self.h = None
-            raise FhxError(rc, "fhx_cni_create(device=%d) failed: no usable MI355X / HIP runtime" % device)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fhx_cni_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def _chk(self, rc):
-        if rc != FHX_OK:
-            raise FhxError(rc, (self.L.fhx_cni_last_error(self.h) or b"").decode())
+    PREFIX = "cni"
 
     def load(self, chr_ids, n1, n2, cc, p, q, bin_size):
         c = _i32(chr_ids)
@@ -1265,28 +1264,14 @@ class HpRefused(FhxError):
         self.why, self.line, self.index = int(why), int(line), int(index)
 
 
-class HpContext:
+class HpContext(_Handle):
     """A HiC-Pro matrix parsed and accumulated on one GPU (fhx_hp_*).  Raises without the library or a GPU."""
+    PREFIX = "hp"
+    REFUSED = HpRefused
 
     def __init__(self, device=0):
-        self.L = lib()
-        self.h = ctypes.c_void_p()
         self.n_slots = self.n_rows = 0
-        rc = self.L.fhx_hp_create(int(device), ctypes.byref(self.h))
-        if rc != FHX_OK:
-            self.h = None
-            raise FhxError(rc, "fhx_hp_create(device=%d) failed: no usable MI355X / HIP runtime" % device)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fhx_hp_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def _chk(self, rc):
-        if rc != FHX_OK:
-            raise FhxError(rc, (self.L.fhx_hp_last_error(self.h) or b"").decode())
+        super().__init__(device)
 
     def load_bins(self, index_base, chr_ids, mids):
         """dense table over [index_base, index_base + len(chr_ids)); chr id -1 = index absent from the bed"""
@@ -1301,9 +1286,7 @@ class HpContext:
         n, why, line, index = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0), ctypes.c_int64(0)
         self.n_rows = 0
         rc = self.L.fhx_hp_parse_matrix(self.h, os.fsencode(path), ctypes.byref(n), ctypes.byref(why), ctypes.byref(line), ctypes.byref(index))
-        if rc != FHX_OK and why.value != HP_OK:
-            raise HpRefused(rc, (self.L.fhx_hp_last_error(self.h) or b"").decode(), why.value, line.value, index.value)
-        self._chk(rc)
+        self._chk(rc, why.value, line.value, index.value)
         self.n_rows = n.value
         return self.n_rows
 
@@ -1338,37 +1321,21 @@ class VpRefused(FhxError):
         self.why, self.line = int(why), int(line)
 
 
-class VpContext:
+class VpContext(_Handle):
     """A validPairs file binned, sorted and counted on one GPU (fhx_vp_*).  Raises without the library or a GPU."""
+    PREFIX = "vp"
+    REFUSED = VpRefused
 
     def __init__(self, device=0):
-        self.L = lib()
-        self.h = ctypes.c_void_p()
         self.n_cells = 0
-        rc = self.L.fhx_vp_create(int(device), ctypes.byref(self.h))
-        if rc != FHX_OK:
-            self.h = None
-            raise FhxError(rc, "fhx_vp_create(device=%d) failed: no usable MI355X / HIP runtime" % device)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fhx_vp_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def _chk(self, rc):
-        if rc != FHX_OK:
-            raise FhxError(rc, (self.L.fhx_vp_last_error(self.h) or b"").decode())
+        super().__init__(device)
 
     def bin_file(self, path, res):
         """-> number of cells; VpRefused for a file outside the device grammar"""
         n, why, line = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
         self.n_cells = 0
         rc = self.L.fhx_vp_bin_file(self.h, os.fsencode(path), int(res), ctypes.byref(n), ctypes.byref(why), ctypes.byref(line))
-        if rc != FHX_OK and why.value != VP_OK:
-            raise VpRefused(rc, (self.L.fhx_vp_last_error(self.h) or b"").decode(), why.value, line.value)
-        self._chk(rc)
+        self._chk(rc, why.value, line.value)
         self.n_cells = n.value
         return self.n_cells
 
@@ -1424,36 +1391,17 @@ class MsRefused(FhxError):
         self.why, self.line = int(why), int(line)
 
 
-class MsContext:
+class MsContext(_Handle):
     """The FDR subset of a significances file made on one GPU (fhx_ms_*).  Raises without the library or a GPU."""
-
-    def __init__(self, device=0):
-        self.L = lib()
-        self.h = ctypes.c_void_p()
-        rc = self.L.fhx_ms_create(int(device), ctypes.byref(self.h))
-        if rc != FHX_OK:
-            self.h = None
-            raise FhxError(rc, "fhx_ms_create(device=%d) failed: no usable MI355X / HIP runtime" % device)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.fhx_ms_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
-    def _chk(self, rc):
-        if rc != FHX_OK:
-            raise FhxError(rc, (self.L.fhx_ms_last_error(self.h) or b"").decode())
+    PREFIX = "ms"
+    REFUSED = MsRefused
 
     def select_file(self, path, fdr_text, key_bound, zero_kept, strict=False, skip_first_line=True):
         """-> bytes of the subset; MsRefused for a file outside the device grammar"""
         n, why, line = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
         rc = self.L.fhx_ms_select_file(self.h, os.fsencode(path), fdr_text, len(fdr_text), int(key_bound), int(bool(zero_kept)),
                                        int(bool(strict)), int(bool(skip_first_line)), ctypes.byref(n), ctypes.byref(why), ctypes.byref(line))
-        if rc != FHX_OK and why.value != MS_OK:
-            raise MsRefused(rc, (self.L.fhx_ms_last_error(self.h) or b"").decode(), why.value, line.value)
-        self._chk(rc)
+        self._chk(rc, why.value, line.value)
         return n.value
 
     def counts(self):

@@ -3,11 +3,10 @@
 //
 // The reference walks the matrix in Python: `i, j, cc = line.split()`, two dict lookups, `fragDic[i][3] += cc;
 // fragDic[j][3] += cc`, five str() and a gzip write per line.  Here the file goes to HBM as it is (two pinned buffers filled
-// by pread, drained by the copy engine) and kernels do everything that is per line:
+// by pread, drained by the copy engine: fhx_textupload.hpp) and kernels do everything that is per line:
 //
-//   hp_scan_text   16 KB of text per workgroup, 64 B per lane as 16-byte loads: newline count per block, and a flag for the
-//                  bytes this path does not take (NUL, non-ASCII, a \r that is not followed by \n)
-//   scan_tiles     exclusive scan of the block counts = the row number of every block's first line            (fhx_scan.hpp)
+//   scan_text, scan_tiles    the newline layer (fhx_textlines.hpp) with the text-mode byte policy: the row number of every
+//                  block's first line, and a flag for NUL, non-ASCII and a \r that is not followed by \n
 //   hp_parse       the lines that begin in a block, one per lane: three tokens, (chr, mid) of i and j gathered from the dense
 //                  bin table (8 B per index, L2-resident), five int32 columns stored coalesced in file order, the count added
 //                  to the totals of bin i and of bin j (a diagonal line `i i c` adds 2c, :40-41) as 64-bit INTEGER atomics:
@@ -23,92 +22,23 @@
 // answer whatever the launch order) and a reason; nothing stays loaded.  No line is ever parsed "approximately".
 #include <hip/hip_runtime.h>
 
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
-#include <atomic>
-#include <cerrno>
-#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
-#include "fhx_cpus.hpp"
-#include "fhx_scan.hpp"
+#include "fhx_textupload.hpp"
 
 namespace hpd {
 
-constexpr int WG = 256;
-constexpr int BLOCK_BYTES = 16384;             // text per workgroup
-constexpr int SEG = BLOCK_BYTES / WG;          // 64 bytes per lane in the newline passes
-constexpr int MAX_LINE = 4096;                 // a longer line is not a regular one
-constexpr unsigned long long NO_ERROR = ~0ull;
+using namespace fhxlines;
+
 constexpr unsigned long long TOTAL_LIMIT = 1ull << 53;
 
 __device__ inline bool is_space(int c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
-
-// ---- pass 1 over the text: newlines per block, and whether any byte is outside what this path takes ---------------------
-__global__ __launch_bounds__(WG) void hp_scan_text(const unsigned char* __restrict__ text, int64_t T, unsigned int* __restrict__ block_nl,
-                                                   unsigned int* __restrict__ bad_bytes) {
-    const int64_t p0 = (int64_t)blockIdx.x * BLOCK_BYTES + (int64_t)threadIdx.x * SEG;
-    unsigned int nl = 0;
-    bool bad = false;
-    if (p0 < T) {
-        const uint4* src = reinterpret_cast<const uint4*>(text + p0);        // the allocation is padded to whole blocks
-        for (int v = 0; v < SEG / 16; ++v) {
-            const uint4 w = src[v];
-            const unsigned int word[4] = {w.x, w.y, w.z, w.w};
-            for (int k = 0; k < 16; ++k) {
-                const int64_t p = p0 + v * 16 + k;
-                if (p >= T) break;
-                const unsigned int c = (word[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                nl += c == '\n';
-                bad |= c == 0 || c >= 0x80;
-                if (c == '\r') bad |= p + 1 >= T || text[p + 1] != '\n';     // text mode would end the line at a lone \r
-            }
-        }
-    }
-    unsigned int total;
-    fhxscan::block_exclusive_scan(nl, &total);
-    if (threadIdx.x == 0) block_nl[blockIdx.x] = total;
-    if (bad) atomicOr(bad_bytes, 1u);
-}
-
-// The lines that BEGIN after a newline of this block (and line 0 in block 0): their start offsets relative to the block, in
-// order, in LDS.  Row number of entry e: e in block 0, block_off[block] + 1 + e elsewhere.
-__device__ inline int block_lines(const unsigned char* __restrict__ text, int64_t T, unsigned short* lstart) {
-    const int64_t p0 = (int64_t)blockIdx.x * BLOCK_BYTES + (int64_t)threadIdx.x * SEG;
-    unsigned long long mask = 0;                                              // bit k: byte k of the segment is a newline
-    if (p0 < T) {
-        const uint4* src = reinterpret_cast<const uint4*>(text + p0);
-        for (int v = 0; v < SEG / 16; ++v) {
-            const uint4 w = src[v];
-            const unsigned int word[4] = {w.x, w.y, w.z, w.w};
-            for (int k = 0; k < 16; ++k) {
-                const unsigned int c = (word[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                if (c == '\n' && p0 + v * 16 + k + 1 < T) mask |= 1ull << (v * 16 + k);        // a newline that ends the text starts no line
-            }
-        }
-    }
-    const unsigned int first = (blockIdx.x == 0 && T > 0) ? 1u : 0u;
-    unsigned int total;
-    unsigned int rank = fhxscan::block_exclusive_scan((unsigned int)__popcll(mask), &total) + first;
-    if (first && threadIdx.x == 0) lstart[0] = 0;
-    while (mask) {
-        const int k = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        lstart[rank++] = (unsigned short)(threadIdx.x * SEG + k + 1);
-    }
-    __syncthreads();
-    return (int)(total + first);
-}
 
 // one lane's walk along its line; `why` keeps the first thing that was wrong with it
 struct Cursor {
@@ -209,7 +139,7 @@ __global__ __launch_bounds__(WG) void hp_parse(const unsigned char* __restrict__
                                                int32_t* __restrict__ chr1, int32_t* __restrict__ mid1, int32_t* __restrict__ chr2,
                                                int32_t* __restrict__ mid2, int32_t* __restrict__ count, unsigned long long* __restrict__ totals,
                                                unsigned long long* __restrict__ first_error, unsigned long long* __restrict__ absent_index) {
-    __shared__ unsigned short lstart[BLOCK_BYTES + 2];      // block 0: the implicit first line + one per newline byte = BLOCK_BYTES + 1 entries
+    __shared__ unsigned short lstart[LSTART_ENTRIES];
     const int n_lines = block_lines(text, T, lstart);
     const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
     const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
@@ -245,7 +175,7 @@ __global__ __launch_bounds__(WG) void hp_parse(const unsigned char* __restrict__
                 count[r] = cnt;
             } else {
                 si = sj = -1;
-                atomicMin(first_error, ((unsigned long long)(r + 1) << 8) | (unsigned long long)c.why);
+                atomicMin(first_error, error_word(r + 1, c.why));
                 if (c.why == FHX_HP_ABSENT) atomicMin(absent_index, ((unsigned long long)(r + 1) << 32) | (unsigned int)(int)absent);
             }
         }
@@ -264,10 +194,7 @@ __global__ __launch_bounds__(WG) void hp_max_total(const unsigned long long* __r
 }  // namespace hpd
 
 // ===================================================================================================================
-struct fhx_hp {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct fhx_hp : fhx::TextHandle {
     // the bin table: slot = index - index_base
     bool have_bins = false;
     int64_t index_base = 0, n_slots = 0;
@@ -277,24 +204,9 @@ struct fhx_hp {
     int64_t n_rows = 0;
     int32_t* d_cols = nullptr;                    // five columns of col_stride elements
     int64_t col_stride = 0;
-    // the upload path
-    static constexpr size_t kChunk = (size_t)32 << 20;
-    void* pinned[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 namespace {
-
-int hfail(fhx_hp* hp, int code, const std::string& msg) {
-    if (hp) hp->err = msg;
-    return code;
-}
-
-#define HP_HIP(call)                                                                                      \
-    do {                                                                                                  \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess) return hfail(hp, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 template <typename T>
 void hfree(T*& p) {
@@ -302,125 +214,35 @@ void hfree(T*& p) {
     p = nullptr;
 }
 
-// device temporaries of one call
-struct Scratch {
-    std::vector<void*> ptrs;
-    ~Scratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t get(T** p, size_t count) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-
-struct Fd {
-    int fd = -1;
-    ~Fd() {
-        if (fd >= 0) ::close(fd);
-    }
-};
-
 void drop_rows(fhx_hp* hp) {
     hfree(hp->d_cols);
     hp->n_rows = 0;
     hp->col_stride = 0;
 }
 
-// the file -> d_text: host threads pread into one of two pinned buffers while the copy engine drains the other
-int upload_file(fhx_hp* hp, int fd, int64_t T, unsigned char* d_text) {
-    for (int k = 0; k < 2; ++k) {
-        if (!hp->pinned[k]) HP_HIP(hipHostMalloc(&hp->pinned[k], fhx_hp::kChunk, hipHostMallocDefault));
-        if (!hp->ev[k]) HP_HIP(hipEventCreateWithFlags(&hp->ev[k], hipEventDisableTiming));
-    }
-    const int n_threads = std::min(fhx::usable_cpus(), 8);
-    bool used[2] = {false, false};
-    int turn = 0;
-    for (int64_t off = 0; off < T; off += (int64_t)fhx_hp::kChunk, turn ^= 1) {
-        const int64_t len = std::min<int64_t>((int64_t)fhx_hp::kChunk, T - off);
-        if (used[turn]) HP_HIP(hipEventSynchronize(hp->ev[turn]));
-        const int64_t slice = (int64_t)4 << 20;
-        const int64_t n_slices = (len + slice - 1) / slice;
-        std::atomic<int64_t> next{0};
-        std::atomic<int> io_errno{0};
-        auto work = [&]() {
-            for (;;) {
-                const int64_t s = next.fetch_add(1);
-                if (s >= n_slices) return;
-                int64_t done = s * slice;
-                const int64_t stop = std::min(len, done + slice);
-                while (done < stop) {
-                    const ssize_t got = ::pread(fd, (char*)hp->pinned[turn] + done, (size_t)(stop - done), (off_t)(off + done));
-                    if (got < 0 && errno == EINTR) continue;
-                    if (got <= 0) {                                           // an error, or the file shrank under us
-                        io_errno = got < 0 ? errno : EIO;
-                        return;
-                    }
-                    done += got;
-                }
-            }
-        };
-        const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, n_slices));
-        std::vector<std::thread> pool;
-        for (int k = 1; k < nt; ++k) pool.emplace_back(work);
-        work();
-        for (auto& th : pool) th.join();
-        if (io_errno) {
-            (void)hipStreamSynchronize(hp->stream);
-            return hfail(hp, FHX_ERR_ARG, std::string("reading the matrix file: ") + std::strerror(io_errno));
-        }
-        HP_HIP(hipMemcpyAsync(d_text + off, hp->pinned[turn], (size_t)len, hipMemcpyHostToDevice, hp->stream));
-        HP_HIP(hipEventRecord(hp->ev[turn], hp->stream));
-        used[turn] = true;
-    }
-    return FHX_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
-int fhx_hp_create(int device, fhx_hp** out) {
-    if (!out) return FHX_ERR_ARG;
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return FHX_ERR_NO_DEVICE;
-    fhx_hp* hp = new fhx_hp();
-    hp->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&hp->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete hp;
-        return FHX_ERR_HIP;
-    }
-    *out = hp;
-    return FHX_OK;
-}
+int fhx_hp_create(int device, fhx_hp** out) { return fhx::text_handle_create(device, out); }
 
 void fhx_hp_destroy(fhx_hp* hp) {
-    if (!hp) return;
-    (void)hipSetDevice(hp->device);
-    if (hp->stream) (void)hipStreamSynchronize(hp->stream);
-    drop_rows(hp);
-    hfree(hp->d_bins);
-    hfree(hp->d_totals);
-    for (int k = 0; k < 2; ++k) {
-        if (hp->pinned[k]) (void)hipHostFree(hp->pinned[k]);
-        if (hp->ev[k]) (void)hipEventDestroy(hp->ev[k]);
-    }
-    if (hp->stream) (void)hipStreamDestroy(hp->stream);
-    delete hp;
+    fhx::text_handle_destroy(hp, [&] {
+        drop_rows(hp);
+        hfree(hp->d_bins);
+        hfree(hp->d_totals);
+    });
 }
 
 const char* fhx_hp_last_error(const fhx_hp* hp) { return hp ? hp->err.c_str() : "null context"; }
 
 int fhx_hp_load_bins(fhx_hp* hp, int64_t index_base, const int32_t* chr_id, const int32_t* mid, int64_t n_slots) {
     if (!hp || n_slots < 0 || (n_slots > 0 && (!chr_id || !mid))) return FHX_ERR_ARG;
-    if (n_slots > ((int64_t)1 << 27)) return hfail(hp, FHX_ERR_UNSUPPORTED, "a bin table of more than 2^27 slots");
+    if (n_slots > ((int64_t)1 << 27)) return hp->fail(FHX_ERR_UNSUPPORTED, "a bin table of more than 2^27 slots");
     if (index_base < -((int64_t)1 << 31) || index_base + n_slots > ((int64_t)1 << 31))
-        return hfail(hp, FHX_ERR_UNSUPPORTED, "bin indices outside int32");
-    HP_HIP(hipSetDevice(hp->device));
-    HP_HIP(hipStreamSynchronize(hp->stream));
+        return hp->fail(FHX_ERR_UNSUPPORTED, "bin indices outside int32");
+    TH_HIP(hp, hipSetDevice(hp->device));
+    TH_HIP(hp, hipStreamSynchronize(hp->stream));
     drop_rows(hp);
     hfree(hp->d_bins);
     hfree(hp->d_totals);
@@ -428,11 +250,11 @@ int fhx_hp_load_bins(fhx_hp* hp, int64_t index_base, const int32_t* chr_id, cons
     std::vector<int2> table((size_t)n_slots);
     for (int64_t s = 0; s < n_slots; ++s) table[(size_t)s] = make_int2(chr_id[s] < 0 ? -1 : chr_id[s], mid[s]);
     const size_t slots = (size_t)std::max<int64_t>(n_slots, 1);
-    HP_HIP(hipMalloc((void**)&hp->d_bins, slots * sizeof(int2)));
-    HP_HIP(hipMalloc((void**)&hp->d_totals, slots * sizeof(unsigned long long)));
-    if (n_slots) HP_HIP(hipMemcpyAsync(hp->d_bins, table.data(), (size_t)n_slots * sizeof(int2), hipMemcpyHostToDevice, hp->stream));
-    HP_HIP(hipMemsetAsync(hp->d_totals, 0, slots * sizeof(unsigned long long), hp->stream));
-    HP_HIP(hipStreamSynchronize(hp->stream));                                 // `table` goes out of scope
+    TH_HIP(hp, hipMalloc((void**)&hp->d_bins, slots * sizeof(int2)));
+    TH_HIP(hp, hipMalloc((void**)&hp->d_totals, slots * sizeof(unsigned long long)));
+    if (n_slots) TH_HIP(hp, hipMemcpyAsync(hp->d_bins, table.data(), (size_t)n_slots * sizeof(int2), hipMemcpyHostToDevice, hp->stream));
+    TH_HIP(hp, hipMemsetAsync(hp->d_totals, 0, slots * sizeof(unsigned long long), hp->stream));
+    TH_HIP(hp, hipStreamSynchronize(hp->stream));                                 // `table` goes out of scope
     hp->index_base = index_base;
     hp->n_slots = n_slots;
     hp->have_bins = true;
@@ -446,66 +268,53 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
     *why = FHX_HP_OK;
     *bad_line = 0;
     *bad_index = 0;
-    if (!hp->have_bins) return hfail(hp, FHX_ERR_ARG, "fhx_hp_load_bins has not been called");
-    HP_HIP(hipSetDevice(hp->device));
-    HP_HIP(hipStreamSynchronize(hp->stream));
+    if (!hp->have_bins) return hp->fail(FHX_ERR_ARG, "fhx_hp_load_bins has not been called");
+    TH_HIP(hp, hipSetDevice(hp->device));
+    TH_HIP(hp, hipStreamSynchronize(hp->stream));
     drop_rows(hp);
     const size_t slots = (size_t)std::max<int64_t>(hp->n_slots, 1);
-    HP_HIP(hipMemsetAsync(hp->d_totals, 0, slots * sizeof(unsigned long long), hp->stream));
-    Fd f;
-    f.fd = ::open(path, O_RDONLY | O_CLOEXEC);
-    if (f.fd < 0) return hfail(hp, FHX_ERR_ARG, std::string(path) + ": " + std::strerror(errno));
-    struct stat sb;
-    if (::fstat(f.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return hfail(hp, FHX_ERR_ARG, std::string(path) + ": not a regular file");
-    const int64_t T = (int64_t)sb.st_size;
+    TH_HIP(hp, hipMemsetAsync(hp->d_totals, 0, slots * sizeof(unsigned long long), hp->stream));
+    fhx::TextFile src;
+    if (const int rc = src.open(path, /*allow_gzip=*/false, &hp->err)) return rc;
+    const int64_t T = src.size();
     if (T == 0) {                                                             // no lines: no rows, all totals zero
-        HP_HIP(hipStreamSynchronize(hp->stream));
+        TH_HIP(hp, hipStreamSynchronize(hp->stream));
         return FHX_OK;
     }
     const int64_t n_blocks = (T + BLOCK_BYTES - 1) / BLOCK_BYTES;
-    if (n_blocks > 0x7fffffffll) return hfail(hp, FHX_ERR_UNSUPPORTED, "a matrix file of more than 32 TB");
+    if (n_blocks > 0x7fffffffll) return hp->fail(FHX_ERR_UNSUPPORTED, "a matrix file of more than 32 TB");
     const bool timing = std::getenv("FHX_TIMING") != nullptr;
     double t_stage[3] = {0, 0, 0};
-    auto t_last = std::chrono::steady_clock::now();
-    auto mark = [&](int k) {                                                  // the stream is idle at every call
-        const auto now = std::chrono::steady_clock::now();
-        t_stage[k] += std::chrono::duration<double>(now - t_last).count();
-        t_last = now;
-    };
-    Scratch tmp;
+    fhx::StageClock clock{t_stage};
+    fhx::Scratch tmp;
     unsigned char* d_text = nullptr;
     unsigned int* d_block_nl = nullptr;
     unsigned long long *d_block_off = nullptr, *d_words = nullptr;
-    HP_HIP(tmp.get(&d_text, (size_t)n_blocks * BLOCK_BYTES + 64));
-    HP_HIP(tmp.get(&d_block_nl, (size_t)n_blocks));
-    HP_HIP(tmp.get(&d_block_off, (size_t)n_blocks));
+    TH_HIP(hp, tmp.get(&d_text, (size_t)n_blocks * BLOCK_BYTES + 64));
+    TH_HIP(hp, tmp.get(&d_block_nl, (size_t)n_blocks));
+    TH_HIP(hp, tmp.get(&d_block_off, (size_t)n_blocks));
     // d_words: [0] newlines in all, [1] smallest (line << 8 | reason), [2] smallest (line << 32 | index) among the absent-index
     // lines, [3] the largest total, [4] bytes-not-taken flag of the scan
-    HP_HIP(tmp.get(&d_words, 5));
-    {
-        const int rc = upload_file(hp, f.fd, T, d_text);
-        if (rc != FHX_OK) return rc;
-    }
-    HP_HIP(hipMemsetAsync(d_text + T, ' ', (size_t)(n_blocks * BLOCK_BYTES + 64 - T), hp->stream));
+    TH_HIP(hp, tmp.get(&d_words, 5));
+    fhx::TextBatch whole;                                                     // the whole file is resident: one batch
+    if (const int rc = fhx::upload_batch(hp, src, "matrix", 0, T, d_text, &whole)) return rc;
     const unsigned long long init[5] = {0ull, NO_ERROR, NO_ERROR, 0ull, 0ull};
-    HP_HIP(hipMemcpyAsync(d_words, init, sizeof(init), hipMemcpyHostToDevice, hp->stream));
-    HP_HIP(hipStreamSynchronize(hp->stream));                                 // the pinned buffers are free again; `init` may go
-    mark(0);
-    hipLaunchKernelGGL(hp_scan_text, dim3((unsigned)n_blocks), dim3(WG), 0, hp->stream, (const unsigned char*)d_text, T, d_block_nl,
+    TH_HIP(hp, hipMemcpyAsync(d_words, init, sizeof(init), hipMemcpyHostToDevice, hp->stream));
+    TH_HIP(hp, hipStreamSynchronize(hp->stream));                             // `init` may go
+    clock.mark(0);
+    hipLaunchKernelGGL(scan_text<TextModeBytes>, dim3((unsigned)n_blocks), dim3(WG), 0, hp->stream, (const unsigned char*)d_text, T, d_block_nl,
                        (unsigned int*)(d_words + 4));
     hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, hp->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
                        d_words);
-    HP_HIP(hipGetLastError());
+    TH_HIP(hp, hipGetLastError());
     unsigned long long n_newlines = 0;
-    unsigned char last = 0;
-    HP_HIP(hipMemcpyAsync(&n_newlines, d_words, sizeof(n_newlines), hipMemcpyDeviceToHost, hp->stream));
-    HP_HIP(hipMemcpyAsync(&last, d_text + T - 1, 1, hipMemcpyDeviceToHost, hp->stream));
-    HP_HIP(hipStreamSynchronize(hp->stream));
-    mark(1);
-    const int64_t n = (int64_t)n_newlines + (last == '\n' ? 0 : 1);
-    if (n > 0x7fffffffll) return hfail(hp, FHX_ERR_UNSUPPORTED, "a matrix of more than 2^31 - 1 lines");
+    TH_HIP(hp, hipMemcpyAsync(&n_newlines, d_words, sizeof(n_newlines), hipMemcpyDeviceToHost, hp->stream));
+    TH_HIP(hp, hipStreamSynchronize(hp->stream));
+    clock.mark(1);
+    const int64_t n = whole.lines(n_newlines);
+    if (n > 0x7fffffffll) return hp->fail(FHX_ERR_UNSUPPORTED, "a matrix of more than 2^31 - 1 lines");
     const int64_t stride = (n + 63) / 64 * 64;                                // every column starts on a 256-byte boundary
-    HP_HIP(hipMalloc((void**)&hp->d_cols, (size_t)std::max<int64_t>(stride, 64) * 5 * sizeof(int32_t)));
+    TH_HIP(hp, hipMalloc((void**)&hp->d_cols, (size_t)std::max<int64_t>(stride, 64) * 5 * sizeof(int32_t)));
     hp->col_stride = stride;
     int32_t* c = hp->d_cols;
     hipLaunchKernelGGL(hp_parse, dim3((unsigned)n_blocks), dim3(WG), 0, hp->stream, (const unsigned char*)d_text, T,
@@ -513,11 +322,11 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
                        c + stride, c + 2 * stride, c + 3 * stride, c + 4 * stride, hp->d_totals, d_words + 1, d_words + 2);
     hipLaunchKernelGGL(hp_max_total, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((hp->n_slots + WG - 1) / WG, 1024))), dim3(WG), 0,
                        hp->stream, (const unsigned long long*)hp->d_totals, (long long)hp->n_slots, d_words + 3);
-    HP_HIP(hipGetLastError());
+    TH_HIP(hp, hipGetLastError());
     unsigned long long words[5] = {0, 0, 0, 0, 0};
-    HP_HIP(hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, hp->stream));
-    HP_HIP(hipStreamSynchronize(hp->stream));
-    mark(2);
+    TH_HIP(hp, hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, hp->stream));
+    TH_HIP(hp, hipStreamSynchronize(hp->stream));
+    clock.mark(2);
     if (timing)
         std::fprintf(stderr, "hicpro matrix on the device (%s): %lld lines, %lld bytes: upload %.6f s; scan %.6f s; parse + accumulate %.6f s\n",
                      path, (long long)n, (long long)T, t_stage[0], t_stage[1], t_stage[2]);
@@ -528,11 +337,11 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
         *why = w;
         *bad_line = line;
         *bad_index = index;
-        return hfail(hp, rc, msg);
+        return hp->fail(rc, msg);
     };
     if (words[1] != NO_ERROR) {
-        const int32_t w = (int32_t)(words[1] & 0xFFu);
-        const int64_t line = (int64_t)(words[1] >> 8);
+        const int32_t w = error_why(words[1]);
+        const int64_t line = error_line(words[1]);
         if (w == FHX_HP_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, 0, "the line count of the scan and the parse kernel disagree");
         if (w == FHX_HP_ABSENT) {
             if ((int64_t)(words[2] >> 32) != line) return refuse(FHX_ERR_INTERNAL, FHX_HP_INTERNAL, line, 0, "error words disagree about the first bad line");
@@ -551,21 +360,21 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
 
 int fhx_hp_totals(fhx_hp* hp, int64_t* tcc) {
     if (!hp || (hp->n_slots > 0 && !tcc)) return FHX_ERR_ARG;
-    if (!hp->have_bins) return hfail(hp, FHX_ERR_ARG, "fhx_hp_load_bins has not been called");
-    HP_HIP(hipSetDevice(hp->device));
-    if (hp->n_slots) HP_HIP(hipMemcpyAsync(tcc, hp->d_totals, (size_t)hp->n_slots * sizeof(int64_t), hipMemcpyDeviceToHost, hp->stream));
-    HP_HIP(hipStreamSynchronize(hp->stream));
+    if (!hp->have_bins) return hp->fail(FHX_ERR_ARG, "fhx_hp_load_bins has not been called");
+    TH_HIP(hp, hipSetDevice(hp->device));
+    if (hp->n_slots) TH_HIP(hp, hipMemcpyAsync(tcc, hp->d_totals, (size_t)hp->n_slots * sizeof(int64_t), hipMemcpyDeviceToHost, hp->stream));
+    TH_HIP(hp, hipStreamSynchronize(hp->stream));
     return FHX_OK;
 }
 
 int fhx_hp_fetch_rows(fhx_hp* hp, int32_t* chr1, int32_t* mid1, int32_t* chr2, int32_t* mid2, int32_t* count) {
     if (!hp) return FHX_ERR_ARG;
     if (hp->n_rows > 0 && (!chr1 || !mid1 || !chr2 || !mid2 || !count)) return FHX_ERR_ARG;
-    HP_HIP(hipSetDevice(hp->device));
+    TH_HIP(hp, hipSetDevice(hp->device));
     int32_t* out[5] = {chr1, mid1, chr2, mid2, count};
     for (int k = 0; k < 5 && hp->n_rows > 0; ++k)
-        HP_HIP(hipMemcpyAsync(out[k], hp->d_cols + k * hp->col_stride, (size_t)hp->n_rows * sizeof(int32_t), hipMemcpyDeviceToHost, hp->stream));
-    HP_HIP(hipStreamSynchronize(hp->stream));
+        TH_HIP(hp, hipMemcpyAsync(out[k], hp->d_cols + k * hp->col_stride, (size_t)hp->n_rows * sizeof(int32_t), hipMemcpyDeviceToHost, hp->stream));
+    TH_HIP(hp, hipStreamSynchronize(hp->stream));
     return FHX_OK;
 }
 

@@ -4,8 +4,8 @@
 // int(mid), int(float(count)).  fhx_host_read_table does that on the host cores (0.8 s for 1.5e8 rows on 16 of them, then five
 // columns to upload and to index); here the inflated text goes to HBM as it is and kernels do the rest:
 //
-//   ti_scan_text   16 KB of text per workgroup: newline count, and the bytes this path does not take (see below)
-//   scan_tiles     exclusive scan of the block counts = the row number of every block's first line           (fhx_scan.hpp)
+//   scan_text, scan_tiles    the newline layer (fhx_textlines.hpp) with the text-mode byte policy: the row number of every
+//                  block's first line, and the bytes this path does not take (see below)
 //   ti_parse       the lines that begin in a block, one per thread: two names, two midpoints, the count.  Names go through a
 //                  64-bit hash into a 16 384-slot table in HBM; a wave inserts each DISTINCT name once (its lanes vote), and
 //                  only when the table does not yet hold it with an earlier position - sorted files touch it a few thousand
@@ -24,74 +24,15 @@
 namespace fhx {
 namespace ingest {
 
-constexpr int WG = 256;
-constexpr int BLOCK_BYTES = 16384;             // text per workgroup
-constexpr int SEG = BLOCK_BYTES / WG;          // 64 bytes per thread in the newline passes
+using namespace fhxlines;
+
 constexpr int TABLE_SLOTS = 16384;
 constexpr int MAX_NAMES = 8192;
 constexpr int NAME_STRIDE = 64;                // names of up to 63 bytes
-constexpr int MAX_LINE = 4096;                 // a longer line is not a regular one
 
-enum : unsigned int { F_BYTES = 1u, F_LINE = 2u, F_TABLE = 4u, F_COLLISION = 8u };
+enum : unsigned int { F_BYTES = REFUSED_BYTES, F_LINE = 2u, F_TABLE = 4u, F_COLLISION = 8u };
 
 __device__ inline bool is_space(int c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
-
-// ---- pass 1 over the text: newlines per block, and the bytes that send the file to the host parser ---------------------
-__global__ __launch_bounds__(WG) void ti_scan_text(const unsigned char* __restrict__ text, int64_t T, unsigned int* __restrict__ block_nl,
-                                                   unsigned int* __restrict__ flags) {
-    const int64_t p0 = (int64_t)blockIdx.x * BLOCK_BYTES + (int64_t)threadIdx.x * SEG;
-    unsigned int nl = 0;
-    bool bad = false;
-    if (p0 < T) {
-        const uint4* src = reinterpret_cast<const uint4*>(text + p0);        // the allocation is padded to whole blocks
-        for (int v = 0; v < SEG / 16; ++v) {
-            const uint4 w = src[v];
-            const unsigned int word[4] = {w.x, w.y, w.z, w.w};
-            for (int k = 0; k < 16; ++k) {
-                const int64_t p = p0 + v * 16 + k;
-                if (p >= T) break;
-                const unsigned int c = (word[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                nl += c == '\n';
-                bad |= c == 0 || c >= 0x80;
-                if (c == '\r') bad |= p + 1 >= T || text[p + 1] != '\n';     // text mode would end the line at a lone \r
-            }
-        }
-    }
-    unsigned int total;
-    fhxscan::block_exclusive_scan(nl, &total);
-    if (threadIdx.x == 0) block_nl[blockIdx.x] = total;
-    if (bad) atomicOr(flags, F_BYTES);
-}
-
-// The lines that BEGIN after a newline of this block (and line 0 in block 0): their start offsets relative to the block, in
-// order, in LDS.  Row number of entry e: e in block 0, block_off[block] + 1 + e elsewhere.
-__device__ inline int block_lines(const unsigned char* __restrict__ text, int64_t T, unsigned short* lstart) {
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t p0 = b0 + (int64_t)threadIdx.x * SEG;
-    unsigned long long mask = 0;                                              // bit k: byte k of the segment is a newline
-    if (p0 < T) {
-        const uint4* src = reinterpret_cast<const uint4*>(text + p0);
-        for (int v = 0; v < SEG / 16; ++v) {
-            const uint4 w = src[v];
-            const unsigned int word[4] = {w.x, w.y, w.z, w.w};
-            for (int k = 0; k < 16; ++k) {
-                const unsigned int c = (word[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                if (c == '\n' && p0 + v * 16 + k + 1 < T) mask |= 1ull << (v * 16 + k);        // a newline that ends the text starts no line
-            }
-        }
-    }
-    const unsigned int first = (blockIdx.x == 0 && T > 0) ? 1u : 0u;
-    unsigned int total;
-    unsigned int rank = fhxscan::block_exclusive_scan((unsigned int)__popcll(mask), &total) + first;
-    if (first && threadIdx.x == 0) lstart[0] = 0;
-    while (mask) {
-        const int k = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        lstart[rank++] = (unsigned short)(threadIdx.x * SEG + k + 1);
-    }
-    __syncthreads();
-    return (int)(total + first);
-}
 
 struct Cursor {
     const unsigned char* text;
@@ -227,7 +168,7 @@ __global__ __launch_bounds__(WG) void ti_parse(const unsigned char* __restrict__
                                                int32_t* __restrict__ mid1, int32_t* __restrict__ mid2, int32_t* __restrict__ count,
                                                unsigned int* __restrict__ slots, unsigned long long* __restrict__ t_hash,
                                                unsigned long long* __restrict__ t_off, unsigned int* __restrict__ flags) {
-    __shared__ unsigned short lstart[BLOCK_BYTES + 2];      // block 0: the implicit first line + one per newline byte = BLOCK_BYTES + 1 entries
+    __shared__ unsigned short lstart[LSTART_ENTRIES];
     const int n_lines = block_lines(text, T, lstart);
     const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
     const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
@@ -275,7 +216,7 @@ __global__ __launch_bounds__(WG) void ti_verify(const unsigned char* __restrict_
                                                 const unsigned int* __restrict__ slots, const short* __restrict__ slot_name,
                                                 const unsigned char* __restrict__ pool, const int* __restrict__ lens,
                                                 unsigned int* __restrict__ flags) {
-    __shared__ unsigned short lstart[BLOCK_BYTES + 2];      // block 0: the implicit first line + one per newline byte = BLOCK_BYTES + 1 entries
+    __shared__ unsigned short lstart[LSTART_ENTRIES];
     const int n_lines = block_lines(text, T, lstart);
     const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
     const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
@@ -390,7 +331,7 @@ static int ingest_parse_resident(fhx_ctx* ctx, DeviceScratch& tmp, unsigned char
     FHX_HIP(hipMemsetAsync(d_flags, 0, sizeof(unsigned int), ctx->stream));
     FHX_HIP(hipMemsetAsync(d_t_hash, 0, (size_t)TABLE_SLOTS * sizeof(unsigned long long), ctx->stream));
     FHX_HIP(hipMemsetAsync(d_t_off, 0xFF, (size_t)TABLE_SLOTS * sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(ti_scan_text, dim3((unsigned)n_blocks), dim3(WG), 0, ctx->stream, (const unsigned char*)d_text, T, d_block_nl, d_flags);
+    hipLaunchKernelGGL(scan_text<TextModeBytes>, dim3((unsigned)n_blocks), dim3(WG), 0, ctx->stream, (const unsigned char*)d_text, T, d_block_nl, d_flags);
     hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
                        d_total);
     unsigned long long n_newlines = 0;

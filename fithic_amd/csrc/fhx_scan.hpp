@@ -1,5 +1,7 @@
-// fhx_scan.hpp - ordered scan helpers shared by the sort-and-segment stages (fhx_kr.hip, fhx_cni.hip): run heads of a
-// sorted u64 key array -> per-tile counts -> exclusive tile offsets.  Tiles of 1024 keys, 256 threads x 4 consecutive keys.
+// fhx_scan.hpp - ordered scan helpers shared by the sort-and-segment stages (fhx_kr.hip, fhx_cni.hip, fhx_validpairs.hip) and by
+// the newline layer of the text paths (fhx_textlines.hpp: fhx_ingest.inc, fhx_hicpro.hip, fhx_validpairs.hip, fhx_sigselect.hip):
+// run heads of a sorted u64 key array -> per-tile counts -> exclusive tile offsets, and the block scan under both.  Tiles of
+// 1024 keys, 256 threads x 4 consecutive keys.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,12 +1,12 @@
 // fhx_sigselect.hip - the FDR subset of a Fit-Hi-C significances file on MI355X (gfx950)
 // (reference: fithic/utils/merge-filter.sh:22, `awk '{if(NR!=1){print $0}}' | awk -v q="$fdr" '{if($7<=q){print $0}}'`).
 //
-// The text goes through HBM in BATCHES cut at the last newline (two pinned buffers filled by pread, drained by the copy engine);
-// only the kept lines come back.  Per batch:
+// The text goes through HBM in BATCHES cut at the last newline (two pinned buffers filled by pread, drained by the copy engine:
+// fhx_textupload.hpp); only the kept lines come back.  Per batch:
 //
-//   ms_scan_text   16 KB of text per workgroup, 64 B per lane as 16-byte loads: newlines per block, and one flag for the batch
-//                  when a byte outside the grammar is seen (ms_select looks at bytes one by one only then)
-//   scan_tiles     exclusive scan of the block counts = the line number of every block's first line             (fhx_scan.hpp)
+//   scan_text, scan_tiles    the newline layer (fhx_textlines.hpp) with this grammar's byte policy: the line number of every
+//                  block's first line, and one flag for the batch when a byte outside the grammar is seen (ms_select looks at
+//                  bytes one by one only then)
 //   ms_select      the lines that begin in a block, one per lane.  One walk along the line splits it on blanks and finds field 7;
 //                  the field is taken only in the shape C's %e writes, D.DDDDDDe[+-]XX[X], and is then
 //                    zero     every digit 0: the number 0, kept when 0 <= fdr (0 < fdr when strict) - the host says which
@@ -25,33 +25,21 @@
 // costs one atomicMin (line << 8 | reason), so the smallest offending line is reported whatever the launch order.
 #include <hip/hip_runtime.h>
 
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
-#include <atomic>
-#include <cerrno>
-#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
-#include "fhx_cpus.hpp"
-#include "fhx_scan.hpp"
+#include "fhx_textupload.hpp"
 
 namespace msd {
 
-constexpr int WG = 256;
-constexpr int BLOCK_BYTES = 16384;             // text per workgroup
-constexpr int SEG = BLOCK_BYTES / WG;          // 64 bytes per lane in the newline passes
-constexpr int MAX_LINE = 4096;                 // a longer line is refused
-constexpr unsigned long long NO_ERROR = ~0ull;
+using namespace fhxlines;
+
 constexpr unsigned long long KEY_EXP = 10000000ull;      // key = (exponent + 308) * 10^7 + the seven digits
 
 // the threshold as the shell passes it: its bytes for the string class, by value
@@ -63,7 +51,8 @@ struct Fdr {
 // the words the kernels of one call share
 struct Words {
     unsigned long long newlines;               // scan_tiles' total of the current batch
-    unsigned long long bad_bytes;              // 1: ms_scan_text saw a byte outside the grammar in the current batch
+    unsigned long long bad_bytes;              // not 0: scan_text saw a byte outside the grammar in the current batch (it ORs
+                                               // REFUSED_BYTES into the word's low half)
     unsigned long long first_error;            // smallest (line << 8 | reason)
     unsigned long long kept_bytes;             // scan_tiles' total of the current batch
     unsigned long long kept_lines;             // of the current batch
@@ -71,59 +60,9 @@ struct Words {
 
 __device__ inline bool refused_byte(unsigned int c) { return c < 0x20u ? (c != '\t' && c != '\n') : c >= 0x7fu; }
 
-// ---- pass 1 over a batch: newlines per block, refused bytes anywhere ------------------------------------------------------------
-__global__ __launch_bounds__(WG) void ms_scan_text(const unsigned char* __restrict__ text, int64_t T, unsigned int* __restrict__ block_nl,
-                                                   Words* __restrict__ words) {
-    const int64_t p0 = (int64_t)blockIdx.x * BLOCK_BYTES + (int64_t)threadIdx.x * SEG;
-    unsigned int nl = 0;
-    bool bad = false;
-    if (p0 < T) {
-        const uint4* src = reinterpret_cast<const uint4*>(text + p0);        // the allocation is padded to whole blocks
-        for (int v = 0; v < SEG / 16; ++v) {
-            const uint4 w = src[v];
-            const unsigned int word[4] = {w.x, w.y, w.z, w.w};
-            for (int k = 0; k < 16; ++k) {
-                const unsigned int c = (word[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                const bool inside = p0 + v * 16 + k < T;
-                nl += (c == '\n' && inside) ? 1u : 0u;
-                bad |= inside && refused_byte(c);
-            }
-        }
-    }
-    unsigned int total;
-    fhxscan::block_exclusive_scan(nl, &total);
-    if (threadIdx.x == 0) block_nl[blockIdx.x] = total;
-    if (bad) __atomic_store_n(&words->bad_bytes, 1ull, __ATOMIC_RELAXED);     // every writer stores the same value
-}
-
-// The lines that BEGIN after a newline of this block (and line 0 in block 0): their start offsets relative to the block, in
-// order, in LDS.  Line number of entry e within the batch: e in block 0, block_off[block] + 1 + e elsewhere.
-__device__ inline int block_lines(const unsigned char* __restrict__ text, int64_t T, unsigned short* lstart) {
-    const int64_t p0 = (int64_t)blockIdx.x * BLOCK_BYTES + (int64_t)threadIdx.x * SEG;
-    unsigned long long mask = 0;                                              // bit k: byte k of the segment is a newline
-    if (p0 < T) {
-        const uint4* src = reinterpret_cast<const uint4*>(text + p0);
-        for (int v = 0; v < SEG / 16; ++v) {
-            const uint4 w = src[v];
-            const unsigned int word[4] = {w.x, w.y, w.z, w.w};
-            for (int k = 0; k < 16; ++k) {
-                const unsigned int c = (word[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                if (c == '\n' && p0 + v * 16 + k + 1 < T) mask |= 1ull << (v * 16 + k);        // a newline that ends the text starts no line
-            }
-        }
-    }
-    const unsigned int first = (blockIdx.x == 0 && T > 0) ? 1u : 0u;
-    unsigned int total;
-    unsigned int rank = fhxscan::block_exclusive_scan((unsigned int)__popcll(mask), &total) + first;
-    if (first && threadIdx.x == 0) lstart[0] = 0;
-    while (mask) {
-        const int k = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        lstart[rank++] = (unsigned short)(threadIdx.x * SEG + k + 1);         // 16384 for a line that starts the next block
-    }
-    __syncthreads();
-    return (int)(total + first);
-}
+struct GrammarBytes {                          // scan_text's policy
+    static __device__ void check(bool& bad, unsigned int c, const unsigned char*, int64_t, int64_t) { bad |= refused_byte(c); }
+};
 
 __device__ inline bool is_digit(int c) { return c >= '0' && c <= '9'; }
 
@@ -171,7 +110,7 @@ __global__ __launch_bounds__(WG) void ms_select(const unsigned char* __restrict_
                                                 int64_t n_lines_batch, int64_t line_base, Fdr fdr, unsigned long long key_bound, int zero_kept,
                                                 int strict, int skip_first_line, int check_bytes, unsigned short* __restrict__ keep_len,
                                                 unsigned int* __restrict__ block_bytes, Words* __restrict__ words) {
-    __shared__ unsigned short lstart[BLOCK_BYTES + 2];      // block 0: the implicit first line + one per newline byte = BLOCK_BYTES + 1 entries
+    __shared__ unsigned short lstart[LSTART_ENTRIES];
     const int n_lines = block_lines(text, T, lstart);
     const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
     const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
@@ -221,7 +160,7 @@ __global__ __launch_bounds__(WG) void ms_select(const unsigned char* __restrict_
                 }
             }
         }
-        if (why) atomicMin(&words->first_error, ((unsigned long long)(line_base + r + 1) << 8) | (unsigned long long)why);
+        if (why) atomicMin(&words->first_error, error_word(line_base + r + 1, why));
         const unsigned int len = (keep && !why) ? (unsigned int)(p - start) + 1u : 0u;      // with its newline, present or not
         if (r < n_lines_batch) keep_len[r] = (unsigned short)len;             // at most MAX_LINE + 1
         my_bytes += len;
@@ -240,7 +179,7 @@ __global__ __launch_bounds__(WG) void ms_select(const unsigned char* __restrict_
 __global__ __launch_bounds__(WG) void ms_gather(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ block_off,
                                                 int64_t n_lines_batch, const unsigned short* __restrict__ keep_len,
                                                 const unsigned long long* __restrict__ out_off, unsigned char* __restrict__ out, int64_t out_capacity) {
-    __shared__ unsigned short lstart[BLOCK_BYTES + 2];
+    __shared__ unsigned short lstart[LSTART_ENTRIES];
     __shared__ unsigned int pre[WG + 1];                    // round-local exclusive prefix of the kept lengths; pre[WG] = their sum
     const int n_lines = block_lines(text, T, lstart);
     const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
@@ -273,155 +212,28 @@ __global__ __launch_bounds__(WG) void ms_gather(const unsigned char* __restrict_
 }  // namespace msd
 
 // ===================================================================================================================
-struct fhx_ms {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct fhx_ms : fhx::TextHandle {
     // the last selection
     std::vector<char> subset;
     int64_t n_lines = 0, n_kept = 0;
     double seconds[FHX_MS_STAGES] = {0, 0, 0, 0, 0};
-    // the upload path
-    static constexpr size_t kChunk = (size_t)32 << 20;
-    void* pinned[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 namespace {
-
-int mfail(fhx_ms* ms, int code, const std::string& msg) {
-    if (ms) ms->err = msg;
-    return code;
-}
-
-#define MS_HIP(call)                                                                                      \
-    do {                                                                                                  \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess) return mfail(ms, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// device temporaries of one call
-struct Scratch {
-    std::vector<void*> ptrs;
-    ~Scratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t get(T** p, size_t count) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-    void drop(void* p) {
-        auto it = std::find(ptrs.begin(), ptrs.end(), p);
-        if (it != ptrs.end()) {
-            (void)hipFree(p);
-            ptrs.erase(it);
-        }
-    }
-};
-
-// the text: a file read with pread, or the inflated bytes of a gzip file
-struct Source {
-    int fd = -1;
-    std::vector<char> inflated;
-    int64_t size = 0;
-    ~Source() {
-        if (fd >= 0) ::close(fd);
-    }
-};
 
 void drop_subset(fhx_ms* ms) {
     std::vector<char>().swap(ms->subset);
     ms->n_lines = ms->n_kept = 0;
 }
 
-// bytes [off, off + len) of the source -> d_text[0, len): host threads fill one of two pinned buffers while the copy engine
-// drains the other.  *last_newline = the offset (within the range) of the range's last newline, -1 without one.
-int upload_range(fhx_ms* ms, Source& src, int64_t off, int64_t len, unsigned char* d_text, int64_t* last_newline) {
-    for (int k = 0; k < 2; ++k) {
-        if (!ms->pinned[k]) MS_HIP(hipHostMalloc(&ms->pinned[k], fhx_ms::kChunk, hipHostMallocDefault));
-        if (!ms->ev[k]) MS_HIP(hipEventCreateWithFlags(&ms->ev[k], hipEventDisableTiming));
-    }
-    const int n_threads = std::min(fhx::usable_cpus(), 8);
-    bool used[2] = {false, false};
-    int turn = 0;
-    *last_newline = -1;
-    for (int64_t done = 0; done < len; done += (int64_t)fhx_ms::kChunk, turn ^= 1) {
-        const int64_t now = std::min<int64_t>((int64_t)fhx_ms::kChunk, len - done);
-        if (used[turn]) MS_HIP(hipEventSynchronize(ms->ev[turn]));
-        char* dst = (char*)ms->pinned[turn];
-        if (src.fd < 0) {
-            std::memcpy(dst, src.inflated.data() + off + done, (size_t)now);
-        } else {
-            const int64_t slice = (int64_t)4 << 20;
-            const int64_t n_slices = (now + slice - 1) / slice;
-            std::atomic<int64_t> next{0};
-            std::atomic<int> io_errno{0};
-            auto work = [&]() {
-                for (;;) {
-                    const int64_t s = next.fetch_add(1);
-                    if (s >= n_slices) return;
-                    int64_t at = s * slice;
-                    const int64_t stop = std::min(now, at + slice);
-                    while (at < stop) {
-                        const ssize_t got = ::pread(src.fd, dst + at, (size_t)(stop - at), (off_t)(off + done + at));
-                        if (got < 0 && errno == EINTR) continue;
-                        if (got <= 0) {                                       // an error, or the file shrank under us
-                            io_errno = got < 0 ? errno : EIO;
-                            return;
-                        }
-                        at += got;
-                    }
-                }
-            };
-            const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, n_slices));
-            std::vector<std::thread> pool;
-            for (int k = 1; k < nt; ++k) pool.emplace_back(work);
-            work();
-            for (auto& th : pool) th.join();
-            if (io_errno) {
-                (void)hipStreamSynchronize(ms->stream);
-                return mfail(ms, FHX_ERR_ARG, std::string("reading the significances file: ") + std::strerror(io_errno));
-            }
-        }
-        if (const void* nl = ::memrchr(dst, '\n', (size_t)now)) *last_newline = done + ((const char*)nl - dst);
-        MS_HIP(hipMemcpyAsync(d_text + done, dst, (size_t)now, hipMemcpyHostToDevice, ms->stream));
-        MS_HIP(hipEventRecord(ms->ev[turn], ms->stream));
-        used[turn] = true;
-    }
-    return FHX_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
-int fhx_ms_create(int device, fhx_ms** out) {
-    if (!out) return FHX_ERR_ARG;
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return FHX_ERR_NO_DEVICE;
-    fhx_ms* ms = new fhx_ms();
-    ms->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ms->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete ms;
-        return FHX_ERR_HIP;
-    }
-    *out = ms;
-    return FHX_OK;
-}
+int fhx_ms_create(int device, fhx_ms** out) { return fhx::text_handle_create(device, out); }
 
 void fhx_ms_destroy(fhx_ms* ms) {
-    if (!ms) return;
-    (void)hipSetDevice(ms->device);
-    if (ms->stream) (void)hipStreamSynchronize(ms->stream);
-    for (int k = 0; k < 2; ++k) {
-        if (ms->pinned[k]) (void)hipHostFree(ms->pinned[k]);
-        if (ms->ev[k]) (void)hipEventDestroy(ms->ev[k]);
-    }
-    if (ms->stream) (void)hipStreamDestroy(ms->stream);
-    delete ms;
+    fhx::text_handle_destroy(ms, [] {});
 }
 
 const char* fhx_ms_last_error(const fhx_ms* ms) { return ms ? ms->err.c_str() : "null context"; }
@@ -433,105 +245,68 @@ int fhx_ms_select_file(fhx_ms* ms, const char* path, const char* fdr_text, int32
     *n_bytes = 0;
     *why = FHX_MS_OK;
     *bad_line = 0;
-    MS_HIP(hipSetDevice(ms->device));
-    MS_HIP(hipStreamSynchronize(ms->stream));
+    TH_HIP(ms, hipSetDevice(ms->device));
+    TH_HIP(ms, hipStreamSynchronize(ms->stream));
     drop_subset(ms);
     for (double& s : ms->seconds) s = 0;
     if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) {
         *why = FHX_MS_FDR;
-        return mfail(ms, FHX_ERR_UNSUPPORTED, "the text of fdr must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
+        return ms->fail(FHX_ERR_UNSUPPORTED, "the text of fdr must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
     }
     Fdr fdr;
     std::memset(&fdr, 0, sizeof(fdr));
     std::memcpy(fdr.text, fdr_text, (size_t)fdr_len);
     fdr.len = fdr_len;
-    auto t_last = std::chrono::steady_clock::now();
-    auto mark = [&](int k) {                                                  // the stream is idle at every call
-        const auto now = std::chrono::steady_clock::now();
-        ms->seconds[k] += std::chrono::duration<double>(now - t_last).count();
-        t_last = now;
-    };
-    // ---- the source: the file itself, or its inflated bytes when it starts with the gzip magic --------------------------------
-    Source src;
-    src.fd = ::open(path, O_RDONLY | O_CLOEXEC);
-    if (src.fd < 0) return mfail(ms, FHX_ERR_ARG, std::string(path) + ": " + std::strerror(errno));
-    struct stat sb;
-    if (::fstat(src.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return mfail(ms, FHX_ERR_ARG, std::string(path) + ": not a regular file");
-    src.size = (int64_t)sb.st_size;
-    unsigned char magic[2] = {0, 0};
-    if (src.size >= 2 && ::pread(src.fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
-        fhx_text* x = nullptr;
-        int rc = fhx_host_inflate(path, 0, &x);
-        if (rc != FHX_OK) {
-            const std::string msg = x ? fhx_text_error(x) : "fhx_host_inflate";
-            fhx_text_free(x);
-            return mfail(ms, rc, msg);
-        }
-        src.inflated.resize((size_t)fhx_text_bytes(x));
-        rc = fhx_text_copy(x, src.inflated.data(), (int64_t)src.inflated.size());
-        fhx_text_free(x);
-        if (rc != FHX_OK) return mfail(ms, rc, "fhx_text_copy");
-        ::close(src.fd);
-        src.fd = -1;
-        src.size = (int64_t)src.inflated.size();
-    }
-    // ---- the batches ---------------------------------------------------------------------------------------------------------
-    int64_t batch_bytes = (int64_t)256 << 20;                                 // FHX_MS_BATCH_BYTES overrides (tests put a batch edge inside a small file)
-    if (const char* e = std::getenv("FHX_MS_BATCH_BYTES")) batch_bytes = std::atoll(e);
-    batch_bytes = std::max<int64_t>(2 * MAX_LINE, std::min<int64_t>(batch_bytes, (int64_t)1 << 31));
-    batch_bytes = std::min(batch_bytes, std::max<int64_t>(src.size, 2 * MAX_LINE));
+    fhx::StageClock clock{ms->seconds};
+    // the file itself, or its inflated bytes when it starts with the gzip magic
+    fhx::TextFile src;
+    if (const int rc = src.open(path, /*allow_gzip=*/true, &ms->err)) return rc;
+    const int64_t batch_bytes = fhx::batch_bytes_for("FHX_MS_BATCH_BYTES", (int64_t)1 << 31, src.size());
     const int64_t max_blocks = (batch_bytes + BLOCK_BYTES - 1) / BLOCK_BYTES;
     const int64_t out_capacity = batch_bytes + 1;                             // every line kept, and the newline the last one lacked
-    Scratch tmp;
+    fhx::Scratch tmp;
     unsigned char *d_text = nullptr, *d_out = nullptr;
     unsigned int *d_block_nl = nullptr, *d_block_bytes = nullptr;
     unsigned long long *d_block_off = nullptr, *d_out_off = nullptr;
     unsigned short* d_keep_len = nullptr;
     int64_t keep_capacity = 0;
     Words* d_words = nullptr;
-    MS_HIP(tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
-    MS_HIP(tmp.get(&d_out, (size_t)out_capacity));
-    MS_HIP(tmp.get(&d_block_nl, (size_t)max_blocks));
-    MS_HIP(tmp.get(&d_block_bytes, (size_t)max_blocks));
-    MS_HIP(tmp.get(&d_block_off, (size_t)max_blocks));
-    MS_HIP(tmp.get(&d_out_off, (size_t)max_blocks));
-    MS_HIP(tmp.get(&d_words, 1));
+    TH_HIP(ms, tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
+    TH_HIP(ms, tmp.get(&d_out, (size_t)out_capacity));
+    TH_HIP(ms, tmp.get(&d_block_nl, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_block_bytes, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_block_off, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_out_off, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_words, 1));
     Words words;
     auto refuse = [&](int rc, int32_t w, int64_t line, const std::string& msg) {
         drop_subset(ms);
         *why = w;
         *bad_line = line;
-        return mfail(ms, rc, msg);
+        return ms->fail(rc, msg);
     };
     int64_t lines = 0, kept = 0;
-    for (int64_t off = 0; off < src.size;) {
-        int64_t len = std::min(batch_bytes, src.size - off), last_nl = -1;
+    for (int64_t off = 0; off < src.size();) {
         std::memset(&words, 0, sizeof(words));
         words.first_error = NO_ERROR;
-        MS_HIP(hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, ms->stream));
-        {
-            const int rc = upload_range(ms, src, off, len, d_text, &last_nl);
-            if (rc != FHX_OK) return rc;
-        }
-        // a batch that does not reach the end of the text ends after its last newline; without one its single line is longer than
-        // MAX_LINE and the select kernel says so
-        if (off + len < src.size && last_nl >= 0) len = last_nl + 1;
-        const int64_t n_blocks = (len + BLOCK_BYTES - 1) / BLOCK_BYTES;
-        MS_HIP(hipMemsetAsync(d_text + len, ' ', (size_t)(n_blocks * BLOCK_BYTES + 64 - len), ms->stream));
-        MS_HIP(hipStreamSynchronize(ms->stream));                             // the pinned buffers are free again
-        mark(0);
-        hipLaunchKernelGGL(ms_scan_text, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len, d_block_nl, d_words);
+        TH_HIP(ms, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, ms->stream));
+        fhx::TextBatch b;
+        if (const int rc = fhx::upload_batch(ms, src, "significances", off, std::min(batch_bytes, src.size() - off), d_text, &b)) return rc;
+        const int64_t len = b.len, n_blocks = b.n_blocks;
+        clock.mark(0);
+        hipLaunchKernelGGL(scan_text<GrammarBytes>, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len, d_block_nl,
+                           (unsigned int*)&d_words->bad_bytes);
         hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
                            &d_words->newlines);
-        MS_HIP(hipGetLastError());
-        MS_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
-        MS_HIP(hipStreamSynchronize(ms->stream));
-        mark(1);
-        const int64_t n = (int64_t)words.newlines + (last_nl == len - 1 ? 0 : 1);
+        TH_HIP(ms, hipGetLastError());
+        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
+        TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        clock.mark(1);
+        const int64_t n = b.lines(words.newlines);
         if (n > keep_capacity) {                                              // one length per line of the batch
             if (d_keep_len) tmp.drop(d_keep_len);
             d_keep_len = nullptr;
-            MS_HIP(tmp.get(&d_keep_len, (size_t)n));
+            TH_HIP(ms, tmp.get(&d_keep_len, (size_t)n));
             keep_capacity = n;
         }
         hipLaunchKernelGGL(ms_select, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
@@ -539,13 +314,13 @@ int fhx_ms_select_file(fhx_ms* ms, const char* path, const char* fdr_text, int32
                            (int)skip_first_line, (int)(words.bad_bytes != 0), d_keep_len, d_block_bytes, d_words);
         hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_bytes, n_blocks, d_out_off,
                            &d_words->kept_bytes);
-        MS_HIP(hipGetLastError());
-        MS_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
-        MS_HIP(hipStreamSynchronize(ms->stream));
-        mark(2);
+        TH_HIP(ms, hipGetLastError());
+        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
+        TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        clock.mark(2);
         if (words.first_error != NO_ERROR) {                                  // earlier batches hold the smaller line numbers
-            const int32_t w = (int32_t)(words.first_error & 0xFFu);
-            const int64_t line = (int64_t)(words.first_error >> 8);
+            const int32_t w = error_why(words.first_error);
+            const int64_t line = error_line(words.first_error);
             if (w == FHX_MS_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, "the line count of the scan and the select kernel disagree");
             return refuse(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
         }
@@ -555,17 +330,17 @@ int fhx_ms_select_file(fhx_ms* ms, const char* path, const char* fdr_text, int32
             hipLaunchKernelGGL(ms_gather, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
                                (const unsigned long long*)d_block_off, n, (const unsigned short*)d_keep_len, (const unsigned long long*)d_out_off, d_out,
                                out_capacity);
-            MS_HIP(hipGetLastError());
-            MS_HIP(hipStreamSynchronize(ms->stream));
+            TH_HIP(ms, hipGetLastError());
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
         }
-        mark(3);
+        clock.mark(3);
         if (bytes > 0) {
             const size_t had = ms->subset.size();
             ms->subset.resize(had + (size_t)bytes);
-            MS_HIP(hipMemcpyAsync(ms->subset.data() + had, d_out, (size_t)bytes, hipMemcpyDeviceToHost, ms->stream));
-            MS_HIP(hipStreamSynchronize(ms->stream));
+            TH_HIP(ms, hipMemcpyAsync(ms->subset.data() + had, d_out, (size_t)bytes, hipMemcpyDeviceToHost, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
         }
-        mark(4);
+        clock.mark(4);
         lines += n;
         kept += (int64_t)words.kept_lines;
         off += len;

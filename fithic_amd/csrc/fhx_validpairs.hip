@@ -1,11 +1,11 @@
 // fhx_validpairs.hip - HiC-Pro's allValidPairs (one line per read pair) binned into Fit-Hi-C's contact counts on MI355X (gfx950)
 // (reference: fithic/utils/validPairs2FitHiC-fixedSize.sh:33-40, the pipeline of five awk, grep, sort, uniq -c and sed).
 //
-// The text goes through HBM in BATCHES cut at the last newline (two pinned buffers filled by pread, drained by the copy engine),
-// so a 100 GB file never has to be resident: only 16 bytes per kept pair accumulate.  Per batch:
+// The text goes through HBM in BATCHES cut at the last newline (two pinned buffers filled by pread, drained by the copy engine:
+// fhx_textupload.hpp), so a 100 GB file never has to be resident: only 16 bytes per kept pair accumulate.  Per batch:
 //
-//   vp_scan_text   16 KB of text per workgroup, 64 B per lane as 16-byte loads: newlines per block
-//   scan_tiles     exclusive scan of the block counts = the line number of every block's first line             (fhx_scan.hpp)
+//   scan_text, scan_tiles    the newline layer (fhx_textlines.hpp), no byte refused there: the line number of every block's
+//                  first line
 //   vp_parse       the lines that begin in a block, one per lane.  One walk along the line splits it on blanks, keeps where
 //                  tokens 2, 3, 5, 6 lie and looks for `chrM` anywhere (grep -v chrM, :34); then the name-length filter (:34),
 //                  the distance filter (pos1-pos2)^2 > 2*res (:35 - the comparison sits INSIDE the sqrt), the bins
@@ -29,35 +29,23 @@
 // (one 64-bit word, atomicMin over line << 8 | reason: the same answer whatever the launch order) and nothing stays loaded.
 #include <hip/hip_runtime.h>
 
-#include <fcntl.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
-#include <atomic>
-#include <cerrno>
-#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
-#include "fhx_cpus.hpp"
-#include "fhx_scan.hpp"
+#include "fhx_textupload.hpp"
 
 namespace vpd {
 
-constexpr int WG = 256;
-constexpr int BLOCK_BYTES = 16384;             // text per workgroup
-constexpr int SEG = BLOCK_BYTES / WG;          // 64 bytes per lane in the newline passes
-constexpr int MAX_LINE = 4096;                 // a longer line is not a regular one
+using namespace fhxlines;
+
 constexpr int NAME_SLOTS = 2048;               // the device name table (open addressing, at most half full)
 constexpr int MAX_NAMES = 1024;
-constexpr unsigned long long NO_ERROR = ~0ull;
 
 // the words the kernels of one call share
 struct Words {
@@ -69,56 +57,8 @@ struct Words {
     unsigned long long n_cells;                // scan_tiles' total of the heads
     unsigned long long max_count;              // largest cell count
     unsigned long long names_overflow;         // 1: a pair named a name the full table could not take
+    unsigned long long scan_flags;             // scan_text's flag word: this path's policy refuses no byte, it stays 0
 };
-
-// ---- pass 1 over a batch: newlines per block -----------------------------------------------------------------------------
-__global__ __launch_bounds__(WG) void vp_scan_text(const unsigned char* __restrict__ text, int64_t T, unsigned int* __restrict__ block_nl) {
-    const int64_t p0 = (int64_t)blockIdx.x * BLOCK_BYTES + (int64_t)threadIdx.x * SEG;
-    unsigned int nl = 0;
-    if (p0 < T) {
-        const uint4* src = reinterpret_cast<const uint4*>(text + p0);        // the allocation is padded to whole blocks
-        for (int v = 0; v < SEG / 16; ++v) {
-            const uint4 w = src[v];
-            const unsigned int word[4] = {w.x, w.y, w.z, w.w};
-            for (int k = 0; k < 16; ++k) {
-                const unsigned int c = (word[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                nl += (c == '\n' && p0 + v * 16 + k < T) ? 1u : 0u;
-            }
-        }
-    }
-    unsigned int total;
-    fhxscan::block_exclusive_scan(nl, &total);
-    if (threadIdx.x == 0) block_nl[blockIdx.x] = total;
-}
-
-// The lines that BEGIN after a newline of this block (and line 0 in block 0): their start offsets relative to the block, in
-// order, in LDS.  Line number of entry e within the batch: e in block 0, block_off[block] + 1 + e elsewhere.
-__device__ inline int block_lines(const unsigned char* __restrict__ text, int64_t T, unsigned short* lstart) {
-    const int64_t p0 = (int64_t)blockIdx.x * BLOCK_BYTES + (int64_t)threadIdx.x * SEG;
-    unsigned long long mask = 0;                                              // bit k: byte k of the segment is a newline
-    if (p0 < T) {
-        const uint4* src = reinterpret_cast<const uint4*>(text + p0);
-        for (int v = 0; v < SEG / 16; ++v) {
-            const uint4 w = src[v];
-            const unsigned int word[4] = {w.x, w.y, w.z, w.w};
-            for (int k = 0; k < 16; ++k) {
-                const unsigned int c = (word[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                if (c == '\n' && p0 + v * 16 + k + 1 < T) mask |= 1ull << (v * 16 + k);        // a newline that ends the text starts no line
-            }
-        }
-    }
-    const unsigned int first = (blockIdx.x == 0 && T > 0) ? 1u : 0u;
-    unsigned int total;
-    unsigned int rank = fhxscan::block_exclusive_scan((unsigned int)__popcll(mask), &total) + first;
-    if (first && threadIdx.x == 0) lstart[0] = 0;
-    while (mask) {
-        const int k = __ffsll((long long)mask) - 1;
-        mask &= mask - 1;
-        lstart[rank++] = (unsigned short)(threadIdx.x * SEG + k + 1);
-    }
-    __syncthreads();
-    return (int)(total + first);
-}
 
 __device__ inline bool is_digit(int c) { return c >= '0' && c <= '9'; }
 __device__ inline bool is_alpha(int c) { return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); }
@@ -188,7 +128,7 @@ __device__ inline int intern_name(unsigned long long* __restrict__ table, unsign
 __global__ __launch_bounds__(WG) void vp_parse(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ block_off,
                                                int64_t n_lines_batch, int64_t line_base, long long res, unsigned long long* __restrict__ names,
                                                ulonglong2* __restrict__ records, unsigned long long capacity, Words* __restrict__ words) {
-    __shared__ unsigned short lstart[BLOCK_BYTES + 2];      // block 0: the implicit first line + one per newline byte = BLOCK_BYTES + 1 entries
+    __shared__ unsigned short lstart[LSTART_ENTRIES];
     __shared__ unsigned long long out_base;
     const int n_lines = block_lines(text, T, lstart);
     const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
@@ -282,7 +222,7 @@ __global__ __launch_bounds__(WG) void vp_parse(const unsigned char* __restrict__
                     }
                 }
             }
-            if (why) atomicMin(&words->first_error, ((unsigned long long)(line_base + r + 1) << 8) | (unsigned long long)why);
+            if (why) atomicMin(&words->first_error, error_word(line_base + r + 1, why));
         }
         unsigned int total;
         const unsigned int at = fhxscan::block_exclusive_scan(keep ? 1u : 0u, &total);
@@ -291,7 +231,7 @@ __global__ __launch_bounds__(WG) void vp_parse(const unsigned char* __restrict__
         if (keep) {
             const unsigned long long pos = out_base + at;
             if (pos < capacity) records[pos] = rec;
-            else atomicMin(&words->first_error, ((unsigned long long)(line_base + row0 + e + 1) << 8) | (unsigned long long)FHX_VP_INTERNAL);
+            else atomicMin(&words->first_error, error_word(line_base + row0 + e + 1, FHX_VP_INTERNAL));
         }
         __syncthreads();                                    // out_base is written again in the next round
     }
@@ -371,66 +311,17 @@ __global__ __launch_bounds__(WG) void vp_cells(const unsigned long long* __restr
 }  // namespace vpd
 
 // ===================================================================================================================
-struct fhx_vp {
-    int device = -1;
-    hipStream_t stream = nullptr;
+struct fhx_vp : fhx::TextHandle {
     fhx_ctx* sorter = nullptr;
-    std::string err;
     // the last binned file
     std::vector<std::string> names;               // bytewise order: a cell's chr column is an index into it
     int64_t n_lines = 0, n_pairs = 0, n_cells = 0;
     int32_t* d_cols = nullptr;                    // five columns of col_stride elements
     int64_t col_stride = 0;
     double seconds[FHX_VP_STAGES] = {0, 0, 0, 0, 0, 0};
-    // the upload path
-    static constexpr size_t kChunk = (size_t)32 << 20;
-    void* pinned[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 namespace {
-
-int vfail(fhx_vp* vp, int code, const std::string& msg) {
-    if (vp) vp->err = msg;
-    return code;
-}
-
-#define VP_HIP(call)                                                                                      \
-    do {                                                                                                  \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess) return vfail(vp, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// device temporaries of one call
-struct Scratch {
-    std::vector<void*> ptrs;
-    ~Scratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t get(T** p, size_t count) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-    void drop(void* p) {
-        auto it = std::find(ptrs.begin(), ptrs.end(), p);
-        if (it != ptrs.end()) {
-            (void)hipFree(p);
-            ptrs.erase(it);
-        }
-    }
-};
-
-// the text: a file read with pread, or the inflated bytes of a gzip file
-struct Source {
-    int fd = -1;
-    std::vector<char> inflated;
-    int64_t size = 0;
-    ~Source() {
-        if (fd >= 0) ::close(fd);
-    }
-};
 
 void drop_cells(fhx_vp* vp) {
     if (vp->d_cols) (void)hipFree(vp->d_cols);
@@ -438,63 +329,6 @@ void drop_cells(fhx_vp* vp) {
     vp->names.clear();
     vp->n_lines = vp->n_pairs = vp->n_cells = 0;
     vp->col_stride = 0;
-}
-
-// bytes [off, off + len) of the source -> d_text[0, len): host threads fill one of two pinned buffers while the copy engine
-// drains the other.  *last_newline = the offset (within the range) of the range's last newline, -1 without one.
-int upload_range(fhx_vp* vp, Source& src, int64_t off, int64_t len, unsigned char* d_text, int64_t* last_newline) {
-    for (int k = 0; k < 2; ++k) {
-        if (!vp->pinned[k]) VP_HIP(hipHostMalloc(&vp->pinned[k], fhx_vp::kChunk, hipHostMallocDefault));
-        if (!vp->ev[k]) VP_HIP(hipEventCreateWithFlags(&vp->ev[k], hipEventDisableTiming));
-    }
-    const int n_threads = std::min(fhx::usable_cpus(), 8);
-    bool used[2] = {false, false};
-    int turn = 0;
-    *last_newline = -1;
-    for (int64_t done = 0; done < len; done += (int64_t)fhx_vp::kChunk, turn ^= 1) {
-        const int64_t now = std::min<int64_t>((int64_t)fhx_vp::kChunk, len - done);
-        if (used[turn]) VP_HIP(hipEventSynchronize(vp->ev[turn]));
-        char* dst = (char*)vp->pinned[turn];
-        if (src.fd < 0) {
-            std::memcpy(dst, src.inflated.data() + off + done, (size_t)now);
-        } else {
-            const int64_t slice = (int64_t)4 << 20;
-            const int64_t n_slices = (now + slice - 1) / slice;
-            std::atomic<int64_t> next{0};
-            std::atomic<int> io_errno{0};
-            auto work = [&]() {
-                for (;;) {
-                    const int64_t s = next.fetch_add(1);
-                    if (s >= n_slices) return;
-                    int64_t at = s * slice;
-                    const int64_t stop = std::min(now, at + slice);
-                    while (at < stop) {
-                        const ssize_t got = ::pread(src.fd, dst + at, (size_t)(stop - at), (off_t)(off + done + at));
-                        if (got < 0 && errno == EINTR) continue;
-                        if (got <= 0) {                                       // an error, or the file shrank under us
-                            io_errno = got < 0 ? errno : EIO;
-                            return;
-                        }
-                        at += got;
-                    }
-                }
-            };
-            const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads, n_slices));
-            std::vector<std::thread> pool;
-            for (int k = 1; k < nt; ++k) pool.emplace_back(work);
-            work();
-            for (auto& th : pool) th.join();
-            if (io_errno) {
-                (void)hipStreamSynchronize(vp->stream);
-                return vfail(vp, FHX_ERR_ARG, std::string("reading the validPairs file: ") + std::strerror(io_errno));
-            }
-        }
-        if (const void* nl = ::memrchr(dst, '\n', (size_t)now)) *last_newline = done + ((const char*)nl - dst);
-        VP_HIP(hipMemcpyAsync(d_text + done, dst, (size_t)now, hipMemcpyHostToDevice, vp->stream));
-        VP_HIP(hipEventRecord(vp->ev[turn], vp->stream));
-        used[turn] = true;
-    }
-    return FHX_OK;
 }
 
 int bits_for(unsigned long long largest) {                                    // bits that hold 0..largest, at least 1
@@ -508,34 +342,20 @@ int bits_for(unsigned long long largest) {                                    //
 extern "C" {
 
 int fhx_vp_create(int device, fhx_vp** out) {
-    if (!out) return FHX_ERR_ARG;
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return FHX_ERR_NO_DEVICE;
-    fhx_vp* vp = new fhx_vp();
-    vp->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&vp->stream, hipStreamNonBlocking) != hipSuccess ||
-        fhx_create(device, &vp->sorter) != FHX_OK) {
-        if (vp->stream) (void)hipStreamDestroy(vp->stream);
-        delete vp;
+    const int rc = fhx::text_handle_create(device, out);
+    if (rc == FHX_OK && fhx_create(device, &(*out)->sorter) != FHX_OK) {
+        fhx_vp_destroy(*out);
+        *out = nullptr;
         return FHX_ERR_HIP;
     }
-    *out = vp;
-    return FHX_OK;
+    return rc;
 }
 
 void fhx_vp_destroy(fhx_vp* vp) {
-    if (!vp) return;
-    (void)hipSetDevice(vp->device);
-    if (vp->stream) (void)hipStreamSynchronize(vp->stream);
-    drop_cells(vp);
-    for (int k = 0; k < 2; ++k) {
-        if (vp->pinned[k]) (void)hipHostFree(vp->pinned[k]);
-        if (vp->ev[k]) (void)hipEventDestroy(vp->ev[k]);
-    }
-    if (vp->sorter) fhx_destroy(vp->sorter);
-    if (vp->stream) (void)hipStreamDestroy(vp->stream);
-    delete vp;
+    fhx::text_handle_destroy(vp, [&] {
+        drop_cells(vp);
+        if (vp->sorter) fhx_destroy(vp->sorter);
+    });
 }
 
 const char* fhx_vp_last_error(const fhx_vp* vp) { return vp ? vp->err.c_str() : "null context"; }
@@ -546,120 +366,83 @@ int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells,
     *n_cells = 0;
     *why = FHX_VP_OK;
     *bad_line = 0;
-    VP_HIP(hipSetDevice(vp->device));
-    VP_HIP(hipStreamSynchronize(vp->stream));
+    TH_HIP(vp, hipSetDevice(vp->device));
+    TH_HIP(vp, hipStreamSynchronize(vp->stream));
     drop_cells(vp);
     for (double& s : vp->seconds) s = 0;
     if (res < 2 || (res & 1) || res > 0x7fffffffll) {
         *why = FHX_VP_RES;
-        return vfail(vp, FHX_ERR_UNSUPPORTED, "the resolution must be an even number from 2 to 2^31 - 2");
+        return vp->fail(FHX_ERR_UNSUPPORTED, "the resolution must be an even number from 2 to 2^31 - 2");
     }
-    auto t_last = std::chrono::steady_clock::now();
-    auto mark = [&](int k) {                                                  // the stream is idle at every call
-        const auto now = std::chrono::steady_clock::now();
-        vp->seconds[k] += std::chrono::duration<double>(now - t_last).count();
-        t_last = now;
-    };
-    // ---- the source: the file itself, or its inflated bytes when it starts with the gzip magic (zcat -f, :33) ----------------
-    Source src;
-    src.fd = ::open(path, O_RDONLY | O_CLOEXEC);
-    if (src.fd < 0) return vfail(vp, FHX_ERR_ARG, std::string(path) + ": " + std::strerror(errno));
-    struct stat sb;
-    if (::fstat(src.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return vfail(vp, FHX_ERR_ARG, std::string(path) + ": not a regular file");
-    src.size = (int64_t)sb.st_size;
-    unsigned char magic[2] = {0, 0};
-    if (src.size >= 2 && ::pread(src.fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
-        fhx_text* x = nullptr;
-        int rc = fhx_host_inflate(path, 0, &x);
-        if (rc != FHX_OK) {
-            const std::string msg = x ? fhx_text_error(x) : "fhx_host_inflate";
-            fhx_text_free(x);
-            return vfail(vp, rc, msg);
-        }
-        src.inflated.resize((size_t)fhx_text_bytes(x));
-        rc = fhx_text_copy(x, src.inflated.data(), (int64_t)src.inflated.size());
-        fhx_text_free(x);
-        if (rc != FHX_OK) return vfail(vp, rc, "fhx_text_copy");
-        ::close(src.fd);
-        src.fd = -1;
-        src.size = (int64_t)src.inflated.size();
-    }
-    // ---- the batches ---------------------------------------------------------------------------------------------------------
-    int64_t batch_bytes = (int64_t)256 << 20;                                 // FHX_VP_BATCH_BYTES overrides (tests put a batch edge inside a small file)
-    if (const char* e = std::getenv("FHX_VP_BATCH_BYTES")) batch_bytes = std::atoll(e);
-    batch_bytes = std::max<int64_t>(2 * MAX_LINE, std::min<int64_t>(batch_bytes, (int64_t)1 << 32));
-    batch_bytes = std::min(batch_bytes, std::max<int64_t>(src.size, 2 * MAX_LINE));
+    fhx::StageClock clock{vp->seconds};
+    // the file itself, or its inflated bytes when it starts with the gzip magic (zcat -f, :33)
+    fhx::TextFile src;
+    if (const int rc = src.open(path, /*allow_gzip=*/true, &vp->err)) return rc;
+    const int64_t batch_bytes = fhx::batch_bytes_for("FHX_VP_BATCH_BYTES", (int64_t)1 << 32, src.size());
     const int64_t max_blocks = (batch_bytes + BLOCK_BYTES - 1) / BLOCK_BYTES;
-    Scratch tmp;
+    fhx::Scratch tmp;
     unsigned char* d_text = nullptr;
     unsigned int* d_block_nl = nullptr;
     unsigned long long *d_block_off = nullptr, *d_names = nullptr;
     Words* d_words = nullptr;
     ulonglong2* d_records = nullptr;
     int64_t capacity = 0;
-    VP_HIP(tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
-    VP_HIP(tmp.get(&d_block_nl, (size_t)max_blocks));
-    VP_HIP(tmp.get(&d_block_off, (size_t)max_blocks));
-    VP_HIP(tmp.get(&d_names, (size_t)NAME_SLOTS));
-    VP_HIP(tmp.get(&d_words, 1));
-    VP_HIP(hipMemsetAsync(d_names, 0, NAME_SLOTS * sizeof(unsigned long long), vp->stream));
+    TH_HIP(vp, tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
+    TH_HIP(vp, tmp.get(&d_block_nl, (size_t)max_blocks));
+    TH_HIP(vp, tmp.get(&d_block_off, (size_t)max_blocks));
+    TH_HIP(vp, tmp.get(&d_names, (size_t)NAME_SLOTS));
+    TH_HIP(vp, tmp.get(&d_words, 1));
+    TH_HIP(vp, hipMemsetAsync(d_names, 0, NAME_SLOTS * sizeof(unsigned long long), vp->stream));
     Words words;
     std::memset(&words, 0, sizeof(words));
     words.first_error = NO_ERROR;
-    VP_HIP(hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, vp->stream));
-    VP_HIP(hipStreamSynchronize(vp->stream));
+    TH_HIP(vp, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, vp->stream));
+    TH_HIP(vp, hipStreamSynchronize(vp->stream));
     auto refuse = [&](int rc, int32_t w, int64_t line, const std::string& msg) {
         drop_cells(vp);
         *why = w;
         *bad_line = line;
-        return vfail(vp, rc, msg);
+        return vp->fail(rc, msg);
     };
     auto refuse_line = [&](unsigned long long word) {
-        const int32_t w = (int32_t)(word & 0xFFu);
-        const int64_t line = (int64_t)(word >> 8);
+        const int32_t w = error_why(word);
+        const int64_t line = error_line(word);
         if (w == FHX_VP_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, "the line count of the scan and the parse kernel disagree");
         return refuse(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
     };
     int64_t lines = 0, pairs = 0;
-    for (int64_t off = 0; off < src.size;) {
-        int64_t len = std::min(batch_bytes, src.size - off), last_nl = -1;
-        {
-            const int rc = upload_range(vp, src, off, len, d_text, &last_nl);
-            if (rc != FHX_OK) return rc;
-        }
-        // a batch that does not reach the end of the text ends after its last newline; without one its single line is longer than
-        // MAX_LINE and the parse kernel says so
-        if (off + len < src.size && last_nl >= 0) len = last_nl + 1;
-        const int64_t n_blocks = (len + BLOCK_BYTES - 1) / BLOCK_BYTES;
-        VP_HIP(hipMemsetAsync(d_text + len, ' ', (size_t)(n_blocks * BLOCK_BYTES + 64 - len), vp->stream));
-        VP_HIP(hipStreamSynchronize(vp->stream));                             // the pinned buffers are free again
-        mark(0);
-        hipLaunchKernelGGL(vp_scan_text, dim3((unsigned)n_blocks), dim3(WG), 0, vp->stream, (const unsigned char*)d_text, len, d_block_nl);
+    for (int64_t off = 0; off < src.size();) {
+        fhx::TextBatch b;
+        if (const int rc = fhx::upload_batch(vp, src, "validPairs", off, std::min(batch_bytes, src.size() - off), d_text, &b)) return rc;
+        const int64_t len = b.len, n_blocks = b.n_blocks;
+        clock.mark(0);
+        hipLaunchKernelGGL(scan_text<AnyByte>, dim3((unsigned)n_blocks), dim3(WG), 0, vp->stream, (const unsigned char*)d_text, len, d_block_nl,
+                           (unsigned int*)&d_words->scan_flags);
         hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
                            &d_words->newlines);
-        VP_HIP(hipGetLastError());
+        TH_HIP(vp, hipGetLastError());
         unsigned long long n_newlines = 0;
-        VP_HIP(hipMemcpyAsync(&n_newlines, &d_words->newlines, sizeof(n_newlines), hipMemcpyDeviceToHost, vp->stream));
-        VP_HIP(hipStreamSynchronize(vp->stream));
-        mark(1);
-        const int64_t n = (int64_t)n_newlines + (last_nl == len - 1 ? 0 : 1);
+        TH_HIP(vp, hipMemcpyAsync(&n_newlines, &d_words->newlines, sizeof(n_newlines), hipMemcpyDeviceToHost, vp->stream));
+        TH_HIP(vp, hipStreamSynchronize(vp->stream));
+        clock.mark(1);
+        const int64_t n = b.lines(n_newlines);
         if (pairs + n >= ((int64_t)1 << 32)) return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_PAIRS, 0, "2^32 or more pairs may be kept: the sort does not take them");
         if (pairs + n > capacity) {                                           // room for every line of the batch to be kept
             const int64_t want = std::max<int64_t>(pairs + n, capacity * 2);
             ulonglong2* bigger = nullptr;
-            VP_HIP(tmp.get(&bigger, (size_t)want));
-            if (pairs) VP_HIP(hipMemcpyAsync(bigger, d_records, (size_t)pairs * sizeof(ulonglong2), hipMemcpyDeviceToDevice, vp->stream));
-            VP_HIP(hipStreamSynchronize(vp->stream));
+            TH_HIP(vp, tmp.get(&bigger, (size_t)want));
+            if (pairs) TH_HIP(vp, hipMemcpyAsync(bigger, d_records, (size_t)pairs * sizeof(ulonglong2), hipMemcpyDeviceToDevice, vp->stream));
+            TH_HIP(vp, hipStreamSynchronize(vp->stream));
             tmp.drop(d_records);
             d_records = bigger;
             capacity = want;
         }
         hipLaunchKernelGGL(vp_parse, dim3((unsigned)n_blocks), dim3(WG), 0, vp->stream, (const unsigned char*)d_text, len,
                            (const unsigned long long*)d_block_off, n, lines, (long long)res, d_names, d_records, (unsigned long long)capacity, d_words);
-        VP_HIP(hipGetLastError());
-        VP_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, vp->stream));
-        VP_HIP(hipStreamSynchronize(vp->stream));
-        mark(2);
+        TH_HIP(vp, hipGetLastError());
+        TH_HIP(vp, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, vp->stream));
+        TH_HIP(vp, hipStreamSynchronize(vp->stream));
+        clock.mark(2);
         if (words.first_error != NO_ERROR) return refuse_line(words.first_error);   // earlier batches hold the smaller line numbers
         lines += n;
         pairs = (int64_t)words.n_records;
@@ -668,18 +451,18 @@ int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells,
     }
     tmp.drop(d_text);
     d_text = nullptr;
-    std::vector<char>().swap(src.inflated);
+    src.release();
     if (words.names_overflow || words.n_names > (unsigned long long)MAX_NAMES)       // after every line has been checked: a line error wins
         return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_NAMES, 0, "more than " + std::to_string(MAX_NAMES) + " distinct chromosome names among the kept pairs");
     vp->n_lines = lines;
     vp->n_pairs = pairs;
     if (pairs == 0) {
-        mark(3);
+        clock.mark(3);
         return FHX_OK;
     }
     // ---- names: ranked bytewise on the host (the packed words compare as the bytes do) --------------------------------------
     std::vector<unsigned long long> table((size_t)NAME_SLOTS);
-    VP_HIP(hipMemcpy(table.data(), d_names, NAME_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    TH_HIP(vp, hipMemcpy(table.data(), d_names, NAME_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     std::vector<std::pair<unsigned long long, int>> present;
     for (int s = 0; s < NAME_SLOTS; ++s)
         if (table[(size_t)s]) present.emplace_back(table[(size_t)s], s);
@@ -701,64 +484,64 @@ int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells,
     int* d_slot_rank = nullptr;
     unsigned int *d_text_rank = nullptr, *d_bin_at_rank = nullptr, *d_perm = nullptr;
     unsigned long long *d_keys = nullptr, *d_sorted = nullptr;
-    VP_HIP(tmp.get(&d_slot_rank, (size_t)NAME_SLOTS));
-    VP_HIP(hipMemcpyAsync(d_slot_rank, slot_rank.data(), NAME_SLOTS * sizeof(int), hipMemcpyHostToDevice, vp->stream));
-    VP_HIP(tmp.get(&d_text_rank, (size_t)n_bins));
-    VP_HIP(tmp.get(&d_bin_at_rank, (size_t)n_bins));
+    TH_HIP(vp, tmp.get(&d_slot_rank, (size_t)NAME_SLOTS));
+    TH_HIP(vp, hipMemcpyAsync(d_slot_rank, slot_rank.data(), NAME_SLOTS * sizeof(int), hipMemcpyHostToDevice, vp->stream));
+    TH_HIP(vp, tmp.get(&d_text_rank, (size_t)n_bins));
+    TH_HIP(vp, tmp.get(&d_bin_at_rank, (size_t)n_bins));
     {
         unsigned long long *d_bin_keys = nullptr, *d_bin_sorted = nullptr;
-        VP_HIP(tmp.get(&d_bin_keys, (size_t)n_bins));
-        VP_HIP(tmp.get(&d_bin_sorted, (size_t)n_bins));
+        TH_HIP(vp, tmp.get(&d_bin_keys, (size_t)n_bins));
+        TH_HIP(vp, tmp.get(&d_bin_sorted, (size_t)n_bins));
         const unsigned grid = (unsigned)std::min<int64_t>((n_bins + WG - 1) / WG, 4096);
         hipLaunchKernelGGL(vp_text_keys, dim3(grid), dim3(WG), 0, vp->stream, (long long)res, n_bins, d_bin_keys);
-        VP_HIP(hipGetLastError());
-        VP_HIP(hipStreamSynchronize(vp->stream));                             // the sorter has a stream of its own
+        TH_HIP(vp, hipGetLastError());
+        TH_HIP(vp, hipStreamSynchronize(vp->stream));                             // the sorter has a stream of its own
         const int rc = fhx_sort_u64(vp->sorter, d_bin_keys, n_bins, d_bin_sorted, d_bin_at_rank);
-        if (rc != FHX_OK) return vfail(vp, rc, std::string("sort of the bin starts: ") + fhx_last_error(vp->sorter));
+        if (rc != FHX_OK) return vp->fail(rc, std::string("sort of the bin starts: ") + fhx_last_error(vp->sorter));
         hipLaunchKernelGGL(vp_invert, dim3(grid), dim3(WG), 0, vp->stream, (const unsigned int*)d_bin_at_rank, n_bins, d_text_rank);
-        VP_HIP(hipGetLastError());
-        VP_HIP(hipStreamSynchronize(vp->stream));
+        TH_HIP(vp, hipGetLastError());
+        TH_HIP(vp, hipStreamSynchronize(vp->stream));
         tmp.drop(d_bin_keys);
         tmp.drop(d_bin_sorted);
     }
-    VP_HIP(tmp.get(&d_keys, (size_t)pairs));
+    TH_HIP(vp, tmp.get(&d_keys, (size_t)pairs));
     {
         const unsigned grid = (unsigned)std::min<int64_t>((pairs + WG - 1) / WG, 8192);
         hipLaunchKernelGGL(vp_keys, dim3(grid), dim3(WG), 0, vp->stream, (const ulonglong2*)d_records, pairs, (const int*)d_slot_rank,
                            (const unsigned int*)d_text_rank, bin_bits, name_bits, d_keys);
-        VP_HIP(hipGetLastError());
-        VP_HIP(hipStreamSynchronize(vp->stream));
+        TH_HIP(vp, hipGetLastError());
+        TH_HIP(vp, hipStreamSynchronize(vp->stream));
     }
     tmp.drop(d_records);
     d_records = nullptr;
-    mark(3);
-    VP_HIP(tmp.get(&d_sorted, (size_t)pairs));
-    VP_HIP(tmp.get(&d_perm, (size_t)pairs));
+    clock.mark(3);
+    TH_HIP(vp, tmp.get(&d_sorted, (size_t)pairs));
+    TH_HIP(vp, tmp.get(&d_perm, (size_t)pairs));
     {
         const int rc = fhx_sort_u64(vp->sorter, d_keys, pairs, d_sorted, d_perm);
-        if (rc != FHX_OK) return vfail(vp, rc, std::string("sort: ") + fhx_last_error(vp->sorter));
+        if (rc != FHX_OK) return vp->fail(rc, std::string("sort: ") + fhx_last_error(vp->sorter));
     }
     tmp.drop(d_keys);
     tmp.drop(d_perm);
-    mark(4);
+    clock.mark(4);
     // ---- run heads -> cells --------------------------------------------------------------------------------------------------
     const int64_t tiles = (pairs + fhxscan::TILE - 1) / fhxscan::TILE;
     unsigned int* d_tile_cnt = nullptr;
     unsigned long long *d_tile_off = nullptr, *d_head_at = nullptr;
-    VP_HIP(tmp.get(&d_tile_cnt, (size_t)tiles));
-    VP_HIP(tmp.get(&d_tile_off, (size_t)tiles));
+    TH_HIP(vp, tmp.get(&d_tile_cnt, (size_t)tiles));
+    TH_HIP(vp, tmp.get(&d_tile_off, (size_t)tiles));
     hipLaunchKernelGGL(fhxscan::count_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned long long*)d_sorted, pairs,
                        d_tile_cnt);
     hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned int*)d_tile_cnt, tiles, d_tile_off,
                        &d_words->n_cells);
-    VP_HIP(hipGetLastError());
+    TH_HIP(vp, hipGetLastError());
     unsigned long long cells = 0;
-    VP_HIP(hipMemcpyAsync(&cells, &d_words->n_cells, sizeof(cells), hipMemcpyDeviceToHost, vp->stream));
-    VP_HIP(hipStreamSynchronize(vp->stream));
+    TH_HIP(vp, hipMemcpyAsync(&cells, &d_words->n_cells, sizeof(cells), hipMemcpyDeviceToHost, vp->stream));
+    TH_HIP(vp, hipStreamSynchronize(vp->stream));
     if (cells == 0 || cells > (unsigned long long)pairs) return refuse(FHX_ERR_INTERNAL, FHX_VP_INTERNAL, 0, "the run heads do not match the keys");
     const int64_t stride = ((int64_t)cells + 63) / 64 * 64;                   // every column starts on a 256-byte boundary
-    VP_HIP(tmp.get(&d_head_at, (size_t)cells));
-    VP_HIP(hipMalloc((void**)&vp->d_cols, (size_t)stride * 5 * sizeof(int32_t)));
+    TH_HIP(vp, tmp.get(&d_head_at, (size_t)cells));
+    TH_HIP(vp, hipMalloc((void**)&vp->d_cols, (size_t)stride * 5 * sizeof(int32_t)));
     vp->col_stride = stride;
     int32_t* c = vp->d_cols;
     hipLaunchKernelGGL(vp_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned long long*)d_sorted, pairs,
@@ -767,11 +550,11 @@ int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells,
                        (const unsigned long long*)d_sorted, pairs, (const unsigned long long*)d_head_at, (int64_t)cells,
                        (const unsigned int*)d_bin_at_rank, bin_bits, name_bits, (long long)res, c, c + stride, c + 2 * stride, c + 3 * stride,
                        c + 4 * stride, &d_words->max_count);
-    VP_HIP(hipGetLastError());
+    TH_HIP(vp, hipGetLastError());
     unsigned long long max_count = 0;
-    VP_HIP(hipMemcpyAsync(&max_count, &d_words->max_count, sizeof(max_count), hipMemcpyDeviceToHost, vp->stream));
-    VP_HIP(hipStreamSynchronize(vp->stream));
-    mark(5);
+    TH_HIP(vp, hipMemcpyAsync(&max_count, &d_words->max_count, sizeof(max_count), hipMemcpyDeviceToHost, vp->stream));
+    TH_HIP(vp, hipStreamSynchronize(vp->stream));
+    clock.mark(5);
     if (max_count > 0x7fffffffull) return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_COUNT, 0, "a cell is hit by more than 2^31 - 1 pairs: the count column is int32");
     vp->n_cells = (int64_t)cells;
     *n_cells = vp->n_cells;
@@ -802,11 +585,11 @@ int fhx_vp_stage_seconds(const fhx_vp* vp, double* seconds) {
 int fhx_vp_fetch_cells(fhx_vp* vp, int32_t* chr1, int32_t* mid1, int32_t* chr2, int32_t* mid2, int32_t* count) {
     if (!vp) return FHX_ERR_ARG;
     if (vp->n_cells > 0 && (!chr1 || !mid1 || !chr2 || !mid2 || !count)) return FHX_ERR_ARG;
-    VP_HIP(hipSetDevice(vp->device));
+    TH_HIP(vp, hipSetDevice(vp->device));
     int32_t* out[5] = {chr1, mid1, chr2, mid2, count};
     for (int k = 0; k < 5 && vp->n_cells > 0; ++k)
-        VP_HIP(hipMemcpyAsync(out[k], vp->d_cols + k * vp->col_stride, (size_t)vp->n_cells * sizeof(int32_t), hipMemcpyDeviceToHost, vp->stream));
-    VP_HIP(hipStreamSynchronize(vp->stream));
+        TH_HIP(vp, hipMemcpyAsync(out[k], vp->d_cols + k * vp->col_stride, (size_t)vp->n_cells * sizeof(int32_t), hipMemcpyDeviceToHost, vp->stream));
+    TH_HIP(vp, hipStreamSynchronize(vp->stream));
     return FHX_OK;
 }
 

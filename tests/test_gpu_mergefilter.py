@@ -4,6 +4,7 @@ texts built round the 16 KB scan blocks and round batch edges, at 0 % and 100 % 
 refusal names the right line, two runs give the same bytes, and combine() equals the combine module on the written subset."""
 import contextlib
 import gzip
+import json
 import os
 import subprocess
 import sys
@@ -164,6 +165,33 @@ def test_70000_lines_with_every_997th_kept(tmp_path):
     want = mm.select(data, "0.05")
     assert want.count(b"\n") == 71
     assert gpu_subset(data, "0.05", tmp_path) == want
+
+
+def test_a_text_of_three_upload_chunks_refills_the_first_pinned_buffer(tmp_path):
+    """The uploader fills two pinned 32 MiB buffers in turn: a text just over 64 MiB + 16 KB, one batch at the default batch size,
+    is three chunks, so buffer 0 is filled again - after the copy engine has drained it.  Two lines alternate, A kept and B
+    dropped as the model classifies them; the subset is then A repeated."""
+    a, b = row(1, KEPT), row(2, DROPPED)
+    assert mm.select(HEADER + a + b, "0.05") == a
+    pairs = ((64 << 20) + BLOCK - len(HEADER)) // len(a + b) + 1
+    data = HEADER + (a + b) * pairs
+    assert (64 << 20) + BLOCK < len(data) <= (64 << 20) + BLOCK + len(a + b) and "FHX_MS_BATCH_BYTES" not in os.environ
+    src, out = str(tmp_path / "sig.txt"), str(tmp_path / "subset.txt")
+    with open(src, "wb") as f:
+        f.write(data)
+    # in a process of its own: a wait on an event that never fires ends at the time limit, as one failed test
+    code = ("import json, sys\n"
+            "from fithic_amd import _capi, mergefilter as mf\n"
+            "ms = _capi.MsContext(0)\n"
+            "n = ms.select_file(sys.argv[1], b'0.05', mf.key_bound('0.05'), True)\n"
+            "open(sys.argv[2], 'wb').write(ms.subset())\n"
+            "print(json.dumps(dict(ms.counts(), returned=n)))\n"
+            "ms.close()\n")
+    r = subprocess.run([sys.executable, "-c", code, src, out], cwd=ROOT, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout) == dict(lines=1 + 2 * pairs, kept=pairs, bytes=pairs * len(a), returned=pairs * len(a))
+    with open(out, "rb") as f:
+        assert f.read() == a * pairs
 
 
 # ---- 4. thresholds and classes ----------------------------------------------------------------------------------------------
