@@ -390,7 +390,7 @@ struct fhx_ctx {
 
     // pass state
     int pass_no = 0;                  // passes completed so far
-    uint8_t *d_skip = nullptr, *d_outlier = nullptr, *d_seen_twice = nullptr;
+    uint8_t *d_skip = nullptr, *d_outlier = nullptr;
     bool skip_active = false;
     unsigned long long *d_hist_cc = nullptr, *d_hist_np = nullptr, *d_out_hist = nullptr;
     DeviceWords* d_words = nullptr;   // the small device values of a pass, by name

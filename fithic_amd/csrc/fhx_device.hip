@@ -67,7 +67,6 @@ void fhx_destroy(fhx_ctx* ctx) {
         dev_free(ctx->d_slot_bias);
         dev_free(ctx->d_skip);
         dev_free(ctx->d_outlier);
-        dev_free(ctx->d_seen_twice);
         dev_free(ctx->d_grow);
         dev_free(ctx->d_hist_cc);
         dev_free(ctx->d_hist_np);
@@ -516,7 +515,6 @@ int fhx_reset_passes(fhx_ctx* ctx) {
     const size_t cap = std::max<size_t>(4, ((size_t)ctx->n_rows + 3) / 4 * 4);
     FHX_HIP(hipMemsetAsync(ctx->d_skip, 0, cap, ctx->stream));
     FHX_HIP(hipMemsetAsync(ctx->d_outlier, 0, cap, ctx->stream));
-    FHX_HIP(hipMemsetAsync(ctx->d_seen_twice, 0, cap, ctx->stream));
     const size_t hist_len = ctx->nonfixed ? cap : (size_t)ctx->n_dist;
     FHX_HIP(hipMemsetAsync(ctx->d_out_hist, 0, hist_len * sizeof(unsigned long long), ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));

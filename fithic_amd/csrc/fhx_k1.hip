@@ -776,7 +776,6 @@ int alloc_row_arrays(fhx_ctx* ctx, int64_t n, int64_t n_dist) {
     dev_free(ctx->d_count);
     dev_free(ctx->d_skip);
     dev_free(ctx->d_outlier);
-    dev_free(ctx->d_seen_twice);
     dev_free(ctx->d_p);
     dev_free(ctx->d_q);
     dev_free(ctx->d_grow);
@@ -785,13 +784,11 @@ int alloc_row_arrays(fhx_ctx* ctx, int64_t n, int64_t n_dist) {
     FHX_HIP(hipMalloc(&ctx->d_count, cap * sizeof(int32_t)));
     FHX_HIP(hipMalloc(&ctx->d_skip, cap));
     FHX_HIP(hipMalloc(&ctx->d_outlier, cap));
-    FHX_HIP(hipMalloc(&ctx->d_seen_twice, cap));
     FHX_HIP(hipMalloc(&ctx->d_p, cap * sizeof(double)));
     FHX_HIP(hipMalloc(&ctx->d_q, cap * sizeof(double)));
     ctx->q_prefilled = false;
     FHX_HIP(hipMemsetAsync(ctx->d_skip, 0, cap, ctx->stream));
     FHX_HIP(hipMemsetAsync(ctx->d_outlier, 0, cap, ctx->stream));
-    FHX_HIP(hipMemsetAsync(ctx->d_seen_twice, 0, cap, ctx->stream));
     // histograms
     dev_free(ctx->d_hist_cc);
     dev_free(ctx->d_hist_np);

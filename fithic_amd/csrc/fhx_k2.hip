@@ -933,7 +933,7 @@ __global__ void k2_extras(K2Params P, double bias_low, double bias_up, double* _
 // outlier bookkeeping for the next pass: skip mask |= outlier, and the multiset of outlier distances
 __global__ void k_fold_outliers(const int32_t* __restrict__ loc1, const int32_t* __restrict__ loc2,
                                 const double* __restrict__ pvals, double thres, uint8_t* __restrict__ skip,
-                                uint8_t* __restrict__ seen_twice, int64_t n, int res, int n_dist,
+                                int64_t n, int res, int n_dist,
                                 const int16_t* __restrict__ slot_chr, const ChrGrid* __restrict__ grid,
                                 unsigned long long* __restrict__ out_hist, unsigned long long* __restrict__ n_out,
                                 unsigned long long* __restrict__ first_dup, const long long* __restrict__ grow) {
@@ -942,10 +942,7 @@ __global__ void k_fold_outliers(const int32_t* __restrict__ loc1, const int32_t*
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         if (!(pvals[i] < thres)) continue;             // NaN is not an outlier (p_val < outlierThres is False)
         ++mine;
-        if (skip[i]) {                             // duplicated line number in the reference's SortedList (A17)
-            seen_twice[i] = 1;
-            atomicMin(first_dup, (unsigned long long)(grow ? grow[i] : i));
-        }
+        if (skip[i]) atomicMin(first_dup, (unsigned long long)(grow ? grow[i] : i));     // duplicated line number in the reference's SortedList (A17)
         skip[i] = 1;
         const int l1 = loc1[i], l2 = loc2[i];
         long long idx;
@@ -969,16 +966,13 @@ __global__ void k_fold_outliers(const int32_t* __restrict__ loc1, const int32_t*
 // outliers of a -r 0 pass: skip mask + the list of their distances (the reference's SortedList outliersdist)
 __global__ void nf_fold_outliers(const int32_t* __restrict__ loc1, const int32_t* __restrict__ loc2,
                                  const double* __restrict__ pvals, double thres, uint8_t* __restrict__ skip,
-                                 uint8_t* __restrict__ seen_twice, int64_t n, const int32_t* __restrict__ slot_mid,
+                                 int64_t n, const int32_t* __restrict__ slot_mid,
                                  unsigned long long* __restrict__ dist_list, unsigned long long* __restrict__ n_out,
                                  unsigned long long* __restrict__ first_dup, const long long* __restrict__ grow) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         if (!(pvals[i] < thres)) continue;
-        if (skip[i]) {
-            seen_twice[i] = 1;
-            atomicMin(first_dup, (unsigned long long)(grow ? grow[i] : i));
-        }
+        if (skip[i]) atomicMin(first_dup, (unsigned long long)(grow ? grow[i] : i));
         skip[i] = 1;
         const int l1 = loc1[i], l2 = loc2[i];
         const int s2 = l2 < 0 ? ~l2 : l2;
@@ -1532,7 +1526,7 @@ int fhx_next_pass(fhx_ctx* ctx, int64_t* n_outliers_total) {
     if (ctx->nonfixed) {
         // the distances of this pass's outliers go to a list (reusing the sort workspace), then into the sorted multiset
         hipLaunchKernelGGL(nf_fold_outliers, dim3(grid_for(ctx->n_rows, 256)), dim3(256), 0, ctx->stream, ctx->d_loc1, ctx->d_loc2,
-                           ctx->d_p, 1.0 / ctx->fit.bh_total_tests, ctx->d_skip, ctx->d_seen_twice, ctx->n_rows,
+                           ctx->d_p, 1.0 / ctx->fit.bh_total_tests, ctx->d_skip, ctx->n_rows,
                            (const int32_t*)ctx->d_slot_mid, ctx->d_keys[0], n_out, first_dup, (const long long*)ctx->d_grow);
         FHX_HIP(hipGetLastError());
         unsigned long long added = 0, dup = ~0ull;
@@ -1554,7 +1548,7 @@ int fhx_next_pass(fhx_ctx* ctx, int64_t* n_outliers_total) {
         return FHX_OK;
     }
     hipLaunchKernelGGL(k_fold_outliers, dim3(grid_for(ctx->n_rows, 256)), dim3(256), 0, ctx->stream, ctx->d_loc1, ctx->d_loc2,
-                       ctx->d_p, 1.0 / ctx->fit.bh_total_tests, ctx->d_skip, ctx->d_seen_twice, ctx->n_rows, (int)ctx->prm.resolution, (int)ctx->n_dist,
+                       ctx->d_p, 1.0 / ctx->fit.bh_total_tests, ctx->d_skip, ctx->n_rows, (int)ctx->prm.resolution, (int)ctx->n_dist,
                        ctx->d_slot_chr, ctx->d_grid, ctx->d_out_hist, n_out, first_dup, (const long long*)ctx->d_grow);
     FHX_HIP(hipGetLastError());
     unsigned long long added = 0, dup = ~0ull;
