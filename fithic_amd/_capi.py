@@ -242,6 +242,13 @@ SYMBOLS = {
     "fhx_ms_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P]),
     "fhx_ms_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
     "fhx_ms_copy_subset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    # the UCSC interact track of the same selection (fithic/utils/visualize-UCSC.sh)
+    "fhx_ms_track_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
+                                         _I64P, _I32P, _I64P]),
+    "fhx_ms_track_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P, _I64P]),
+    "fhx_ms_track_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
+    "fhx_ms_copy_track": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    "fhx_ms_score_text": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
 }
 
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
@@ -1378,8 +1385,10 @@ def vp_write_contacts(path, names, chr1, mid1, chr2, mid2, count, gzip_level=1, 
 
 
 (MS_OK, MS_TOKENS, MS_FIELD, MS_BYTES, MS_LONG_LINE, MS_FDR, MS_INTERNAL) = range(7)
+MS_MIDPOINT, MS_NAME, MS_KEPT = 7, 8, 9                             # refusals of the interact track alone
 MS_FDR_BYTES = 32
 MS_STAGE_NAMES = ("read_upload", "newline_scan", "select", "gather", "copy_out")
+MS_TRACK_STAGE_NAMES = ("read_upload", "newline_scan", "select", "deferred_round_trip", "format", "copy_out")
 
 
 class MsRefused(FhxError):
@@ -1420,3 +1429,38 @@ class MsContext(_Handle):
         buf = np.empty(self.counts()["bytes"], np.uint8)
         self._chk(self.L.fhx_ms_copy_subset(self.h, buf.ctypes.data_as(ctypes.c_void_p), len(buf)))
         return buf.tobytes()
+
+    def track_file(self, path, fdr_text, key_bound, zero_kept):
+        """the interact track of the rows with field 7 < fdr -> its bytes; MsRefused for a file outside the device grammar"""
+        n, why, line = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self.L.fhx_ms_track_file(self.h, os.fsencode(path), fdr_text, len(fdr_text), int(key_bound), int(bool(zero_kept)),
+                                      ctypes.byref(n), ctypes.byref(why), ctypes.byref(line))
+        self._chk(rc, why.value, line.value)
+        return n.value
+
+    def track_counts(self):
+        """lines read, lines kept, kept lines whose score the host made, bytes of the track"""
+        a, b, c, d = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self.L.fhx_ms_track_counts(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+        return dict(lines=a.value, kept=b.value, deferred=c.value, bytes=d.value)
+
+    def track_stage_seconds(self):
+        out = np.zeros(len(MS_TRACK_STAGE_NAMES), np.float64)
+        self._chk(self.L.fhx_ms_track_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
+        return dict(zip(MS_TRACK_STAGE_NAMES, out.tolist()))
+
+    def track(self):
+        """the script's two fixed lines and one line per kept row, in file order"""
+        buf = np.empty(self.track_counts()["bytes"], np.uint8)
+        self._chk(self.L.fhx_ms_copy_track(self.h, buf.ctypes.data_as(ctypes.c_void_p), len(buf)))
+        return buf.tobytes()
+
+
+def ms_score_text(field, certify=False):
+    """The two score fields of an interact line for one field 7, as bytes: the deferred route (the host's strtod, log and awk's number
+    printing), or with certify the kernel's route run on the host - b"" where it would defer.  Needs no GPU."""
+    out = ctypes.create_string_buffer(32)
+    n = lib().fhx_ms_score_text(field, len(field), int(bool(certify)), out, 32)
+    if n < 0:
+        raise FhxError(n, "fhx_ms_score_text(%r)" % (field,))
+    return out.raw[:n]

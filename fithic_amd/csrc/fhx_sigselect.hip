@@ -21,7 +21,8 @@
 //                  into LDS, lanes assigned by OUTPUT byte (a binary search in the 256 prefixes), so stores are coalesced at
 //                  1 % kept and at 100 %.  A final line without its newline gets one, as awk's print gives it.
 //
-// The subset of each batch is copied to the host and appended.  No device-side strtod, no atomics per line: a refused line
+// The subset of each batch is copied to the host and appended.  The UCSC interact track of the same selection (strict, no line
+// skipped) is made by the kernels of fhx_sigtrack.inc, included at the end of this file.  No device-side strtod, no atomics per line: a refused line
 // costs one atomicMin (line << 8 | reason), so the smallest offending line is reported whatever the launch order.
 #include <hip/hip_runtime.h>
 
@@ -34,6 +35,7 @@
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
+#include "fhx_score.hpp"
 #include "fhx_textupload.hpp"
 
 namespace msd {
@@ -217,6 +219,10 @@ struct fhx_ms : fhx::TextHandle {
     std::vector<char> subset;
     int64_t n_lines = 0, n_kept = 0;
     double seconds[FHX_MS_STAGES] = {0, 0, 0, 0, 0};
+    // the last interact track (fhx_sigtrack.inc)
+    std::vector<char> track;
+    int64_t t_lines = 0, t_kept = 0, t_deferred = 0;
+    double t_seconds[FHX_MS_TRACK_STAGES] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -376,3 +382,5 @@ int fhx_ms_copy_subset(const fhx_ms* ms, void* dst, int64_t capacity) {
 }
 
 }  // extern "C"
+
+#include "fhx_sigtrack.inc"

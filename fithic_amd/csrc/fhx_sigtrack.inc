@@ -1,0 +1,584 @@
+// fhx_sigtrack.inc - the UCSC interact track of the significant contacts on MI355X (gfx950); included by fhx_sigselect.hip
+// (reference: fithic/utils/visualize-UCSC.sh:16-18, `awk -v q=Q '{if($7<q){print $0}}' | awk '{print $1, ($2-1), ($4+1), NR,
+// int(-log($7)/log(10)), -log($7)/log(10), "EXP", "0", $1, ($2-1), ($2+1), "SOURCE_NAME", ".", $3, ($4-1), ($4+1),
+// "TARGET_NAME", "+"}'` behind two fixed lines).
+//
+// Per batch, behind scan_text / scan_tiles of the selection:
+//
+//   ut_select      one line per lane, one walk over its tokens: the grammar, ms_select's decision with `$7 < q` and no line
+//                  skipped - but a field 7 that starts with a letter on FILE LINE 1 is a string above every accepted threshold,
+//                  and that line is only dropped - and for a kept line the bytes of its track line without NR.  The score comes
+//                  from fhx_score.hpp: certified on the device, or the line is flagged DEFERRED and its score bytes are left
+//                  out.  Per block: kept lines, deferred lines.
+//   scan_tiles x2  -> the number of kept lines before every block (NR is this exclusive scan plus the kept lines of the
+//                  earlier batches, never an atomic), and the slot of every block's first deferred line
+//   ut_defer       field 7 of the deferred lines, 16 bytes a slot; the host answers with the two fields as mawk's own calls make
+//                  them (fhx::score::host_fields), 32 bytes a slot
+//   ut_measure     the final length of every track line: + the digits of NR, + the host's score bytes.  Per block: bytes.
+//   scan_tiles     -> the offset of every block's lines in the track
+//   ut_format      256 lines per round, their lengths scanned; every lane writes its line into a 16 KB window of LDS (a round
+//                  longer than that takes several windows; a lane writes only what falls into the current one), and the
+//                  window goes out with consecutive lanes on consecutive bytes.  Order is file order.
+// A track line can be two and a half times its input line, so nothing here is sized by the input: d_out grows to what ut_measure found.
+namespace utd {
+
+using namespace fhxlines;
+using namespace msd;
+
+constexpr int NAME_BYTES = 63;                 // tokens 1 and 3
+constexpr int MID_DIGITS = 9;                  // tokens 2 and 4: v + 1 stays below 2^31, where awk prints integers as integers
+constexpr int DEFER_IN = 16, DEFER_OUT = 32;   // bytes per deferred line, to the host and back (byte 0: the length)
+constexpr int WINDOW = 16384;                  // LDS bytes of ut_format
+constexpr unsigned int DEFERRED = 0x8000u;     // in a line's info word; the low 15 bits are a length (0: dropped)
+constexpr int FIXED_BYTES = 45;                // 16 blanks and the newline, EXP 0 SOURCE_NAME . TARGET_NAME +
+
+struct TrackWords {
+    unsigned long long newlines;
+    unsigned long long bad_bytes;
+    unsigned long long first_error;
+    unsigned long long kept_lines;             // scan_tiles' totals of the current batch
+    unsigned long long deferred;
+    unsigned long long out_bytes;
+};
+
+// one line split on blanks: tokens 1 to 4 and field 7, relative to the line's first byte
+struct Line {
+    int why, tok, len;                         // len: without the newline
+    int b1, n1, b2, n2, b3, n3, b4, n4, fb, fn;
+};
+
+__device__ inline void walk(const unsigned char* __restrict__ text, int64_t T, int64_t start, int check_bytes, Line& L) {
+    L.why = 0;
+    L.b1 = L.n1 = L.b2 = L.n2 = L.b3 = L.n3 = L.b4 = L.n4 = L.fb = L.fn = 0;
+    int tok = 0, begin = 0, k = 0;
+    bool in_tok = false;
+    auto close = [&](int end) {
+        const int n = end - begin;
+        if (tok == 1) { L.b1 = begin; L.n1 = n; }
+        else if (tok == 2) { L.b2 = begin; L.n2 = n; }
+        else if (tok == 3) { L.b3 = begin; L.n3 = n; }
+        else if (tok == 4) { L.b4 = begin; L.n4 = n; }
+        else if (tok == 7) { L.fb = begin; L.fn = n; }
+    };
+    for (;; ++k) {
+        const int64_t p = start + k;
+        const int c = p < T ? (int)text[p] : '\n';                            // the end of the text ends the line
+        if (c == '\n') break;
+        if (k >= MAX_LINE) {
+            L.why = FHX_MS_LONG_LINE;
+            break;
+        }
+        if (check_bytes && refused_byte((unsigned int)c)) {
+            L.why = FHX_MS_BYTES;
+            break;
+        }
+        const bool blank = c == ' ' || c == '\t';
+        if (!blank && !in_tok) {
+            in_tok = true;
+            ++tok;
+            begin = k;
+        } else if (blank && in_tok) {
+            in_tok = false;
+            close(k);
+        }
+    }
+    if (in_tok) close(k);
+    L.tok = tok;
+    L.len = k;
+}
+
+// 1 to 9 digits -> their value, -1 otherwise
+__device__ inline int midpoint(const unsigned char* __restrict__ text, int64_t b, int n) {
+    if (n < 1 || n > MID_DIGITS) return -1;
+    int v = 0;
+    for (int k = 0; k < n; ++k) {
+        const int c = text[b + k];
+        if (!is_digit(c)) return -1;
+        v = v * 10 + (c - '0');
+    }
+    return v;
+}
+
+__device__ inline int digits_of(long long v) {                                // of the decimal text, a minus sign included
+    int n = v < 0 ? 2 : 1;
+    unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
+    while (u >= 10ull) {
+        u /= 10ull;
+        ++n;
+    }
+    return n;
+}
+
+// the lines of a block in rounds of WG: entry e of the round's lane, its line number in the batch, whether both exist
+struct Round {
+    int e;
+    int64_t r;
+    bool valid;
+};
+__device__ inline Round round_of(int base, int n_lines, int64_t row0, int64_t n_lines_batch) {
+    Round q;
+    q.e = base + (int)threadIdx.x;
+    q.r = row0 + q.e;
+    q.valid = q.e < n_lines && q.r < n_lines_batch;
+    return q;
+}
+
+// ---- the selection, the grammar and the length of every kept line without NR ---------------------------------------------------
+__global__ __launch_bounds__(WG) void ut_select(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ block_off,
+                                                int64_t n_lines_batch, int64_t line_base, Fdr fdr, unsigned long long key_bound, int zero_kept,
+                                                int check_bytes, unsigned short* __restrict__ info, unsigned int* __restrict__ block_kept,
+                                                unsigned int* __restrict__ block_deferred, TrackWords* __restrict__ words) {
+    __shared__ unsigned short lstart[LSTART_ENTRIES];
+    const int n_lines = block_lines(text, T, lstart);
+    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
+    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    unsigned int my_kept = 0, my_deferred = 0;
+    for (int e = threadIdx.x; e < n_lines; e += WG) {
+        const int64_t r = row0 + e;
+        const int64_t start = b0 + lstart[e];
+        Line L;
+        walk(text, T, start, check_bytes, L);
+        int why = L.why, cls = 0, v2 = 0, v4 = 0;
+        unsigned long long key = 0;
+        bool keep = false;
+        if (!why && r >= n_lines_batch) why = FHX_MS_INTERNAL;                // the scan and this kernel disagree about the lines
+        if (!why && L.tok < 7) why = FHX_MS_TOKENS;
+        const int f0 = why ? 0 : (int)text[start + L.fb] | 0x20;
+        const bool header = !why && line_base + r == 0 && f0 >= 'a' && f0 <= 'z';       // `q-value`: a string, and above every q
+        if (!why && !header) {
+            cls = classify(text, start + L.fb, L.fn, &key);
+            v2 = midpoint(text, start + L.b2, L.n2);
+            v4 = midpoint(text, start + L.b4, L.n4);
+            if (cls == 0) why = FHX_MS_FIELD;
+            else if (v2 < 0 || v4 < 0) why = FHX_MS_MIDPOINT;
+            else if (L.n1 > NAME_BYTES || L.n3 > NAME_BYTES) why = FHX_MS_NAME;
+            else if (cls == 1) keep = zero_kept != 0;
+            else if (cls == 2) keep = key <= key_bound;
+            else keep = compare_text(text, start + L.fb, L.fn, fdr) < 0;
+        }
+        if (why) atomicMin(&words->first_error, error_word(line_base + r + 1, why));
+        unsigned int word = 0;
+        if (keep && !why) {
+            int score = 7;                                                    // inf inf
+            if (cls == 2) {
+                char buf[fhx::score::MAX_TEXT];
+                score = fhx::score::certified(buf, fhx::score::approximate(key % KEY_EXP, (int)(key / KEY_EXP) - 308));
+            } else if (cls == 3) score = 0;
+            word = (unsigned int)(FIXED_BYTES + 2 * L.n1 + L.n3 + 2 * digits_of((long long)v2 - 1) + digits_of((long long)v2 + 1) +
+                                  digits_of((long long)v4 - 1) + 2 * digits_of((long long)v4 + 1) + score);
+            if (score == 0) {
+                word |= DEFERRED;
+                ++my_deferred;
+            }
+            ++my_kept;
+        }
+        if (r < n_lines_batch) info[r] = (unsigned short)word;
+    }
+    unsigned int total_kept, total_deferred;
+    fhxscan::block_exclusive_scan(my_kept, &total_kept);                      // every lane of the block arrives here
+    fhxscan::block_exclusive_scan(my_deferred, &total_deferred);
+    if (threadIdx.x == 0) {
+        block_kept[blockIdx.x] = total_kept;
+        block_deferred[blockIdx.x] = total_deferred;
+    }
+}
+
+// ---- field 7 of the deferred lines, in file order ------------------------------------------------------------------------------
+__global__ __launch_bounds__(WG) void ut_defer(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ block_off,
+                                               int64_t n_lines_batch, const unsigned short* __restrict__ info,
+                                               const unsigned long long* __restrict__ deferred_off, unsigned char* __restrict__ fields,
+                                               int64_t n_slots) {
+    __shared__ unsigned short lstart[LSTART_ENTRIES];
+    const int n_lines = block_lines(text, T, lstart);
+    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
+    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    int64_t slot0 = (int64_t)deferred_off[blockIdx.x];
+    for (int base = 0; base < n_lines; base += WG) {
+        const Round q = round_of(base, n_lines, row0, n_lines_batch);
+        const bool mine = q.valid && (info[q.r] & DEFERRED);
+        unsigned int total;
+        const int64_t slot = slot0 + fhxscan::block_exclusive_scan(mine ? 1u : 0u, &total);
+        if (mine && slot < n_slots) {
+            const int64_t start = b0 + lstart[q.e];
+            Line L;
+            walk(text, T, start, 0, L);
+            for (int k = 0; k < DEFER_IN; ++k) fields[slot * DEFER_IN + k] = k < L.fn && k < DEFER_IN - 1 ? text[start + L.fb + k] : (unsigned char)0;
+        }
+        slot0 += total;
+    }
+}
+
+// ---- the final length of every track line --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(WG) void ut_measure(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ block_off,
+                                                 int64_t n_lines_batch, unsigned short* __restrict__ info,
+                                                 const unsigned long long* __restrict__ kept_off, const unsigned long long* __restrict__ deferred_off,
+                                                 int64_t kept_base, const unsigned char* __restrict__ scores, int64_t n_slots,
+                                                 unsigned int* __restrict__ block_bytes) {
+    __shared__ unsigned short lstart[LSTART_ENTRIES];
+    const int n_lines = block_lines(text, T, lstart);
+    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    int64_t nr0 = kept_base + (int64_t)kept_off[blockIdx.x] + 1, slot0 = (int64_t)deferred_off[blockIdx.x];
+    unsigned int my_bytes = 0;
+    for (int base = 0; base < n_lines; base += WG) {
+        const Round q = round_of(base, n_lines, row0, n_lines_batch);
+        const unsigned int word = q.valid ? (unsigned int)info[q.r] : 0u;
+        const bool kept = word != 0, deferred = (word & DEFERRED) != 0;
+        unsigned int total;                                                   // kept lines in the low half, deferred ones in the high half
+        const unsigned int rank = fhxscan::block_exclusive_scan((kept ? 1u : 0u) | (deferred ? 0x10000u : 0u), &total);
+        if (kept) {
+            unsigned int len = (word & ~DEFERRED) + (unsigned int)digits_of(nr0 + (rank & 0xFFFFu));
+            const int64_t slot = slot0 + (rank >> 16);
+            if (deferred && slot < n_slots) len += scores[slot * DEFER_OUT];
+            info[q.r] = (unsigned short)(len | (word & DEFERRED));
+            my_bytes += len;
+        }
+        nr0 += total & 0xFFFFu;
+        slot0 += total >> 16;
+    }
+    unsigned int total_bytes;
+    fhxscan::block_exclusive_scan(my_bytes, &total_bytes);
+    if (threadIdx.x == 0) block_bytes[blockIdx.x] = total_bytes;
+}
+
+// ---- the track lines, dense and in file order ----------------------------------------------------------------------------------
+// what a lane writes of its line: the bytes that fall into the window [w0, w0 + WINDOW) of the round
+struct WindowSink {
+    unsigned char* lds;
+    unsigned int pos, w0;
+    __device__ void put(int c) {
+        const unsigned int at = pos++ - w0;                                   // wraps to a huge value below the window
+        if (at < (unsigned int)WINDOW) lds[at] = (unsigned char)c;
+    }
+    __device__ void bytes(const unsigned char* __restrict__ src, int n) {
+        for (int k = 0; k < n; ++k) put(src[k]);
+    }
+    __device__ void literal(const char* s) {
+        for (; *s; ++s) put(*s);
+    }
+    __device__ void number(long long v) {
+        char tmp[24];
+        const int n = fhx::fmt::put_i64(tmp, v);
+        for (int k = 0; k < n; ++k) put(tmp[k]);
+    }
+};
+
+__global__ __launch_bounds__(WG) void ut_format(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ block_off,
+                                                int64_t n_lines_batch, int64_t line_base, const unsigned short* __restrict__ info,
+                                                const unsigned long long* __restrict__ kept_off, const unsigned long long* __restrict__ deferred_off,
+                                                int64_t kept_base, const unsigned char* __restrict__ scores, int64_t n_slots,
+                                                const unsigned long long* __restrict__ out_off, unsigned char* __restrict__ out, int64_t out_capacity,
+                                                TrackWords* __restrict__ words) {
+    __shared__ unsigned short lstart[LSTART_ENTRIES];
+    __shared__ unsigned char window[WINDOW];
+    const int n_lines = block_lines(text, T, lstart);
+    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
+    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    int64_t nr0 = kept_base + (int64_t)kept_off[blockIdx.x] + 1, slot0 = (int64_t)deferred_off[blockIdx.x];
+    int64_t at = (int64_t)out_off[blockIdx.x];
+    for (int base = 0; base < n_lines; base += WG) {        // n_lines is the same for every lane
+        const Round q = round_of(base, n_lines, row0, n_lines_batch);
+        const unsigned int word = q.valid ? (unsigned int)info[q.r] : 0u;
+        const unsigned int len = word & ~DEFERRED;
+        const bool kept = len != 0, deferred = (word & DEFERRED) != 0;
+        unsigned int counts, total;
+        const unsigned int rank = fhxscan::block_exclusive_scan((kept ? 1u : 0u) | (deferred ? 0x10000u : 0u), &counts);
+        const unsigned int pre = fhxscan::block_exclusive_scan(len, &total);
+        // the line's pieces, once for all its windows
+        const unsigned char* line = text + b0 + (kept ? (int64_t)lstart[q.e] : 0);
+        Line L;
+        char score[fhx::score::MAX_TEXT];
+        int score_len = 0, v2 = 0, v4 = 0;
+        if (kept) {
+            walk(text, T, b0 + lstart[q.e], 0, L);
+            v2 = midpoint(line, L.b2, L.n2);
+            v4 = midpoint(line, L.b4, L.n4);
+            unsigned long long key = 0;
+            const int cls = classify(line, L.fb, L.fn, &key);
+            const int64_t slot = slot0 + (rank >> 16);
+            if (deferred) {
+                if (slot < n_slots) {
+                    score_len = min((int)scores[slot * DEFER_OUT], DEFER_OUT - 1);
+                    for (int k = 0; k < score_len && k < fhx::score::MAX_TEXT; ++k) score[k] = (char)scores[slot * DEFER_OUT + 1 + k];
+                }
+            } else if (cls == 2) {
+                score_len = fhx::score::certified(score, fhx::score::approximate(key % KEY_EXP, (int)(key / KEY_EXP) - 308));
+            } else {
+                score_len = 7;
+                score[0] = score[4] = 'i', score[1] = score[5] = 'n', score[2] = score[6] = 'f', score[3] = ' ';
+            }
+            score_len = min(score_len, fhx::score::MAX_TEXT);
+        }
+        for (unsigned int w0 = 0; w0 < total; w0 += WINDOW) {
+            if (kept && pre < w0 + WINDOW && pre + len > w0) {
+                WindowSink s{window, pre, w0};
+                s.bytes(line + L.b1, L.n1);
+                s.put(' ');
+                s.number((long long)v2 - 1);
+                s.put(' ');
+                s.number((long long)v4 + 1);
+                s.put(' ');
+                s.number(nr0 + (rank & 0xFFFFu));
+                s.put(' ');
+                s.bytes((const unsigned char*)score, score_len);
+                s.literal(" EXP 0 ");
+                s.bytes(line + L.b1, L.n1);
+                s.put(' ');
+                s.number((long long)v2 - 1);
+                s.put(' ');
+                s.number((long long)v2 + 1);
+                s.literal(" SOURCE_NAME . ");
+                s.bytes(line + L.b3, L.n3);
+                s.put(' ');
+                s.number((long long)v4 - 1);
+                s.put(' ');
+                s.number((long long)v4 + 1);
+                s.literal(" TARGET_NAME +\n");
+                // what was written is what ut_measure counted, or nothing of this call is kept
+                if (s.pos - pre != len) atomicMin(&words->first_error, error_word(line_base + q.r + 1, FHX_MS_INTERNAL));
+            }
+            __syncthreads();
+            const unsigned int n = min(total - w0, (unsigned int)WINDOW);
+            for (unsigned int j = threadIdx.x; j < n; j += WG)
+                if (at + w0 + j < out_capacity) out[at + w0 + j] = window[j];
+            __syncthreads();                                // the window is written again
+        }
+        at += total;
+        nr0 += counts & 0xFFFFu;
+        slot0 += counts >> 16;
+    }
+}
+
+}  // namespace utd
+
+// ===================================================================================================================
+namespace {
+
+const char kTrackHead[] =
+    "track type=interact name=\"Your_Fit-Hi-C_Interactions\" description=\"Fit-Hi-C_Interactions\" interactDirectional=true useScore=on "
+    "maxHeightPixels=50:100:200 visibility=full\n"
+    "#chrom  chromStart  chromEnd  name  score  value  exp  color  sourceChrom  sourceStart  sourceEnd  sourceName  sourceStrand  targetChrom  "
+    "targetStart  targetEnd  targetName  targetStrand\n";
+
+void drop_track(fhx_ms* ms) {
+    std::vector<char>().swap(ms->track);
+    ms->t_lines = ms->t_kept = ms->t_deferred = 0;
+}
+
+// a device array of one call that grows to what a batch needs
+template <typename T>
+hipError_t grow(fhx::Scratch& tmp, T** p, int64_t* capacity, int64_t need) {
+    if (need <= *capacity) return hipSuccess;
+    if (*p) tmp.drop(*p);
+    *p = nullptr;
+    *capacity = 0;
+    const hipError_t e = tmp.get(p, (size_t)need);
+    if (e == hipSuccess) *capacity = need;
+    return e;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhx_ms_score_text(const char* field, int32_t len, int32_t certify, char* out, int32_t capacity) {
+    if (!field || !out || len < 1 || len > 15 || capacity < fhx::score::MAX_TEXT) return FHX_ERR_ARG;
+    if (!certify) return fhx::score::host_fields(field, len, out);
+    // the kernel's route with the host's log10: the same cells, the same digits
+    int e = 0;
+    unsigned long long m = 0;
+    if ((len != 12 && len != 13) || field[1] != '.' || field[8] != 'e' || (field[9] != '+' && field[9] != '-')) return FHX_ERR_ARG;
+    for (int k = 0; k < 8; ++k)
+        if (k != 1) {
+            if (field[k] < '0' || field[k] > '9') return FHX_ERR_ARG;
+            m = m * 10 + (unsigned long long)(field[k] - '0');
+        }
+    for (int k = 10; k < len; ++k) {
+        if (field[k] < '0' || field[k] > '9') return FHX_ERR_ARG;
+        e = e * 10 + (field[k] - '0');
+    }
+    if (m < 1000000ull || e > 308) return FHX_ERR_ARG;
+    return fhx::score::certified(out, fhx::score::approximate(m, field[9] == '-' ? -e : e));
+}
+
+int fhx_ms_track_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept, int64_t* n_bytes,
+                      int32_t* why, int64_t* bad_line) {
+    using namespace utd;
+    if (!ms || !path || !fdr_text || !n_bytes || !why || !bad_line) return FHX_ERR_ARG;
+    *n_bytes = 0;
+    *why = FHX_MS_OK;
+    *bad_line = 0;
+    TH_HIP(ms, hipSetDevice(ms->device));
+    TH_HIP(ms, hipStreamSynchronize(ms->stream));
+    drop_track(ms);
+    for (double& s : ms->t_seconds) s = 0;
+    if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) {
+        *why = FHX_MS_FDR;
+        return ms->fail(FHX_ERR_UNSUPPORTED, "the text of the threshold must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
+    }
+    Fdr fdr;
+    std::memset(&fdr, 0, sizeof(fdr));
+    std::memcpy(fdr.text, fdr_text, (size_t)fdr_len);
+    fdr.len = fdr_len;
+    fhx::StageClock clock{ms->t_seconds};
+    fhx::TextFile src;
+    if (const int rc = src.open(path, /*allow_gzip=*/true, &ms->err)) return rc;
+    const int64_t batch_bytes = fhx::batch_bytes_for("FHX_MS_BATCH_BYTES", (int64_t)1 << 31, src.size());
+    const int64_t max_blocks = (batch_bytes + BLOCK_BYTES - 1) / BLOCK_BYTES;
+    fhx::Scratch tmp;
+    unsigned char *d_text = nullptr, *d_out = nullptr, *d_fields = nullptr, *d_scores = nullptr;
+    unsigned int *d_block_nl = nullptr, *d_block_kept = nullptr, *d_block_deferred = nullptr, *d_block_bytes = nullptr;
+    unsigned long long *d_block_off = nullptr, *d_kept_off = nullptr, *d_deferred_off = nullptr, *d_out_off = nullptr;
+    unsigned short* d_info = nullptr;
+    int64_t info_capacity = 0, out_capacity = 0, fields_capacity = 0, scores_capacity = 0;
+    TrackWords* d_words = nullptr;
+    TH_HIP(ms, tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
+    TH_HIP(ms, tmp.get(&d_block_nl, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_block_kept, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_block_deferred, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_block_bytes, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_block_off, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_kept_off, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_deferred_off, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_out_off, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_words, 1));
+    TrackWords words;
+    std::vector<unsigned char> fields, scores;
+    auto refuse = [&](int rc, int32_t w, int64_t line, const std::string& msg) {
+        drop_track(ms);
+        *why = w;
+        *bad_line = line;
+        return ms->fail(rc, msg);
+    };
+    auto refuse_word = [&](unsigned long long word) {
+        const int32_t w = error_why(word);
+        const int64_t line = error_line(word);
+        if (w == FHX_MS_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, "the kernels of the track disagree about line " + std::to_string(line));
+        return refuse(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
+    };
+    ms->track.assign(kTrackHead, kTrackHead + sizeof(kTrackHead) - 1);
+    int64_t lines = 0, kept = 0, deferred_lines = 0;
+    for (int64_t off = 0; off < src.size();) {
+        std::memset(&words, 0, sizeof(words));
+        words.first_error = NO_ERROR;
+        TH_HIP(ms, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, ms->stream));
+        fhx::TextBatch b;
+        if (const int rc = fhx::upload_batch(ms, src, "significances", off, std::min(batch_bytes, src.size() - off), d_text, &b)) return rc;
+        const int64_t len = b.len, n_blocks = b.n_blocks;
+        clock.mark(0);
+        hipLaunchKernelGGL(scan_text<GrammarBytes>, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len, d_block_nl,
+                           (unsigned int*)&d_words->bad_bytes);
+        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
+                           &d_words->newlines);
+        TH_HIP(ms, hipGetLastError());
+        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
+        TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        clock.mark(1);
+        const int64_t n = b.lines(words.newlines);
+        TH_HIP(ms, grow(tmp, &d_info, &info_capacity, n));
+        hipLaunchKernelGGL(ut_select, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
+                           (const unsigned long long*)d_block_off, n, lines, fdr, (unsigned long long)key_bound, (int)zero_kept,
+                           (int)(words.bad_bytes != 0), d_info, d_block_kept, d_block_deferred, d_words);
+        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_kept, n_blocks, d_kept_off,
+                           &d_words->kept_lines);
+        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_deferred, n_blocks,
+                           d_deferred_off, &d_words->deferred);
+        TH_HIP(ms, hipGetLastError());
+        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
+        TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        clock.mark(2);
+        if (words.first_error != NO_ERROR) return refuse_word(words.first_error);          // earlier batches hold the smaller line numbers
+        const int64_t batch_kept = (int64_t)words.kept_lines, n_slots = (int64_t)words.deferred;
+        if (batch_kept > n || n_slots > batch_kept) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "more kept lines than lines");
+        if (kept + batch_kept > (int64_t)INT32_MAX)
+            return refuse(FHX_ERR_UNSUPPORTED, FHX_MS_KEPT, 0, "more than 2^31 - 1 lines pass: awk prints NR as an integer only below 2^31");
+        if (n_slots > 0) {                                                    // the deferred round trip
+            TH_HIP(ms, grow(tmp, &d_fields, &fields_capacity, n_slots * DEFER_IN));
+            TH_HIP(ms, grow(tmp, &d_scores, &scores_capacity, n_slots * DEFER_OUT));
+            hipLaunchKernelGGL(ut_defer, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
+                               (const unsigned long long*)d_block_off, n, (const unsigned short*)d_info, (const unsigned long long*)d_deferred_off,
+                               d_fields, n_slots);
+            TH_HIP(ms, hipGetLastError());
+            fields.resize((size_t)(n_slots * DEFER_IN));
+            scores.assign((size_t)(n_slots * DEFER_OUT), 0);
+            TH_HIP(ms, hipMemcpyAsync(fields.data(), d_fields, fields.size(), hipMemcpyDeviceToHost, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+            for (int64_t k = 0; k < n_slots; ++k) {
+                const char* f = (const char*)fields.data() + k * DEFER_IN;
+                char text[fhx::score::MAX_TEXT + 8];
+                const int got = fhx::score::host_fields(f, (int)strnlen(f, DEFER_IN - 1), text);
+                if (got < 3 || got > fhx::score::MAX_TEXT) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "a deferred score has no text");
+                scores[(size_t)(k * DEFER_OUT)] = (unsigned char)got;
+                std::memcpy(scores.data() + k * DEFER_OUT + 1, text, (size_t)got);
+            }
+            TH_HIP(ms, hipMemcpyAsync(d_scores, scores.data(), scores.size(), hipMemcpyHostToDevice, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        }
+        clock.mark(3);
+        int64_t bytes = 0;
+        if (batch_kept > 0) {
+            hipLaunchKernelGGL(ut_measure, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
+                               (const unsigned long long*)d_block_off, n, d_info, (const unsigned long long*)d_kept_off,
+                               (const unsigned long long*)d_deferred_off, kept, (const unsigned char*)d_scores, n_slots, d_block_bytes);
+            hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_bytes, n_blocks, d_out_off,
+                               &d_words->out_bytes);
+            TH_HIP(ms, hipGetLastError());
+            TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+            bytes = (int64_t)words.out_bytes;
+            TH_HIP(ms, grow(tmp, &d_out, &out_capacity, bytes));
+            hipLaunchKernelGGL(ut_format, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
+                               (const unsigned long long*)d_block_off, n, lines, (const unsigned short*)d_info, (const unsigned long long*)d_kept_off,
+                               (const unsigned long long*)d_deferred_off, kept, (const unsigned char*)d_scores, n_slots,
+                               (const unsigned long long*)d_out_off, d_out, out_capacity, d_words);
+            TH_HIP(ms, hipGetLastError());
+            TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+            if (words.first_error != NO_ERROR) return refuse_word(words.first_error);
+        }
+        clock.mark(4);
+        if (bytes > 0) {
+            const size_t had = ms->track.size();
+            ms->track.resize(had + (size_t)bytes);
+            TH_HIP(ms, hipMemcpyAsync(ms->track.data() + had, d_out, (size_t)bytes, hipMemcpyDeviceToHost, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        }
+        clock.mark(5);
+        lines += n;
+        kept += batch_kept;
+        deferred_lines += n_slots;
+        off += len;
+    }
+    ms->t_lines = lines;
+    ms->t_kept = kept;
+    ms->t_deferred = deferred_lines;
+    *n_bytes = (int64_t)ms->track.size();
+    if (std::getenv("FHX_TIMING"))
+        std::fprintf(stderr, "interact track on the device (%s): %lld lines, %lld kept, %lld deferred (%lld bytes): read + upload %.6f s; scan %.6f s; "
+                     "select %.6f s; deferred round trip %.6f s; format %.6f s; copy out %.6f s\n", path, (long long)lines, (long long)kept,
+                     (long long)deferred_lines, (long long)ms->track.size(), ms->t_seconds[0], ms->t_seconds[1], ms->t_seconds[2], ms->t_seconds[3],
+                     ms->t_seconds[4], ms->t_seconds[5]);
+    return FHX_OK;
+}
+
+int fhx_ms_track_counts(const fhx_ms* ms, int64_t* n_lines, int64_t* n_kept, int64_t* n_deferred, int64_t* n_bytes) {
+    if (!ms) return FHX_ERR_ARG;
+    if (n_lines) *n_lines = ms->t_lines;
+    if (n_kept) *n_kept = ms->t_kept;
+    if (n_deferred) *n_deferred = ms->t_deferred;
+    if (n_bytes) *n_bytes = (int64_t)ms->track.size();
+    return FHX_OK;
+}
+
+int fhx_ms_track_stage_seconds(const fhx_ms* ms, double* seconds) {
+    if (!ms || !seconds) return FHX_ERR_ARG;
+    for (int k = 0; k < FHX_MS_TRACK_STAGES; ++k) seconds[k] = ms->t_seconds[k];
+    return FHX_OK;
+}
+
+int fhx_ms_copy_track(const fhx_ms* ms, void* dst, int64_t capacity) {
+    if (!ms || capacity < (int64_t)ms->track.size() || (!dst && !ms->track.empty())) return FHX_ERR_ARG;
+    if (!ms->track.empty()) std::memcpy(dst, ms->track.data(), ms->track.size());
+    return FHX_OK;
+}
+
+}  // extern "C"

@@ -15,7 +15,7 @@ The selection runs in kernels (csrc/fhx_sigselect.hip) and is made on the TEXT o
     1.000000e-320 is dropped ('1' > '0'), with fdr = 5 it is kept;
   * everything else is compared as a number, through one integer key per field and a bound found here by bisection with float().
 `select(..., strict=True, skip_first_line=False)` is the selection visualize-UCSC.sh makes (`$7 < q`, no header drop); the
-interact track itself is not written here.
+interact track itself is written by fithic_amd.ucsc.
 
 The script hands the subset to Combine with -H 0, and Combine then lists the chromosomes with `cut -f1 | sort -k1,1 | uniq`:
 cut splits at TABS only, so a kept line without a tab is listed whole, its first token is taken as one more chromosome to

@@ -698,6 +698,30 @@ int fhx_ms_counts(const fhx_ms* ms, int64_t* n_lines, int64_t* n_kept, int64_t* 
 int fhx_ms_stage_seconds(const fhx_ms* ms, double* seconds);       /* FHX_MS_STAGES host clocks of the last call */
 int fhx_ms_copy_subset(const fhx_ms* ms, void* dst, int64_t capacity);   /* the n_bytes of the last selection */
 
+/* ---- the UCSC interact track of the significant contacts (fithic/utils/visualize-UCSC.sh:16-18; csrc/fhx_sigtrack.inc,
+ * csrc/fhx_score.hpp), on the same handle.  The selection is fhx_ms_select_file's with strict = 1 and no line skipped, plus one
+ * rule: on FILE LINE 1 a field 7 that starts with an ASCII letter (`q-value`) is a string above every accepted threshold, and the
+ * line is dropped without a refusal (fewer than 7 tokens are refused there too).  Every kept line becomes
+ *   $1 ($2-1) ($4+1) NR int(-log($7)/log(10)) -log($7)/log(10) EXP 0 $1 ($2-1) ($2+1) SOURCE_NAME . $3 ($4-1) ($4+1) TARGET_NAME +
+ * joined by single blanks, NR counting the kept lines from 1, behind the script's two fixed lines; the whole text stays in host
+ * memory.  The two score fields are the bytes mawk 1.3.4 prints: written in the kernel where an error bound certifies them,
+ * otherwise DEFERRED - field 7 goes to the host, which makes awk's own libm calls, and the line is completed on the device.
+ * Taken beyond fhx_ms_select_file's grammar, on every line that is parsed, kept or not: tokens 2 and 4 are 1 to 9 ASCII digits
+ * (leading zeros allowed), tokens 1 and 3 at most 63 bytes. */
+#define FHX_MS_MIDPOINT 7          /* token 2 or 4 is not 1 to 9 digits */
+#define FHX_MS_NAME 8              /* token 1 or 3 is longer than 63 bytes */
+#define FHX_MS_KEPT 9              /* more than 2^31 - 1 lines pass: awk prints NR through %.6g from there (no line number) */
+#define FHX_MS_TRACK_STAGES 6      /* read + upload, newline scan, select, deferred round trip, measure + format, copy out */
+int fhx_ms_track_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept,
+                      int64_t* n_bytes, int32_t* why, int64_t* bad_line);
+int fhx_ms_track_counts(const fhx_ms* ms, int64_t* n_lines, int64_t* n_kept, int64_t* n_deferred, int64_t* n_bytes);
+int fhx_ms_track_stage_seconds(const fhx_ms* ms, double* seconds);  /* FHX_MS_TRACK_STAGES host clocks of the last call */
+int fhx_ms_copy_track(const fhx_ms* ms, void* dst, int64_t capacity);    /* the n_bytes of the last track */
+/* The two score fields and the blank between them for one field 7 (1 to 15 bytes) into out (24 bytes at least) -> their length.
+ * certify = 0: the deferred route (strtod, log, the division, awk's number printing); certify = 1: the kernel's route run on the
+ * host, 0 when it would defer.  Host only: needs no GPU. */
+int fhx_ms_score_text(const char* field, int32_t len, int32_t certify, char* out, int32_t capacity);
+
 #ifdef __cplusplus
 }
 #endif
