@@ -113,6 +113,8 @@ SYMBOLS = {
     "fhx_device_ptr": (_P, [_P, ctypes.c_int]),
     "fhx_n_sorted": (ctypes.c_int64, [_P]),
     "fhx_bh_sort_stats": (ctypes.c_int, [_P, _I64P]),
+    "fhx_k3_pass_info": (ctypes.c_int, [_P, _I64P]),
+    "fhx_debug_k3_tiles_per_group": (ctypes.c_int, [_P, ctypes.c_int]),
     "fhx_kernel_seconds": (ctypes.c_int, [_P, _F64P, _F64P, _F64P]),
     "fhx_kernel_seconds_total": (ctypes.c_int, [_P, _F64P, _I64P, ctypes.c_int]),
     "fhx_kernel_events_dropped": (ctypes.c_int, [_P, _I64P]),
@@ -729,6 +731,16 @@ class Context:
         self._check(self._L.fhx_bh_sort_stats(self._h, n))
         return dict(zip(("passes", "low_bit", "beyond_lists", "inversions", "runs_by_thread", "long_run_inversions", "segments", "segment_keys"),
                         [int(v) for v in n]))
+
+    def k3_pass_info(self):
+        """which path the last bh() took through K3: the eight slots of fhx_k3_pass_info (include/fithic_mi355x.h)"""
+        n = (ctypes.c_int64 * 8)()
+        self._check(self._L.fhx_k3_pass_info(self._h, n))
+        return [int(v) for v in n]
+
+    def debug_k3_tiles_per_group(self, per):
+        """test hook (fhx_debug_k3_tiles_per_group): 1..4 tiles per workgroup in the scattered compaction, 0: the library's choice"""
+        self._check(self._L.fhx_debug_k3_tiles_per_group(self._h, int(per)))
 
     def kernel_events_dropped(self):
         """passes of K1, K2, K3, heavy launch whose events were overwritten unread since the last reset (0 = the sums are complete)"""

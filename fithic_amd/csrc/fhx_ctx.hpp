@@ -468,6 +468,11 @@ struct fhx_ctx {
     hipEvent_t ev_k3 = nullptr;                       // the copy into h_k3; auto_cutoff's mark behind K2 when its caller recorded none
     int64_t k3_last_kept = -1, k3_last_rows = -1;     // survivors and rows of the last fhx_bh: whether the dense-q launches are worth enqueueing
     int64_t sort_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the last large sort of K3 (fhx_bh_sort_stats)
+    // what the last fhx_bh decided on the host (fhx_k3_pass_info adds the device's two words when asked): [0] dense launches enqueued,
+    // [1] survivors by the histogram, [3] tiles per workgroup of k3_compact<false>, [4] sort taken, [5] far_below, [6] q_is_ones
+    int64_t k3_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool have_k3_info = false;
+    int k3_force_per = 0;                             // fhx_debug_k3_tiles_per_group (tests): 1..4 replaces compact_pvalues' choice, 0: none
     std::vector<int64_t> fdr_counts;
     fhx::DistState* dist = nullptr;                 // communicator + exchange buffers of sharded runs (fhx_dist.inc)
     bool dist_ndist_agreed = false;                   // sharded runs: the histogram length was made equal on all ranks
@@ -664,7 +669,7 @@ void launch_bh_scan_tiles(fhx_ctx* ctx, double* tile_max, const unsigned long lo
                           double* total_max, int64_t n_bound, unsigned long long* fault);
 void launch_bh_apply(fhx_ctx* ctx, int tiles, const unsigned long long* keys, const unsigned int* vals, const unsigned long long* n_ptr,
                      int64_t n_fixed, double n_tests, double rank0, const double* tile_carry, const double* extra_carry, double* q_out,
-                     double* dense, const unsigned long long* dense_flag);
+                     double* dense, const unsigned long long* dense_flag, const double* p_rows = nullptr);
 void launch_scatter_q(fhx_ctx* ctx, int64_t n_rows, const unsigned int* rows, const double* q_sorted, const unsigned long long* n_ptr,
                       double* q);
 void launch_fdr_hist(fhx_ctx* ctx, const double* q, int64_t n, unsigned long long* buckets);

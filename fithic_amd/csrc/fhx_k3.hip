@@ -268,7 +268,9 @@ __global__ __launch_bounds__(CP_THREADS) void k3_compact(const double* __restric
 
 // The whole q column in row order, once: 1.0, the row's own NaN, or - for the rows k3_compact<true> kept - the survivor's q from the
 // dense array (consecutive kept rows of a wave step read consecutive entries).  Same tiles and wave chunks as k3_compact.
-__global__ __launch_bounds__(CP_THREADS) void k3_fill_q(const double* __restrict__ p, int64_t n, DenseQ dq, double* __restrict__ q) {
+// (own_zero: N > 0 - a q of zero then belongs to a p of zero, and the reference's running maximum hands such a row its own zero,
+// -0.0 for a p of -0.0: the sorted keys hold one zero for both, so the sign is read back from p here)
+__global__ __launch_bounds__(CP_THREADS) void k3_fill_q(const double* __restrict__ p, int64_t n, DenseQ dq, double* __restrict__ q, bool own_zero) {
     if (dq.flag && *dq.flag == 0ull) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned long long lane_lt = (1ull << lane) - 1ull;
@@ -292,6 +294,8 @@ __global__ __launch_bounds__(CP_THREADS) void k3_fill_q(const double* __restrict
             double q0 = 1.0, q1 = 1.0;
             if ((keep.x >> lane) & 1ull) q0 = mine[b0];
             if ((keep.y >> lane) & 1ull) q1 = mine[b1];
+            if (own_zero && q0 == 0.0) q0 = copysign(0.0, p[i]);
+            if (own_zero && q1 == 0.0) q1 = copysign(0.0, p[i + 1]);
             if ((nan.x >> lane) & 1ull) q0 = p[i];
             if ((nan.y >> lane) & 1ull) q1 = p[i + 1];
             if (i + 1 < n)
@@ -753,7 +757,8 @@ __global__ __launch_bounds__(BH_THREADS) void bh_apply(const unsigned long long*
                                                        double n_tests, double rank0, const double* __restrict__ tile_carry,
                                                        const double* __restrict__ extra_carry, double* __restrict__ q_out,
                                                        double* __restrict__ dense,
-                                                       const unsigned long long* __restrict__ dense_flag) {
+                                                       const unsigned long long* __restrict__ dense_flag,
+                                                       const double* __restrict__ p_rows) {
     __shared__ double wtot[BH_THREADS / 64];
     const bool into_dense = dense && (!dense_flag || *dense_flag != 0ull);    // the values are compact indices: q goes to the dense array
     if (into_dense) q_out = dense;
@@ -785,11 +790,14 @@ __global__ __launch_bounds__(BH_THREADS) void bh_apply(const unsigned long long*
     for (int r = 0; r < BH_ITEMS; ++r) {
         const int64_t i = first + r;
         if (i < n) {
-            const double qv = fmax(v[r], carry);
+            double qv = fmax(v[r], carry);
             if (vals && into_dense)
                 q_out[vals[i]] = qv;                                     // the dense array: k3_fill_q reads it right behind this launch
-            else if (vals)
+            else if (vals) {
+                // (p_rows, N > 0: a q of zero belongs to a p of zero and takes that zero's own sign - see k3_fill_q)
+                if (p_rows && qv == 0.0 && n_tests > 0.0) qv = copysign(0.0, p_rows[vals[i]]);
                 __builtin_nontemporal_store(qv, q_out + vals[i]);       // one 8-byte store into a line nobody else touches soon: no allocate
+            }
             else
                 q_out[i] = qv;
         }
@@ -807,11 +815,16 @@ __global__ void k_iota_u32(unsigned int* __restrict__ v, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) v[i] = (unsigned int)i;
 }
 
+// (p: the rows' own p-values - the sharded sequence only runs with N > 0, where a q of zero takes the sign of its p, see k3_fill_q)
 __global__ void k_scatter_q(const unsigned int* __restrict__ rows, const double* __restrict__ q_sorted,
-                            const unsigned long long* __restrict__ n_ptr, double* __restrict__ q) {
+                            const unsigned long long* __restrict__ n_ptr, double* __restrict__ q, const double* __restrict__ p) {
     const int64_t n = (int64_t)*n_ptr;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) q[rows[i]] = q_sorted[i];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        double v = q_sorted[i];
+        if (v == 0.0) v = copysign(0.0, p[rows[i]]);
+        q[rows[i]] = v;
+    }
 }
 
 // plot_qvalues' 51 buckets (fithic.py:1235-1254): counts of floor(q/0.001), NaN -> bucket of 1.0
@@ -1109,13 +1122,13 @@ void launch_bh_scan_tiles(fhx_ctx* ctx, double* tile_max, const unsigned long lo
 }
 void launch_bh_apply(fhx_ctx* ctx, int tiles, const unsigned long long* keys, const unsigned int* vals, const unsigned long long* n_ptr,
                      int64_t n_fixed, double n_tests, double rank0, const double* tile_carry, const double* extra_carry, double* q_out,
-                     double* dense, const unsigned long long* dense_flag) {
+                     double* dense, const unsigned long long* dense_flag, const double* p_rows) {
     hipLaunchKernelGGL(bh_apply, dim3(tiles), dim3(BH_THREADS), 0, ctx->stream, keys, vals, n_ptr, n_fixed, n_tests, rank0, tile_carry,
-                       extra_carry, q_out, dense, dense_flag);
+                       extra_carry, q_out, dense, dense_flag, p_rows);
 }
 void launch_scatter_q(fhx_ctx* ctx, int64_t n_rows, const unsigned int* rows, const double* q_sorted, const unsigned long long* n_ptr,
                       double* q) {
-    hipLaunchKernelGGL(k_scatter_q, dim3(grid_for(n_rows, 256)), dim3(256), 0, ctx->stream, rows, q_sorted, n_ptr, q);
+    hipLaunchKernelGGL(k_scatter_q, dim3(grid_for(n_rows, 256)), dim3(256), 0, ctx->stream, rows, q_sorted, n_ptr, q, (const double*)ctx->d_p);
 }
 void launch_fdr_hist(fhx_ctx* ctx, const double* q, int64_t n, unsigned long long* buckets) {
     hipLaunchKernelGGL(k_fdr_hist, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, q, n, buckets);
@@ -1163,6 +1176,10 @@ struct K3Pass {
     bool n_is_bound = false;                      // n_kept is the histogram's upper bound: the exact number is in *counter
     int sorted_buf = 0;                           // the pair of keys / vals that holds the sorted survivors
     OsPending pend;                               // the one-sweep sort's second half, when sort_kept left it to its caller
+    // what the steps chose, for fhx_k3_pass_info
+    int tiles_per_wg = 0;                         // of k3_compact<false> (0: not launched)
+    bool q_is_ones = false;                       // k3_compact<false> was told the q column holds 1.0 already
+    int sort_taken = 0;                           // 0: nothing to sort, 1: LDS tile sorts, 2: one-sweep, 3: radix_passes
 };
 
 // the cutoff key from this GPU's own histogram of pass.p, and the survivors' number on its way to the host
@@ -1219,7 +1236,10 @@ static int compact_pvalues(fhx_ctx* ctx, K3Pass& pass) {
         const bool ones = ctx->q_prefilled && pass.q == ctx->d_q && pass.p == ctx->d_p;
         // tiles per workgroup: as many as leave every CU its two workgroups several times over (a shard keeps one tile per workgroup)
         const int64_t n_tiles = (pass.n + CP_TILE - 1) / CP_TILE;
-        const int per = (int)std::max<int64_t>(1, std::min<int64_t>(4, n_tiles / 2048));
+        int per = (int)std::max<int64_t>(1, std::min<int64_t>(4, n_tiles / 2048));
+        if (ctx->k3_force_per && pass.p == ctx->d_p) per = ctx->k3_force_per;      // fhx_debug_k3_tiles_per_group (tests)
+        pass.tiles_per_wg = per;
+        pass.q_is_ones = ones;
         hipLaunchKernelGGL(k3_compact<false>, dim3(grid_for((n_tiles + per - 1) / per, 1, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, pass.p,
                            pass.n, pass.keys[0], pass.vals[0], pass.q, pass.counter, pass.cutoff, off, ones, per);
     }
@@ -1253,12 +1273,14 @@ static int sort_kept(fhx_ctx* ctx, K3Pass& pass, bool defer) {
     for (int k = 0; k < 8; ++k) ctx->sort_stats[k] = 0;
     if (pass.n_kept <= KS_MAX_KEYS && !small_off) {                // tile sort in LDS + merge by rank: two launches (see ks_tile_sort)
         pass.sorted_buf = pass.n_kept > 0 ? small_sort(ctx, pass.keys, pass.vals, pass.counter, pass.n_kept) : 0;
+        pass.sort_taken = pass.n_kept > 0 ? 1 : 0;
         FHX_HIP(hipGetLastError());
         return FHX_OK;
     }
     const char* se = std::getenv("FHX_K3_SORT");                  // "legacy": round 4's count / scan / scatter passes (A/B runs)
     const bool legacy = se && std::strcmp(se, "legacy") == 0;
     if (pass.ctrl && !legacy && pass.n_kept <= OS_MAX_KEYS) {
+        pass.sort_taken = 2;
         const int rc = onesweep_launch(ctx, pass.keys, pass.vals, pass.counter, pass.n_kept, pass.key_hi, pass.ctrl, &pass.pend);
         if (rc != FHX_OK) return rc;
         pass.sorted_buf = pass.pend.src;                   // (the finish never changes the buffer pair)
@@ -1266,6 +1288,7 @@ static int sort_kept(fhx_ctx* ctx, K3Pass& pass, bool defer) {
         bool moved = false;
         return onesweep_finish(ctx, &pass.pend, &moved);
     }
+    pass.sort_taken = 3;
     return radix_passes(ctx, pass.keys, pass.vals, pass.counter, sort_blocks_for(pass.n_kept), pass.key_hi, SORT_BITS_LARGE, 0, &pass.sorted_buf);
 }
 
@@ -1319,9 +1342,10 @@ static int bh_from_sorted(fhx_ctx* ctx, const K3Pass& pass) {
     launch_bh_tile_max(ctx, tiles, keys, pass.counter, 0, pass.n_total_tests, 0.0, pass.tile_max);
     launch_bh_scan_tiles(ctx, pass.tile_max, pass.counter, 0, 0.0, nullptr, pass.n_kept, fault);
     launch_bh_apply(ctx, tiles, keys, pass.vals[pass.sorted_buf], pass.counter, 0, pass.n_total_tests, 0.0, pass.tile_max, nullptr, pass.q,
-                    dq ? dq->dense : nullptr, dq ? dq->flag : nullptr);
+                    dq ? dq->dense : nullptr, dq ? dq->flag : nullptr, pass.p);
     if (dq)
-        hipLaunchKernelGGL(k3_fill_q, dim3(grid_for(pass.n, CP_TILE, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, pass.p, pass.n, *dq, pass.q);
+        hipLaunchKernelGGL(k3_fill_q, dim3(grid_for(pass.n, CP_TILE, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, pass.p, pass.n, *dq, pass.q,
+                           pass.n_total_tests > 0.0);
     FHX_HIP(hipGetLastError());
     return FHX_OK;
 }
@@ -1492,10 +1516,40 @@ int fhx_bh(fhx_ctx* ctx, double n_total_tests) {
     ctx->n_sorted = pass.n_is_bound ? -2 : pass.n_kept;  // -2: fhx_n_sorted reads the device counter when somebody asks
     ctx->k3_last_kept = pass.n_kept;                     // (the histogram's bound or the exact number: either serves the guess above)
     ctx->k3_last_rows = ctx->n_rows;
+    ctx->k3_info[0] = dense ? 1 : 0;
+    ctx->k3_info[1] = pass.n_kept;
+    ctx->k3_info[3] = pass.tiles_per_wg;
+    ctx->k3_info[4] = pass.sort_taken;
+    ctx->k3_info[5] = far_below ? 1 : 0;
+    ctx->k3_info[6] = pass.q_is_ones ? 1 : 0;
+    ctx->have_k3_info = true;
     FHX_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
     ctx->ev_valid[2] = true;
     ctx->ev_folded[2] = false;
     ctx->have_q = true;
+    return FHX_OK;
+}
+
+int fhx_k3_pass_info(fhx_ctx* ctx, int64_t* out8) {
+    if (!ctx || !out8) return FHX_ERR_ARG;
+    if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
+    if (!ctx->have_k3_info) return fail(ctx, FHX_ERR_ARG, "fhx_bh must run first");
+    FHX_HIP(hipSetDevice(ctx->device));
+    // the device's two words are read now, behind everything the stream holds: fhx_bh itself never waits for them
+    unsigned long long dense = 0, kept = 0;
+    FHX_HIP(hipMemcpyAsync(&dense, &ctx->d_words->k3_dense, sizeof(dense), hipMemcpyDeviceToHost, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(&kept, &ctx->d_words->bh_kept, sizeof(kept), hipMemcpyDeviceToHost, ctx->stream));
+    FHX_HIP(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 8; ++k) out8[k] = ctx->k3_info[k];
+    if (out8[0]) out8[0] = dense ? 2 : 1;              // enqueued: the variant the device chose (DeviceWords::k3_dense)
+    out8[2] = (int64_t)kept;
+    out8[7] = 0;
+    return FHX_OK;
+}
+
+int fhx_debug_k3_tiles_per_group(fhx_ctx* ctx, int per) {
+    if (!ctx || per < 0 || per > 4) return FHX_ERR_ARG;
+    ctx->k3_force_per = per;
     return FHX_OK;
 }
 
@@ -1558,7 +1612,7 @@ int fhx_bh_scatter(fhx_ctx* ctx, const void* d_q_sorted_local) {
     FHX_HIP(hipSetDevice(ctx->device));
     if (d_q_sorted_local)                       // NULL is legal when this rank holds no p < 1 at all
         hipLaunchKernelGGL(k_scatter_q, dim3(grid_for(ctx->n_rows, 256)), dim3(256), 0, ctx->stream, ctx->d_vals[ctx->sorted_buf],
-                       (const double*)d_q_sorted_local, &ctx->d_words->bh_kept, ctx->d_q);
+                       (const double*)d_q_sorted_local, &ctx->d_words->bh_kept, ctx->d_q, (const double*)ctx->d_p);
     FHX_HIP(hipGetLastError());
     FHX_HIP(hipStreamSynchronize(ctx->stream));
     ctx->have_q = true;

@@ -296,6 +296,18 @@ int64_t fhx_n_sorted(fhx_ctx* ctx);
  * every bit of every key was sorted after all), inversions met, runs sorted by one thread each, inversions found in runs too
  * long for that, such runs sorted as segments of their own, keys in them. */
 int fhx_bh_sort_stats(fhx_ctx* ctx, int64_t* out8);
+/* Which path the last fhx_bh took through K3 (diagnostics, tests).  Read when asked, never collected inside fhx_bh: the call waits
+ * for the stream and copies two device words.  out8 = [0] 0: the dense-q launches (k3_compact<true>, k3_fill_q) were not enqueued,
+ * 1: enqueued and the device chose the scattered variant, 2: the device chose the dense variant; [1] rows below the cutoff by the key
+ * histogram; [2] the same by the compaction's device counter; [3] tiles per workgroup handed to the scattered compaction; [4] the
+ * sort: 0 none (no survivor), 1 the in-LDS tile sorts, 2 the one-sweep passes, 3 the count / scan / scatter passes; [5] 1 when the
+ * last pass's survivor count (under a tenth of the rows) kept the dense launches from being enqueued; [6] 1 when the compaction
+ * relied on a q column filled with 1.0 behind fhx_pass_stats; [7] 0.  FHX_ERR_ARG before the first fhx_bh. */
+int fhx_k3_pass_info(fhx_ctx* ctx, int64_t* out8);
+/* Test hook: per = 1..4 replaces the library's choice of tiles per workgroup in the scattered compaction of this context's later
+ * fhx_bh and fhx_bh_local_sort calls (the library itself goes beyond 1 only from 6.7e7 rows on), 0 gives the choice back;
+ * anything else is FHX_ERR_ARG.  Results do not depend on it.  Not for production callers. */
+int fhx_debug_k3_tiles_per_group(fhx_ctx* ctx, int per);
 /* Seconds the kernels of the last pass took on the context's stream (HIP events): k1, k2, k3. */
 int fhx_kernel_seconds(fhx_ctx* ctx, double* k1, double* k2, double* k3);
 /* The same summed over the passes since the last reset, without stopping the stream after each of them: sums4 = seconds of K1, K2,
