@@ -251,6 +251,13 @@ SYMBOLS = {
     "fhx_ms_track_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
     "fhx_ms_copy_track": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     "fhx_ms_score_text": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32]),
+    # the per-chromosome FDR subsets on the same handle
+    "fhx_ms_split_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
+                                         ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _I64P]),
+    "fhx_ms_split_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, ctypes.POINTER(ctypes.c_int32), _I64P, _I64P, ctypes.c_int32]),
+    "fhx_ms_split_names": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
+    "fhx_ms_split_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
+    "fhx_ms_copy_split": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64]),
 }
 
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
@@ -1398,9 +1405,12 @@ def vp_write_contacts(path, names, chr1, mid1, chr2, mid2, count, gzip_level=1, 
 
 (MS_OK, MS_TOKENS, MS_FIELD, MS_BYTES, MS_LONG_LINE, MS_FDR, MS_INTERNAL) = range(7)
 MS_MIDPOINT, MS_NAME, MS_KEPT = 7, 8, 9                             # refusals of the interact track alone
+MS_NAME_TAB, MS_NAME_BYTES, MS_NAME_NUMERIC, MS_NAMES = 10, 11, 12, 13     # refusals of the per-chromosome split alone
+MS_SPLIT_NAMES, MS_SPLIT_NAME_BYTES = 4096, 64
 MS_FDR_BYTES = 32
 MS_STAGE_NAMES = ("read_upload", "newline_scan", "select", "gather", "copy_out")
 MS_TRACK_STAGE_NAMES = ("read_upload", "newline_scan", "select", "deferred_round_trip", "format", "copy_out")
+MS_SPLIT_STAGE_NAMES = ("read_upload", "newline_scan", "names_select", "sort_gather", "copy_out")
 
 
 class MsRefused(FhxError):
@@ -1465,6 +1475,42 @@ class MsContext(_Handle):
         """the script's two fixed lines and one line per kept row, in file order"""
         buf = np.empty(self.track_counts()["bytes"], np.uint8)
         self._chk(self.L.fhx_ms_copy_track(self.h, buf.ctypes.data_as(ctypes.c_void_p), len(buf)))
+        return buf.tobytes()
+
+    def split_file(self, path, fdr_text, key_bound, zero_kept):
+        """the subsets of the rows with field 1 == field 3 and field 7 <= fdr, one per name of field 1 -> the number of names;
+        MsRefused for a file outside the device grammar"""
+        n, why, line = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self.L.fhx_ms_split_file(self.h, os.fsencode(path), fdr_text, len(fdr_text), int(key_bound), int(bool(zero_kept)),
+                                      ctypes.byref(n), ctypes.byref(why), ctypes.byref(line))
+        self._chk(rc, why.value, line.value)
+        return n.value
+
+    def split_counts(self):
+        """lines read, and per name (in the order of split_names) its kept lines and their bytes"""
+        a, n = ctypes.c_int64(0), ctypes.c_int32(0)
+        self._chk(self.L.fhx_ms_split_counts(self.h, ctypes.byref(a), ctypes.byref(n), None, None, 0))
+        kept, nbytes = np.zeros(max(n.value, 1), np.int64), np.zeros(max(n.value, 1), np.int64)
+        self._chk(self.L.fhx_ms_split_counts(self.h, None, None, _ptr(kept, ctypes.c_int64), _ptr(nbytes, ctypes.c_int64), n.value))
+        return dict(lines=a.value, kept=kept[:n.value].tolist(), bytes=nbytes[:n.value].tolist())
+
+    def split_names(self):
+        """the names of field 1 as bytes, in no particular order; split_text(k) is the subset of the k-th"""
+        n = len(self.split_counts()["kept"])
+        buf = np.zeros(max(n, 1) * MS_SPLIT_NAME_BYTES, np.uint8)
+        self._chk(self.L.fhx_ms_split_names(self.h, buf.ctypes.data_as(ctypes.c_void_p), n))
+        raw = buf.tobytes()
+        return [raw[k * MS_SPLIT_NAME_BYTES:(k + 1) * MS_SPLIT_NAME_BYTES].rstrip(b"\0") for k in range(n)]
+
+    def split_stage_seconds(self):
+        out = np.zeros(len(MS_SPLIT_STAGE_NAMES), np.float64)
+        self._chk(self.L.fhx_ms_split_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
+        return dict(zip(MS_SPLIT_STAGE_NAMES, out.tolist()))
+
+    def split_text(self, index, n_bytes):
+        """the kept lines of one name, verbatim and in file order, each ending in a newline"""
+        buf = np.empty(int(n_bytes), np.uint8)
+        self._chk(self.L.fhx_ms_copy_split(self.h, int(index), buf.ctypes.data_as(ctypes.c_void_p), len(buf)))
         return buf.tobytes()
 
 

@@ -22,7 +22,8 @@
 //                  1 % kept and at 100 %.  A final line without its newline gets one, as awk's print gives it.
 //
 // The subset of each batch is copied to the host and appended.  The UCSC interact track of the same selection (strict, no line
-// skipped) is made by the kernels of fhx_sigtrack.inc, included at the end of this file.  No device-side strtod, no atomics per line: a refused line
+// skipped) is made by the kernels of fhx_sigtrack.inc, the per-chromosome subsets of merge-filter-parallelized.sh by those of
+// fhx_sigsplit.inc, both included at the end of this file.  No device-side strtod, no atomics per line: a refused line
 // costs one atomicMin (line << 8 | reason), so the smallest offending line is reported whatever the launch order.
 #include <hip/hip_runtime.h>
 
@@ -223,6 +224,16 @@ struct fhx_ms : fhx::TextHandle {
     std::vector<char> track;
     int64_t t_lines = 0, t_kept = 0, t_deferred = 0;
     double t_seconds[FHX_MS_TRACK_STAGES] = {0, 0, 0, 0, 0, 0};
+    // the last per-chromosome split (fhx_sigsplit.inc): one entry per name of field 1, in slot order
+    struct SplitName {
+        std::string name;
+        std::vector<char> text;
+        int64_t lines = 0;
+    };
+    std::vector<SplitName> split;
+    int64_t s_lines = 0;
+    double s_seconds[FHX_MS_SPLIT_STAGES] = {0, 0, 0, 0, 0};
+    fhx_ctx* sorter = nullptr;                 // made by the first split call: selections and tracks do not pay for it
 };
 
 namespace {
@@ -239,7 +250,9 @@ extern "C" {
 int fhx_ms_create(int device, fhx_ms** out) { return fhx::text_handle_create(device, out); }
 
 void fhx_ms_destroy(fhx_ms* ms) {
-    fhx::text_handle_destroy(ms, [] {});
+    fhx::text_handle_destroy(ms, [&] {
+        if (ms->sorter) fhx_destroy(ms->sorter);
+    });
 }
 
 const char* fhx_ms_last_error(const fhx_ms* ms) { return ms ? ms->err.c_str() : "null context"; }
@@ -384,3 +397,4 @@ int fhx_ms_copy_subset(const fhx_ms* ms, void* dst, int64_t capacity) {
 }  // extern "C"
 
 #include "fhx_sigtrack.inc"
+#include "fhx_sigsplit.inc"

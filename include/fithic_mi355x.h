@@ -734,6 +734,33 @@ int fhx_ms_copy_track(const fhx_ms* ms, void* dst, int64_t capacity);    /* the 
  * host, 0 when it would defer.  Host only: needs no GPU. */
 int fhx_ms_score_text(const char* field, int32_t len, int32_t certify, char* out, int32_t capacity);
 
+/* ---- the per-chromosome FDR subsets of a significances file (fithic/utils/merge-filter-parallelized.sh:21-25;
+ * csrc/fhx_sigsplit.inc), on the same handle.  The script lists field 1 of EVERY line (`cut -f1 | sort | uniq`, line 1 included) and,
+ * once per listed name c, keeps the rows with `NR != 1 && $1 == c && $3 == c && $7 <= fdr`.  Here one read of the file gives
+ * every subset: the `$7` decision is fhx_ms_select_file's (not strict, line 1 dropped), the names of field 1 are interned on the
+ * device (at most FHX_MS_SPLIT_NAMES), the kept lines are sorted by (name, file offset) and gathered so that each name's lines
+ * reach the host as one run per batch, verbatim and in file order, each ending in a newline.  A name with no kept line (a name
+ * seen only in trans rows or only on line 1) is still listed, with an empty subset.
+ * Taken beyond fhx_ms_select_file's grammar, on every line (on line 1: the rules for token 1 only): token 1 starts in column 0
+ * and is ended by a tab (cut's field 1 and awk's $1 are then the same bytes); tokens 1 and 3 are 1 to 63 bytes of
+ * [A-Za-z0-9_.-] that start with a letter, a digit or `_`; a name that starts with a digit is a decimal integer of at most 15
+ * digits without a leading zero, or holds `_` or a letter other than a-f, x, p in either case (strtod cannot consume it whole) -
+ * so awk's `$1 == c` between two accepted names is byte equality.  Names are returned in no particular order. */
+#define FHX_MS_NAME_TAB 10         /* token 1 does not start in column 0, or is not ended by a tab */
+#define FHX_MS_NAME_BYTES 11       /* token 1 or 3 holds a byte outside [A-Za-z0-9_.-] or starts with `.` or `-` */
+#define FHX_MS_NAME_NUMERIC 12     /* token 1 or 3 starts with a digit and awk would, or might, compare it as a number */
+#define FHX_MS_NAMES 13            /* more than FHX_MS_SPLIT_NAMES distinct names in field 1 (no line number) */
+#define FHX_MS_SPLIT_NAMES 4096
+#define FHX_MS_SPLIT_NAME_BYTES 64 /* per name in fhx_ms_split_names: the name, then zero bytes */
+#define FHX_MS_SPLIT_STAGES 5      /* read + upload, newline scan, names + select, sort + gather, copy out */
+int fhx_ms_split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept,
+                      int32_t* n_names, int32_t* why, int64_t* bad_line);
+/* lines read, names listed, and per name (capacity entries at least, either array may be NULL) its kept lines and their bytes */
+int fhx_ms_split_counts(const fhx_ms* ms, int64_t* n_lines, int32_t* n_names, int64_t* kept_lines, int64_t* kept_bytes, int32_t capacity);
+int fhx_ms_split_names(const fhx_ms* ms, char* dst, int32_t capacity);   /* FHX_MS_SPLIT_NAME_BYTES per name, capacity names */
+int fhx_ms_split_stage_seconds(const fhx_ms* ms, double* seconds);  /* FHX_MS_SPLIT_STAGES host clocks of the last call */
+int fhx_ms_copy_split(const fhx_ms* ms, int32_t index, void* dst, int64_t capacity);   /* the subset of name `index` */
+
 #ifdef __cplusplus
 }
 #endif
