@@ -258,12 +258,25 @@ SYMBOLS = {
     "fhx_ms_split_names": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "fhx_ms_split_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
     "fhx_ms_copy_split": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64]),
+    # Juicer dump text -> contact counts (fithic/utils/createFitHiCContacts-hic_old.sh, createFitHiCContacts-hic.py)
+    "fhx_jc_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "fhx_jc_destroy": (None, [ctypes.c_void_p]),
+    "fhx_jc_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
+    "fhx_jc_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "fhx_jc_convert_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int32,
+                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _I64P, _I32P, _I64P]),
+    "fhx_jc_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P]),
+    "fhx_jc_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
+    "fhx_jc_copy_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
+    "fhx_jc_fetch_rows": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
+    "fhx_jc_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
+    "fhx_jc_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
 }
 
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
 # not recompile K1, K3, the Knight-Ruiz path or the host stages.  Flags are the same for every unit - -ffp-contract=off matters
 # for bit-exactness on the host (FITPACK, lgamma tables) as much as on the device (fhx_bdtrc.hpp).
-SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
+SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_juicer.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
 COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread"]
 LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-lz", "-ldl"]
 OBJ_DIR = os.path.join(CSRC, "_obj")
@@ -1522,3 +1535,64 @@ def ms_score_text(field, certify=False):
     if n < 0:
         raise FhxError(n, "fhx_ms_score_text(%r)" % (field,))
     return out.raw[:n]
+
+
+# ---- Juicer dump text -> contact counts (fhx_jc_*) -------------------------------------------------------------------------
+(JC_OK, JC_BYTES, JC_LONG_LINE, JC_TOKENS, JC_BIN, JC_GRID, JC_RANGE, JC_COUNT, JC_FRACTION, JC_INTERNAL) = range(10)
+JC_STAGE_NAMES = ("read_upload", "newline_scan", "parse", "format", "copy_out")
+
+
+class JcRefused(FhxError):
+    """fhx_jc_convert_file refused the file: why = one of JC_*, line = the smallest offending 1-based line"""
+
+    def __init__(self, code, message, why, line):
+        super().__init__(code, message)
+        self.why, self.line = int(why), int(line)
+
+
+class JcContext(_Handle):
+    """Juicer dump files converted on one GPU (fhx_jc_*): their output text and, in midpoint mode, their rows in HBM.  Raises
+    without the library or a GPU."""
+    PREFIX = "jc"
+    REFUSED = JcRefused
+
+    def reset(self):
+        self._chk(self.L.fhx_jc_reset(self.h))
+
+    def convert_file(self, path, name1, name2, resolution=0, ids=(0, 0), keep_text=True, keep_rows=False):
+        """one dump appended to the handle's text and / or rows -> its number of lines; resolution 0 is verbatim mode.  JcRefused
+        for a file outside the device grammar: the handle is then empty."""
+        n, why, line = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self.L.fhx_jc_convert_file(self.h, os.fsencode(path), name1.encode(), name2.encode(), int(resolution), int(ids[0]), int(ids[1]),
+                                        int(bool(keep_text)), int(bool(keep_rows)), ctypes.byref(n), ctypes.byref(why), ctypes.byref(line))
+        self._chk(rc, why.value, line.value)
+        return n.value
+
+    def counts(self):
+        """lines read, rows kept, bytes of text kept"""
+        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._chk(self.L.fhx_jc_counts(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return dict(lines=a.value, rows=b.value, bytes=c.value)
+
+    def stage_seconds(self):
+        out = np.zeros(len(JC_STAGE_NAMES), np.float64)
+        self._chk(self.L.fhx_jc_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
+        return dict(zip(JC_STAGE_NAMES, out.tolist()))
+
+    def text(self):
+        """the output lines kept so far, in the order of the calls and of the lines"""
+        buf = np.empty(self.counts()["bytes"], np.uint8)
+        self._chk(self.L.fhx_jc_copy_text(self.h, buf.ctypes.data_as(ctypes.c_void_p), len(buf)))
+        return buf.tobytes()
+
+    def fetch_rows(self):
+        """(chr1, mid1, chr2, mid2, count), int32, in the order of the calls and of the lines"""
+        cols = [np.zeros(self.counts()["rows"], np.int32) for _ in range(5)]
+        self._chk(self.L.fhx_jc_fetch_rows(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
+        return cols
+
+    def device_ptrs(self):
+        return [self.L.fhx_jc_device_ptr(self.h, k) or 0 for k in range(5)]
+
+    def stream(self):
+        return self.L.fhx_jc_stream(self.h) or 0

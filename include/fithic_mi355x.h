@@ -761,6 +761,48 @@ int fhx_ms_split_names(const fhx_ms* ms, char* dst, int32_t capacity);   /* FHX_
 int fhx_ms_split_stage_seconds(const fhx_ms* ms, double* seconds);  /* FHX_MS_SPLIT_STAGES host clocks of the last call */
 int fhx_ms_copy_split(const fhx_ms* ms, int32_t index, void* dst, int64_t capacity);   /* the subset of name `index` */
 
+/* ---- Juicer dump text -> Fit-Hi-C contact counts (fithic/utils/createFitHiCContacts-hic_old.sh:6 and
+ * fithic/utils/createFitHiCContacts-hic.py:93; csrc/fhx_juicer.hip).  The input is what `juicer_tools dump` / `straw` prints for
+ * one chromosome pair, `binX binY count` per line, plain or gzipped; it goes through HBM in batches cut at the last newline
+ * (FHX_JC_BATCH_BYTES overrides the batch size of 256 MB; 8192 at least).  Every line gives exactly one output line.
+ *   resolution == 0, VERBATIM mode (the old script): `name1 \t $1 \t name2 \t $2 \t $3 \n` with awk's fields copied as text - split
+ *     at runs of blank and tab, a missing field empty, tokens after the third ignored, a last line without a newline given one.
+ *   resolution >= 1, MIDPOINT mode (the .py): `name1 \t binX+int(R/2) \t name2 \t binY+int(R/2) \t count \n`, the count as Python's
+ *     str() of a whole float (`17`, `17.0` and `017` give `17.0`); the five int32 columns (id1, mid1, id2, mid2, count) are made
+ *     at row = line number.  Grammar: exactly three tokens; the bins 1 to 10 digits without a sign, multiples of R, midpoint at
+ *     most 2^31 - 1; the count `digits` or `digits.` and one or more `0`, at most 15 digits, at most 2^24.
+ * A name is 1 to FHX_JC_NAME_BYTES bytes of [A-Za-z0-9_.-] (FHX_ERR_ARG otherwise).  keep_text appends the output text to the
+ * handle's text, keep_rows (midpoint mode) appends the rows to the handle's columns in HBM: several dumps make one table.
+ * Anything else is refused and the handle is left empty (rows and text of earlier calls included): *why = one of FHX_JC_*, checked
+ * in this order on a line, *bad_line = the smallest offending 1-based line of this file.  Return value: FHX_ERR_UNSUPPORTED. */
+#define FHX_JC_OK 0
+#define FHX_JC_BYTES 1             /* a NUL, another control byte than tab (\r included), DEL, a non-ASCII byte */
+#define FHX_JC_LONG_LINE 2         /* a line of more than 4096 bytes */
+#define FHX_JC_TOKENS 3            /* midpoint mode: not exactly three tokens */
+#define FHX_JC_BIN 4               /* binX or binY is not 1 to 10 digits */
+#define FHX_JC_GRID 5              /* binX or binY is no multiple of the resolution */
+#define FHX_JC_RANGE 6             /* bin + int(R/2) is above 2^31 - 1 */
+#define FHX_JC_COUNT 7             /* the count is no number, has more than 15 digits or is above 2^24 */
+#define FHX_JC_FRACTION 8          /* a fraction, an exponent, a sign, nan or inf: a raw (NONE) dump is expected */
+#define FHX_JC_INTERNAL 9          /* a device-side consistency check failed */
+#define FHX_JC_NAME_BYTES 66       /* `chr` + 63 */
+#define FHX_JC_STAGES 5            /* read + upload, newline scan, parse, format, copy out: summed over the calls since the last reset */
+typedef struct fhx_jc fhx_jc;
+int fhx_jc_create(int device, fhx_jc** out);
+void fhx_jc_destroy(fhx_jc* jc);
+const char* fhx_jc_last_error(const fhx_jc* jc);
+int fhx_jc_reset(fhx_jc* jc);                                      /* drops rows, text and stage clocks */
+int fhx_jc_convert_file(fhx_jc* jc, const char* path, const char* name1, const char* name2, int64_t resolution, int32_t id1, int32_t id2,
+                        int32_t keep_text, int32_t keep_rows, int64_t* n_lines, int32_t* why, int64_t* bad_line);
+int fhx_jc_counts(const fhx_jc* jc, int64_t* n_lines, int64_t* n_rows, int64_t* n_bytes);
+int fhx_jc_stage_seconds(const fhx_jc* jc, double* seconds);
+int fhx_jc_copy_text(const fhx_jc* jc, void* dst, int64_t capacity);      /* the n_bytes kept so far */
+int fhx_jc_fetch_rows(fhx_jc* jc, int32_t* chr1, int32_t* mid1, int32_t* chr2, int32_t* mid2, int32_t* count);   /* n_rows each */
+/* the kept columns in HBM (which = 0..4: chr1, mid1, chr2, mid2, count; NULL without rows) and the stream that wrote them; valid
+ * until the next fhx_jc_convert_file / fhx_jc_reset / fhx_jc_destroy */
+void* fhx_jc_device_ptr(fhx_jc* jc, int32_t which);
+void* fhx_jc_stream(fhx_jc* jc);
+
 #ifdef __cplusplus
 }
 #endif
