@@ -405,8 +405,8 @@ template <int R>
 struct CfState {
     double pm[R], qm[R], p0[R], q0[R];        // pkm2, qkm2, pkm1, qkm1
     double result[R];
-    // lane masks, wave-uniform (SGPR pairs): which lanes are finished (converged or given up - they keep iterating and are
-    // ignored) and which must be recomputed by the caller
+    // lane masks, wave-uniform (SGPR pairs): which lanes are finished (converged or given up - they go on iterating, as copies
+    // of a lane that is not, and are ignored) and which must be recomputed by the caller
     unsigned long long done[R], irregular[R];
 };
 
@@ -414,14 +414,42 @@ __device__ __forceinline__ bool cf_lane_bit(unsigned long long m) {
     return (m >> (threadIdx.x & 63)) & 1ull;
 }
 
+// v of lane `src` (wave-uniform) for the lanes with `take`, the lane's own v for the others
+__device__ __forceinline__ double cf_copy_lane(bool take, double v, int src) {
+    const double w = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
+    return take ? w : v;
+}
+
+// the folded convergence test of cf_swapped_step: true for a lane one of whose e[r], |c2[r]| is not above 2^-600 (by the high
+// words; derivation in cf_swapped_step).  R minima and one compare.
 template <int R>
-__device__ __forceinline__ void cf_swapped_step(CfState<R>& S, const CfRow c, const double (&arg)[R]) {
+__device__ __forceinline__ bool cf_fold_fails(const double (&e)[R], const double (&c2)[R]) {
+    static_assert(R == 1 || R == 2 || R == 4, "one minimum tree per row count");
+    // one asm statement per row count, as in cf_swapped_renorm: the compiler separates asm statements by a wait state each
+    unsigned int m, t;
+    if constexpr (R == 4) {
+        asm("v_min3_f32 %0, %2, %3, %4\n\tv_min3_f32 %1, |%6|, |%7|, |%8|\n\tv_min3_f32 %0, %0, %1, %5\n\tv_min_f32 %0, %0, |%9|"
+            : "=&v"(m), "=&v"(t)
+            : "v"(__double2hiint(e[0])), "v"(__double2hiint(e[1])), "v"(__double2hiint(e[2])), "v"(__double2hiint(e[3])),
+              "v"(__double2hiint(c2[0])), "v"(__double2hiint(c2[1])), "v"(__double2hiint(c2[2])), "v"(__double2hiint(c2[3])));
+    } else if constexpr (R == 2) {
+        asm("v_min3_f32 %0, %1, %2, |%3|\n\tv_min_f32 %0, %0, |%4|"
+            : "=&v"(m)
+            : "v"(__double2hiint(e[0])), "v"(__double2hiint(e[1])), "v"(__double2hiint(c2[0])), "v"(__double2hiint(c2[1])));
+    } else {
+        asm("v_min_f32 %0, %1, |%2|" : "=v"(m) : "v"(__double2hiint(e[0])), "v"(__double2hiint(c2[0])));
+    }
+    (void)t;
+    return !(__builtin_bit_cast(float, m) > __builtin_bit_cast(float, 0x1A700000u));        // high word of 2^-600
+}
+
+template <int R>
+__device__ __forceinline__ void cf_swapped_step(CfState<R>& S, const CfRow c, double (&arg)[R]) {
     // Written stage by stage ACROSS the rows (and across the two divisions of a row, which do not depend on each other): the
     // compiler keeps this order, so every instruction sits 2R (the divisions) or R (the recurrence, the test) instructions
     // behind its producer instead of right behind it.
     double p1[R], q1[R], p2[R], q2[R];
     double na[R], nb[R], ta[R], tb[R];
-    unsigned long long exact[R], any_exact = 0ull;
     // xk_a = -(x*k1*k2)/(k3*k4), xk_b = (x*k5*k6)/(k7*k8): lean_div with the tabulated reciprocals
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -482,23 +510,52 @@ __device__ __forceinline__ void cf_swapped_step(CfState<R>& S, const CfRow c, co
     // c2 must not have lost bits to underflow and p2, q0 must not be zero: |c2| > 2^-600 (values are <= 2^17).  q2 == 0
     // shows up as q0 == 0 one iteration later - or in the caller's final check - and sends the row to the per-lane loop like
     // every other unusual state.
+    //
+    // ONE compare per wave step.  What the loop needs from the test is one bit per wave - does any lane, for any of its R
+    // rows, fail the proof? - and the per-row lane masks only inside the exact block (about 1 % of the wave steps).  So:
+    //   e = fma(-T, |c2|, |d|)   one rounding of the exact |d| - T |c2|: e > 0 IS the premise above (rounding is monotone, a
+    //                            value <= 0 never rounds to one > 0), where fl(T |c2|) had a rounding of its own;
+    //   m = min over the lane's 2R values e[r], |c2[r]|, taken on their HIGH WORDS read as binary32 (cf_swapped_renorm's
+    //       trick: for finite doubles below 2^1017 the high word orders like the double, negative ones included);
+    //   m > hi(2^-600) as binary32, i.e. every e[r] and every |c2[r]| >= 2^-600 (1 + 2^-20): both premises for every row.
+    // A lane that fails sends the wave to the exact block, which first forms the per-row masks with the statements every step
+    // used to run and then decides as before: a false alarm costs time, never a bit.  The other way round, a row that passes here has
+    // |d| > T |c2| exactly; fl(T |c2|) may lie half an ulp above T |c2|, so |d| == fl(T |c2|) passes here and did not pass the
+    // two-rounding compare - the proof above needs the exact premise only, the exact block would have found t >= 3 MACHEP.
+    // That is 5R - 3 instructions (c2, d, e per row; R minima; one compare) where the per-row compares took 5R.
+    // NaN and infinity: v_min*_f32 skips a quiet NaN operand, and the high word of a double infinity or NaN (and of anything
+    // from 2^1017 up) reads as a binary32 NaN, so the folded compare does not see a non-finite e or c2 unless all 2R are.
+    //   * An infinity cannot arise for rows inside cf_swapped_regular: the range proof above (growth <= 4x per iteration,
+    //     renormalised every 8th) keeps every value below 2^17 and every product below 2^34; with finite operands e, c2 and d
+    //     are finite, and without an infinity no NaN is born (inf - inf and 0 * inf are its only sources here).
+    //   * If a NaN did stand in p (or q) it would stay: p1 = p0 - pm * xk and p2 = p1 + p0 * xk are NaN when pm or p0 is, so
+    //     both values of the next state are; ldexp keeps it.  Such a row never converges here.  Either some lane sends the
+    //     wave to the exact block - there the per-row compares are false for it, the window check fails and it is handed back
+    //     at once - or it runs to the cap and cf_swapped_uniform's final check fabs(p0) > 2^-300 && fabs(q0) > 2^-300 is false
+    //     for it: handed back to the per-lane loop either way, as the two-rounding compare would have done at the first NaN.
+    // One compare has no `& ~done[r]` term, so a lane without a live row of its own would send its wave to the exact block at
+    // every remaining step once its state has converged or degenerated.  Such lanes therefore run COPIES of live rows: a
+    // lane that is marked done takes arg and the four recurrence values of the first lane of its slot r that is not done
+    // (v_readlane, in the exact block only) and from then on computes, bit for bit, what that lane computes - it fails the
+    // compare exactly when a live lane does.  Every done lane of the slot is re-seeded whenever one more finishes, because the
+    // lane they copy may be the one that finished.  result[r], done[r] and irregular[r] are not touched, nothing of a done
+    // lane is read again.  A slot with no unfinished lane keeps its state: the block is entered, finds nothing and leaves.
 #pragma unroll
     for (int r = 0; r < R; ++r) na[r] = p2[r] * S.q0[r];                                  // c2
 #pragma unroll
     for (int r = 0; r < R; ++r) nb[r] = __builtin_fma(S.p0[r], q2[r], -na[r]);            // d
 #pragma unroll
-    for (int r = 0; r < R; ++r) ta[r] = kCfLazyT * fabs(na[r]);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const unsigned long long differ = __builtin_amdgcn_ballot_w64(fabs(nb[r]) > ta[r]) & __builtin_amdgcn_ballot_w64(fabs(na[r]) > 0x1p-600);
-        exact[r] = ~(differ | S.done[r]);
-        any_exact |= exact[r];
-    }
-    if (__builtin_expect(any_exact != 0ull, 0)) {                       // wave-uniform branch; Cephes' statements, literally
+    for (int r = 0; r < R; ++r) ta[r] = __builtin_fma(-kCfLazyT, fabs(na[r]), fabs(nb[r]));   // e
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(cf_fold_fails<R>(ta, na)) != 0ull, 0)) {     // wave-uniform branch
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            if (exact[r] == 0ull) continue;                             // wave-uniform
-            const bool mine = cf_lane_bit(exact[r]);
+            // the per-row masks, by the statements every step used to run
+            const double tc = kCfLazyT * fabs(na[r]);
+            const unsigned long long differ = __builtin_amdgcn_ballot_w64(fabs(nb[r]) > tc) & __builtin_amdgcn_ballot_w64(fabs(na[r]) > 0x1p-600);
+            const unsigned long long exact = ~(differ | S.done[r]);
+            if (exact == 0ull) continue;                                // wave-uniform
+            // Cephes' statements, literally
+            const bool mine = cf_lane_bit(exact);
             const bool window = fabs(S.p0[r]) > 0x1p-300 && fabs(S.q0[r]) > 0x1p-300 && fabs(p2[r]) > 0x1p-300 && fabs(q2[r]) > 0x1p-300;
             const bool go = mine && window;
             // inside the window every operand is in lean_div's (2^-300 < |p|, |q| <= 2^17; ans - rr is 0 or >= 2^-370)
@@ -510,6 +567,16 @@ __device__ __forceinline__ void cf_swapped_step(CfState<R>& S, const CfRow c, co
             if (cf_lane_bit(fin)) S.result[r] = rr;
             S.done[r] |= fin | bad;
             S.irregular[r] |= bad;
+            const unsigned long long running = ~S.done[r];
+            if ((fin | bad) != 0ull && running != 0ull) {               // wave-uniform: done lanes become copies of a running one
+                const int src = __builtin_ctzll(running);
+                const bool idle = cf_lane_bit(S.done[r]);
+                arg[r] = cf_copy_lane(idle, arg[r], src);
+                p1[r] = cf_copy_lane(idle, p1[r], src);
+                q1[r] = cf_copy_lane(idle, q1[r], src);
+                p2[r] = cf_copy_lane(idle, p2[r], src);
+                q2[r] = cf_copy_lane(idle, q2[r], src);
+            }
         }
     }
 #pragma unroll
@@ -541,10 +608,12 @@ __device__ __forceinline__ void cf_swapped_renorm(CfState<R>& S) {      // same 
     }
 }
 
-// arg[r] = x of row r; irregular[r]: in = rows this lane does not really have (or that are outside cf_swapped_regular), out =
-// rows that must be recomputed by the per-lane loop; result[r] = Cephes' incbcf value for the other rows
+// arg[r] = x of row r, overwritten (a lane that is done goes on with a copy of a running lane's row, see cf_swapped_step);
+// irregular[r]: in = rows outside cf_swapped_regular, out = rows that must be recomputed by the per-lane loop; result[r] =
+// Cephes' incbcf value for the other rows.  A lane without a row of its own must be given a copy of a row of the same (a, b):
+// to the loop it is a row like any other, and the caller ignores what comes back for it.
 template <int R>
-__device__ __forceinline__ void cf_swapped_uniform(CfRowConstPtr rows, const double (&arg)[R], bool (&irregular)[R], double (&result)[R]) {
+__device__ __forceinline__ void cf_swapped_uniform(CfRowConstPtr rows, double (&arg)[R], bool (&irregular)[R], double (&result)[R]) {
     CfState<R> S;
     unsigned long long all_done = ~0ull;
 #pragma unroll
@@ -556,6 +625,10 @@ __device__ __forceinline__ void cf_swapped_uniform(CfRowConstPtr rows, const dou
         S.result[r] = 1.0;
         S.irregular[r] = __builtin_amdgcn_ballot_w64(irregular[r]);
         S.done[r] = S.irregular[r];
+        // rows irregular on input are done from the start: they run a regular lane's x (if the slot has none they keep theirs -
+        // whatever their values become, the exact block finds no lane of theirs to decide about)
+        const unsigned long long running = ~S.done[r];
+        if (S.done[r] != 0ull && running != 0ull) arg[r] = cf_copy_lane(irregular[r], arg[r], __builtin_ctzll(running));
     }
     static_assert(kCfIters % 8 == 4, "blocks of 8 iterations, then one of 4");
     int i = 0;

@@ -684,7 +684,7 @@ __global__ __launch_bounds__(K2H_THREADS) __attribute__((amdgpu_waves_per_eu(WPE
     // 170 us: dropped.)
     // tasks are handed out by a counter (round 4): with a fixed stride a 1/8 shard of C3 gave 27 % of the waves four tasks and
     // the others three - the launch took 4/3.3 of its share of the full-size one (profiles/history/r04_tl_shard8.txt).  One returning
-    // atomic per 300 x 92 instructions of work.
+    // atomic per 300 x 89 instructions of work.
     const unsigned int n_waves = gridDim.x * (K2H_THREADS / 64);
     // the clock this launch runs at (boxes differ by 4 %: what "the VALU issue floor" is in milliseconds depends on it): one wave
     // leaves s_memtime (shader cycles) and s_memrealtime (constant rate) at its start and its end - stored at once, nothing kept
@@ -711,6 +711,10 @@ __global__ __launch_bounds__(K2H_THREADS) __attribute__((amdgpu_waves_per_eu(WPE
         // bdtrc_count_class<BC_CF_SWAPPED>: incbet_finish(bb, aa, 1 - xx, xx, incbcf(bb, aa, 1 - xx), flag = 1, ...)
         const double fk = (double)c - 1.0;
         const double aa = fk + 1.0, bb = T.n - fk;
+        // a lane behind the bucket's entries (padding) runs a copy of the bucket's last entry: cf_swapped_step tests once per
+        // wave, so every lane has to hold a row that behaves like a live one.  have[r] stays false: nothing of the copy is
+        // stored, counted or handed back.  (first < live: a task starts inside its bucket's entries.)
+        const unsigned int last = live > first ? live - 1u : first;
         QEntry e[R];
         bool have[R], irregular[R];
         double w1[R], cf[R];
@@ -718,17 +722,15 @@ __global__ __launch_bounds__(K2H_THREADS) __attribute__((amdgpu_waves_per_eu(WPE
         for (int r = 0; r < R; ++r) {
             const unsigned int j = first + (unsigned int)r * 64u + (unsigned int)lane;
             have[r] = j < live;
-            e[r].row = 0u;
-            e[r].count = is_inter ? -c : c;
-            e[r].prior = 0.5;
-            if (have[r]) e[r] = sorted[j];
+            e[r] = sorted[have[r] ? j : last];
             w1[r] = 1.0 - e[r].prior;
-            irregular[r] = !have[r] || !dev::cf_swapped_regular(bb, aa, w1[r]);
+            irregular[r] = !dev::cf_swapped_regular(bb, aa, w1[r]);
         }
         const dev::CfRowConstPtr rows = (dev::CfRowConstPtr)(uintptr_t)(tab + (size_t)b * dev::kCfIters);
-        dev::cf_swapped_uniform<R>(rows, w1, irregular, cf);                  // every lane of the wave takes part
+        dev::cf_swapped_uniform<R>(rows, w1, irregular, cf);                  // every lane of the wave takes part; w1 is overwritten
 #pragma unroll
         for (int r = 0; r < R; ++r) {
+            w1[r] = 1.0 - e[r].prior;
             double pv = 0.0;
             const bool mine = have[r] && !irregular[r];
             if (have[r]) {
