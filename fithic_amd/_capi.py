@@ -167,6 +167,11 @@ SYMBOLS = {
                                                       _I32P, _I32P, _I32P, ctypes.c_int64, _I64P, _I64P]),
     "fhx_write_significances_device_range": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.c_int64,
                                                             ctypes.c_int64, ctypes.c_int32, _I64P, _I64P]),
+    # the FDR subset of a pass from its resident columns (csrc/fhx_sigresident.inc)
+    "fhx_significant_select": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64,
+                                              ctypes.c_int32, ctypes.c_int32, _I64P, _I64P, _I64P, _I32P, _I64P]),
+    "fhx_significant_copy_text": (ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_int64]),
+    "fhx_significant_copy_rows": (ctypes.c_int, [_P, _I64P, ctypes.c_int64]),
     "fhx_ingest_contacts_file_slice": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _I64P, _I32P, _I32P, _I32P]),
     "fhx_set_global_rows_range": (ctypes.c_int, [_P, ctypes.c_int64]),
     "fhx_text_part_bounds": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _I64P, _I64P]),
@@ -725,6 +730,31 @@ class Context:
         self._check(self._L.fhx_write_significances_device(self._h, os.fsencode(path), arr_names, len(names), *ptrs, n, ctypes.byref(rows),
                                                            ctypes.byref(nbytes)))
         return rows.value, nbytes.value
+
+    def significant_select(self, names, fdr_text, key_bound, zero_kept, strict=False):
+        """fhx_significant_select: the FDR subset of the pass from its resident columns -> (n_emitted, n_kept, text, rows).  A q
+        outside the grammar raises MsRefused (why, the line the row has in the file the pass writes); a kept row the device
+        formatter does not cover raises FhxError with code FHX_ERR_UNSUPPORTED."""
+        arr_names = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
+        emitted, kept, nbytes = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        why, line = ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self._L.fhx_significant_select(self._h, arr_names, len(names), fdr_text, len(fdr_text), int(key_bound), 1 if zero_kept else 0,
+                                            1 if strict else 0, ctypes.byref(emitted), ctypes.byref(kept), ctypes.byref(nbytes),
+                                            ctypes.byref(why), ctypes.byref(line))
+        if rc != FHX_OK and why.value:
+            raise MsRefused(rc, (self._L.fhx_last_error(self._h) or b"").decode(), why.value, line.value)
+        self._check(rc)
+        return emitted.value, kept.value, self.significant_text(nbytes.value), self.significant_rows(kept.value)
+
+    def significant_text(self, n_bytes):
+        buf = np.empty(max(int(n_bytes), 1), np.uint8)
+        self._check(self._L.fhx_significant_copy_text(self._h, buf.ctypes.data_as(_P), int(n_bytes)))
+        return buf[:int(n_bytes)].tobytes()
+
+    def significant_rows(self, n_kept):
+        rows = np.empty(max(int(n_kept), 1), np.int64)
+        self._check(self._L.fhx_significant_copy_rows(self._h, _ptr(rows, ctypes.c_int64), int(n_kept)))
+        return rows[:int(n_kept)]
 
     def get_array(self, which):
         n = ctypes.c_int64(0)

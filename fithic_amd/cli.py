@@ -51,7 +51,25 @@ def parse_args(argv=None):
                              "counts reaches 2^31. 'reference' (default) narrows it to a C int exactly as scipy.special.bdtrc does under "
                              "fithic.py, so the output is the reference's bit for bit - nan p/q for totals in [2^31, 2^32); 'wide' uses the "
                              "true total. A line on stderr says which ran whenever the two differ")
-    return parser.parse_args(argv)
+    parser.add_argument("--significant", dest="significant", metavar="FDR", default=None,
+                        help="engine option, not in the reference: after the last pass also write <prefix>.fdr_subset.txt.gz, the rows with "
+                             "q-value <= FDR exactly as utils/merge-filter.sh selects them, and <prefix>.merged.txt.gz, its merging of "
+                             "neighbouring contacts (not with -r 0), <prefix> being <lib>.spline_pass<N>[.res<R>]. The rows are chosen from "
+                             "the q-values on the GPU, not from the written file")
+    parser.add_argument("--significant-only", dest="significant_only", action="store_true",
+                        help="engine option, with --significant: write no .significances.txt.gz in any pass (not with --gpus above 1)")
+    args = parser.parse_args(argv)
+    if args.significant_only and args.significant is None:
+        parser.error("--significant-only needs --significant FDR")
+    if args.significant_only and args.gpus > 1:
+        parser.error("--significant-only is not available with --gpus above 1: the sharded run selects from the written file")
+    if args.significant is not None:
+        from . import mergefilter
+        try:
+            mergefilter.fdr_text(args.significant)
+        except ValueError as e:
+            parser.error("--significant: %s" % e)
+    return args
 
 
 def main(argv=None):
@@ -157,6 +175,7 @@ def main(argv=None):
             sys.exit(2)
         F.gpus = args.gpus
         F.totals = args.totals
+        F.significant_only = args.significant_only
         F.logfile = os.path.join(outputPath, libName + ".fithic.log")
 
         (mainDic, observedInterAllCount, observedInterAllSum, observedIntraAllSum, observedIntraInRangeSum) = \
@@ -201,12 +220,15 @@ def main(argv=None):
                 from . import plots
                 plots.compare_Spline_FDR(FDRXinit, FDRYinit, FDRX, FDRY, os.path.join(outputPath, libName + ".spline_FDR_comparison"), str(i))
                 plots.compareFits_Spline(splineXinit, splineYinit, splineX, splineY, os.path.join(outputPath, libName + ".spline_comparison"), str(i))
+        if args.significant is not None:
+            F.write_significant(args.significant, resolution)
         print("=========================")
         print("Fit-Hi-C completed successfully")
         print("\n")
     finally:
         stuck = F.session_stuck()
         F.reset_session()
+        F.significant_only = False
         F.gpus = 1                             # a --gpus N of this call does not outlive it (callers of the stage functions set their own)
         if stuck:
             # --gpus N lost a rank while this process's own rank sat in a collective: that thread can never return, and a normal

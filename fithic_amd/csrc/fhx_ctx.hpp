@@ -415,6 +415,10 @@ struct fhx_ctx {
     hipEvent_t ev_fit_copy = nullptr;           // the last copy out of h_fit_stage
     double *d_p = nullptr, *d_q = nullptr;
     bool have_p = false, have_q = false;
+    bool outliers_folded = false;               // fhx_next_pass has run on this p: the pass is over (fhx_pvalues starts the next one)
+    // the last fhx_significant_select (fhx_sigresident.inc): the kept rows' text and their loaded-row numbers; empty after a refusal
+    std::vector<char> sig_text;
+    std::vector<int64_t> sig_rows;
 
     // sort workspace
     unsigned long long *d_keys[2] = {nullptr, nullptr};

@@ -47,6 +47,73 @@ struct Cols {
 };
 
 // ---- row text ------------------------------------------------------------------------------------------------------
+// The three steps of a row, shared with the selection from resident columns (fhx_sigresident.inc): who the row is, whether the
+// reference's output loop prints it, and its text.
+struct RowId {
+    int c1, c2, m1, m2;
+};
+
+__device__ __forceinline__ RowId row_identity(const Cols& C, int64_t r) {
+    RowId id;
+    if (C.chr1) {
+        id.c1 = C.chr1[r];
+        id.c2 = C.chr2[r];
+        id.m1 = C.mid1[r];
+        id.m2 = C.mid2[r];
+    } else {                                           // invert ingest (k0_slots / nf_finish_rows)
+        const int s1 = C.loc1[r], l2 = C.loc2[r], s2 = l2 < 0 ? ~l2 : l2;
+        id.c1 = C.slot_chr[s1];
+        id.c2 = C.slot_chr[s2];
+        id.m1 = C.slot_mid ? C.slot_mid[s1] : (s1 - C.grid[id.c1].base) * C.res + C.grid[id.c1].off;
+        id.m2 = C.slot_mid ? C.slot_mid[s2] : (s2 - C.grid[id.c2].base) * C.res + C.grid[id.c2].off;
+    }
+    return id;
+}
+
+__device__ __forceinline__ bool row_emitted(const Cols& C, const RowId& id) {
+    if (id.c1 != id.c2) return C.mode == FHX_MODE_ALL || C.mode == FHX_MODE_INTER_ONLY;                       // fithic.py:1197
+    long long d = (long long)id.m1 - (long long)id.m2;
+    d = d < 0 ? -d : d;
+    return (C.mode == FHX_MODE_ALL || C.mode == FHX_MODE_INTRA_ONLY) && d >= C.dist_low && d <= C.dist_up;   // :1205-1207
+}
+
+// the row's text with its newline into buf (288 bytes); its length, or 0 for a row the formatter does not cover
+__device__ __forceinline__ int row_text(const Cols& C, int64_t r, const RowId& id, char* buf) {
+    const int c1 = id.c1, c2 = id.c2;
+    bool ok = c1 >= 0 && c1 < C.n_names && c2 >= 0 && c2 < C.n_names;
+    int n = 0;
+    if (ok) {
+        const int a0 = C.name_off[c1], a1 = C.name_off[c1 + 1], b0 = C.name_off[c2], b1 = C.name_off[c2 + 1];
+        ok = (a1 - a0) <= 24 && (b1 - b0) <= 24;
+        if (ok) {
+            for (int k = a0; k < a1; ++k) buf[n++] = C.names[k];
+            buf[n++] = '\t';
+            n += fmt::put_i64(buf + n, id.m1);
+            buf[n++] = '\t';
+            for (int k = b0; k < b1; ++k) buf[n++] = C.names[k];
+            buf[n++] = '\t';
+            n += fmt::put_i64(buf + n, id.m2);
+            buf[n++] = '\t';
+            n += fmt::put_i64(buf + n, C.count[r]);
+            buf[n++] = '\t';
+            const double vals[4] = {C.p[r], C.q[r], C.b1[r], C.b2[r]};
+            for (int k = 0; k < 4 && ok; ++k) {
+                const int w = fmt::fmt_e6(vals[k], buf + n);
+                ok = w > 0;
+                n += ok ? w : 0;
+                buf[n++] = '\t';
+            }
+            if (ok) {
+                const int w = fmt::fmt_f6(C.expcc[r], buf + n);
+                ok = w > 0 && n + w + 1 < ROW_STRIDE;
+                n += ok ? w : 0;
+                buf[n++] = '\n';
+            }
+        }
+    }
+    return (!ok || n >= ROW_STRIDE) ? 0 : n;
+}
+
 __global__ __launch_bounds__(WG) void em_format(Cols C, unsigned char* __restrict__ rowtext, unsigned char* __restrict__ rowlen,
                                                 unsigned int* __restrict__ wg_len, int* __restrict__ unsupported,
                                                 unsigned long long* __restrict__ rows_emitted) {
@@ -56,65 +123,11 @@ __global__ __launch_bounds__(WG) void em_format(Cols C, unsigned char* __restric
     unsigned char* out = lds + threadIdx.x * LDS_STRIDE;
     int len = 0;
     if (r < C.n_rows) {
-        int c1, c2, m1, m2;
-        if (C.chr1) {
-            c1 = C.chr1[r];
-            c2 = C.chr2[r];
-            m1 = C.mid1[r];
-            m2 = C.mid2[r];
-        } else {                                           // invert ingest (k0_slots / nf_finish_rows)
-            const int s1 = C.loc1[r], l2 = C.loc2[r], s2 = l2 < 0 ? ~l2 : l2;
-            c1 = C.slot_chr[s1];
-            c2 = C.slot_chr[s2];
-            m1 = C.slot_mid ? C.slot_mid[s1] : (s1 - C.grid[c1].base) * C.res + C.grid[c1].off;
-            m2 = C.slot_mid ? C.slot_mid[s2] : (s2 - C.grid[c2].base) * C.res + C.grid[c2].off;
-        }
-        const bool inter = c1 != c2;
-        bool emit;
-        if (inter) {
-            emit = C.mode == FHX_MODE_ALL || C.mode == FHX_MODE_INTER_ONLY;                        // fithic.py:1197
-        } else {
-            long long d = (long long)m1 - (long long)m2;
-            d = d < 0 ? -d : d;
-            emit = (C.mode == FHX_MODE_ALL || C.mode == FHX_MODE_INTRA_ONLY) && d >= C.dist_low && d <= C.dist_up;   // :1205-1207
-        }
-        if (emit) {
-            bool ok = c1 >= 0 && c1 < C.n_names && c2 >= 0 && c2 < C.n_names;
+        const RowId id = row_identity(C, r);
+        if (row_emitted(C, id)) {
             char buf[288];
-            int n = 0;
-            if (ok) {
-                const int a0 = C.name_off[c1], a1 = C.name_off[c1 + 1], b0 = C.name_off[c2], b1 = C.name_off[c2 + 1];
-                ok = (a1 - a0) <= 24 && (b1 - b0) <= 24;
-                if (ok) {
-                    for (int k = a0; k < a1; ++k) buf[n++] = C.names[k];
-                    buf[n++] = '\t';
-                    n += fmt::put_i64(buf + n, m1);
-                    buf[n++] = '\t';
-                    for (int k = b0; k < b1; ++k) buf[n++] = C.names[k];
-                    buf[n++] = '\t';
-                    n += fmt::put_i64(buf + n, m2);
-                    buf[n++] = '\t';
-                    n += fmt::put_i64(buf + n, C.count[r]);
-                    buf[n++] = '\t';
-                    const double vals[4] = {C.p[r], C.q[r], C.b1[r], C.b2[r]};
-                    for (int k = 0; k < 4 && ok; ++k) {
-                        const int w = fmt::fmt_e6(vals[k], buf + n);
-                        ok = w > 0;
-                        n += ok ? w : 0;
-                        buf[n++] = '\t';
-                    }
-                    if (ok) {
-                        const int w = fmt::fmt_f6(C.expcc[r], buf + n);
-                        ok = w > 0 && n + w + 1 < ROW_STRIDE;
-                        n += ok ? w : 0;
-                        buf[n++] = '\n';
-                    }
-                }
-            }
-            if (!ok || n >= ROW_STRIDE) {
-                atomicOr(unsupported, 1);
-                n = 0;
-            }
+            const int n = row_text(C, r, id, buf);
+            if (n == 0) atomicOr(unsupported, 1);
             len = n;
             for (int k = 0; k < n; ++k) out[k] = (unsigned char)buf[k];
         }

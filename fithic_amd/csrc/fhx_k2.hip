@@ -1248,6 +1248,7 @@ static int finish_k2(fhx_ctx* ctx, const K2Plan& plan, const K2Params& P_rows, c
     ctx->ev_folded[1] = false;
     ctx->have_p = true;
     ctx->have_q = false;
+    ctx->outliers_folded = false;
     ctx->n_sorted = -1;
     return FHX_OK;                                                 // (K3's cutoff word says "keep every p": k2_closed)
 }
@@ -1545,6 +1546,7 @@ int fhx_next_pass(fhx_ctx* ctx, int64_t* n_outliers_total) {
         ctx->n_outliers_total += (int64_t)added;
         if (dup != ~0ull) ctx->skip_limit = std::min<int64_t>(ctx->skip_limit, (int64_t)dup);
         ctx->skip_active = true;
+        ctx->outliers_folded = true;
         ctx->pass_no += 1;
         if (n_outliers_total) *n_outliers_total = ctx->n_outliers_total;
         return FHX_OK;
@@ -1563,6 +1565,7 @@ int fhx_next_pass(fhx_ctx* ctx, int64_t* n_outliers_total) {
     ctx->n_outliers_total += (int64_t)added;
     if (dup != ~0ull) ctx->skip_limit = std::min<int64_t>(ctx->skip_limit, (int64_t)dup);
     ctx->skip_active = true;
+    ctx->outliers_folded = true;
     ctx->pass_no += 1;
     if (n_outliers_total) *n_outliers_total = ctx->n_outliers_total;
     return check_fault(ctx);

@@ -1,0 +1,426 @@
+// fhx_sigresident.inc - the FDR subset of a pass taken from its RESIDENT columns (included by fhx_device.hip behind fhx_emit.inc,
+// inside its extern "C" block): what fhx_ms_select_file gives for the file fhx_write_significances_device writes, without the
+// file.  The rows merge-filter.sh drops are never formatted, deflated, inflated or uploaded.
+//
+// The decision is the script's, made on the %e TEXT of q (fhx_sigkey.hpp, shared with ms_select), and the kept rows' text is
+// the writer's (emit::row_identity / row_emitted / row_text, shared with em_format).  On the context's stream:
+//
+//   sr_decide      one loaded row per lane.  The emit predicate; q -> fmt_e6 -> classify -> zero / numeric key / string compare;
+//                  one flag byte per row (not emitted, emitted and dropped, kept); per workgroup the emitted and the kept count.
+//                  A q whose text the classes leave out (nan, inf, a sign, exponent 308) costs one atomicMin (row << 8 | reason).
+//                  fmt_e6 has no text for 2^64 and more: from the first double that prints e+308 on that is the same refusal,
+//                  below it the call is FHX_ERR_UNSUPPORTED as the writer's is.
+//                  Bracket: every normal q below `lo` is kept and every one above `hi` (and below 1e300) dropped unformatted; lo
+//                  and hi are the doubles nearest the %e fields of the key bound and of the key after it, and rounding a double
+//                  to seven digits is monotone, so the bracket decides exactly as the text does.  FHX_SR_NO_BRACKET=1 formats all.
+//   scan_tiles x2  the workgroup's emitted rank and kept rank
+//   sr_rows        the kept rows' numbers compacted, ascending (file order), and their five columns gathered behind them, so
+//                  that k2_extras and the formatter run over the kept rows alone
+//   k2_extras      ExpCC and the two biases of the kept rows
+//   sr_measure     one kept row per lane: the length of its text; per workgroup the bytes
+//   scan_tiles     the workgroup's byte offset
+//   sr_format      256 kept rows per workgroup: each lane writes its row into an LDS window that starts on a 16-byte boundary
+//                  of the output, and the window leaves 16 bytes a lane; only the ragged ends go bytewise.  Every store is
+//                  checked against the scanned total; what a lane wrote is compared with what sr_measure counted.
+}  // extern "C"
+
+#include <cfloat>
+
+#include "fhx_sigkey.hpp"
+
+namespace fhx {
+namespace sigres {
+
+using emit::Cols;
+using emit::RowId;
+
+constexpr int WG = 256;
+constexpr unsigned char NOT_EMITTED = 0, DROPPED = 1, KEPT = 2;
+constexpr unsigned long long NO_BAD_ROW = ~0ull;
+constexpr int WINDOW = WG * emit::ROW_STRIDE + 16;      // the longest round, moved up to 15 bytes into its first 16
+
+struct Words {
+    unsigned long long first_bad;              // smallest (loaded row << 8 | reason)
+    unsigned long long n_emitted, n_kept, n_bytes;      // the three scans' totals
+    unsigned int unsupported;                  // a kept row (or a q) the formatter does not cover
+    unsigned int internal;                     // sr_format wrote another length than sr_measure counted
+};
+
+struct Decision {
+    msd::Fdr fdr;
+    unsigned long long key_bound;
+    int zero_kept, strict, bracket;
+    double lo, hi;
+    double e308;                               // the smallest double %e prints with an exponent of 308
+};
+
+// two counts of a workgroup from one predicate pair, thread 0 stores them
+__device__ __forceinline__ void count_pair(bool a, bool b, unsigned int* out_a, unsigned int* out_b) {
+    __shared__ unsigned int wa[WG / 64], wb[WG / 64];
+    const unsigned long long ma = __ballot(a), mb = __ballot(b);
+    if ((threadIdx.x & 63) == 0) {
+        wa[threadIdx.x >> 6] = (unsigned int)__popcll(ma);
+        wb[threadIdx.x >> 6] = (unsigned int)__popcll(mb);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out_a[blockIdx.x] = wa[0] + wa[1] + wa[2] + wa[3];
+        out_b[blockIdx.x] = wb[0] + wb[1] + wb[2] + wb[3];
+    }
+}
+
+__global__ __launch_bounds__(WG) void sr_decide(Cols C, Decision D, unsigned char* __restrict__ flags, unsigned int* __restrict__ wg_emitted,
+                                                unsigned int* __restrict__ wg_kept, Words* __restrict__ words) {
+    const int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x;
+    unsigned char flag = NOT_EMITTED;
+    if (r < C.n_rows) {
+        const RowId id = emit::row_identity(C, r);
+        if (emit::row_emitted(C, id)) {
+            const double q = C.q[r];
+            const bool plain = q >= DBL_MIN && q < 1e300;                     // a normal double whose exponent field is not 308
+            bool keep = false;
+            int why = 0;
+            if (D.bracket && plain && q < D.lo) keep = true;
+            else if (D.bracket && plain && q > D.hi) keep = false;
+            else {
+                char field[16];                                               // at most -D.DDDDDDe-XXX
+                const int w = fmt::fmt_e6(q, field);
+                if (w <= 0 && q >= D.e308) why = FHX_MS_FIELD;                // fmt_e6 stops at 2^64, but this one's exponent is known
+                else if (w <= 0) atomicOr(&words->unsupported, 1u);           // 2^64 and more: the writer has no text for it either
+                else {
+                    unsigned long long key = 0;
+                    const int cls = msd::classify((const unsigned char*)field, 0, w, &key);
+                    if (cls == 0) why = FHX_MS_FIELD;
+                    else if (cls == 1) keep = D.zero_kept != 0;
+                    else if (cls == 2) keep = key <= D.key_bound;             // the host's bound is the strict one when strict
+                    else {
+                        const int cmp = msd::compare_text((const unsigned char*)field, 0, w, D.fdr);
+                        keep = D.strict ? cmp < 0 : cmp <= 0;
+                    }
+                }
+            }
+            if (why) atomicMin(&words->first_bad, ((unsigned long long)r << 8) | (unsigned long long)why);
+            flag = (keep && !why) ? KEPT : DROPPED;
+        }
+        flags[r] = flag;
+    }
+    count_pair(flag != NOT_EMITTED, flag == KEPT, wg_emitted, wg_kept);
+}
+
+// the kept rows of a workgroup behind its kept rank: row number and the columns the formatter and k2_extras read
+__global__ __launch_bounds__(WG) void sr_rows(const unsigned char* __restrict__ flags, int64_t n_rows, const unsigned long long* __restrict__ kept_off,
+                                              int64_t n_kept, const int32_t* __restrict__ loc1, const int32_t* __restrict__ loc2,
+                                              const int32_t* __restrict__ count, const double* __restrict__ p, const double* __restrict__ q,
+                                              int64_t* __restrict__ rows, int32_t* __restrict__ k_loc1, int32_t* __restrict__ k_loc2,
+                                              int32_t* __restrict__ k_count, double* __restrict__ k_p, double* __restrict__ k_q) {
+    const int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x;
+    const bool kept = r < n_rows && flags[r] == KEPT;
+    unsigned int total;
+    const unsigned int rank = fhxscan::block_exclusive_scan(kept ? 1u : 0u, &total);
+    const int64_t k = (int64_t)kept_off[blockIdx.x] + rank;
+    if (kept && k < n_kept) {
+        rows[k] = r;
+        k_loc1[k] = loc1[r];
+        k_loc2[k] = loc2[r];
+        k_count[k] = count[r];
+        k_p[k] = p[r];
+        k_q[k] = q[r];
+    }
+}
+
+// K = the kept rows as a Cols of their own (identity rebuilt from the gathered slots)
+__global__ __launch_bounds__(WG) void sr_measure(Cols K, unsigned char* __restrict__ rowlen, unsigned int* __restrict__ wg_bytes,
+                                                 Words* __restrict__ words) {
+    const int64_t k = (int64_t)blockIdx.x * WG + threadIdx.x;
+    unsigned int len = 0;
+    if (k < K.n_rows) {
+        char buf[288];
+        len = (unsigned int)emit::row_text(K, k, emit::row_identity(K, k), buf);
+        if (len == 0) atomicOr(&words->unsupported, 1u);
+        rowlen[k] = (unsigned char)len;
+    }
+    unsigned int total;
+    fhxscan::block_exclusive_scan(len, &total);
+    if (threadIdx.x == 0) wg_bytes[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(WG) void sr_format(Cols K, const unsigned char* __restrict__ rowlen, const unsigned long long* __restrict__ wg_off,
+                                                unsigned char* __restrict__ out, int64_t out_bytes, Words* __restrict__ words) {
+    __shared__ __attribute__((aligned(16))) unsigned char window[WINDOW];
+    const int64_t k = (int64_t)blockIdx.x * WG + threadIdx.x;
+    const unsigned int len = k < K.n_rows ? (unsigned int)rowlen[k] : 0u;
+    unsigned int total;
+    const unsigned int pre = fhxscan::block_exclusive_scan(len, &total);
+    const int64_t at = (int64_t)wg_off[blockIdx.x];
+    const unsigned int mis = (unsigned int)(at & 15);                         // the window starts on a 16-byte boundary of the output
+    if (len) {
+        char buf[288];
+        const unsigned int n = (unsigned int)emit::row_text(K, k, emit::row_identity(K, k), buf);
+        if (n != len) atomicOr(&words->internal, 1u);
+        else
+            for (unsigned int j = 0; j < n; ++j) window[mis + pre + j] = (unsigned char)buf[j];     // mis + pre + n <= 15 + 256 * 191
+    }
+    __syncthreads();
+    const unsigned int lo = mis, hi = mis + total;                            // the window's bytes that are output
+    const int64_t g = at - (int64_t)mis;                                      // of the window's first byte: 16 | g
+    for (unsigned int j = threadIdx.x * 16u; j < hi; j += WG * 16u) {
+        if (j >= lo && j + 16u <= hi && g + (int64_t)j + 16 <= out_bytes) {
+            *reinterpret_cast<uint4*>(out + g + j) = *reinterpret_cast<const uint4*>(window + j);
+        } else {
+            for (unsigned int b = j; b < j + 16u; ++b)
+                if (b >= lo && b < hi && g + (int64_t)b < out_bytes) out[g + b] = window[b];
+        }
+    }
+}
+
+// the doubles nearest the %e field of `key` (0: below every numeric field) and of the key after it (none: +inf)
+inline void bracket_of(uint64_t key, double* lo, double* hi) {
+    auto field_value = [](uint64_t k) {
+        char text[32];
+        std::snprintf(text, sizeof(text), "%llu.%06llue%+03d", (unsigned long long)(k % msd::KEY_EXP / 1000000ull),
+                      (unsigned long long)(k % 1000000ull), (int)(k / msd::KEY_EXP) - 308);
+        return std::strtod(text, nullptr);
+    };
+    const uint64_t lowest = 0ull * msd::KEY_EXP + 2225074ull, highest = 615ull * msd::KEY_EXP + 9999999ull;      // e-308 ... e+307
+    if (key < lowest) {
+        *lo = 0.0;
+        *hi = field_value(lowest);
+        return;
+    }
+    *lo = field_value(key);
+    if (key >= highest) {
+        *hi = HUGE_VAL;
+        return;
+    }
+    const uint64_t next = key % msd::KEY_EXP == 9999999ull ? (key / msd::KEY_EXP + 1) * msd::KEY_EXP + 1000000ull : key + 1;
+    *hi = field_value(next);
+}
+
+// the smallest double that C's %e prints with an exponent of 308 (rounding to seven digits is monotone)
+inline double first_e308() {
+    auto is_308 = [](double v) {
+        char text[32];
+        std::snprintf(text, sizeof(text), "%e", v);
+        return std::strstr(text, "e+308") != nullptr;
+    };
+    double v = std::strtod("9.9999995e+307", nullptr);
+    while (is_308(v)) v = std::nextafter(v, 0.0);
+    while (!is_308(v)) v = std::nextafter(v, HUGE_VAL);
+    return v;
+}
+
+}  // namespace sigres
+}  // namespace fhx
+
+namespace {
+
+void drop_significant(fhx_ctx* ctx) {
+    std::vector<char>().swap(ctx->sig_text);
+    std::vector<int64_t>().swap(ctx->sig_rows);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, const char* fdr_text, int32_t fdr_len, uint64_t key_bound,
+                           int32_t zero_kept, int32_t strict, int64_t* n_emitted, int64_t* n_kept, int64_t* n_bytes, int32_t* why,
+                           int64_t* bad_line) {
+    using namespace fhx::sigres;
+    if (!ctx || !chr_names || n_names <= 0 || !fdr_text || !n_emitted || !n_kept || !n_bytes || !why || !bad_line) return FHX_ERR_ARG;
+    *n_emitted = *n_kept = *n_bytes = 0;
+    *why = FHX_MS_OK;
+    *bad_line = 0;
+    drop_significant(ctx);
+    if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
+    if (!ctx->have_p || !ctx->have_q) return fail(ctx, FHX_ERR_ARG, "p and q must have been computed (fhx_pvalues, fhx_bh)");
+    if (ctx->outliers_folded) return fail(ctx, FHX_ERR_ARG, "fhx_next_pass has closed the pass: select before it");
+    if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) {
+        *why = FHX_MS_FDR;
+        return fail(ctx, FHX_ERR_UNSUPPORTED, "the text of fdr must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
+    }
+    if (!ctx->d_loc1 || !ctx->d_slot_chr || (!ctx->nonfixed && !ctx->d_grid) || (ctx->nonfixed && !ctx->d_slot_mid))
+        return fail(ctx, FHX_ERR_ARG, "no resident rows to rebuild the identity columns from");
+    FHX_HIP(hipSetDevice(ctx->device));
+    FHX_HIP(hipStreamSynchronize(ctx->stream));       // K3 is through: had it seen more survivors than it was sized for, say so
+    {
+        const int rc = check_fault(ctx);
+        if (rc != FHX_OK) return rc;
+    }
+    const int64_t n = ctx->n_rows;
+    if (n == 0) return FHX_OK;
+    const bool timing = std::getenv("FHX_TIMING") != nullptr;
+    double seconds[5] = {0, 0, 0, 0, 0};               // decide, rank scans, rows + ExpCC/bias, measure + format, copy out
+    auto t_last = std::chrono::steady_clock::now();
+    auto mark = [&](int stage) {                       // every call site has just synchronised the stream
+        const auto t = std::chrono::steady_clock::now();
+        seconds[stage] += std::chrono::duration<double>(t - t_last).count();
+        t_last = t;
+    };
+    Decision D;
+    std::memset(&D, 0, sizeof(D));
+    std::memcpy(D.fdr.text, fdr_text, (size_t)fdr_len);
+    D.fdr.len = fdr_len;
+    D.key_bound = key_bound;
+    D.zero_kept = zero_kept;
+    D.strict = strict;
+    D.bracket = std::getenv("FHX_SR_NO_BRACKET") ? 0 : 1;
+    bracket_of(key_bound, &D.lo, &D.hi);
+    D.e308 = first_e308();
+
+    std::vector<char> blob;
+    std::vector<int32_t> name_off(n_names + 1, 0);
+    for (int i = 0; i < n_names; ++i) {
+        if (!chr_names[i]) return fail(ctx, FHX_ERR_ARG, "a chromosome name is missing");
+        const size_t l = std::strlen(chr_names[i]);
+        blob.insert(blob.end(), chr_names[i], chr_names[i] + l);
+        name_off[i + 1] = (int32_t)blob.size();
+    }
+    if (blob.empty()) blob.push_back(0);
+
+    const int64_t n_wg = (n + WG - 1) / WG;
+    DeviceScratch G;
+    unsigned char* d_flags = nullptr;
+    unsigned int *d_wg_emitted = nullptr, *d_wg_kept = nullptr;
+    unsigned long long *d_emit_off = nullptr, *d_kept_off = nullptr;
+    Words* d_words = nullptr;
+    char* d_names = nullptr;
+    int32_t* d_name_off = nullptr;
+    FHX_HIP(G.get(&d_flags, (size_t)n));
+    FHX_HIP(G.get(&d_wg_emitted, (size_t)n_wg * 4));
+    FHX_HIP(G.get(&d_wg_kept, (size_t)n_wg * 4));
+    FHX_HIP(G.get(&d_emit_off, (size_t)n_wg * 8));
+    FHX_HIP(G.get(&d_kept_off, (size_t)n_wg * 8));
+    FHX_HIP(G.get(&d_words, sizeof(Words)));
+    FHX_HIP(G.get(&d_names, blob.size()));
+    FHX_HIP(G.get(&d_name_off, name_off.size() * 4));
+    Words words;
+    std::memset(&words, 0, sizeof(words));
+    words.first_bad = NO_BAD_ROW;
+    FHX_HIP(hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(d_names, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(d_name_off, name_off.data(), name_off.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    // every loaded row: identity from the resident slots, q resident; p, the biases and ExpCC are not read by sr_decide
+    Cols C{nullptr, nullptr, nullptr, nullptr, ctx->d_count, ctx->d_loc1, ctx->d_loc2, ctx->d_slot_chr, ctx->nonfixed ? ctx->d_slot_mid : nullptr,
+           ctx->d_grid, (int32_t)ctx->prm.resolution, ctx->d_p, ctx->d_q, nullptr, nullptr, nullptr, d_names, d_name_off, n_names, n,
+           ctx->prm.mode, ctx->prm.dist_low, ctx->prm.dist_up};
+    hipLaunchKernelGGL(sr_decide, dim3((unsigned)n_wg), dim3(WG), 0, ctx->stream, C, D, d_flags, d_wg_emitted, d_wg_kept, d_words);
+    FHX_HIP(hipGetLastError());
+    if (timing) {
+        FHX_HIP(hipStreamSynchronize(ctx->stream));
+        mark(0);
+    }
+    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_emitted, n_wg, d_emit_off,
+                       &d_words->n_emitted);
+    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_kept, n_wg, d_kept_off,
+                       &d_words->n_kept);
+    FHX_HIP(hipGetLastError());
+    FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
+    FHX_HIP(hipStreamSynchronize(ctx->stream));
+    mark(1);
+    if (words.first_bad != NO_BAD_ROW) {
+        // the line the row has in the file the pass writes: the header, then the emitted rows before it
+        const int64_t bad_row = (int64_t)(words.first_bad >> 8), wg = bad_row / WG;
+        unsigned long long before = 0;
+        unsigned char head[WG];
+        FHX_HIP(hipMemcpyAsync(&before, d_emit_off + wg, 8, hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipMemcpyAsync(head, d_flags + wg * WG, (size_t)(bad_row - wg * WG + 1), hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipStreamSynchronize(ctx->stream));
+        for (int64_t k = 0; k < bad_row - wg * WG; ++k) before += head[k] != NOT_EMITTED;
+        *why = (int32_t)(words.first_bad & 0xFFu);
+        *bad_line = 2 + (int64_t)before;
+        return fail(ctx, FHX_ERR_UNSUPPORTED, "line " + std::to_string(*bad_line) + " of the pass's file (loaded row " + std::to_string(bad_row) +
+                                                  ") is outside the device grammar (reason " + std::to_string(*why) + ")");
+    }
+    const char* not_covered = "a row does not fit the device formatter (name longer than 24 bytes, a value of 2^63 or more, or a row of 192 "
+                              "bytes or more): select from the written file";
+    if (words.unsupported) return fail(ctx, FHX_ERR_UNSUPPORTED, not_covered);
+    const int64_t emitted = (int64_t)words.n_emitted, kept = (int64_t)words.n_kept;
+    if (emitted > n || kept > emitted) return fail(ctx, FHX_ERR_INTERNAL, "more kept rows than emitted ones");
+    std::vector<char> text;
+    std::vector<int64_t> rows((size_t)kept);
+    if (kept > 0) {
+        const int64_t k_wg = (kept + WG - 1) / WG;
+        int64_t* d_rows = nullptr;
+        int32_t *d_kloc1 = nullptr, *d_kloc2 = nullptr, *d_kcount = nullptr;
+        double *d_kp = nullptr, *d_kq = nullptr, *d_b1 = nullptr, *d_b2 = nullptr, *d_e = nullptr;
+        unsigned char *d_len = nullptr, *d_out = nullptr;
+        unsigned int* d_wg_bytes = nullptr;
+        unsigned long long* d_wg_off = nullptr;
+        FHX_HIP(G.get(&d_rows, (size_t)kept * 8));
+        FHX_HIP(G.get(&d_kloc1, (size_t)kept * 4));
+        FHX_HIP(G.get(&d_kloc2, (size_t)kept * 4));
+        FHX_HIP(G.get(&d_kcount, (size_t)kept * 4));
+        FHX_HIP(G.get(&d_kp, (size_t)kept * 8));
+        FHX_HIP(G.get(&d_kq, (size_t)kept * 8));
+        FHX_HIP(G.get(&d_b1, (size_t)kept * 8));
+        FHX_HIP(G.get(&d_b2, (size_t)kept * 8));
+        FHX_HIP(G.get(&d_e, (size_t)kept * 8));
+        FHX_HIP(G.get(&d_len, (size_t)kept));
+        FHX_HIP(G.get(&d_wg_bytes, (size_t)k_wg * 4));
+        FHX_HIP(G.get(&d_wg_off, (size_t)k_wg * 8));
+        hipLaunchKernelGGL(sr_rows, dim3((unsigned)n_wg), dim3(WG), 0, ctx->stream, (const unsigned char*)d_flags, n,
+                           (const unsigned long long*)d_kept_off, kept, (const int32_t*)ctx->d_loc1, (const int32_t*)ctx->d_loc2,
+                           (const int32_t*)ctx->d_count, (const double*)ctx->d_p, (const double*)ctx->d_q, d_rows, d_kloc1, d_kloc2, d_kcount, d_kp,
+                           d_kq);
+        // ExpCC and the biases as the writer prints them (fithic.py:1075-1078, :1105-1108), of the kept rows alone
+        K2Params P = make_k2_params(ctx);
+        P.loc1 = d_kloc1;
+        P.loc2 = d_kloc2;
+        P.count = d_kcount;
+        P.n = kept;
+        launch_k2_extras(ctx, P, kept, d_e, d_b1, d_b2);
+        FHX_HIP(hipGetLastError());
+        if (timing) {
+            FHX_HIP(hipStreamSynchronize(ctx->stream));
+            mark(2);
+        }
+        Cols K{nullptr, nullptr, nullptr, nullptr, d_kcount, d_kloc1, d_kloc2, ctx->d_slot_chr, ctx->nonfixed ? ctx->d_slot_mid : nullptr,
+               ctx->d_grid, (int32_t)ctx->prm.resolution, d_kp, d_kq, d_b1, d_b2, d_e, d_names, d_name_off, n_names, kept,
+               ctx->prm.mode, ctx->prm.dist_low, ctx->prm.dist_up};
+        hipLaunchKernelGGL(sr_measure, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, d_len, d_wg_bytes, d_words);
+        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_bytes, k_wg, d_wg_off,
+                           &d_words->n_bytes);
+        FHX_HIP(hipGetLastError());
+        FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipStreamSynchronize(ctx->stream));
+        if (words.unsupported) return fail(ctx, FHX_ERR_UNSUPPORTED, not_covered);
+        const int64_t bytes = (int64_t)words.n_bytes;
+        if (bytes <= 0 || bytes > kept * (int64_t)fhx::emit::ROW_STRIDE) return fail(ctx, FHX_ERR_INTERNAL, "more text than the kept rows can hold");
+        FHX_HIP(G.get(&d_out, (size_t)bytes));
+        hipLaunchKernelGGL(sr_format, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, (const unsigned char*)d_len,
+                           (const unsigned long long*)d_wg_off, d_out, bytes, d_words);
+        FHX_HIP(hipGetLastError());
+        FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipStreamSynchronize(ctx->stream));
+        mark(3);
+        if (words.internal) return fail(ctx, FHX_ERR_INTERNAL, "the formatter wrote another length than it measured");
+        text.resize((size_t)bytes);
+        FHX_HIP(hipMemcpyAsync(text.data(), d_out, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipMemcpyAsync(rows.data(), d_rows, (size_t)kept * 8, hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipStreamSynchronize(ctx->stream));
+        mark(4);
+    }
+    ctx->sig_text.swap(text);
+    ctx->sig_rows.swap(rows);
+    *n_emitted = emitted;
+    *n_kept = kept;
+    *n_bytes = (int64_t)ctx->sig_text.size();
+    if (timing)
+        std::fprintf(stderr, "fhx_significant_select: %lld rows, %lld emitted, %lld kept (%lld bytes): decide %.6f s; rank scans %.6f s; "
+                     "rows + ExpCC/bias %.6f s; measure + format %.6f s; copy out %.6f s\n", (long long)n, (long long)emitted, (long long)kept,
+                     (long long)*n_bytes, seconds[0], seconds[1], seconds[2], seconds[3], seconds[4]);
+    return FHX_OK;
+}
+
+int fhx_significant_copy_text(fhx_ctx* ctx, void* dst, int64_t capacity) {
+    if (!ctx || capacity < (int64_t)ctx->sig_text.size() || (!dst && !ctx->sig_text.empty())) return FHX_ERR_ARG;
+    if (!ctx->sig_text.empty()) std::memcpy(dst, ctx->sig_text.data(), ctx->sig_text.size());
+    return FHX_OK;
+}
+
+int fhx_significant_copy_rows(fhx_ctx* ctx, int64_t* rows, int64_t capacity) {
+    if (!ctx || capacity < (int64_t)ctx->sig_rows.size() || (!rows && !ctx->sig_rows.empty())) return FHX_ERR_ARG;
+    if (!ctx->sig_rows.empty()) std::memcpy(rows, ctx->sig_rows.data(), ctx->sig_rows.size() * sizeof(int64_t));
+    return FHX_OK;
+}

@@ -37,19 +37,12 @@
 
 #include "../../include/fithic_mi355x.h"
 #include "fhx_score.hpp"
+#include "fhx_sigkey.hpp"
 #include "fhx_textupload.hpp"
 
 namespace msd {
 
 using namespace fhxlines;
-
-constexpr unsigned long long KEY_EXP = 10000000ull;      // key = (exponent + 308) * 10^7 + the seven digits
-
-// the threshold as the shell passes it: its bytes for the string class, by value
-struct Fdr {
-    unsigned char text[FHX_MS_FDR_BYTES];
-    int len;
-};
 
 // the words the kernels of one call share
 struct Words {
@@ -66,47 +59,6 @@ __device__ inline bool refused_byte(unsigned int c) { return c < 0x20u ? (c != '
 struct GrammarBytes {                          // scan_text's policy
     static __device__ void check(bool& bad, unsigned int c, const unsigned char*, int64_t, int64_t) { bad |= refused_byte(c); }
 };
-
-__device__ inline bool is_digit(int c) { return c >= '0' && c <= '9'; }
-
-// Field 7 at text[b, b + len): 0 = not the %e shape (or one the classes leave out), 1 = zero, 2 = numeric (*key set), 3 = string.
-__device__ inline int classify(const unsigned char* __restrict__ text, int64_t b, int len, unsigned long long* key) {
-    if (len != 12 && len != 13) return 0;
-    const int d0 = text[b];
-    if (!is_digit(d0) || text[b + 1] != '.' || text[b + 8] != 'e') return 0;
-    unsigned long long mant = (unsigned long long)(d0 - '0');
-    for (int k = 2; k < 8; ++k) {
-        const int c = text[b + k];
-        if (!is_digit(c)) return 0;
-        mant = mant * 10 + (unsigned long long)(c - '0');
-    }
-    const int sign = text[b + 9];
-    if (sign != '+' && sign != '-') return 0;
-    int ex = 0;
-    for (int k = 10; k < len; ++k) {
-        const int c = text[b + k];
-        if (!is_digit(c)) return 0;
-        ex = ex * 10 + (c - '0');
-    }
-    if (mant == 0) return 1;
-    if (d0 == '0') return 0;                                                  // 0.000001e-03: not what %e writes
-    if (sign == '-') ex = -ex;
-    if (ex == 308) return 0;                                                  // numeric up to 1.797693e+308, a string above: left out
-    if (ex > 308) return 3;
-    if (ex < -308 || (ex == -308 && mant < 2225074ull)) return 3;
-    *key = (unsigned long long)(ex + 308) * KEY_EXP + mant;
-    return 2;
-}
-
-// awk's string comparison of the field with the text of fdr: memcmp over the common length, then the lengths
-__device__ inline int compare_text(const unsigned char* __restrict__ text, int64_t b, int len, const Fdr& fdr) {
-    const int common = len < fdr.len ? len : fdr.len;
-    for (int k = 0; k < common; ++k) {
-        const int a = text[b + k], q = fdr.text[k];
-        if (a != q) return a < q ? -1 : 1;
-    }
-    return len < fdr.len ? -1 : (len > fdr.len ? 1 : 0);
-}
 
 // ---- pass 2: keep or drop every line --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WG) void ms_select(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ block_off,

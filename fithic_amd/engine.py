@@ -148,6 +148,26 @@ class Engine:
     def fdr_counts(self):
         return self.ctx.get_array(_capi.A_FDR_COUNTS)
 
+    def significant(self, fdr, names, strict=False, path=None):
+        """The FDR subset of this pass from its resident q (csrc/fhx_sigresident.inc), between run_pass / bh and next_pass:
+        the mergefilter.Selection that mergefilter.select(file, fdr, strict) returns for the file this pass writes - same text,
+        same n_lines (the header counted), same n_kept - without writing it.  `fdr` is text, as the shell passes it; `names` are
+        the chromosome names the writer is given.  A q outside the grammar raises the ValueError mergefilter raises for that file,
+        with the line the row would have in it (`path` only names the file in that message); a kept row the device formatter does
+        not cover raises _capi.FhxError with code FHX_ERR_UNSUPPORTED - select from the written file then."""
+        from . import mergefilter
+        text = mergefilter.fdr_text(fdr)
+        bound = mergefilter.key_bound(text, strict)
+        zero_kept = 0 < float(text) if strict else 0 <= float(text)
+        t0 = time.perf_counter()
+        try:
+            emitted, kept, subset, _ = self.ctx.significant_select(names, text, bound, zero_kept, strict)
+        except _capi.MsRefused as e:
+            if e.why in (_capi.MS_INTERNAL, _capi.MS_FDR):
+                raise
+            raise mergefilter._refusal_at("%s, line %d" % (path or "the significances of this pass", e.line), e.why, "") from None
+        return mergefilter.Selection(subset, emitted + 1, kept, {"significant_select": time.perf_counter() - t0}, self.device)
+
     def next_pass(self):
         """Fold this pass's outliers (p < 1/N) into the skip mask and the outlier-distance multiset."""
         return self.ctx.next_pass()

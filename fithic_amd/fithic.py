@@ -48,6 +48,7 @@ gpus = 1                   # > 1: contact rows sharded over that many GPUs (fith
 # int as scipy does with the reference's Python ints, so the files equal fithic.py's (nan p and q for 2^31 <= total < 2^32);
 # "wide": the true total.  A line on stderr says which ran whenever it matters (engine.totals_notice).
 totals = "reference"
+significant_only = False   # cli --significant-only: fit_Spline writes no .significances.txt.gz (write_significant takes the subset)
 
 
 class _Session:
@@ -70,6 +71,7 @@ class _Session:
         self.pass_started = 0
         self.main_dic = None          # the dict read_Interactions handed out, and what it held then (_main_dic_sig)
         self.main_dic_sig = None
+        self.last_prefix = None       # <outfilename>[.res<R>] of the last fit_Spline
         self.outlier_refs = None      # (outliersline, len, outliersdist, len) as fit_Spline left them: the engine's own lists
 
     def mode(self):
@@ -488,6 +490,63 @@ def calculateProbabilities(mainDic, binStats, resolution, outfilename, observedI
     return [x, y, yerr]
 
 
+def _write_significances(S, name):
+    """<prefix>.significances.txt.gz of the pass the engine holds (fithic/fithic.py:1167-1213)"""
+    eng, con = S.engine, S.contacts
+    mode_id = MODES["All" if allReg else ("interOnly" if interOnly else "intraOnly")]
+    # The GPU formats and deflates the rows from the resident p and q (fhx_write_significances_device); the host writer takes
+    # over for a sharded run (each rank holds a part of the rows), for rows the device formatter does not cover, or on request.
+    on_device = hasattr(eng.ctx, "write_significances_device") and not os.environ.get("FHX_HOST_WRITER")
+    if on_device:
+        try:
+            eng.ctx.write_significances_device(name, S.chroms.names)      # identity columns: the rows resident since ingest
+            S.values = True
+        except _capi.FhxError as e:
+            if e.code != _capi.FHX_ERR_UNSUPPORTED:
+                raise
+            on_device = False
+    if not on_device:
+        v = eng.fetch(p=True, q=True, expcc=True, bias=True)
+        S.values = v
+        _capi.host_write_significances(name, S.chroms.names, con.chr1, con.mid1, con.chr2, con.mid2, con.count, v["p"], v["q"],
+                                       v["b1"], v["b2"], v["expcc"], mode_id, distLowThres, distUpThres)
+
+
+def write_significant(fdr, resolution):
+    """cli --significant FDR, after the last fit_Spline and before anything folds its outliers: <prefix>.fdr_subset.txt.gz (the rows
+    of <prefix>.significances.txt.gz with q <= fdr as merge-filter.sh chooses them) and, on a bin lattice, <prefix>.merged.txt.gz
+    (its CombineNearbyInteraction step), <prefix> being the last pass's <lib>.spline_pass<N>[.res<R>].  The subset comes from the
+    pass's resident q (Engine.significant); a sharded run, or a kept row the device formatter does not cover, takes it from the
+    written file instead (mergefilter.select) - the same bytes either way."""
+    from . import combine, mergefilter
+    S = _S
+    prefix = S.last_prefix
+    name = prefix + ".significances.txt.gz"
+    chosen = None
+    if hasattr(S.engine, "significant"):
+        try:
+            chosen = S.engine.significant(fdr, S.chroms.names, path=name)
+        except _capi.FhxError as e:
+            if e.code != _capi.FHX_ERR_UNSUPPORTED or isinstance(e, _capi.MsRefused):
+                raise
+    if chosen is None:
+        if significant_only:                               # no pass wrote the file: it exists for the selection alone
+            _write_significances(S, name)
+        try:
+            chosen = mergefilter.select(name, fdr, device=device)
+        finally:
+            if significant_only:
+                os.remove(name)
+    print("Writing the %d rows with q <= %s to file %s" % (chosen.n_kept, fdr, prefix + ".fdr_subset.txt.gz"))
+    chosen.write_subset(prefix + ".fdr_subset.txt.gz")
+    if not resolution:
+        print("No merged file: merging nearby contacts needs a bin lattice, and -r 0 has none")
+        return
+    names, rec = chosen.merged(resolution)
+    print("Writing the merged contacts to file %s" % (prefix + ".merged.txt.gz"))
+    combine.write_merged(prefix + ".merged.txt.gz", names, rec, resolution)
+
+
 def fit_Spline(mainDic, x, y, yerr, infilename, outfilename, biasDic, outliersline, outliersdist, observedIntraInRangeSum,
                possibleIntraInRangeCount, possibleInterAllCount, observedInterAllCount, observedIntraAllSum,
                observedInterAllSum, biasLowerBound, biasUpperBound, resolution, passNo):
@@ -518,24 +577,12 @@ def fit_Spline(mainDic, x, y, yerr, infilename, outfilename, biasDic, outliersli
         print("stage: K2 + K3 took %.3f s" % (time.time() - t_stage))
         t_stage = time.time()
     name = outfilename + (".res" + str(resolution) if resolution else "") + ".significances.txt.gz"
-    print("Writing p-values and q-values to file %s" % (outfilename + ".significances.txt"))
-    mode_id = MODES["All" if allReg else ("interOnly" if interOnly else "intraOnly")]
-    # The GPU formats and deflates the rows from the resident p and q (fhx_write_significances_device); the host writer takes
-    # over for a sharded run (each rank holds a part of the rows), for rows the device formatter does not cover, or on request.
-    on_device = hasattr(eng.ctx, "write_significances_device") and not os.environ.get("FHX_HOST_WRITER")
-    if on_device:
-        try:
-            eng.ctx.write_significances_device(name, S.chroms.names)      # identity columns: the rows resident since ingest
-            S.values = True
-        except _capi.FhxError as e:
-            if e.code != _capi.FHX_ERR_UNSUPPORTED:
-                raise
-            on_device = False
-    if not on_device:
-        v = eng.fetch(p=True, q=True, expcc=True, bias=True)
-        S.values = v
-        _capi.host_write_significances(name, S.chroms.names, con.chr1, con.mid1, con.chr2, con.mid2, con.count, v["p"], v["q"],
-                                       v["b1"], v["b2"], v["expcc"], mode_id, distLowThres, distUpThres)
+    S.last_prefix = outfilename + (".res" + str(resolution) if resolution else "")
+    if significant_only:                                    # cli --significant-only: the subset is taken from the resident q
+        S.values = True
+    else:
+        print("Writing p-values and q-values to file %s" % (outfilename + ".significances.txt"))
+        _write_significances(S, name)
     if os.environ.get("FHX_TIMING"):
         print("stage: format + deflate + write took %.3f s" % (time.time() - t_stage))
     t_stage = time.time()

@@ -102,15 +102,20 @@ def _refusal(path, e):
     """the exception a refused file is reported with (module docstring, `Known deviations`)"""
     if e.why in (_capi.MS_INTERNAL, _capi.MS_FDR):
         return e
-    where = "%s, line %d" % (path, e.line)
     with open(path, "rb") as f:
         gzipped = f.read(2) == b"\x1f\x8b"
     text = _line_of(path, e.line).decode("latin-1") if not gzipped else ""
-    if e.why == _capi.MS_BYTES:
+    return _refusal_at("%s, line %d" % (path, e.line), e.why, text)
+
+
+def _refusal_at(where, why, text):
+    """the ValueError for reason `why` at `where` ("<file>, line <n>"), `text` being the line when it is at hand ("" for a gzipped
+    file and for a line that was never written: Engine.significant)"""
+    if why == _capi.MS_BYTES:
         return ValueError("%s: a NUL, a non-ASCII byte or a control byte other than tab and newline (\\r is one): %r" % (where, text[:80]))
-    if e.why == _capi.MS_LONG_LINE:
+    if why == _capi.MS_LONG_LINE:
         return ValueError("%s: a line of more than 4096 bytes" % where + _ACCEPTS)
-    if e.why == _capi.MS_TOKENS:
+    if why == _capi.MS_TOKENS:
         return ValueError("%s: %d token(s) where at least 7 are expected (chr1 mid1 chr2 mid2 count p q): %r"
                           % (where, len(text.split()), text[:80]) + _ACCEPTS)
     return ValueError("%s: field 7 is not written as %%e writes a non-negative finite double (D.DDDDDDe[+-]XX), or its exponent "

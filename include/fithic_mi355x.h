@@ -522,6 +522,22 @@ int fhx_write_significances_device(fhx_ctx* ctx, const char* path, const char* c
  * file they hold; concatenated in file order the pieces are the reference's file (fithic/fithic.py:1167-1219). */
 int fhx_write_significances_device_range(fhx_ctx* ctx, const char* path, const char* const* chr_names, int32_t n_names, int64_t row_begin,
                                          int64_t row_end, int32_t with_header, int64_t* rows_written, int64_t* bytes_written);
+/* The FDR subset of the pass taken from its resident columns: the lines fhx_ms_select_file (below) keeps of the file
+ * fhx_write_significances_device writes - the same bytes, or the same refusal - without that file.  Every loaded row gets the
+ * writer's emit predicate and merge-filter.sh's decision on the %e text of its q (zero / numeric key <= key_bound / string
+ * compare with fdr_text; key_bound, zero_kept and strict as for fhx_ms_select_file, whose line 1 is the header and no candidate);
+ * only the kept rows are formatted.  Valid after fhx_bh of a pass and before fhx_next_pass (FHX_ERR_ARG otherwise).
+ *   *n_emitted  rows the writer would print (the file has *n_emitted + 1 lines); *n_kept, *n_bytes: the subset.
+ * Refused, nothing retrievable: an emitted row whose q is nan, inf, negative (-0.0 too) or prints an exponent of 308 -
+ * FHX_ERR_UNSUPPORTED, *why = FHX_MS_FIELD, *bad_line = the line the smallest such row has in the written file (2 + the emitted
+ * rows before it); a KEPT row the device formatter does not cover (a name longer than 24 bytes, a row of 192 bytes or more) -
+ * FHX_ERR_UNSUPPORTED with *why = 0: select from the written file instead.  FHX_SR_NO_BRACKET=1 formats every emitted q instead of
+ * deciding normal doubles outside [lo, hi] by value (the same subset; measurements and tests). */
+int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, const char* fdr_text, int32_t fdr_len,
+                           uint64_t key_bound, int32_t zero_kept, int32_t strict, int64_t* n_emitted, int64_t* n_kept, int64_t* n_bytes,
+                           int32_t* why, int64_t* bad_line);
+int fhx_significant_copy_text(fhx_ctx* ctx, void* dst, int64_t capacity);     /* the n_bytes of the last selection */
+int fhx_significant_copy_rows(fhx_ctx* ctx, int64_t* rows, int64_t capacity); /* loaded-row numbers of the kept rows, ascending */
 
 /* ---- Knight-Ruiz bias vectors (fithic/utils/HiCKRy.py; SURVEY 8f rank 4, the step before Fit-Hi-C) --------------------
  * One fhx_kr per GPU, independent of fhx_ctx.  Call order: load_loci -> load_pairs -> [remove_sparse] -> balance -> bias.
