@@ -172,6 +172,15 @@ SYMBOLS = {
                                               ctypes.c_int32, ctypes.c_int32, _I64P, _I64P, _I64P, _I32P, _I64P]),
     "fhx_significant_copy_text": (ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_int64]),
     "fhx_significant_copy_rows": (ctypes.c_int, [_P, _I64P, ctypes.c_int64]),
+    # the interact track and the per-chromosome subsets from the same columns (csrc/fhx_sigresident_track.inc, fhx_sigresident_split.inc)
+    "fhx_significant_track": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64,
+                                             ctypes.c_int32, _I64P, _I64P, _I64P, _I64P, _I32P, _I64P]),
+    "fhx_significant_copy_track": (ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_int64]),
+    "fhx_significant_split": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64,
+                                             ctypes.c_int32, _I64P, _I32P, _I32P, _I64P]),
+    "fhx_significant_split_counts": (ctypes.c_int, [_P, _I64P, _I64P, ctypes.c_int32]),
+    "fhx_significant_split_names": (ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_int32]),
+    "fhx_significant_copy_split": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64]),
     "fhx_ingest_contacts_file_slice": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _I64P, _I32P, _I32P, _I32P]),
     "fhx_set_global_rows_range": (ctypes.c_int, [_P, ctypes.c_int64]),
     "fhx_text_part_bounds": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.c_int32, _I64P, _I64P]),
@@ -755,6 +764,53 @@ class Context:
         rows = np.empty(max(int(n_kept), 1), np.int64)
         self._check(self._L.fhx_significant_copy_rows(self._h, _ptr(rows, ctypes.c_int64), int(n_kept)))
         return rows[:int(n_kept)]
+
+    def significant_track(self, names, fdr_text, key_bound, zero_kept):
+        """fhx_significant_track: the interact track of the pass from its resident columns -> (n_emitted, n_kept, n_deferred, text).
+        Refusals as for significant_select, plus MS_MIDPOINT and MS_NAME on any emitted row."""
+        arr_names = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
+        emitted, kept, deferred, nbytes = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        why, line = ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self._L.fhx_significant_track(self._h, arr_names, len(names), fdr_text, len(fdr_text), int(key_bound), 1 if zero_kept else 0,
+                                           ctypes.byref(emitted), ctypes.byref(kept), ctypes.byref(deferred), ctypes.byref(nbytes),
+                                           ctypes.byref(why), ctypes.byref(line))
+        if rc != FHX_OK and why.value:
+            raise MsRefused(rc, (self._L.fhx_last_error(self._h) or b"").decode(), why.value, line.value)
+        self._check(rc)
+        return emitted.value, kept.value, deferred.value, self.significant_track_text(nbytes.value)
+
+    def significant_track_text(self, n_bytes):
+        buf = np.empty(max(int(n_bytes), 1), np.uint8)
+        self._check(self._L.fhx_significant_copy_track(self._h, buf.ctypes.data_as(_P), int(n_bytes)))
+        return buf[:int(n_bytes)].tobytes()
+
+    def significant_split(self, names, fdr_text, key_bound, zero_kept):
+        """fhx_significant_split: the per-chromosome FDR subsets of the pass from its resident columns ->
+        (n_emitted, [(name, kept rows, text)] in bytewise order of the names).  Refusals as for significant_select, plus the name
+        rules on any emitted row and MS_NAMES."""
+        arr_names = (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
+        emitted, listed = ctypes.c_int64(0), ctypes.c_int32(0)
+        why, line = ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self._L.fhx_significant_split(self._h, arr_names, len(names), fdr_text, len(fdr_text), int(key_bound), 1 if zero_kept else 0,
+                                           ctypes.byref(emitted), ctypes.byref(listed), ctypes.byref(why), ctypes.byref(line))
+        if rc != FHX_OK and why.value:
+            raise MsRefused(rc, (self._L.fhx_last_error(self._h) or b"").decode(), why.value, line.value)
+        self._check(rc)
+        return emitted.value, self.significant_split_parts(listed.value)
+
+    def significant_split_parts(self, n_listed):
+        n = int(n_listed)
+        kept, nbytes = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        self._check(self._L.fhx_significant_split_counts(self._h, _ptr(kept, ctypes.c_int64), _ptr(nbytes, ctypes.c_int64), n))
+        raw = np.zeros(max(n, 1) * MS_SPLIT_NAME_BYTES, np.uint8)
+        self._check(self._L.fhx_significant_split_names(self._h, raw.ctypes.data_as(_P), n))
+        raw = raw.tobytes()
+        parts = []
+        for k in range(n):
+            buf = np.empty(max(int(nbytes[k]), 1), np.uint8)
+            self._check(self._L.fhx_significant_copy_split(self._h, k, buf.ctypes.data_as(_P), int(nbytes[k])))
+            parts.append((raw[k * MS_SPLIT_NAME_BYTES:(k + 1) * MS_SPLIT_NAME_BYTES].rstrip(b"\0"), int(kept[k]), buf[:int(nbytes[k])].tobytes()))
+        return parts
 
     def get_array(self, which):
         n = ctypes.c_int64(0)

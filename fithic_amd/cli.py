@@ -58,9 +58,20 @@ def parse_args(argv=None):
                              "the q-values on the GPU, not from the written file")
     parser.add_argument("--significant-only", dest="significant_only", action="store_true",
                         help="engine option, with --significant: write no .significances.txt.gz in any pass (not with --gpus above 1)")
+    parser.add_argument("--significant-track", dest="significant_track", action="store_true",
+                        help="engine option, with --significant: also write <prefix>.interact.txt, the UCSC interact track of the rows "
+                             "with q-value < FDR exactly as utils/visualize-UCSC.sh makes it, from the q-values on the GPU")
+    parser.add_argument("--significant-split", dest="significant_split", action="store_true",
+                        help="engine option, with --significant: also write the tree <prefix>.fdr_split/<chr>/ of "
+                             "utils/merge-filter-parallelized.sh - per chromosome its subset, its job file and (not with -r 0) its "
+                             "postmerged file - from the q-values on the GPU")
     args = parser.parse_args(argv)
     if args.significant_only and args.significant is None:
         parser.error("--significant-only needs --significant FDR")
+    if args.significant_track and args.significant is None:
+        parser.error("--significant-track needs --significant FDR")
+    if args.significant_split and args.significant is None:
+        parser.error("--significant-split needs --significant FDR")
     if args.significant_only and args.gpus > 1:
         parser.error("--significant-only is not available with --gpus above 1: the sharded run selects from the written file")
     if args.significant is not None:
@@ -221,7 +232,7 @@ def main(argv=None):
                 plots.compare_Spline_FDR(FDRXinit, FDRYinit, FDRX, FDRY, os.path.join(outputPath, libName + ".spline_FDR_comparison"), str(i))
                 plots.compareFits_Spline(splineXinit, splineYinit, splineX, splineY, os.path.join(outputPath, libName + ".spline_comparison"), str(i))
         if args.significant is not None:
-            F.write_significant(args.significant, resolution)
+            F.write_significant(args.significant, resolution, track=args.significant_track, split=args.significant_split)
         print("=========================")
         print("Fit-Hi-C completed successfully")
         print("\n")

@@ -419,6 +419,16 @@ struct fhx_ctx {
     // the last fhx_significant_select (fhx_sigresident.inc): the kept rows' text and their loaded-row numbers; empty after a refusal
     std::vector<char> sig_text;
     std::vector<int64_t> sig_rows;
+    // the last fhx_significant_split (fhx_sigresident_split.inc): one buffer, and per listed name (bytewise order) its stretch of it;
+    // empty after a refusal.  sig_sorter: the sort context the first split makes
+    struct SigRun {
+        std::string name;
+        int64_t offset = 0, bytes = 0, rows = 0;
+    };
+    std::vector<char> sig_split_text;
+    std::vector<SigRun> sig_split;
+    fhx_ctx* sig_sorter = nullptr;
+    std::vector<char> sig_track;                // the last fhx_significant_track (fhx_sigresident_track.inc): the whole file; empty after a refusal
 
     // sort workspace
     unsigned long long *d_keys[2] = {nullptr, nullptr};

@@ -52,6 +52,8 @@ int fhx_warmup(int device) {
 
 void fhx_destroy(fhx_ctx* ctx) {
     if (!ctx) return;
+    if (ctx->sig_sorter) fhx_destroy(ctx->sig_sorter);
+    ctx->sig_sorter = nullptr;
     (void)fhx_comm_destroy(ctx);
     if (ctx->device >= 0) {
         (void)hipSetDevice(ctx->device);
@@ -668,6 +670,8 @@ int fhx_kernel_events_dropped(fhx_ctx* ctx, int64_t* dropped4) {
 #include "fhx_dist.inc"
 #include "fhx_emit.inc"
 #include "fhx_sigresident.inc"
+#include "fhx_sigresident_track.inc"
+#include "fhx_sigresident_split.inc"
 #include "fhx_inflate.inc"
 #include "fhx_textlines.hpp"
 #include "fhx_ingest.inc"

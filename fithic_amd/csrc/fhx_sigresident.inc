@@ -22,11 +22,16 @@
 //   sr_format      256 kept rows per workgroup: each lane writes its row into an LDS window that starts on a 16-byte boundary
 //                  of the output, and the window leaves 16 bytes a lane; only the ragged ends go bytewise.  Every store is
 //                  checked against the scanned total; what a lane wrote is compared with what sr_measure counted.
+//
+// The same front - the state rules, sr_decide, the two rank scans, the refusal with its line, sr_rows - serves the interact track
+// (fhx_sigresident_track.inc) and the per-chromosome subsets (fhx_sigresident_split.inc): sr_decide is a template over the view,
+// and decide_rows<VIEW> / gather_kept below are what the three C calls share.
 }  // extern "C"
 
 #include <cfloat>
 
 #include "fhx_sigkey.hpp"
+#include "fhx_trackline.hpp"
 
 namespace fhx {
 namespace sigres {
@@ -42,6 +47,7 @@ constexpr int WINDOW = WG * emit::ROW_STRIDE + 16;      // the longest round, mo
 struct Words {
     unsigned long long first_bad;              // smallest (loaded row << 8 | reason)
     unsigned long long n_emitted, n_kept, n_bytes;      // the three scans' totals
+    unsigned long long n_deferred;             // the track's fourth: kept rows whose score the host writes
     unsigned int unsupported;                  // a kept row (or a q) the formatter does not cover
     unsigned int internal;                     // sr_format wrote another length than sr_measure counted
 };
@@ -69,10 +75,29 @@ __device__ __forceinline__ void count_pair(bool a, bool b, unsigned int* out_a, 
     }
 }
 
+// bytes of chromosome c's name (0 for an id the names do not cover: row_text refuses that row)
+__device__ __forceinline__ int name_bytes(const Cols& C, int c) { return c >= 0 && c < C.n_names ? C.name_off[c + 1] - C.name_off[c] : 0; }
+
+// What the decision is for.  SUBSET: merge-filter.sh's, and nothing else.
+// TRACK: the rules the track's file route applies to every parsed line beyond field 7 - both midpoints 1 to 9 digits, both names
+// at most 63 bytes - hold for every emitted row, kept or not, behind the same word and in trackline::refusal's order (field 7
+// first: fhx_sigtrack.inc, ut_select, `why = refusal(cls, ...)`).
+// SPLIT: the name rules of the per-chromosome split hold for both names of every emitted row, looked up per chromosome id in the
+// table the host made with namerule::name_grammar, and they come BEFORE field 7 (fhx_sigsplit.inc, mp_select: name_grammar of
+// token 1, of token 3, then classify); a row is kept only when it is cis (`$1 == c && $3 == c`); every emitted row marks its
+// first chromosome as listed (`cut -f1`) with a plain store of the same value, skipped where the lane before holds the same id.
+enum View { SUBSET = 0, TRACK = 1, SPLIT = 2 };
+struct SplitTables {
+    const unsigned char* name_why;             // per chromosome id: 0 or the reason its name is refused for
+    unsigned char* listed;                     // per chromosome id: set when an emitted row has it as its first chromosome
+};
+
+template <int VIEW>
 __global__ __launch_bounds__(WG) void sr_decide(Cols C, Decision D, unsigned char* __restrict__ flags, unsigned int* __restrict__ wg_emitted,
-                                                unsigned int* __restrict__ wg_kept, Words* __restrict__ words) {
+                                                unsigned int* __restrict__ wg_kept, Words* __restrict__ words, SplitTables S) {
     const int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x;
     unsigned char flag = NOT_EMITTED;
+    int listed_id = -1;
     if (r < C.n_rows) {
         const RowId id = emit::row_identity(C, r);
         if (emit::row_emitted(C, id)) {
@@ -99,10 +124,24 @@ __global__ __launch_bounds__(WG) void sr_decide(Cols C, Decision D, unsigned cha
                     }
                 }
             }
+            if constexpr (VIEW == TRACK)
+                why = trackline::refusal(why ? 0 : 2, trackline::midpoint_ok(id.m1) && trackline::midpoint_ok(id.m2), name_bytes(C, id.c1),
+                                         name_bytes(C, id.c2));
+            if constexpr (VIEW == SPLIT) {
+                const bool known = id.c1 >= 0 && id.c1 < C.n_names && id.c2 >= 0 && id.c2 < C.n_names;
+                const int name_why = !known ? FHX_MS_INTERNAL : (S.name_why[id.c1] ? S.name_why[id.c1] : S.name_why[id.c2]);
+                if (name_why) why = name_why;
+                keep = keep && id.c1 == id.c2;
+                if (known) listed_id = id.c1;
+            }
             if (why) atomicMin(&words->first_bad, ((unsigned long long)r << 8) | (unsigned long long)why);
             flag = (keep && !why) ? KEPT : DROPPED;
         }
         flags[r] = flag;
+    }
+    if constexpr (VIEW == SPLIT) {
+        const int before = __shfl_up(listed_id, 1, 64);
+        if (listed_id >= 0 && ((threadIdx.x & 63) == 0 || before != listed_id)) S.listed[listed_id] = 1;
     }
     count_pair(flag != NOT_EMITTED, flag == KEPT, wg_emitted, wg_kept);
 }
@@ -144,6 +183,22 @@ __global__ __launch_bounds__(WG) void sr_measure(Cols K, unsigned char* __restri
     if (threadIdx.x == 0) wg_bytes[blockIdx.x] = total;
 }
 
+// A workgroup's text out of its LDS window, whose byte `mis` is byte `at` of the output (mis = at & 15, so the window starts on a
+// 16-byte boundary of the output): one 16-byte store per lane, the ragged ends bytewise, nothing at or past out_bytes
+__device__ __forceinline__ void window_out(const unsigned char* window, unsigned int mis, unsigned int total, int64_t at,
+                                           unsigned char* __restrict__ out, int64_t out_bytes) {
+    const unsigned int lo = mis, hi = mis + total;                            // the window's bytes that are output
+    const int64_t g = at - (int64_t)mis;                                      // of the window's first byte: 16 | g
+    for (unsigned int j = threadIdx.x * 16u; j < hi; j += WG * 16u) {
+        if (j >= lo && j + 16u <= hi && g + (int64_t)j + 16 <= out_bytes) {
+            *reinterpret_cast<uint4*>(out + g + j) = *reinterpret_cast<const uint4*>(window + j);
+        } else {
+            for (unsigned int b = j; b < j + 16u; ++b)
+                if (b >= lo && b < hi && g + (int64_t)b < out_bytes) out[g + b] = window[b];
+        }
+    }
+}
+
 __global__ __launch_bounds__(WG) void sr_format(Cols K, const unsigned char* __restrict__ rowlen, const unsigned long long* __restrict__ wg_off,
                                                 unsigned char* __restrict__ out, int64_t out_bytes, Words* __restrict__ words) {
     __shared__ __attribute__((aligned(16))) unsigned char window[WINDOW];
@@ -161,16 +216,7 @@ __global__ __launch_bounds__(WG) void sr_format(Cols K, const unsigned char* __r
             for (unsigned int j = 0; j < n; ++j) window[mis + pre + j] = (unsigned char)buf[j];     // mis + pre + n <= 15 + 256 * 191
     }
     __syncthreads();
-    const unsigned int lo = mis, hi = mis + total;                            // the window's bytes that are output
-    const int64_t g = at - (int64_t)mis;                                      // of the window's first byte: 16 | g
-    for (unsigned int j = threadIdx.x * 16u; j < hi; j += WG * 16u) {
-        if (j >= lo && j + 16u <= hi && g + (int64_t)j + 16 <= out_bytes) {
-            *reinterpret_cast<uint4*>(out + g + j) = *reinterpret_cast<const uint4*>(window + j);
-        } else {
-            for (unsigned int b = j; b < j + 16u; ++b)
-                if (b >= lo && b < hi && g + (int64_t)b < out_bytes) out[g + b] = window[b];
-        }
-    }
+    window_out(window, mis, total, at, out, out_bytes);
 }
 
 // the doubles nearest the %e field of `key` (0: below every numeric field) and of the key after it (none: +inf)
@@ -219,19 +265,49 @@ void drop_significant(fhx_ctx* ctx) {
     std::vector<int64_t>().swap(ctx->sig_rows);
 }
 
-}  // namespace
+const char* const kNotCovered = "a row does not fit the device formatter (name longer than 24 bytes, a value of 2^63 or more, or a row of 192 "
+                                "bytes or more): select from the written file";
 
-extern "C" {
+// host clocks of one call's stages; every mark() follows a synchronisation of the stream
+struct StageSeconds {
+    double s[6] = {0, 0, 0, 0, 0, 0};
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    void mark(int stage) {
+        const auto t = std::chrono::steady_clock::now();
+        s[stage] += std::chrono::duration<double>(t - last).count();
+        last = t;
+    }
+};
 
-int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, const char* fdr_text, int32_t fdr_len, uint64_t key_bound,
-                           int32_t zero_kept, int32_t strict, int64_t* n_emitted, int64_t* n_kept, int64_t* n_bytes, int32_t* why,
-                           int64_t* bad_line) {
+// What one decision over the loaded rows leaves on the device (sr_decide and the two rank scans), for the subset and for the
+// track; G owns every block until the call returns.
+struct Decided {
+    DeviceScratch G;
+    fhx::sigres::Words words;
+    fhx::sigres::Words* d_words = nullptr;
+    unsigned char* d_flags = nullptr;
+    unsigned long long* d_kept_off = nullptr;
+    char* d_names = nullptr;
+    int32_t* d_name_off = nullptr;
+    unsigned char* d_listed = nullptr;         // SPLIT: one byte per chromosome id
+    int64_t n = 0, n_wg = 0, emitted = 0, kept = 0;
+};
+
+// The kept rows compacted in file order with the columns behind them (sr_rows)
+struct KeptRows {
+    int64_t* d_rows = nullptr;
+    int32_t *d_loc1 = nullptr, *d_loc2 = nullptr, *d_count = nullptr;
+    double *d_p = nullptr, *d_q = nullptr;
+};
+
+// The state rules, the decision and its refusals, shared by fhx_significant_select and fhx_significant_track (TRACK: the track's
+// rules for midpoints and names on every emitted row; SPLIT: `name_why` holds the reason per chromosome id, and F.d_listed says
+// afterwards which ids the file lists).  F.n == 0: the context holds no rows and nothing was launched.
+template <int VIEW>
+int decide_rows(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, const char* fdr_text, int32_t fdr_len, uint64_t key_bound,
+                int32_t zero_kept, int32_t strict, int32_t* why, int64_t* bad_line, bool timing, Decided& F, StageSeconds& T,
+                const std::vector<unsigned char>* name_why = nullptr) {
     using namespace fhx::sigres;
-    if (!ctx || !chr_names || n_names <= 0 || !fdr_text || !n_emitted || !n_kept || !n_bytes || !why || !bad_line) return FHX_ERR_ARG;
-    *n_emitted = *n_kept = *n_bytes = 0;
-    *why = FHX_MS_OK;
-    *bad_line = 0;
-    drop_significant(ctx);
     if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
     if (!ctx->have_p || !ctx->have_q) return fail(ctx, FHX_ERR_ARG, "p and q must have been computed (fhx_pvalues, fhx_bh)");
     if (ctx->outliers_folded) return fail(ctx, FHX_ERR_ARG, "fhx_next_pass has closed the pass: select before it");
@@ -248,15 +324,9 @@ int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n
         if (rc != FHX_OK) return rc;
     }
     const int64_t n = ctx->n_rows;
+    F.n = n;
     if (n == 0) return FHX_OK;
-    const bool timing = std::getenv("FHX_TIMING") != nullptr;
-    double seconds[5] = {0, 0, 0, 0, 0};               // decide, rank scans, rows + ExpCC/bias, measure + format, copy out
-    auto t_last = std::chrono::steady_clock::now();
-    auto mark = [&](int stage) {                       // every call site has just synchronised the stream
-        const auto t = std::chrono::steady_clock::now();
-        seconds[stage] += std::chrono::duration<double>(t - t_last).count();
-        t_last = t;
-    };
+    T.last = std::chrono::steady_clock::now();
     Decision D;
     std::memset(&D, 0, sizeof(D));
     std::memcpy(D.fdr.text, fdr_text, (size_t)fdr_len);
@@ -279,52 +349,59 @@ int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n
     if (blob.empty()) blob.push_back(0);
 
     const int64_t n_wg = (n + WG - 1) / WG;
-    DeviceScratch G;
-    unsigned char* d_flags = nullptr;
+    F.n_wg = n_wg;
+    DeviceScratch& G = F.G;
     unsigned int *d_wg_emitted = nullptr, *d_wg_kept = nullptr;
-    unsigned long long *d_emit_off = nullptr, *d_kept_off = nullptr;
-    Words* d_words = nullptr;
-    char* d_names = nullptr;
-    int32_t* d_name_off = nullptr;
-    FHX_HIP(G.get(&d_flags, (size_t)n));
+    unsigned long long* d_emit_off = nullptr;
+    FHX_HIP(G.get(&F.d_flags, (size_t)n));
     FHX_HIP(G.get(&d_wg_emitted, (size_t)n_wg * 4));
     FHX_HIP(G.get(&d_wg_kept, (size_t)n_wg * 4));
     FHX_HIP(G.get(&d_emit_off, (size_t)n_wg * 8));
-    FHX_HIP(G.get(&d_kept_off, (size_t)n_wg * 8));
-    FHX_HIP(G.get(&d_words, sizeof(Words)));
-    FHX_HIP(G.get(&d_names, blob.size()));
-    FHX_HIP(G.get(&d_name_off, name_off.size() * 4));
-    Words words;
+    FHX_HIP(G.get(&F.d_kept_off, (size_t)n_wg * 8));
+    FHX_HIP(G.get(&F.d_words, sizeof(Words)));
+    FHX_HIP(G.get(&F.d_names, blob.size()));
+    FHX_HIP(G.get(&F.d_name_off, name_off.size() * 4));
+    Words& words = F.words;
     std::memset(&words, 0, sizeof(words));
     words.first_bad = NO_BAD_ROW;
-    FHX_HIP(hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, ctx->stream));
-    FHX_HIP(hipMemcpyAsync(d_names, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
-    FHX_HIP(hipMemcpyAsync(d_name_off, name_off.data(), name_off.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(F.d_words, &words, sizeof(words), hipMemcpyHostToDevice, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(F.d_names, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(F.d_name_off, name_off.data(), name_off.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     // every loaded row: identity from the resident slots, q resident; p, the biases and ExpCC are not read by sr_decide
     Cols C{nullptr, nullptr, nullptr, nullptr, ctx->d_count, ctx->d_loc1, ctx->d_loc2, ctx->d_slot_chr, ctx->nonfixed ? ctx->d_slot_mid : nullptr,
-           ctx->d_grid, (int32_t)ctx->prm.resolution, ctx->d_p, ctx->d_q, nullptr, nullptr, nullptr, d_names, d_name_off, n_names, n,
+           ctx->d_grid, (int32_t)ctx->prm.resolution, ctx->d_p, ctx->d_q, nullptr, nullptr, nullptr, F.d_names, F.d_name_off, n_names, n,
            ctx->prm.mode, ctx->prm.dist_low, ctx->prm.dist_up};
-    hipLaunchKernelGGL(sr_decide, dim3((unsigned)n_wg), dim3(WG), 0, ctx->stream, C, D, d_flags, d_wg_emitted, d_wg_kept, d_words);
+    SplitTables S{nullptr, nullptr};
+    if (VIEW == SPLIT) {
+        if (!name_why || (int32_t)name_why->size() != n_names) return fail(ctx, FHX_ERR_INTERNAL, "the split has no reason per chromosome id");
+        unsigned char* d_name_why = nullptr;
+        FHX_HIP(G.get(&d_name_why, (size_t)n_names));
+        FHX_HIP(G.get(&F.d_listed, (size_t)n_names));
+        FHX_HIP(hipMemcpyAsync(d_name_why, name_why->data(), (size_t)n_names, hipMemcpyHostToDevice, ctx->stream));
+        FHX_HIP(hipMemsetAsync(F.d_listed, 0, (size_t)n_names, ctx->stream));
+        S = SplitTables{d_name_why, F.d_listed};
+    }
+    hipLaunchKernelGGL(sr_decide<VIEW>, dim3((unsigned)n_wg), dim3(WG), 0, ctx->stream, C, D, F.d_flags, d_wg_emitted, d_wg_kept, F.d_words, S);
     FHX_HIP(hipGetLastError());
     if (timing) {
         FHX_HIP(hipStreamSynchronize(ctx->stream));
-        mark(0);
+        T.mark(0);
     }
     hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_emitted, n_wg, d_emit_off,
-                       &d_words->n_emitted);
-    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_kept, n_wg, d_kept_off,
-                       &d_words->n_kept);
+                       &F.d_words->n_emitted);
+    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_kept, n_wg, F.d_kept_off,
+                       &F.d_words->n_kept);
     FHX_HIP(hipGetLastError());
-    FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
+    FHX_HIP(hipMemcpyAsync(&words, F.d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
-    mark(1);
+    T.mark(1);
     if (words.first_bad != NO_BAD_ROW) {
         // the line the row has in the file the pass writes: the header, then the emitted rows before it
         const int64_t bad_row = (int64_t)(words.first_bad >> 8), wg = bad_row / WG;
         unsigned long long before = 0;
         unsigned char head[WG];
         FHX_HIP(hipMemcpyAsync(&before, d_emit_off + wg, 8, hipMemcpyDeviceToHost, ctx->stream));
-        FHX_HIP(hipMemcpyAsync(head, d_flags + wg * WG, (size_t)(bad_row - wg * WG + 1), hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipMemcpyAsync(head, F.d_flags + wg * WG, (size_t)(bad_row - wg * WG + 1), hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipStreamSynchronize(ctx->stream));
         for (int64_t k = 0; k < bad_row - wg * WG; ++k) before += head[k] != NOT_EMITTED;
         *why = (int32_t)(words.first_bad & 0xFFu);
@@ -332,51 +409,84 @@ int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n
         return fail(ctx, FHX_ERR_UNSUPPORTED, "line " + std::to_string(*bad_line) + " of the pass's file (loaded row " + std::to_string(bad_row) +
                                                   ") is outside the device grammar (reason " + std::to_string(*why) + ")");
     }
-    const char* not_covered = "a row does not fit the device formatter (name longer than 24 bytes, a value of 2^63 or more, or a row of 192 "
-                              "bytes or more): select from the written file";
-    if (words.unsupported) return fail(ctx, FHX_ERR_UNSUPPORTED, not_covered);
-    const int64_t emitted = (int64_t)words.n_emitted, kept = (int64_t)words.n_kept;
-    if (emitted > n || kept > emitted) return fail(ctx, FHX_ERR_INTERNAL, "more kept rows than emitted ones");
+    if (words.unsupported) return fail(ctx, FHX_ERR_UNSUPPORTED, kNotCovered);
+    F.emitted = (int64_t)words.n_emitted;
+    F.kept = (int64_t)words.n_kept;
+    if (F.emitted > n || F.kept > F.emitted) return fail(ctx, FHX_ERR_INTERNAL, "more kept rows than emitted ones");
+    return FHX_OK;
+}
+
+// sr_rows over a decision with kept rows; nothing is synchronised
+int gather_kept(fhx_ctx* ctx, Decided& F, KeptRows& R) {
+    using namespace fhx::sigres;
+    const int64_t kept = F.kept;
+    FHX_HIP(F.G.get(&R.d_rows, (size_t)kept * 8));
+    FHX_HIP(F.G.get(&R.d_loc1, (size_t)kept * 4));
+    FHX_HIP(F.G.get(&R.d_loc2, (size_t)kept * 4));
+    FHX_HIP(F.G.get(&R.d_count, (size_t)kept * 4));
+    FHX_HIP(F.G.get(&R.d_p, (size_t)kept * 8));
+    FHX_HIP(F.G.get(&R.d_q, (size_t)kept * 8));
+    hipLaunchKernelGGL(sr_rows, dim3((unsigned)F.n_wg), dim3(WG), 0, ctx->stream, (const unsigned char*)F.d_flags, F.n,
+                       (const unsigned long long*)F.d_kept_off, kept, (const int32_t*)ctx->d_loc1, (const int32_t*)ctx->d_loc2,
+                       (const int32_t*)ctx->d_count, (const double*)ctx->d_p, (const double*)ctx->d_q, R.d_rows, R.d_loc1, R.d_loc2, R.d_count, R.d_p,
+                       R.d_q);
+    FHX_HIP(hipGetLastError());
+    return FHX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, const char* fdr_text, int32_t fdr_len, uint64_t key_bound,
+                           int32_t zero_kept, int32_t strict, int64_t* n_emitted, int64_t* n_kept, int64_t* n_bytes, int32_t* why,
+                           int64_t* bad_line) {
+    using namespace fhx::sigres;
+    if (!ctx || !chr_names || n_names <= 0 || !fdr_text || !n_emitted || !n_kept || !n_bytes || !why || !bad_line) return FHX_ERR_ARG;
+    *n_emitted = *n_kept = *n_bytes = 0;
+    *why = FHX_MS_OK;
+    *bad_line = 0;
+    drop_significant(ctx);
+    const bool timing = std::getenv("FHX_TIMING") != nullptr;
+    Decided F;
+    StageSeconds T;                                    // decide, rank scans, rows + ExpCC/bias, measure + format, copy out
+    if (const int rc = decide_rows<fhx::sigres::SUBSET>(ctx, chr_names, n_names, fdr_text, fdr_len, key_bound, zero_kept, strict, why, bad_line, timing, F, T))
+        return rc;
+    if (F.n == 0) return FHX_OK;
+    const int64_t n = F.n, emitted = F.emitted, kept = F.kept;
+    DeviceScratch& G = F.G;
+    Words& words = F.words;
+    Words* d_words = F.d_words;
     std::vector<char> text;
     std::vector<int64_t> rows((size_t)kept);
     if (kept > 0) {
         const int64_t k_wg = (kept + WG - 1) / WG;
-        int64_t* d_rows = nullptr;
-        int32_t *d_kloc1 = nullptr, *d_kloc2 = nullptr, *d_kcount = nullptr;
-        double *d_kp = nullptr, *d_kq = nullptr, *d_b1 = nullptr, *d_b2 = nullptr, *d_e = nullptr;
+        KeptRows R;
+        double *d_b1 = nullptr, *d_b2 = nullptr, *d_e = nullptr;
         unsigned char *d_len = nullptr, *d_out = nullptr;
         unsigned int* d_wg_bytes = nullptr;
         unsigned long long* d_wg_off = nullptr;
-        FHX_HIP(G.get(&d_rows, (size_t)kept * 8));
-        FHX_HIP(G.get(&d_kloc1, (size_t)kept * 4));
-        FHX_HIP(G.get(&d_kloc2, (size_t)kept * 4));
-        FHX_HIP(G.get(&d_kcount, (size_t)kept * 4));
-        FHX_HIP(G.get(&d_kp, (size_t)kept * 8));
-        FHX_HIP(G.get(&d_kq, (size_t)kept * 8));
         FHX_HIP(G.get(&d_b1, (size_t)kept * 8));
         FHX_HIP(G.get(&d_b2, (size_t)kept * 8));
         FHX_HIP(G.get(&d_e, (size_t)kept * 8));
         FHX_HIP(G.get(&d_len, (size_t)kept));
         FHX_HIP(G.get(&d_wg_bytes, (size_t)k_wg * 4));
         FHX_HIP(G.get(&d_wg_off, (size_t)k_wg * 8));
-        hipLaunchKernelGGL(sr_rows, dim3((unsigned)n_wg), dim3(WG), 0, ctx->stream, (const unsigned char*)d_flags, n,
-                           (const unsigned long long*)d_kept_off, kept, (const int32_t*)ctx->d_loc1, (const int32_t*)ctx->d_loc2,
-                           (const int32_t*)ctx->d_count, (const double*)ctx->d_p, (const double*)ctx->d_q, d_rows, d_kloc1, d_kloc2, d_kcount, d_kp,
-                           d_kq);
+        if (const int rc = gather_kept(ctx, F, R)) return rc;
         // ExpCC and the biases as the writer prints them (fithic.py:1075-1078, :1105-1108), of the kept rows alone
         K2Params P = make_k2_params(ctx);
-        P.loc1 = d_kloc1;
-        P.loc2 = d_kloc2;
-        P.count = d_kcount;
+        P.loc1 = R.d_loc1;
+        P.loc2 = R.d_loc2;
+        P.count = R.d_count;
         P.n = kept;
         launch_k2_extras(ctx, P, kept, d_e, d_b1, d_b2);
         FHX_HIP(hipGetLastError());
         if (timing) {
             FHX_HIP(hipStreamSynchronize(ctx->stream));
-            mark(2);
+            T.mark(2);
         }
-        Cols K{nullptr, nullptr, nullptr, nullptr, d_kcount, d_kloc1, d_kloc2, ctx->d_slot_chr, ctx->nonfixed ? ctx->d_slot_mid : nullptr,
-               ctx->d_grid, (int32_t)ctx->prm.resolution, d_kp, d_kq, d_b1, d_b2, d_e, d_names, d_name_off, n_names, kept,
+        Cols K{nullptr, nullptr, nullptr, nullptr, R.d_count, R.d_loc1, R.d_loc2, ctx->d_slot_chr, ctx->nonfixed ? ctx->d_slot_mid : nullptr,
+               ctx->d_grid, (int32_t)ctx->prm.resolution, R.d_p, R.d_q, d_b1, d_b2, d_e, F.d_names, F.d_name_off, n_names, kept,
                ctx->prm.mode, ctx->prm.dist_low, ctx->prm.dist_up};
         hipLaunchKernelGGL(sr_measure, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, d_len, d_wg_bytes, d_words);
         hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_bytes, k_wg, d_wg_off,
@@ -384,7 +494,7 @@ int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n
         FHX_HIP(hipGetLastError());
         FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipStreamSynchronize(ctx->stream));
-        if (words.unsupported) return fail(ctx, FHX_ERR_UNSUPPORTED, not_covered);
+        if (words.unsupported) return fail(ctx, FHX_ERR_UNSUPPORTED, kNotCovered);
         const int64_t bytes = (int64_t)words.n_bytes;
         if (bytes <= 0 || bytes > kept * (int64_t)fhx::emit::ROW_STRIDE) return fail(ctx, FHX_ERR_INTERNAL, "more text than the kept rows can hold");
         FHX_HIP(G.get(&d_out, (size_t)bytes));
@@ -393,13 +503,13 @@ int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n
         FHX_HIP(hipGetLastError());
         FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipStreamSynchronize(ctx->stream));
-        mark(3);
+        T.mark(3);
         if (words.internal) return fail(ctx, FHX_ERR_INTERNAL, "the formatter wrote another length than it measured");
         text.resize((size_t)bytes);
         FHX_HIP(hipMemcpyAsync(text.data(), d_out, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
-        FHX_HIP(hipMemcpyAsync(rows.data(), d_rows, (size_t)kept * 8, hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipMemcpyAsync(rows.data(), R.d_rows, (size_t)kept * 8, hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipStreamSynchronize(ctx->stream));
-        mark(4);
+        T.mark(4);
     }
     ctx->sig_text.swap(text);
     ctx->sig_rows.swap(rows);
@@ -409,7 +519,7 @@ int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n
     if (timing)
         std::fprintf(stderr, "fhx_significant_select: %lld rows, %lld emitted, %lld kept (%lld bytes): decide %.6f s; rank scans %.6f s; "
                      "rows + ExpCC/bias %.6f s; measure + format %.6f s; copy out %.6f s\n", (long long)n, (long long)emitted, (long long)kept,
-                     (long long)*n_bytes, seconds[0], seconds[1], seconds[2], seconds[3], seconds[4]);
+                     (long long)*n_bytes, T.s[0], T.s[1], T.s[2], T.s[3], T.s[4]);
     return FHX_OK;
 }
 

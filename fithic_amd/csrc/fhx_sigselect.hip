@@ -36,9 +36,11 @@
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
+#include "fhx_namerule.hpp"
 #include "fhx_score.hpp"
 #include "fhx_sigkey.hpp"
 #include "fhx_textupload.hpp"
+#include "fhx_trackline.hpp"
 
 namespace msd {
 

@@ -34,9 +34,10 @@ using utd::Line;
 using utd::Round;
 using utd::round_of;
 using utd::walk;
+using fhx::namerule::name_grammar;        // what a name may be: fhx_namerule.hpp, shared with the resident route
 
 constexpr int SLOTS = FHX_MS_SPLIT_NAMES;      // 4096 = 2^12: the slot field of a record
-constexpr int NAME_STRIDE = 64;                // a name of up to 63 bytes, and its length in byte 63
+constexpr int NAME_STRIDE = fhx::namerule::NAME_STRIDE;      // a name of up to 63 bytes, and its length in byte 63
 constexpr unsigned int NO_SLOT = 0xFFFFu;
 constexpr int LEN_BITS = 13, START_BITS = 31;  // 4097 < 2^13; a batch has at most 2^31 bytes
 constexpr int ROUND = 256;                     // sorted records per workgroup of mp_gather
@@ -51,29 +52,6 @@ struct SplitWords {
 };
 
 __device__ inline bool name_end(int c) { return c == '\t' || c == ' ' || c == '\n'; }
-__device__ inline bool is_letter(int c) { return (c | 0x20) >= 'a' && (c | 0x20) <= 'z'; }
-
-// A name awk compares with another accepted name as STRINGS, and a shell word takes as it is: 0 or the reason.
-__device__ inline int name_grammar(const unsigned char* __restrict__ s, int n) {
-    if (n > NAME_STRIDE - 1) return FHX_MS_NAME;
-    bool all_digits = true, certain = false;                                  // certain: strtod cannot consume the name whole
-    for (int k = 0; k < n; ++k) {
-        const int c = s[k];
-        const bool letter = is_letter(c), digit = is_digit(c);
-        if (!letter && !digit && c != '_' && c != '.' && c != '-') return FHX_MS_NAME_BYTES;
-        if (k == 0 && !letter && !digit && c != '_') return FHX_MS_NAME_BYTES;
-        all_digits &= digit;
-        if (c == '_') certain = true;
-        if (letter) {
-            const int l = c | 0x20;
-            if (!(l >= 'a' && l <= 'f') && l != 'x' && l != 'p') certain = true;
-        }
-    }
-    if (n < 1) return FHX_MS_NAME_BYTES;
-    if (!is_digit(s[0])) return 0;
-    if (all_digits) return (n <= 15 && (n == 1 || s[0] != '0')) ? 0 : FHX_MS_NAME_NUMERIC;
-    return certain ? 0 : FHX_MS_NAME_NUMERIC;
-}
 
 // the table: hash[slot] (0 = empty), off[slot] = the smallest file offset the name was seen at.  -1: no slot is left.
 __device__ inline int table_insert(unsigned long long* __restrict__ t_hash, unsigned long long* __restrict__ t_off,

@@ -19,18 +19,15 @@
 //   ut_format      256 lines per round, their lengths scanned; every lane writes its line into a 16 KB window of LDS (a round
 //                  longer than that takes several windows; a lane writes only what falls into the current one), and the
 //                  window goes out with consecutive lanes on consecutive bytes.  Order is file order.
+// What a line is made of - the grammar beyond field 7, its length, the DEFERRED marking, the writer - is fhx_trackline.hpp.
 // A track line can be two and a half times its input line, so nothing here is sized by the input: d_out grows to what ut_measure found.
 namespace utd {
 
 using namespace fhxlines;
 using namespace msd;
+using namespace fhx::trackline;           // the line itself: fhx_trackline.hpp, shared with the resident route
 
-constexpr int NAME_BYTES = 63;                 // tokens 1 and 3
-constexpr int MID_DIGITS = 9;                  // tokens 2 and 4: v + 1 stays below 2^31, where awk prints integers as integers
-constexpr int DEFER_IN = 16, DEFER_OUT = 32;   // bytes per deferred line, to the host and back (byte 0: the length)
 constexpr int WINDOW = 16384;                  // LDS bytes of ut_format
-constexpr unsigned int DEFERRED = 0x8000u;     // in a line's info word; the low 15 bits are a length (0: dropped)
-constexpr int FIXED_BYTES = 45;                // 16 blanks and the newline, EXP 0 SOURCE_NAME . TARGET_NAME +
 
 struct TrackWords {
     unsigned long long newlines;
@@ -87,28 +84,6 @@ __device__ inline void walk(const unsigned char* __restrict__ text, int64_t T, i
     L.len = k;
 }
 
-// 1 to 9 digits -> their value, -1 otherwise
-__device__ inline int midpoint(const unsigned char* __restrict__ text, int64_t b, int n) {
-    if (n < 1 || n > MID_DIGITS) return -1;
-    int v = 0;
-    for (int k = 0; k < n; ++k) {
-        const int c = text[b + k];
-        if (!is_digit(c)) return -1;
-        v = v * 10 + (c - '0');
-    }
-    return v;
-}
-
-__device__ inline int digits_of(long long v) {                                // of the decimal text, a minus sign included
-    int n = v < 0 ? 2 : 1;
-    unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
-    while (u >= 10ull) {
-        u /= 10ull;
-        ++n;
-    }
-    return n;
-}
-
 // the lines of a block in rounds of WG: entry e of the round's lane, its line number in the batch, whether both exist
 struct Round {
     int e;
@@ -149,9 +124,8 @@ __global__ __launch_bounds__(WG) void ut_select(const unsigned char* __restrict_
             cls = classify(text, start + L.fb, L.fn, &key);
             v2 = midpoint(text, start + L.b2, L.n2);
             v4 = midpoint(text, start + L.b4, L.n4);
-            if (cls == 0) why = FHX_MS_FIELD;
-            else if (v2 < 0 || v4 < 0) why = FHX_MS_MIDPOINT;
-            else if (L.n1 > NAME_BYTES || L.n3 > NAME_BYTES) why = FHX_MS_NAME;
+            why = refusal(cls, v2 >= 0 && v4 >= 0, L.n1, L.n3);
+            if (why) {}                                                       // nothing of the file is kept
             else if (cls == 1) keep = zero_kept != 0;
             else if (cls == 2) keep = key <= key_bound;
             else keep = compare_text(text, start + L.fb, L.fn, fdr) < 0;
@@ -159,17 +133,9 @@ __global__ __launch_bounds__(WG) void ut_select(const unsigned char* __restrict_
         if (why) atomicMin(&words->first_error, error_word(line_base + r + 1, why));
         unsigned int word = 0;
         if (keep && !why) {
-            int score = 7;                                                    // inf inf
-            if (cls == 2) {
-                char buf[fhx::score::MAX_TEXT];
-                score = fhx::score::certified(buf, fhx::score::approximate(key % KEY_EXP, (int)(key / KEY_EXP) - 308));
-            } else if (cls == 3) score = 0;
-            word = (unsigned int)(FIXED_BYTES + 2 * L.n1 + L.n3 + 2 * digits_of((long long)v2 - 1) + digits_of((long long)v2 + 1) +
-                                  digits_of((long long)v4 - 1) + 2 * digits_of((long long)v4 + 1) + score);
-            if (score == 0) {
-                word |= DEFERRED;
-                ++my_deferred;
-            }
+            char buf[fhx::score::MAX_TEXT];
+            word = line_word(L.n1, L.n3, v2, v4, score_text(cls, key, buf));
+            if (word & DEFERRED) ++my_deferred;
             ++my_kept;
         }
         if (r < n_lines_batch) info[r] = (unsigned short)word;
@@ -202,7 +168,7 @@ __global__ __launch_bounds__(WG) void ut_defer(const unsigned char* __restrict__
             const int64_t start = b0 + lstart[q.e];
             Line L;
             walk(text, T, start, 0, L);
-            for (int k = 0; k < DEFER_IN; ++k) fields[slot * DEFER_IN + k] = k < L.fn && k < DEFER_IN - 1 ? text[start + L.fb + k] : (unsigned char)0;
+            defer_field(fields, slot, text + start + L.fb, L.fn);
         }
         slot0 += total;
     }
@@ -226,10 +192,9 @@ __global__ __launch_bounds__(WG) void ut_measure(const unsigned char* __restrict
         unsigned int total;                                                   // kept lines in the low half, deferred ones in the high half
         const unsigned int rank = fhxscan::block_exclusive_scan((kept ? 1u : 0u) | (deferred ? 0x10000u : 0u), &total);
         if (kept) {
-            unsigned int len = (word & ~DEFERRED) + (unsigned int)digits_of(nr0 + (rank & 0xFFFFu));
-            const int64_t slot = slot0 + (rank >> 16);
-            if (deferred && slot < n_slots) len += scores[slot * DEFER_OUT];
-            info[q.r] = (unsigned short)(len | (word & DEFERRED));
+            const unsigned int done = final_word(word, nr0 + (rank & 0xFFFFu), scores, slot0 + (rank >> 16), n_slots);
+            const unsigned int len = done & ~DEFERRED;
+            info[q.r] = (unsigned short)done;
             my_bytes += len;
         }
         nr0 += total & 0xFFFFu;
@@ -248,17 +213,6 @@ struct WindowSink {
     __device__ void put(int c) {
         const unsigned int at = pos++ - w0;                                   // wraps to a huge value below the window
         if (at < (unsigned int)WINDOW) lds[at] = (unsigned char)c;
-    }
-    __device__ void bytes(const unsigned char* __restrict__ src, int n) {
-        for (int k = 0; k < n; ++k) put(src[k]);
-    }
-    __device__ void literal(const char* s) {
-        for (; *s; ++s) put(*s);
-    }
-    __device__ void number(long long v) {
-        char tmp[24];
-        const int n = fhx::fmt::put_i64(tmp, v);
-        for (int k = 0; k < n; ++k) put(tmp[k]);
     }
 };
 
@@ -294,45 +248,12 @@ __global__ __launch_bounds__(WG) void ut_format(const unsigned char* __restrict_
             v4 = midpoint(line, L.b4, L.n4);
             unsigned long long key = 0;
             const int cls = classify(line, L.fb, L.fn, &key);
-            const int64_t slot = slot0 + (rank >> 16);
-            if (deferred) {
-                if (slot < n_slots) {
-                    score_len = min((int)scores[slot * DEFER_OUT], DEFER_OUT - 1);
-                    for (int k = 0; k < score_len && k < fhx::score::MAX_TEXT; ++k) score[k] = (char)scores[slot * DEFER_OUT + 1 + k];
-                }
-            } else if (cls == 2) {
-                score_len = fhx::score::certified(score, fhx::score::approximate(key % KEY_EXP, (int)(key / KEY_EXP) - 308));
-            } else {
-                score_len = 7;
-                score[0] = score[4] = 'i', score[1] = score[5] = 'n', score[2] = score[6] = 'f', score[3] = ' ';
-            }
-            score_len = min(score_len, fhx::score::MAX_TEXT);
+            score_len = deferred ? host_score(scores, slot0 + (rank >> 16), n_slots, score) : score_text(cls, key, score);
         }
         for (unsigned int w0 = 0; w0 < total; w0 += WINDOW) {
             if (kept && pre < w0 + WINDOW && pre + len > w0) {
                 WindowSink s{window, pre, w0};
-                s.bytes(line + L.b1, L.n1);
-                s.put(' ');
-                s.number((long long)v2 - 1);
-                s.put(' ');
-                s.number((long long)v4 + 1);
-                s.put(' ');
-                s.number(nr0 + (rank & 0xFFFFu));
-                s.put(' ');
-                s.bytes((const unsigned char*)score, score_len);
-                s.literal(" EXP 0 ");
-                s.bytes(line + L.b1, L.n1);
-                s.put(' ');
-                s.number((long long)v2 - 1);
-                s.put(' ');
-                s.number((long long)v2 + 1);
-                s.literal(" SOURCE_NAME . ");
-                s.bytes(line + L.b3, L.n3);
-                s.put(' ');
-                s.number((long long)v4 - 1);
-                s.put(' ');
-                s.number((long long)v4 + 1);
-                s.literal(" TARGET_NAME +\n");
+                write_line(s, line + L.b1, L.n1, v2, line + L.b3, L.n3, v4, nr0 + (rank & 0xFFFFu), score, score_len);
                 // what was written is what ut_measure counted, or nothing of this call is kept
                 if (s.pos - pre != len) atomicMin(&words->first_error, error_word(line_base + q.r + 1, FHX_MS_INTERNAL));
             }
@@ -352,12 +273,6 @@ __global__ __launch_bounds__(WG) void ut_format(const unsigned char* __restrict_
 
 // ===================================================================================================================
 namespace {
-
-const char kTrackHead[] =
-    "track type=interact name=\"Your_Fit-Hi-C_Interactions\" description=\"Fit-Hi-C_Interactions\" interactDirectional=true useScore=on "
-    "maxHeightPixels=50:100:200 visibility=full\n"
-    "#chrom  chromStart  chromEnd  name  score  value  exp  color  sourceChrom  sourceStart  sourceEnd  sourceName  sourceStrand  targetChrom  "
-    "targetStart  targetEnd  targetName  targetStrand\n";
 
 void drop_track(fhx_ms* ms) {
     std::vector<char>().swap(ms->track);
@@ -455,7 +370,7 @@ int fhx_ms_track_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_
         if (w == FHX_MS_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, "the kernels of the track disagree about line " + std::to_string(line));
         return refuse(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
     };
-    ms->track.assign(kTrackHead, kTrackHead + sizeof(kTrackHead) - 1);
+    ms->track.assign(HEAD, HEAD + sizeof(HEAD) - 1);
     int64_t lines = 0, kept = 0, deferred_lines = 0;
     for (int64_t off = 0; off < src.size();) {
         std::memset(&words, 0, sizeof(words));
@@ -499,17 +414,9 @@ int fhx_ms_track_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_
                                d_fields, n_slots);
             TH_HIP(ms, hipGetLastError());
             fields.resize((size_t)(n_slots * DEFER_IN));
-            scores.assign((size_t)(n_slots * DEFER_OUT), 0);
             TH_HIP(ms, hipMemcpyAsync(fields.data(), d_fields, fields.size(), hipMemcpyDeviceToHost, ms->stream));
             TH_HIP(ms, hipStreamSynchronize(ms->stream));
-            for (int64_t k = 0; k < n_slots; ++k) {
-                const char* f = (const char*)fields.data() + k * DEFER_IN;
-                char text[fhx::score::MAX_TEXT + 8];
-                const int got = fhx::score::host_fields(f, (int)strnlen(f, DEFER_IN - 1), text);
-                if (got < 3 || got > fhx::score::MAX_TEXT) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "a deferred score has no text");
-                scores[(size_t)(k * DEFER_OUT)] = (unsigned char)got;
-                std::memcpy(scores.data() + k * DEFER_OUT + 1, text, (size_t)got);
-            }
+            if (!answer_deferred(fields.data(), n_slots, &scores)) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "a deferred score has no text");
             TH_HIP(ms, hipMemcpyAsync(d_scores, scores.data(), scores.size(), hipMemcpyHostToDevice, ms->stream));
             TH_HIP(ms, hipStreamSynchronize(ms->stream));
         }

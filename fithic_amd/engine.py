@@ -168,6 +168,49 @@ class Engine:
             raise mergefilter._refusal_at("%s, line %d" % (path or "the significances of this pass", e.line), e.why, "") from None
         return mergefilter.Selection(subset, emitted + 1, kept, {"significant_select": time.perf_counter() - t0}, self.device)
 
+    def track(self, qval, names, path=None):
+        """The UCSC interact track of this pass from its resident q (csrc/fhx_sigresident_track.inc), between run_pass / bh and
+        next_pass: the ucsc.Track that ucsc.track(file, qval) returns for the file this pass writes - same text, same n_lines (the
+        header counted), n_kept and n_deferred - without writing it.  Arguments, refusals and the FHX_ERR_UNSUPPORTED case as for
+        significant(); the track's rules for midpoints and names hold for every row the writer would print."""
+        from . import mergefilter, ucsc
+        text = mergefilter.fdr_text(qval)
+        bound = mergefilter.key_bound(text, strict=True)
+        t0 = time.perf_counter()
+        try:
+            emitted, kept, deferred, track = self.ctx.significant_track(names, text, bound, 0 < float(text))
+        except _capi.MsRefused as e:
+            if e.why in (_capi.MS_INTERNAL, _capi.MS_FDR):
+                raise
+            where = path or "the significances of this pass"
+            if e.why == _capi.MS_KEPT:
+                raise ucsc._refusal_kept(where) from None
+            raise ucsc._refusal_at("%s, line %d" % (where, e.line), e.why, "") from None
+        return ucsc.Track(track, dict(lines=emitted + 1, kept=kept, deferred=deferred), {"significant_track": time.perf_counter() - t0},
+                          self.device)
+
+    def split(self, fdr, names, path=None):
+        """The per-chromosome FDR subsets of this pass from its resident q (csrc/fhx_sigresident_split.inc), between run_pass / bh
+        and next_pass: the mergefilter_parallel.Split that mergefilter_parallel.split(file, fdr) returns for the file this pass
+        writes - same chromosomes, same subsets, same n_lines - without writing it, so that mergefilter_parallel.write_tree takes
+        it as it is.  Arguments, refusals and the FHX_ERR_UNSUPPORTED case as for significant(); the split's name rules hold for
+        both names of every row the writer would print."""
+        from . import mergefilter, mergefilter_parallel
+        text = mergefilter.fdr_text(fdr)
+        bound = mergefilter.key_bound(text)
+        t0 = time.perf_counter()
+        try:
+            emitted, parts = self.ctx.significant_split(names, text, bound, 0 <= float(text))
+        except _capi.MsRefused as e:
+            if e.why in (_capi.MS_INTERNAL, _capi.MS_FDR):
+                raise
+            where = path or "the significances of this pass"
+            if e.why == _capi.MS_NAMES:
+                raise mergefilter_parallel._refusal_names(where) from None
+            raise mergefilter_parallel._refusal_at("%s, line %d" % (where, e.line), e.why, "") from None
+        return mergefilter_parallel.Split({name: sub for name, _, sub in parts}, {name: kept for name, kept, _ in parts}, emitted + 1,
+                                          {"significant_split": time.perf_counter() - t0}, self.device)
+
     def next_pass(self):
         """Fold this pass's outliers (p < 1/N) into the skip mask and the outlier-distance multiset."""
         return self.ctx.next_pass()

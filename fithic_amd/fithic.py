@@ -512,39 +512,68 @@ def _write_significances(S, name):
                                        v["b1"], v["b2"], v["expcc"], mode_id, distLowThres, distUpThres)
 
 
-def write_significant(fdr, resolution):
+def write_significant(fdr, resolution, track=False, split=False):
     """cli --significant FDR, after the last fit_Spline and before anything folds its outliers: <prefix>.fdr_subset.txt.gz (the rows
     of <prefix>.significances.txt.gz with q <= fdr as merge-filter.sh chooses them) and, on a bin lattice, <prefix>.merged.txt.gz
-    (its CombineNearbyInteraction step), <prefix> being the last pass's <lib>.spline_pass<N>[.res<R>].  The subset comes from the
-    pass's resident q (Engine.significant); a sharded run, or a kept row the device formatter does not cover, takes it from the
-    written file instead (mergefilter.select) - the same bytes either way."""
-    from . import combine, mergefilter
+    (its CombineNearbyInteraction step), <prefix> being the last pass's <lib>.spline_pass<N>[.res<R>].  With `track`
+    (--significant-track) also <prefix>.interact.txt, the UCSC track visualize-UCSC.sh makes of the rows with q < fdr; with `split`
+    (--significant-split) also the tree <prefix>.fdr_split/<chr>/ that merge-filter-parallelized.sh makes, postmerged files
+    included on a bin lattice.  Each product comes from the pass's resident q (Engine.significant / track / split); a sharded run,
+    or a kept row the device formatter does not cover, takes it from the written file instead (mergefilter.select, ucsc.track,
+    mergefilter_parallel.split) - the same bytes either way.  Under --significant-only that file is written at most once, for
+    whichever products need it, and removed after the last of them."""
+    from . import combine, mergefilter, mergefilter_parallel, ucsc
     S = _S
     prefix = S.last_prefix
     name = prefix + ".significances.txt.gz"
-    chosen = None
-    if hasattr(S.engine, "significant"):
+    written = []
+
+    def direct(method, threshold):
+        """the product from the resident q, or None where the file route has to make it"""
+        if not hasattr(S.engine, method):
+            return None
         try:
-            chosen = S.engine.significant(fdr, S.chroms.names, path=name)
+            return getattr(S.engine, method)(threshold, S.chroms.names, path=name)
         except _capi.FhxError as e:
             if e.code != _capi.FHX_ERR_UNSUPPORTED or isinstance(e, _capi.MsRefused):
                 raise
-    if chosen is None:
-        if significant_only:                               # no pass wrote the file: it exists for the selection alone
+        return None
+
+    def the_file():
+        if significant_only and not written:               # no pass wrote the file: it exists for the selections alone
             _write_significances(S, name)
-        try:
-            chosen = mergefilter.select(name, fdr, device=device)
-        finally:
-            if significant_only:
-                os.remove(name)
-    print("Writing the %d rows with q <= %s to file %s" % (chosen.n_kept, fdr, prefix + ".fdr_subset.txt.gz"))
-    chosen.write_subset(prefix + ".fdr_subset.txt.gz")
-    if not resolution:
-        print("No merged file: merging nearby contacts needs a bin lattice, and -r 0 has none")
-        return
-    names, rec = chosen.merged(resolution)
-    print("Writing the merged contacts to file %s" % (prefix + ".merged.txt.gz"))
-    combine.write_merged(prefix + ".merged.txt.gz", names, rec, resolution)
+            written.append(name)
+        return name
+
+    try:
+        chosen = direct("significant", fdr)
+        if chosen is None:
+            chosen = mergefilter.select(the_file(), fdr, device=device)
+        print("Writing the %d rows with q <= %s to file %s" % (chosen.n_kept, fdr, prefix + ".fdr_subset.txt.gz"))
+        chosen.write_subset(prefix + ".fdr_subset.txt.gz")
+        if not resolution:
+            print("No merged file: merging nearby contacts needs a bin lattice, and -r 0 has none")
+        else:
+            names, rec = chosen.merged(resolution)
+            print("Writing the merged contacts to file %s" % (prefix + ".merged.txt.gz"))
+            combine.write_merged(prefix + ".merged.txt.gz", names, rec, resolution)
+        if track:
+            lines = direct("track", fdr)
+            if lines is None:
+                lines = ucsc.track(the_file(), fdr, device=device)
+            print("Writing the UCSC interact track of the %d rows with q < %s to file %s" % (lines.n_kept, fdr, prefix + ".interact.txt"))
+            lines.write(prefix + ".interact.txt")
+        if split:
+            parts = direct("split", fdr)
+            if parts is None:
+                parts = mergefilter_parallel.split(the_file(), fdr, device=device)
+            print("Writing the per-chromosome subsets of %d chromosomes to directory %s" % (len(parts.chromosomes), prefix + ".fdr_split"))
+            if not resolution:
+                print("No postmerged files: merging nearby contacts needs a bin lattice, and -r 0 has none")
+            mergefilter_parallel.write_tree(parts, prefix + ".fdr_split", resolution, utilityfolder="", merge=bool(resolution))
+    finally:
+        for path in written:
+            os.remove(path)
 
 
 def fit_Spline(mainDic, x, y, yerr, infilename, outfilename, biasDic, outliersline, outliersdist, observedIntraInRangeSum,

@@ -30,6 +30,9 @@ of [A-Za-z0-9_.-] starting with a letter, a digit or `_` (each becomes a directo
 starts with a digit is a decimal integer of at most 15 digits without a leading zero, or holds `_` or a letter other than
 a-f, x, p in either case (2L, 3R, 10_random: strtod cannot consume it whole) - 01, 1.5, 1e3, 0x1, 2a are refused.  At most 4096
 distinct names.  There is no CPU implementation here: without the library or a GPU the entry points raise.
+
+`fithic --significant FDR --significant-split` and Engine.split make the same tree straight from a pass's resident q-values
+(csrc/fhx_sigresident_split.inc), without the significances file being written or read back.
 """
 import os
 import re
@@ -67,21 +70,32 @@ def job_text(outdir, name, resolution, utilityfolder=""):
         utilityfolder, outdir, name, name, resolution, outdir, name, name)
 
 
+def _refusal_names(path):
+    return ValueError("%s: more than %d distinct names in field 1" % (path, _capi.MS_SPLIT_NAMES) + _ACCEPTS)
+
+
 def _refusal(path, e):
     """the exception a refused file is reported with (module docstring, `Known deviations`)"""
     if e.why == _capi.MS_NAMES:
-        return ValueError("%s: more than %d distinct names in field 1" % (path, _capi.MS_SPLIT_NAMES) + _ACCEPTS)
+        return _refusal_names(path)
     if e.why not in (_capi.MS_NAME, _capi.MS_NAME_TAB, _capi.MS_NAME_BYTES, _capi.MS_NAME_NUMERIC):
         return mergefilter._refusal(path, e)
-    where = "%s, line %d" % (path, e.line)
     with open(path, "rb") as f:
         gzipped = f.read(2) == b"\x1f\x8b"
     text = _line_of(path, e.line).decode("latin-1") if not gzipped else ""
-    if e.why == _capi.MS_NAME_TAB:
+    return _refusal_at("%s, line %d" % (path, e.line), e.why, text)
+
+
+def _refusal_at(where, why, text):
+    """the ValueError for reason `why` at `where` ("<file>, line <n>"), `text` being the line when it is at hand ("" for a gzipped
+    file and for a line that was never written: Engine.split)"""
+    if why not in (_capi.MS_NAME, _capi.MS_NAME_TAB, _capi.MS_NAME_BYTES, _capi.MS_NAME_NUMERIC):
+        return mergefilter._refusal_at(where, why, text)
+    if why == _capi.MS_NAME_TAB:
         return ValueError("%s: the chromosome name must start in column 0 and be ended by a tab: %r" % (where, text[:80]) + _ACCEPTS)
-    if e.why == _capi.MS_NAME:
+    if why == _capi.MS_NAME:
         return ValueError("%s: a chromosome name of more than %d bytes: %r" % (where, MAX_NAME, text[:80]) + _ACCEPTS)
-    if e.why == _capi.MS_NAME_BYTES:
+    if why == _capi.MS_NAME_BYTES:
         return ValueError("%s: a chromosome name is 1 to %d bytes of [A-Za-z0-9_.-] and starts with a letter, a digit or _: %r"
                           % (where, MAX_NAME, text[:80]) + _ACCEPTS)
     return ValueError("%s: a chromosome name that starts with a digit and that awk would, or might, compare as a number (01, 1.5, 1e3, "

@@ -27,6 +27,9 @@ awk prints $4+1 as 2.14748e+09 from 2^31 - 1 on, and takes signs, fractions and 
 more than 2^31 - 1 kept rows (awk prints NR through %.6g from there).  These rules hold for every parsed line, kept or not; a
 line 1 dropped by the header rule only has to satisfy the byte, length and token-count rules.  There is no CPU implementation
 here: without the library or a GPU the entry points raise.
+
+`fithic --significant FDR --significant-track` and Engine.track make the same track straight from a pass's resident q-values
+(csrc/fhx_sigresident_track.inc), without the significances file being written or read back.
 """
 import sys
 
@@ -35,20 +38,31 @@ from . import _capi, mergefilter
 _ACCEPTS = mergefilter._ACCEPTS.replace("fithic_amd.mergefilter", "fithic_amd.ucsc")
 
 
+def _refusal_kept(path):
+    return ValueError("%s: more than 2^31 - 1 rows pass the threshold" % path + _ACCEPTS)
+
+
 def _refusal(path, e):
     """the exception a refused file is reported with (module docstring, `Known deviations`)"""
     if e.why == _capi.MS_KEPT:
-        return ValueError("%s: more than 2^31 - 1 rows pass the threshold" % path + _ACCEPTS)
+        return _refusal_kept(path)
     if e.why not in (_capi.MS_MIDPOINT, _capi.MS_NAME):
         inherited = mergefilter._refusal(path, e)
         if isinstance(inherited, ValueError):
             return ValueError(str(inherited).replace("fithic_amd.mergefilter", "fithic_amd.ucsc"))
         return inherited
-    where = "%s, line %d" % (path, e.line)
     with open(path, "rb") as f:
         gzipped = f.read(2) == b"\x1f\x8b"
     text = mergefilter._line_of(path, e.line).decode("latin-1") if not gzipped else ""
-    if e.why == _capi.MS_MIDPOINT:
+    return _refusal_at("%s, line %d" % (path, e.line), e.why, text)
+
+
+def _refusal_at(where, why, text):
+    """the ValueError for reason `why` at `where` ("<file>, line <n>"), `text` being the line when it is at hand ("" for a gzipped
+    file and for a line that was never written: Engine.track)"""
+    if why not in (_capi.MS_MIDPOINT, _capi.MS_NAME):
+        return ValueError(str(mergefilter._refusal_at(where, why, text)).replace("fithic_amd.mergefilter", "fithic_amd.ucsc"))
+    if why == _capi.MS_MIDPOINT:
         return ValueError("%s: fragmentMid1 and fragmentMid2 (tokens 2 and 4) are expected as 1 to 9 digits without a sign: %r"
                           % (where, text[:80]) + _ACCEPTS)
     return ValueError("%s: a chromosome name (token 1 or 3) of more than 63 bytes: %r" % (where, text[:80]) + _ACCEPTS)

@@ -538,6 +538,40 @@ int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n
                            int32_t* why, int64_t* bad_line);
 int fhx_significant_copy_text(fhx_ctx* ctx, void* dst, int64_t capacity);     /* the n_bytes of the last selection */
 int fhx_significant_copy_rows(fhx_ctx* ctx, int64_t* rows, int64_t capacity); /* loaded-row numbers of the kept rows, ascending */
+/* The UCSC interact track of the pass taken from its resident columns (csrc/fhx_sigresident_track.inc): the text fhx_ms_track_file
+ * (below) makes of the file fhx_write_significances_device writes - the same bytes, the script's two fixed lines included, or the
+ * same refusal - without that file.  The decision is fhx_significant_select's with strict = 1 (key_bound and zero_kept as for
+ * fhx_ms_track_file); line 1 of that file is fithic's header, which the track drops, so the file route's n_lines is *n_emitted + 1.
+ * Same state rules as fhx_significant_select; a context without rows gives the two fixed lines.
+ *   *n_kept lines behind the fixed two, *n_deferred of them with a score written by the host, *n_bytes the whole text.
+ * Refused, nothing retrievable, FHX_ERR_UNSUPPORTED with *bad_line = the line the smallest such row has in the written file: an
+ * EMITTED row, kept or not, whose q is outside the grammar (*why = FHX_MS_FIELD), whose midpoint is outside 0 ... 999 999 999
+ * (FHX_MS_MIDPOINT) or whose name has more than 63 bytes (FHX_MS_NAME); a row with several faults reports the first of these.
+ * More than 2^31 - 1 kept rows: FHX_MS_KEPT, no line.  A KEPT row with a name of more than 24 bytes: FHX_ERR_UNSUPPORTED with
+ * *why = 0 - make the track from the written file instead.  The result of fhx_significant_select is left as it is. */
+int fhx_significant_track(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, const char* fdr_text, int32_t fdr_len,
+                          uint64_t key_bound, int32_t zero_kept, int64_t* n_emitted, int64_t* n_kept, int64_t* n_deferred,
+                          int64_t* n_bytes, int32_t* why, int64_t* bad_line);
+int fhx_significant_copy_track(fhx_ctx* ctx, void* dst, int64_t capacity);    /* the n_bytes of the last track */
+/* The per-chromosome FDR subsets of the pass taken from its resident columns (csrc/fhx_sigresident_split.inc): what
+ * fhx_ms_split_file (below) makes of the file fhx_write_significances_device writes - the same list, the same bytes per name, or
+ * the same refusal - without that file.  The list is field 1 of every line of that file: the literal `chr1` of fithic's header and
+ * the first chromosome of every emitted row (trans rows of an -x All or interOnly run included); a row goes to name c when it is
+ * emitted, both its chromosomes are c and `$7 <= fdr` holds (the decision of fhx_significant_select with strict = 0).  A listed
+ * name without such a row has an empty subset.  Same state rules as fhx_significant_select; a context without rows lists `chr1`.
+ *   *n_emitted as for fhx_significant_select; *n_listed names, in bytewise order.
+ * Refused, nothing retrievable, FHX_ERR_UNSUPPORTED with *bad_line = the line the smallest such row has in the written file: an
+ * EMITTED row, kept or not, one of whose names fhx_ms_split_file would refuse (FHX_MS_NAME, FHX_MS_NAME_BYTES,
+ * FHX_MS_NAME_NUMERIC; the first name before the second) or, after the names, whose q is outside the grammar (FHX_MS_FIELD).
+ * More than FHX_MS_SPLIT_NAMES listed names: FHX_MS_NAMES, no line.  A KEPT row the device formatter does not cover:
+ * FHX_ERR_UNSUPPORTED with *why = 0 - split the written file instead.  The results of fhx_significant_select and
+ * fhx_significant_track are left as they are. */
+int fhx_significant_split(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, const char* fdr_text, int32_t fdr_len,
+                          uint64_t key_bound, int32_t zero_kept, int64_t* n_emitted, int32_t* n_listed, int32_t* why, int64_t* bad_line);
+/* per listed name (capacity entries at least, either array may be NULL) its kept rows and their bytes */
+int fhx_significant_split_counts(fhx_ctx* ctx, int64_t* kept_rows, int64_t* kept_bytes, int32_t capacity);
+int fhx_significant_split_names(fhx_ctx* ctx, char* dst, int32_t capacity);   /* FHX_MS_SPLIT_NAME_BYTES per name, bytewise order */
+int fhx_significant_copy_split(fhx_ctx* ctx, int32_t index, void* dst, int64_t capacity);   /* the subset of name `index` */
 
 /* ---- Knight-Ruiz bias vectors (fithic/utils/HiCKRy.py; SURVEY 8f rank 4, the step before Fit-Hi-C) --------------------
  * One fhx_kr per GPU, independent of fhx_ctx.  Call order: load_loci -> load_pairs -> [remove_sparse] -> balance -> bias.
