@@ -209,6 +209,7 @@ SYMBOLS = {
     "fhx_kr_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "fhx_kr_load_loci": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, ctypes.c_int64]),
     "fhx_kr_load_pairs": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _F64P, ctypes.c_int64, _I64P]),
+    "fhx_kr_load_pairs_resident": (ctypes.c_int, [ctypes.c_void_p, _P, _I64P]),
     "fhx_kr_shape": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P, _I64P]),
     "fhx_kr_get_csr": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _I64P, _I32P, _F64P]),
     "fhx_kr_row_sums": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
@@ -1278,6 +1279,16 @@ class KrContext(_Handle):
         z = np.ascontiguousarray(value, np.float64)
         bad = ctypes.c_int64(-1)
         rc = self.L.fhx_kr_load_pairs(self.h, *[_ptr(v, ctypes.c_int32) for v in a], _ptr(z, ctypes.c_double), len(z), ctypes.byref(bad))
+        if rc == FHX_ERR_REFERENCE_EXIT and bad.value >= 0:
+            raise KeyError(bad.value)
+        self._chk(rc)
+
+    def load_pairs_resident(self, engine_ctx):
+        """The same matrix from the contact rows `engine_ctx` (a Context on this GPU) holds, loaded with the chromosome ids of
+        load_loci: KeyError(row) as load_pairs; FhxError(FHX_ERR_UNSUPPORTED) when a count of its text was not an integer as
+        written - load_pairs with the file's float counts then."""
+        bad = ctypes.c_int64(-1)
+        rc = self.L.fhx_kr_load_pairs_resident(self.h, engine_ctx._h, ctypes.byref(bad))
         if rc == FHX_ERR_REFERENCE_EXIT and bad.value >= 0:
             raise KeyError(bad.value)
         self._chk(rc)

@@ -65,7 +65,25 @@ def parse_args(argv=None):
                         help="engine option, with --significant: also write the tree <prefix>.fdr_split/<chr>/ of "
                              "utils/merge-filter-parallelized.sh - per chromosome its subset, its job file and (not with -r 0) its "
                              "postmerged file - from the q-values on the GPU")
+    parser.add_argument("--kr", dest="kr", action="store_true",
+                        help="engine option, not in the reference: compute the biases by Knight-Ruiz balancing of this run's contact "
+                             "counts, as utils/HiCKRy.py does before fithic.py, instead of reading them with -t; the matrix is made "
+                             "from the rows the GPU already holds (not with -t, not with --gpus above 1)")
+    parser.add_argument("--kr-percent", dest="kr_percent", type=float, default=None, metavar="X",
+                        help="engine option, with --kr: HiCKRy's -x, the share of the sparsest rows to remove. DEFAULT is 0.05")
+    parser.add_argument("--kr-output", dest="kr_output", default=None, metavar="PATH",
+                        help="engine option, with --kr: also write the bias file HiCKRy would have written to PATH")
     args = parser.parse_args(argv)
+    if args.kr_percent is not None and not args.kr:
+        parser.error("--kr-percent needs --kr")
+    if args.kr_output is not None and not args.kr:
+        parser.error("--kr-output needs --kr")
+    if args.kr and args.biasfile is not None:
+        parser.error("--kr computes the biases: it cannot be combined with -t BIASFILE")
+    if args.kr and args.gpus > 1:
+        parser.error("--kr is not available with --gpus above 1: each rank holds a part of the rows")
+    if args.kr_percent is None:
+        args.kr_percent = 0.05
     if args.significant_only and args.significant is None:
         parser.error("--significant-only needs --significant FDR")
     if args.significant_track and args.significant is None:
@@ -134,6 +152,8 @@ def main(argv=None):
         else:
             print("Bias file not found")
             sys.exit(2)
+    elif args.kr:
+        print("Biases will be computed from the contact counts by Knight-Ruiz balancing, removing %s of the sparsest rows" % args.kr_percent)
     else:
         print("No bias file")
     biasFile = args.biasfile
@@ -194,7 +214,10 @@ def main(argv=None):
         binStats = F.makeBinsFromInteractions(mainDic, noOfBins, observedIntraInRangeSum)
         (binStats, noOfFrags, maxPossibleGenomicDist, possibleIntraInRangeCount, possibleInterAllCount, interChrProb,
          baselineIntraChrProb) = F.generate_FragPairs(observedInterAllCount, observedInterAllSum, binStats, fragsFile, resolution)
-        biasDic = F.read_biases(biasFile) if biasFile else 0
+        if args.kr:
+            biasDic = F.kr_biases(fragsFile, args.kr_percent, args.kr_output)
+        else:
+            biasDic = F.read_biases(biasFile) if biasFile else 0
         (x, y, yerr) = F.calculateProbabilities(mainDic, binStats, resolution, os.path.join(outputPath, libName + ".fithic_pass1"),
                                                 observedIntraInRangeSum)
         t_first = time.time()

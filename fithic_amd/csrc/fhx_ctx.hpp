@@ -380,6 +380,10 @@ struct fhx_ctx {
     // pairs (device) + grid
     int64_t n_rows = 0;
     int32_t *d_loc1 = nullptr, *d_loc2 = nullptr, *d_count = nullptr;
+    // every count of the loaded rows was an integer as written: int32 arrays are (fhx_load_pairs, fhx_load_pairs_device); rows the
+    // device parser read are unless a count had a non-zero fractional digit (fhx_ingest.inc: F_FRACTION).  Only
+    // fhx_kr_load_pairs_resident asks: HiCKRy balances float(count), the rows hold int(float(count))
+    bool counts_integral = true;
     std::vector<ChrGrid> grid;
     ChrGrid* d_grid = nullptr;
     int16_t* d_slot_chr = nullptr;

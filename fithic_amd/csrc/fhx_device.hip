@@ -183,6 +183,7 @@ int fhx_load_pairs_device(fhx_ctx* ctx, const void* c1, const void* m1, const vo
     // context's own stream is non-blocking (no implicit ordering with the default stream), so this wait is what makes rows that
     // were just written by the caller's kernels safe to read here.
     FHX_HIP(hipStreamSynchronize((hipStream_t)stream));
+    ctx->counts_integral = true;                 // int32 columns (the commit of a parsed text says otherwise after this call)
     ctx->offgrid = false;
     ctx->nonfixed = ctx->have_params && ctx->prm.resolution == 0;
     if (ctx->have_params && ctx->nonfixed)
@@ -205,6 +206,7 @@ int fhx_load_pairs(fhx_ctx* ctx, const int32_t* chr1, const int32_t* mid1, const
         if (n) FHX_HIP(hipMemcpyAsync(d[k], h[k], (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     }
     FHX_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->counts_integral = true;
     ctx->offgrid = false;
     ctx->nonfixed = ctx->have_params && ctx->prm.resolution == 0;
     const int rc = (ctx->have_params && ctx->nonfixed) ? ingest_device_rows_nonfixed(ctx, d[0], d[1], d[2], d[3], d[4], n)

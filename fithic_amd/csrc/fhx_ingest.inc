@@ -16,7 +16,8 @@
 //
 // ONLY THE REGULAR FILE IS TAKEN: ASCII text, no NUL, no \r outside \r\n, five tokens per line, names of 1..63 bytes, midpoints
 // [+-]?digits (at most 10 digits, within int32), count = digits[.digits] (at most 15 digits, integer part within int32: the
-// reference's int(float(text)) is then the integer part as written).  Anything else - an underscore in a number, an exponent,
+// reference's int(float(text)) is then the integer part as written; a non-zero digit behind the point is remembered in the
+// context, fhx_ctx::counts_integral).  Anything else - an underscore in a number, an exponent,
 // a signed count, a sixth token, an empty line, a malformed line whose error the caller must see -
 // returns FHX_ERR_UNSUPPORTED before anything is loaded and the caller parses the same inflated text with
 // fhx_host_parse_text, whose grammar is Python's.  No row is ever parsed "approximately".
@@ -30,7 +31,8 @@ constexpr int TABLE_SLOTS = 16384;
 constexpr int MAX_NAMES = 8192;
 constexpr int NAME_STRIDE = 64;                // names of up to 63 bytes
 
-enum : unsigned int { F_BYTES = REFUSED_BYTES, F_LINE = 2u, F_TABLE = 4u, F_COLLISION = 8u };
+enum : unsigned int { F_BYTES = REFUSED_BYTES, F_LINE = 2u, F_TABLE = 4u, F_COLLISION = 8u,
+                      F_FRACTION = 16u };      // some count has a non-zero fractional digit: refuses nothing, the context remembers it
 
 __device__ inline bool is_space(int c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
 
@@ -96,9 +98,10 @@ struct Cursor {
     // int(float(text)) of digits[.digits] (either side of the point may be empty, not both): with at most 15 digits in all the
     // double nearest the decimal cannot reach the next integer (the gap to it is >= 10^(k-15) for k integer digits, half an ulp
     // is < 1.2 * 10^(k-16)), so the truncation is the integer part as written.  Signs, exponents, inf/nan: the host parser's.
-    __device__ bool count(int* out) {
+    __device__ bool count(int* out, bool* fraction) {
         long long v = 0;
         int ni = 0, nf = 0, c;
+        bool nonzero = false;
         for (;;) {
             c = at();
             if (c < '0' || c > '9') break;
@@ -112,12 +115,14 @@ struct Cursor {
                 c = at();
                 if (c < '0' || c > '9') break;
                 if (++nf > 15) return false;
+                nonzero |= c != '0';
                 ++p;
             }
         }
         if (ni + nf == 0 || ni + nf > 15 || !is_space(c)) return false;
         if (v > 2147483647ll) return false;
         *out = (int)v;
+        *fraction = nonzero;                                                 // "3.0", "3." and "03.000" are integers as written
         return true;
     }
 };
@@ -172,21 +177,22 @@ __global__ __launch_bounds__(WG) void ti_parse(const unsigned char* __restrict__
     const int n_lines = block_lines(text, T, lstart);
     const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
     const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
-    bool bad = false;
+    bool bad = false, fraction = false;
     for (int base = 0; base < n_lines; base += WG) {
         const int e = base + threadIdx.x;
         const bool active = e < n_lines;
         unsigned long long h1 = 0, h2 = 0;
         int64_t o1 = 0, o2 = 0;
         int l1, l2, m1 = 0, m2 = 0, cnt = 0;
-        bool ok = false;
+        bool ok = false, frac = false;
         if (active) {
             Cursor c{text, T, b0 + lstart[e], 0};
             c.limit = c.p + MAX_LINE;
             ok = c.next_token() && c.name(&h1, &o1, &l1) && c.next_token() && c.integer(&m1) && c.next_token() &&
-                 c.name(&h2, &o2, &l2) && c.next_token() && c.integer(&m2) && c.next_token() && c.count(&cnt);
+                 c.name(&h2, &o2, &l2) && c.next_token() && c.integer(&m2) && c.next_token() && c.count(&cnt, &frac);
             if (ok) ok = !c.next_token() && c.at() == '\n';                  // a sixth token, or a line longer than this path takes
             bad |= !ok;
+            fraction |= ok && frac;
         }
         const int s1 = wave_insert(ok, h1, o1, t_hash, t_off, flags);
         const int s2 = wave_insert(ok, h2, o2, t_hash, t_off, flags);
@@ -199,6 +205,7 @@ __global__ __launch_bounds__(WG) void ti_parse(const unsigned char* __restrict__
         }
     }
     if (bad) atomicOr(flags, F_LINE);
+    if (fraction) atomicOr(flags, F_FRACTION);
 }
 
 __global__ void ti_fetch_names(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ offs, int n,
@@ -280,6 +287,7 @@ struct fhx_ctx::TextIngest {
     int64_t n_rows = 0;
     int32_t *d_mid1 = nullptr, *d_mid2 = nullptr, *d_count = nullptr;
     unsigned int* d_slots = nullptr;
+    bool fraction = false;                     // F_FRACTION: d_count holds the integer part of some count that had more
     std::vector<std::string> names;            // order of first appearance
     std::vector<int> name_slot;                // table slot of each
     ~TextIngest() {
@@ -364,6 +372,7 @@ static int ingest_parse_resident(fhx_ctx* ctx, DeviceScratch& tmp, unsigned char
     mark("parse");
     if (flags & F_LINE) return refuse("a line that is not `name int name int digits`");
     if (flags & F_TABLE) return refuse("more chromosome names than the device table holds");
+    st->fraction = (flags & F_FRACTION) != 0;
     std::vector<std::pair<unsigned long long, int>> seen;                   // (first offset, slot)
     for (int s = 0; s < TABLE_SLOTS; ++s)
         if (t_hash[s]) seen.emplace_back(t_off[s], s);
@@ -656,6 +665,7 @@ static int ingest_contacts_commit_timed(fhx_ctx* ctx, const int32_t* ids, int32_
         ~Drop() { ingest_drop(c); }
     } drop{ctx};
     const int64_t n = st->n_rows;
+    const bool fraction = st->fraction;
     std::vector<int32_t> slot_id(TABLE_SLOTS, -1);
     for (int i = 0; i < n_ids; ++i) slot_id[(size_t)st->name_slot[(size_t)i]] = ids[i];
     DeviceScratch tmp;
@@ -673,6 +683,7 @@ static int ingest_contacts_commit_timed(fhx_ctx* ctx, const int32_t* ids, int32_
     *t_map = since();
     // an empty text holds no columns: any valid pointer stands in for them
     const int rc = fhx_load_pairs_device(ctx, d_c1, n ? st->d_mid1 : d_c1, d_c2, n ? st->d_mid2 : d_c1, n ? st->d_count : d_c1, n, nullptr);
+    if (rc == FHX_OK) ctx->counts_integral = !fraction;
     *t_load = since() - *t_map;
     return rc;
 }
@@ -797,6 +808,7 @@ int fhx_ingest_contacts_commit_shard(fhx_ctx* ctx, const int32_t* ids, const uin
         ~Drop() { ingest_drop(c); }
     } drop{ctx};
     const int64_t n = st->n_rows;
+    const bool fraction = st->fraction;        // (of any row of the text, kept here or not)
     std::vector<int32_t> slot_id(TABLE_SLOTS, -1);
     std::vector<unsigned char> slot_mine(TABLE_SLOTS, 0);
     for (int i = 0; i < n_ids; ++i) {
@@ -848,6 +860,7 @@ int fhx_ingest_contacts_commit_shard(fhx_ctx* ctx, const int32_t* ids, const uin
     st->d_mid1 = st->d_mid2 = st->d_count = nullptr;
     int rc = fhx_load_pairs_device(ctx, o[0], o[1], o[2], o[3], o[4], (int64_t)total, nullptr);
     if (rc != FHX_OK) return rc;
+    ctx->counts_integral = !fraction;
     // file positions: the -p >= 3 semantics (fhx_set_global_rows), the order of the significances file, the outlier line numbers
     dev_free(ctx->d_grow);
     const size_t gcap = std::max<size_t>(4, ((size_t)total + 3) / 4 * 4);

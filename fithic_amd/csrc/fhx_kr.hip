@@ -7,6 +7,7 @@
 //   balance    HiCKRy.py:139-243  Newton / conjugate-gradient iteration; one SpMV per inner step, everything else is
 //                                 n-sized vector work; the control flow (thresholds, breaks) runs on the host on scalars
 //   bias       HiCKRy.py:103-115  (1/x) / mean(1/x), -1 at the removed rows
+//   resident   fhx_kr_resident.inc  the same assembly from the rows an engine context holds in HBM (`fithic --kr`)
 //
 // HBM layout: CSR with int64 indptr, int32 column, double value (12 B per stored cell); all vectors double.
 // The dominant kernel is kr_spmv: one wave64 per row, four consecutive cells per lane (16-byte column and value loads, a wave
@@ -31,8 +32,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/fithic_mi355x.h"
-#include "fhx_scan.hpp"
+#include "fhx_ctx.hpp"                  // the engine's context: fhx_kr_load_pairs_resident reads its resident rows
 
 namespace krd {
 
@@ -432,8 +432,10 @@ __global__ __launch_bounds__(THREADS) void kr_lookup(int64_t m, const int32_t* c
 using fhxscan::block_exclusive_scan;
 using fhxscan::is_head;
 
-// every run head adds its run one by one (stable sort => file order) and writes one CSR cell
-__global__ __launch_bounds__(THREADS) void kr_emit_cells(const unsigned long long* keys, const unsigned int* perm, const double* z,
+// every run head adds its run one by one (stable sort => file order) and writes one CSR cell.  ZT = double: the values of
+// fhx_kr_load_pairs; int32_t: the engine's resident counts, widened here (fhx_kr_resident.inc)
+template <typename ZT>
+__global__ __launch_bounds__(THREADS) void kr_emit_cells(const unsigned long long* keys, const unsigned int* perm, const ZT* z,
                                                          int64_t m, int64_t N, int64_t n, const unsigned long long* tile_offsets,
                                                          unsigned long long* cell_key, int32_t* col, double* val) {
     const int64_t base = (int64_t)blockIdx.x * TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
@@ -450,10 +452,10 @@ __global__ __launch_bounds__(THREADS) void kr_emit_cells(const unsigned long lon
         const int64_t i = base + k;
         const unsigned long long key = keys[i];
         unsigned int src = perm[i];
-        double s = z[src >= m ? src - m : src];
+        double s = (double)z[src >= m ? src - m : src];
         for (int64_t j = i + 1; j < N && keys[j] == key; ++j) {
             src = perm[j];
-            s = s + z[src >= m ? src - m : src];
+            s = s + (double)z[src >= m ? src - m : src];
         }
         cell_key[pos] = key;
         col[pos] = (int32_t)(key % (unsigned long long)n);
@@ -682,6 +684,59 @@ double numpy_sum(const double* a, int64_t n) {
     return acc;
 }
 
+// The 2m cell keys of m rows (row i: keys[i] and keys[m + i]; freed here) -> the CSR of the full matrix: stable sort, run heads,
+// one cell per run with the values z[row] of the run added in row order, row pointers.  kr->d_indptr is allocated by the caller.
+template <typename ZT>
+int assemble_cells(fhx_kr* kr, unsigned long long*& keys, const ZT* z, int64_t m) {
+    const int64_t n = kr->n_full, N = 2 * m;
+    unsigned long long *skeys = nullptr, *tile_off = nullptr, *cell_key = nullptr;
+    unsigned int *perm = nullptr, *tile_cnt = nullptr;
+    auto cleanup = [&]() {
+        kfree(keys); kfree(skeys); kfree(tile_off); kfree(cell_key); kfree(perm); kfree(tile_cnt);
+    };
+#define KR_TRY(call)                                                                                         \
+    do {                                                                                                     \
+        hipError_t e_ = (call);                                                                              \
+        if (e_ != hipSuccess) {                                                                              \
+            cleanup();                                                                                       \
+            return kfail(kr, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));                \
+        }                                                                                                    \
+    } while (0)
+    // stable sort of the 2m cell keys
+    KR_TRY(hipMalloc(&skeys, (size_t)N * 8));
+    KR_TRY(hipMalloc(&perm, (size_t)N * 4));
+    const int rc = fhx_sort_u64(kr->sorter, keys, N, skeys, perm);
+    if (rc != FHX_OK) {
+        cleanup();
+        return kfail(kr, rc, std::string("sort: ") + fhx_last_error(kr->sorter));
+    }
+    kfree(keys);
+    // run heads -> cells
+    const int64_t tiles = (N + krd::TILE - 1) / krd::TILE;
+    KR_TRY(hipMalloc(&tile_cnt, (size_t)tiles * 4));
+    KR_TRY(hipMalloc(&tile_off, (size_t)tiles * 8));
+    hipLaunchKernelGGL(fhxscan::count_heads, dim3((unsigned)tiles), dim3(krd::THREADS), 0, kr->stream, skeys, N, tile_cnt);
+    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(krd::THREADS), 0, kr->stream, tile_cnt, tiles, tile_off, kr->d_counter + 1);
+    KR_TRY(hipGetLastError());
+    unsigned long long nnz = 0;
+    KR_TRY(hipMemcpyAsync(&nnz, kr->d_counter + 1, 8, hipMemcpyDeviceToHost, kr->stream));
+    KR_TRY(hipStreamSynchronize(kr->stream));
+    KR_TRY(hipMalloc(&cell_key, (size_t)nnz * 8));
+    KR_TRY(hipMalloc(&kr->d_col, (size_t)(nnz + krd::KR_PAD) * 4));
+    KR_TRY(hipMalloc(&kr->d_val, (size_t)(nnz + krd::KR_PAD) * 8));
+    hipLaunchKernelGGL(krd::kr_emit_cells<ZT>, dim3((unsigned)tiles), dim3(krd::THREADS), 0, kr->stream, skeys, perm, z, m, N, n, tile_off,
+                       cell_key, kr->d_col, kr->d_val);
+    hipLaunchKernelGGL(krd::kr_indptr, dim3((unsigned)std::min<int64_t>((n + 256) / 256, 4096)), dim3(256), 0, kr->stream, cell_key,
+                       (int64_t)nnz, n, kr->d_indptr);
+    KR_TRY(hipGetLastError());
+    KR_TRY(hipStreamSynchronize(kr->stream));
+    cleanup();
+#undef KR_TRY
+    kr->nnz_full = kr->nnz = (int64_t)nnz;
+    kr->n = n;
+    return FHX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -760,12 +815,9 @@ int fhx_kr_load_pairs(fhx_kr* kr, const int32_t* chr1, const int32_t* mid1, cons
     }
     int32_t *c1 = nullptr, *m1 = nullptr, *c2 = nullptr, *m2 = nullptr, *lidx = nullptr;
     double* z = nullptr;
-    unsigned long long *keys = nullptr, *skeys = nullptr, *lkeys = nullptr, *tile_off = nullptr, *cell_key = nullptr;
-    unsigned int *perm = nullptr, *tile_cnt = nullptr;
-    int rc = FHX_OK;
+    unsigned long long *keys = nullptr, *lkeys = nullptr;
     auto cleanup = [&]() {
-        kfree(c1); kfree(m1); kfree(c2); kfree(m2); kfree(lidx); kfree(z); kfree(keys); kfree(skeys); kfree(lkeys);
-        kfree(tile_off); kfree(cell_key); kfree(perm); kfree(tile_cnt);
+        kfree(c1); kfree(m1); kfree(c2); kfree(m2); kfree(lidx); kfree(z); kfree(keys); kfree(lkeys);
     };
 #define KR_TRY(call)                                                                                         \
     do {                                                                                                     \
@@ -808,39 +860,10 @@ int fhx_kr_load_pairs(fhx_kr* kr, const int32_t* chr1, const int32_t* mid1, cons
         return kfail(kr, FHX_ERR_REFERENCE_EXIT, "row " + std::to_string(missing) +
                      " names a locus that is not in the fragments file (the reference raises KeyError, HiCKRy.py:44-45)");
     }
-    // stable sort of the 2m cell keys
-    KR_TRY(hipMalloc(&skeys, (size_t)N * 8));
-    KR_TRY(hipMalloc(&perm, (size_t)N * 4));
-    rc = fhx_sort_u64(kr->sorter, keys, N, skeys, perm);
-    if (rc != FHX_OK) {
-        cleanup();
-        return kfail(kr, rc, std::string("sort: ") + fhx_last_error(kr->sorter));
-    }
-    kfree(keys);
-    // run heads -> cells
-    const int64_t tiles = (N + krd::TILE - 1) / krd::TILE;
-    KR_TRY(hipMalloc(&tile_cnt, (size_t)tiles * 4));
-    KR_TRY(hipMalloc(&tile_off, (size_t)tiles * 8));
-    hipLaunchKernelGGL(fhxscan::count_heads, dim3((unsigned)tiles), dim3(krd::THREADS), 0, kr->stream, skeys, N, tile_cnt);
-    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(krd::THREADS), 0, kr->stream, tile_cnt, tiles, tile_off, kr->d_counter + 1);
-    KR_TRY(hipGetLastError());
-    unsigned long long nnz = 0;
-    KR_TRY(hipMemcpyAsync(&nnz, kr->d_counter + 1, 8, hipMemcpyDeviceToHost, kr->stream));
-    KR_TRY(hipStreamSynchronize(kr->stream));
-    KR_TRY(hipMalloc(&cell_key, (size_t)nnz * 8));
-    KR_TRY(hipMalloc(&kr->d_col, (size_t)(nnz + krd::KR_PAD) * 4));
-    KR_TRY(hipMalloc(&kr->d_val, (size_t)(nnz + krd::KR_PAD) * 8));
-    hipLaunchKernelGGL(krd::kr_emit_cells, dim3((unsigned)tiles), dim3(krd::THREADS), 0, kr->stream, skeys, perm, z, m, N, n, tile_off,
-                       cell_key, kr->d_col, kr->d_val);
-    hipLaunchKernelGGL(krd::kr_indptr, dim3((unsigned)std::min<int64_t>((n + 256) / 256, 4096)), dim3(256), 0, kr->stream, cell_key,
-                       (int64_t)nnz, n, kr->d_indptr);
-    KR_TRY(hipGetLastError());
-    KR_TRY(hipStreamSynchronize(kr->stream));
-    cleanup();
 #undef KR_TRY
-    kr->nnz_full = kr->nnz = (int64_t)nnz;
-    kr->n = n;
-    return FHX_OK;
+    const int rc = assemble_cells(kr, keys, (const double*)z, m);       // sort, run heads, cells, row pointers
+    cleanup();
+    return rc;
 }
 
 int fhx_kr_shape(const fhx_kr* kr, int64_t* n_full, int64_t* nnz_full, int64_t* n_reduced, int64_t* nnz_reduced) {
@@ -1228,3 +1251,5 @@ int fhx_kr_bias(fhx_kr* kr, double* bias) {
 }
 
 }  // extern "C"
+
+#include "fhx_kr_resident.inc"          // fhx_kr_load_pairs_resident: the matrix from an engine context's resident rows

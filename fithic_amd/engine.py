@@ -211,6 +211,31 @@ class Engine:
         return mergefilter_parallel.Split({name: sub for name, _, sub in parts}, {name: kept for name, kept, _ in parts}, emitted + 1,
                                           {"significant_split": time.perf_counter() - t0}, self.device)
 
+    def kr_bias(self, frag_chr, frag_mid, perc=0.05, tol=1e-6, echo=False):
+        """The Knight-Ruiz bias vector of HiCKRy (fithic/utils/HiCKRy.py) from the contact rows resident in this engine
+        (csrc/fhx_kr_resident.inc): what hickry.loadfastfithicInteractions + returnBias give for the file the rows came from,
+        bit for bit, without reading it again.  frag_chr, frag_mid: the fragment lines, chromosome ids as the rows were loaded
+        with.  Returns (bias, one value per fragment line with -1 at the removed rows; the fhx_kr_info as a dict).  Every
+        loaded row counts whatever the passes have skipped; the rows and the pass state are left as they are.  `echo`: print
+        HiCKRy's lines.  KeyError(row) for a row whose locus is no fragment line; _capi.FhxError with code
+        FHX_ERR_UNSUPPORTED when a count of the contacts text was not an integer as written - the matrix is then the file's
+        (hickry.loadfastfithicInteractions)."""
+        import contextlib
+        import io
+        from . import hickry
+        t0 = time.time()
+        kr = _capi.KrContext(self.device)
+        try:
+            kr.load_loci(frag_chr, frag_mid)
+            kr.load_pairs_resident(self.ctx)
+            with contextlib.nullcontext() if echo else contextlib.redirect_stdout(io.StringIO()):
+                print("Creating sparse matrix...")                  # (said once it exists: a refusal leaves the lines to the file route)
+                print("Sparse matrix creation took %s seconds" % (time.time() - t0))
+                bias, info = hickry._bias_and_info(hickry.DeviceMatrix(kr), perc, tol)
+            return bias.reshape(-1), info
+        finally:
+            kr.close()
+
     def next_pass(self):
         """Fold this pass's outliers (p < 1/N) into the skip mask and the outlier-distance multiset."""
         return self.ctx.next_pass()

@@ -9,6 +9,7 @@ its files in every stage: `resolution` (the engine needs the fixed-size grid bef
     makeBinsFromInteractions(mainDic, noOfBins, observedIntraInRangeSum, outliersdist=None)        :463
     generate_FragPairs(observedInterAllCount, observedInterAllSum, binStats, fragsfile, resolution) :561
     read_biases(infilename)                                                                         :798
+    kr_biases(fragsfile, perc, output=None)                  in its place under --kr: fithic/utils/HiCKRy.py on this run's rows
     calculateProbabilities(mainDic, binStats, resolution, outfilename, observedIntraInRangeSum)     :843
     fit_Spline(mainDic, x, y, yerr, infilename, outfilename, biasDic, outliersline, outliersdist, ...)  :925
     benjamini_hochberg_correction(p_values, num_total_tests)                   fithic/myStats.py:24
@@ -452,16 +453,65 @@ def read_biases(infilename):
     t0 = time.time()
     S = _S
     bc, bm, bv = tables.read_bias(infilename, S.chroms)
+    out = _adopt_biases(S, bc, bm, bv, infilename)
+    print("Bias file read. Time took %s" % (time.time() - t0))
+    return out
+
+
+def _adopt_biases(S, bc, bm, bv, source):
+    """the bias rows into the engine, read_biases' lines into the log -> the lazy {chrom: {mid: bias}}"""
     S.configure()
     S.engine.load_bias(bc, bm, bv)
-    S.bias_path, S.bias_loaded = infilename, True
+    S.bias_path, S.bias_loaded = source, True
     bot, med, top = tables.bias_quantiles(bv)
     _log("5th quantile of biases: %s\n50th quantile of biases: %s\n95th quantile of biases: %s\n" % (bot, med, top))
     vals = np.where((bv < biasLowerBound) | np.isnan(bv) | (bv > biasUpperBound), -1.0, bv)
     discard = int(((bv < biasLowerBound) | np.isnan(bv) | (bv > biasUpperBound)).sum())
     out = _BiasDic((list(S.chroms.names), bc, bm, vals), len(bv))
     _log("Out of %s loci %s were discarded with biases not in range [%s-%s]\n\n" % (len(bv), discard, biasLowerBound, biasUpperBound))
-    print("Bias file read. Time took %s" % (time.time() - t0))
+    return out
+
+
+def kr_biases(fragsfile, perc=0.05, output=None):
+    """cli --kr, where read_biases stands: the Knight-Ruiz biases of HiCKRy (fithic/utils/HiCKRy.py, `-x perc`) computed from the
+    contacts of this run instead of read from a file.  Loads them into the engine, prints HiCKRy's lines as hickry.main does, writes
+    read_biases' lines into the log and returns the same lazy {chrom: {mid: bias}}; with `output` the bias file HiCKRy would have
+    written is written too (hickry.outputBias: reading it back gives the same doubles, so `-t output` repeats this run).
+      resident  Engine.kr_bias: the matrix is assembled from the rows the GPU parsed for this run (csrc/fhx_kr_resident.inc);
+      file      hickry.loadfastfithicInteractions on the contacts file: a sharded engine, rows that came through the host parser, or
+                a count that was not an integer as written (HiCKRy balances float(count), the engine's rows hold int(float(count))).
+    The same bias, bit for bit, either way."""
+    from . import hickry
+    S = _S
+    t0 = time.time()
+    if S.engine is None or S.contacts is None:
+        raise ValueError("fithic_amd: kr_biases needs read_Interactions first (the biases are computed from its contact rows)")
+    if S.frags_path == fragsfile:
+        fc, fm, _ = S.frag_table
+    else:
+        fc, fm, _ = tables.read_fragments(fragsfile, S.chroms)
+    route, bias = "file", None
+    if hasattr(S.engine, "kr_bias") and hasattr(S.contacts, "rows"):      # one GPU holds every row, parsed by the device
+        try:
+            bias, _ = S.engine.kr_bias(fc, fm, perc, echo=True)
+            route = "resident"
+        except _capi.FhxError as e:
+            if e.code != _capi.FHX_ERR_UNSUPPORTED:
+                raise
+    if bias is None:
+        hickry.device = device
+        matrix, _ = hickry.loadfastfithicInteractions(S.contacts_path, fragsfile)
+        try:
+            bias = hickry.returnBias(matrix, perc).reshape(-1)
+        finally:
+            matrix.kr.close()
+    hickry.checkBias(bias)
+    if output:
+        names = S.chroms.names
+        hickry.outputBias(bias, [(names[c], int(m)) for c, m in zip(fc.tolist(), fm.tolist())], output)
+    out = _adopt_biases(S, fc, fm, np.ascontiguousarray(bias, np.float64), output)
+    print("stage: Knight-Ruiz biases of %d loci took %.3f s (%s)"
+          % (len(bias), time.time() - t0, "resident rows" if route == "resident" else "contacts file"))
     return out
 
 

@@ -98,6 +98,11 @@ def loadfastfithicInteractions(interactionsFile, fragsFile):
 
 def returnBias(rawMatrix, perc):
     """HiCKRy.py:56-72."""
+    return _bias_and_info(rawMatrix, perc)[0]
+
+
+def _bias_and_info(rawMatrix, perc, tol=1e-6):
+    """returnBias, and the fhx_kr_info of its balance as a dict (Engine.kr_bias hands both out)"""
     mtxAndRemoved = removeZeroDiagonalCSR(rawMatrix, perc)
     print("Sparse rows removed")
     initialSize = rawMatrix.shape
@@ -106,8 +111,8 @@ def returnBias(rawMatrix, perc):
     newSize = rawMatrix.shape
     print("New matrix size: %s rows and %s columns" % (newSize[0], newSize[1]))
     print("Normalizing with KR Algorithm")
-    knightRuizAlg(rawMatrix)
-    return rawMatrix.kr.bias().reshape(-1, 1)            # computeBiasVector + addZeroBiases, on the engine's x
+    knightRuizAlg(rawMatrix, tol)
+    return rawMatrix.kr.bias().reshape(-1, 1), rawMatrix.info   # computeBiasVector + addZeroBiases, on the engine's x
 
 
 def removeZeroDiagonalCSR(mtx, perc):

@@ -574,7 +574,8 @@ int fhx_significant_split_names(fhx_ctx* ctx, char* dst, int32_t capacity);   /*
 int fhx_significant_copy_split(fhx_ctx* ctx, int32_t index, void* dst, int64_t capacity);   /* the subset of name `index` */
 
 /* ---- Knight-Ruiz bias vectors (fithic/utils/HiCKRy.py; SURVEY 8f rank 4, the step before Fit-Hi-C) --------------------
- * One fhx_kr per GPU, independent of fhx_ctx.  Call order: load_loci -> load_pairs -> [remove_sparse] -> balance -> bias.
+ * One fhx_kr per GPU, independent of fhx_ctx.  Call order: load_loci -> load_pairs (or load_pairs_resident) -> [remove_sparse] ->
+ * balance -> bias.
  * Summation orders are fixed by the kernels (csrc/fhx_kr.hip header) and restated by oracle/kr_oracle.c. */
 typedef struct fhx_kr fhx_kr;
 typedef struct fhx_kr_info {
@@ -598,6 +599,15 @@ int fhx_kr_load_loci(fhx_kr* kr, const int32_t* chr, const int32_t* mid, int64_t
  * locus is not in the fragments file returns FHX_ERR_REFERENCE_EXIT (KeyError) and its row number. */
 int fhx_kr_load_pairs(fhx_kr* kr, const int32_t* chr1, const int32_t* mid1, const int32_t* chr2, const int32_t* mid2,
                       const double* value, int64_t m, int64_t* first_unknown_row);
+/* The same matrix from the contact rows an engine context holds on the same device (HiCKRy.py:18-54 without a second read of
+ * the interactions file; csrc/fhx_kr_resident.inc): fhx_kr_load_loci has run with the fragment lines, whose chromosome ids are
+ * the ids the context's rows were loaded with.  Every loaded row enters the matrix, whatever the pass state and the contact
+ * type; neither the rows nor the pass state change.  On success the context is in the state fhx_kr_load_pairs leaves for the same
+ * rows, bit for bit.  FHX_ERR_ARG: no rows, or another device.  FHX_ERR_REFERENCE_EXIT: as fhx_kr_load_pairs, the row being the
+ * file position where the context carries them (fhx_set_global_rows).  FHX_ERR_UNSUPPORTED: some count of the contacts text
+ * had a non-zero fractional digit ("3.5"; "3.0" and "3." are integers) - HiCKRy balances float(count), the rows hold
+ * int(float(count)): use fhx_kr_load_pairs.  Rows given as int32 arrays (fhx_load_pairs, fhx_load_pairs_device) are integers. */
+int fhx_kr_load_pairs_resident(fhx_kr* kr, fhx_ctx* ctx, int64_t* first_unknown_row);
 int fhx_kr_shape(const fhx_kr* kr, int64_t* n_full, int64_t* nnz_full, int64_t* n_reduced, int64_t* nnz_reduced);
 /* which 0 = raw matrix, 1 = after remove_sparse; any output pointer may be NULL */
 int fhx_kr_get_csr(fhx_kr* kr, int32_t which, int64_t* indptr, int32_t* col, double* val);
