@@ -115,6 +115,8 @@ SYMBOLS = {
     "fhx_bh_sort_stats": (ctypes.c_int, [_P, _I64P]),
     "fhx_k3_pass_info": (ctypes.c_int, [_P, _I64P]),
     "fhx_debug_k3_tiles_per_group": (ctypes.c_int, [_P, ctypes.c_int]),
+    "fhx_debug_k1_wide": (ctypes.c_int, [_P, ctypes.c_int]),
+    "fhx_k3_compact_variant": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32)]),
     "fhx_kernel_seconds": (ctypes.c_int, [_P, _F64P, _F64P, _F64P]),
     "fhx_kernel_seconds_total": (ctypes.c_int, [_P, _F64P, _I64P, ctypes.c_int]),
     "fhx_kernel_events_dropped": (ctypes.c_int, [_P, _I64P]),
@@ -840,14 +842,21 @@ class Context:
                         [int(v) for v in n]))
 
     def k3_pass_info(self):
-        """which path the last bh() took through K3: the eight slots of fhx_k3_pass_info (include/fithic_mi355x.h)"""
+        """which path the last bh() took through K3: the eight slots of fhx_k3_pass_info and, as a ninth, fhx_k3_compact_variant
+        (include/fithic_mi355x.h)"""
         n = (ctypes.c_int64 * 8)()
         self._check(self._L.fhx_k3_pass_info(self._h, n))
-        return [int(v) for v in n]
+        v = ctypes.c_int32(0)
+        self._check(self._L.fhx_k3_compact_variant(self._h, ctypes.byref(v)))       # [8]: 0 / 1 / 2, the sparse compaction
+        return [int(x) for x in n] + [v.value]
 
     def debug_k3_tiles_per_group(self, per):
         """test hook (fhx_debug_k3_tiles_per_group): 1..4 tiles per workgroup in the scattered compaction, 0: the library's choice"""
         self._check(self._L.fhx_debug_k3_tiles_per_group(self._h, int(per)))
+
+    def debug_k1_wide(self, on):
+        """test hook (fhx_debug_k1_wide): True makes pass_stats read the three int32 columns instead of the key column"""
+        self._check(self._L.fhx_debug_k1_wide(self._h, 1 if on else 0))
 
     def kernel_events_dropped(self):
         """passes of K1, K2, K3, heavy launch whose events were overwritten unread since the last reset (0 = the sums are complete)"""

@@ -214,6 +214,9 @@ struct DeviceWords {
     unsigned long long k2_next[K2_COUNTER_WORDS - 1];
     // k3_cutoff's decision: this pass takes q through the dense array (fhx_k3.hip: DenseQ).  written and read inside fhx_bh
     alignas(128) unsigned long long k3_dense;
+    // k3_cutoff's other decision: so few rows lie below the cutoff that k3_compact_sparse does the compaction.  written (auto_cutoff's
+    // launch) and read inside fhx_bh; fhx_k3_compact_variant reads it afterwards
+    unsigned long long k3_sparse;
     // fhx_get_array(FHX_A_FDR_COUNTS): zeroed there, filled by launch_fdr_hist, copied to the host, all in that call
     alignas(128) unsigned long long fdr_buckets[FDR_BUCKETS];
 };
@@ -380,6 +383,12 @@ struct fhx_ctx {
     // pairs (device) + grid
     int64_t n_rows = 0;
     int32_t *d_loc1 = nullptr, *d_loc2 = nullptr, *d_count = nullptr;
+    // K1's key column (fhx_k1key.hpp), fixed-size mode only: 4 B per row that hold what k1_classify_hist needs of the three columns.
+    // k1key_valid: k0_slots wrote it for the rows the three columns hold now (alloc_row_arrays clears it; a writer of the columns
+    // that does not write keys leaves it cleared and K1 reads the columns)
+    uint32_t* d_k1key = nullptr;
+    bool k1key_valid = false;
+    bool k1_force_wide = false;                       // fhx_debug_k1_wide (tests): launch_k1 runs the three-column kernel
     // every count of the loaded rows was an integer as written: int32 arrays are (fhx_load_pairs, fhx_load_pairs_device); rows the
     // device parser read are unless a count had a non-zero fractional digit (fhx_ingest.inc: F_FRACTION).  Only
     // fhx_kr_load_pairs_resident asks: HiCKRy balances float(count), the rows hold int(float(count))
@@ -490,6 +499,7 @@ struct fhx_ctx {
     // [1] survivors by the histogram, [3] tiles per workgroup of k3_compact<false>, [4] sort taken, [5] far_below, [6] q_is_ones
     int64_t k3_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool have_k3_info = false;
+    bool k3_sparse_enqueued = false;                  // the last fhx_bh launched k3_compact_sparse beside k3_compact<false> (fhx_k3_compact_variant)
     int k3_force_per = 0;                             // fhx_debug_k3_tiles_per_group (tests): 1..4 replaces compact_pvalues' choice, 0: none
     std::vector<int64_t> fdr_counts;
     fhx::DistState* dist = nullptr;                 // communicator + exchange buffers of sharded runs (fhx_dist.inc)
@@ -680,7 +690,8 @@ void launch_rs_scan(fhx_ctx* ctx, int nblk);                     // exclusive sc
 int fill_top_hist(fhx_ctx* ctx);
 // the one launch site of each of these kernels; what a caller does not use is spelled out: null pointers, dense_min ~0, n_bound -1
 void launch_k3_cutoff(fhx_ctx* ctx, const unsigned long long* hist, double n_tests, unsigned long long* d_cutoff,
-                      unsigned long long* n_below, unsigned long long dense_min, unsigned long long* dense_flag, const CutoffToHost& host);
+                      unsigned long long* n_below, unsigned long long dense_min, unsigned long long* dense_flag, const CutoffToHost& host,
+                      unsigned long long sparse_max = 0, unsigned long long* sparse_flag = nullptr);
 void launch_bh_tile_max(fhx_ctx* ctx, int tiles, const unsigned long long* keys, const unsigned long long* n_ptr, int64_t n_fixed,
                         double n_tests, double rank0, double* tile_max);
 void launch_bh_scan_tiles(fhx_ctx* ctx, double* tile_max, const unsigned long long* n_ptr, int64_t n_fixed, double carry_in,

@@ -64,6 +64,7 @@ void fhx_destroy(fhx_ctx* ctx) {
         dev_free(ctx->d_loc1);
         dev_free(ctx->d_loc2);
         dev_free(ctx->d_count);
+        dev_free(ctx->d_k1key);
         dev_free(ctx->d_grid);
         dev_free(ctx->d_slot_chr);
         dev_free(ctx->d_slot_bias);

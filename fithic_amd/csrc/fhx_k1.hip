@@ -2,6 +2,7 @@
 // fithic/fithic.py:389-454), the -r 0 / off-grid slotting by sort + run detection, the per-row device arrays
 // (one of the device translation units of libfithic_mi355x.so; shared declarations: fhx_ctx.hpp)
 #include "fhx_ctx.hpp"
+#include "fhx_k1key.hpp"
 
 namespace fhx {
 
@@ -49,15 +50,19 @@ __global__ void k0_extent(const int32_t* __restrict__ chr, const int32_t* __rest
 __global__ void k0_slots(const int32_t* __restrict__ chr1, const int32_t* __restrict__ mid1,
                          const int32_t* __restrict__ chr2, const int32_t* __restrict__ mid2,
                          const int32_t* __restrict__ cnt, int64_t n, int res, const ChrGrid* __restrict__ grid,
-                         int32_t* __restrict__ loc1, int32_t* __restrict__ loc2, int32_t* __restrict__ count) {
+                         int32_t* __restrict__ loc1, int32_t* __restrict__ loc2, int32_t* __restrict__ count,
+                         uint32_t* __restrict__ key) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const int c1 = chr1[i], c2 = chr2[i];
         const int s1 = grid[c1].base + mid1[i] / res;
         const int s2 = grid[c2].base + mid2[i] / res;
+        const int l2 = (c1 == c2) ? s2 : ~s2;     // sign bit carries "inter-chromosomal"
+        const int c = cnt[i];
         loc1[i] = s1;
-        loc2[i] = (c1 == c2) ? s2 : ~s2;          // sign bit carries "inter-chromosomal"
-        count[i] = cnt[i];
+        loc2[i] = l2;
+        count[i] = c;
+        key[i] = k1key::pack_row(s1, l2, c);      // what K1 reads of the row, in 4 bytes instead of 12 (fhx_k1key.hpp)
     }
 }
 
@@ -76,10 +81,14 @@ constexpr int K1_LDS_BINS = 6144;      // 6144 * (8 + 4) B = 72 KiB -> two workg
 constexpr int K1_WIDE_BINS = 24576;
 constexpr int K1_WIDE_THREADS = 1024;
 
-template <int THREADS, bool WIDE>
+// KEYED = true (every pass of a fixed-size run): a row is its 32-bit key (fhx_k1key.hpp, written by k0_slots) - 4 B per row where
+// the three columns are 12, and those 12 were the whole kernel: 1.78 GB in 0.31 ms on C3, the HBM read rate.  A key with the
+// escape bit sends its row to the three columns, inside a branch.  KEYED = false reads the columns for every row: the kernel as it
+// was, kept as the reference of tests/test_gpu_k1_keys.py (fhx_debug_k1_wide) and for row sets nobody wrote keys for.
+template <int THREADS, bool WIDE, bool KEYED>
 __global__ __launch_bounds__(THREADS) void k1_classify_hist(
     const int32_t* __restrict__ loc1, const int32_t* __restrict__ loc2, const int32_t* __restrict__ count,
-    const uint8_t* __restrict__ skip, int64_t skip_limit, const long long* __restrict__ grow, int64_t n, int lo_idx,
+    const uint32_t* __restrict__ key, const uint8_t* __restrict__ skip, int64_t skip_limit, const long long* __restrict__ grow, int64_t n, int lo_idx,
     int hi_idx,
     unsigned long long* __restrict__ hist_sumcc, unsigned long long* __restrict__ hist_npairs,
     K1Sums* __restrict__ sums) {
@@ -139,15 +148,33 @@ __global__ __launch_bounds__(THREADS) void k1_classify_hist(
         }
     };
 
-    // 4 rows per lane per step: 16-byte coalesced loads of each of the three columns
+    // a row by its key: the decoded (d, count) go through one() as (d, 0, count) - |d - 0| = d -, an inter row as loc2 = -1
+    auto keyed = [&](uint32_t k, int64_t row, int sk) {
+        const k1key::Row r = k1key::unpack(k);
+        if (r.escape)
+            one(loc1[row], loc2[row], count[row], sk);
+        else
+            one(r.d, r.inter ? -1 : 0, r.count, sk);
+    };
+
+    // 4 rows per lane per step: 16-byte coalesced loads of each of the three columns (KEYED: one of the key column)
     const int64_t n4 = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int4* a4 = reinterpret_cast<const int4*>(loc1);
     const int4* b4 = reinterpret_cast<const int4*>(loc2);
     const int4* c4 = reinterpret_cast<const int4*>(count);
+    const uint4* k4 = reinterpret_cast<const uint4*>(key);
     const uchar4* s4 = reinterpret_cast<const uchar4*>(skip);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-        const int4 a = a4[i], b = b4[i], c = c4[i];
+        int4 a, b, c;
+        uint4 k;
+        if (KEYED) {
+            k = k4[i];
+        } else {
+            a = a4[i];
+            b = b4[i];
+            c = c4[i];
+        }
         uchar4 s = make_uchar4(0, 0, 0, 0);
         // rows after the first duplicated outlier line are not skipped any more (fithic.py:408-412)
         if (skip && grow) {                       // shard: compare file positions, not local positions
@@ -164,14 +191,25 @@ __global__ __launch_bounds__(THREADS) void k1_classify_hist(
             if (r + 2 > skip_limit) s.z = 0;
             if (r + 3 > skip_limit) s.w = 0;
         }
-        one(a.x, b.x, c.x, s.x);
-        one(a.y, b.y, c.y, s.y);
-        one(a.z, b.z, c.z, s.z);
-        one(a.w, b.w, c.w, s.w);
+        if (KEYED) {
+            keyed(k.x, (i << 2), s.x);
+            keyed(k.y, (i << 2) + 1, s.y);
+            keyed(k.z, (i << 2) + 2, s.z);
+            keyed(k.w, (i << 2) + 3, s.w);
+        } else {
+            one(a.x, b.x, c.x, s.x);
+            one(a.y, b.y, c.y, s.y);
+            one(a.z, b.z, c.z, s.z);
+            one(a.w, b.w, c.w, s.w);
+        }
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const int64_t i = (n4 << 2) + threadIdx.x;
-        one(loc1[i], loc2[i], count[i], (skip && (grow ? grow[i] : i) <= skip_limit) ? skip[i] : 0);
+        const int sk = (skip && (grow ? grow[i] : i) <= skip_limit) ? skip[i] : 0;
+        if (KEYED)
+            keyed(key[i], i, sk);
+        else
+            one(loc1[i], loc2[i], count[i], sk);
     }
 
     __syncthreads();
@@ -759,9 +797,10 @@ int ingest_device_rows(fhx_ctx* ctx, const int32_t* c1, const int32_t* m1, const
     }
     mark("row arrays + workspace allocated");
     hipLaunchKernelGGL(k0_slots, dim3(blocks), dim3(256), 0, ctx->stream, c1, m1, c2, m2, cnt, n, res, ctx->d_grid,
-                       ctx->d_loc1, ctx->d_loc2, ctx->d_count);
+                       ctx->d_loc1, ctx->d_loc2, ctx->d_count, ctx->d_k1key);
     FHX_HIP(hipGetLastError());
     FHX_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->k1key_valid = true;
     mark("locus slots");
     if (timing) std::fprintf(stderr, "fhx_load_pairs_device: %lld rows:%s\n", (long long)n, t_report.c_str());
     return FHX_OK;
@@ -774,6 +813,8 @@ int alloc_row_arrays(fhx_ctx* ctx, int64_t n, int64_t n_dist) {
     dev_free(ctx->d_loc1);
     dev_free(ctx->d_loc2);
     dev_free(ctx->d_count);
+    dev_free(ctx->d_k1key);
+    ctx->k1key_valid = false;
     dev_free(ctx->d_skip);
     dev_free(ctx->d_outlier);
     dev_free(ctx->d_p);
@@ -782,6 +823,7 @@ int alloc_row_arrays(fhx_ctx* ctx, int64_t n, int64_t n_dist) {
     FHX_HIP(hipMalloc(&ctx->d_loc1, cap * sizeof(int32_t)));
     FHX_HIP(hipMalloc(&ctx->d_loc2, cap * sizeof(int32_t)));
     FHX_HIP(hipMalloc(&ctx->d_count, cap * sizeof(int32_t)));
+    if (!ctx->nonfixed) FHX_HIP(hipMalloc(&ctx->d_k1key, cap * sizeof(uint32_t)));      // K1's key column: written by k0_slots alone
     FHX_HIP(hipMalloc(&ctx->d_skip, cap));
     FHX_HIP(hipMalloc(&ctx->d_outlier, cap));
     FHX_HIP(hipMalloc(&ctx->d_p, cap * sizeof(double)));
@@ -937,24 +979,40 @@ int fhx::launch_k1(fhx_ctx* ctx) {
     const uint8_t* skip = ctx->skip_active ? ctx->d_skip : (const uint8_t*)nullptr;
     const long long* grow = (ctx->skip_limit != INT64_MAX) ? (const long long*)ctx->d_grow : (const long long*)nullptr;
     const int lo_i = (int)std::min<int64_t>(lo, INT32_MAX);
+    // the key column is read when k0_slots wrote one for these very rows (any other writer of the row arrays leaves k1key_valid
+    // false) and no test asked for the three-column kernel (fhx_debug_k1_wide)
+    const bool keyed = ctx->d_k1key && ctx->k1key_valid && !ctx->k1_force_wide;
+    const uint32_t* key = keyed ? ctx->d_k1key : (const uint32_t*)nullptr;
     if (hi - lo + 1 > K1_LDS_BINS) {                                                 // more distance values than the 12-B window holds
         const size_t lds = (size_t)K1_WIDE_BINS * 6;
         static bool attr_done = false;
         if (!attr_done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k1_classify_hist<K1_WIDE_THREADS, true>),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k1_classify_hist<K1_WIDE_THREADS, true, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k1_classify_hist<K1_WIDE_THREADS, true, false>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             attr_done = true;
         }
         const int blocks = grid_for((ctx->n_rows + 3) / 4, K1_WIDE_THREADS, 256);
-        hipLaunchKernelGGL((k1_classify_hist<K1_WIDE_THREADS, true>), dim3(blocks), dim3(K1_WIDE_THREADS), lds, ctx->stream, ctx->d_loc1,
-                           ctx->d_loc2, ctx->d_count, skip, ctx->skip_limit, grow, ctx->n_rows, lo_i, (int)hi, ctx->d_hist_cc,
-                           ctx->d_hist_np, ctx->d_sums);
+        if (keyed)
+            hipLaunchKernelGGL((k1_classify_hist<K1_WIDE_THREADS, true, true>), dim3(blocks), dim3(K1_WIDE_THREADS), lds, ctx->stream,
+                               ctx->d_loc1, ctx->d_loc2, ctx->d_count, key, skip, ctx->skip_limit, grow, ctx->n_rows, lo_i, (int)hi,
+                               ctx->d_hist_cc, ctx->d_hist_np, ctx->d_sums);
+        else
+            hipLaunchKernelGGL((k1_classify_hist<K1_WIDE_THREADS, true, false>), dim3(blocks), dim3(K1_WIDE_THREADS), lds, ctx->stream,
+                               ctx->d_loc1, ctx->d_loc2, ctx->d_count, key, skip, ctx->skip_limit, grow, ctx->n_rows, lo_i, (int)hi,
+                               ctx->d_hist_cc, ctx->d_hist_np, ctx->d_sums);
     } else {
         const size_t lds = (size_t)K1_LDS_BINS * (sizeof(unsigned long long) + sizeof(unsigned int));
         const int blocks = grid_for((ctx->n_rows + 3) / 4, K1_THREADS, 512);
-        hipLaunchKernelGGL((k1_classify_hist<K1_THREADS, false>), dim3(blocks), dim3(K1_THREADS), lds, ctx->stream, ctx->d_loc1,
-                           ctx->d_loc2, ctx->d_count, skip, ctx->skip_limit, grow, ctx->n_rows, lo_i, (int)hi, ctx->d_hist_cc,
-                           ctx->d_hist_np, ctx->d_sums);
+        if (keyed)
+            hipLaunchKernelGGL((k1_classify_hist<K1_THREADS, false, true>), dim3(blocks), dim3(K1_THREADS), lds, ctx->stream, ctx->d_loc1,
+                               ctx->d_loc2, ctx->d_count, key, skip, ctx->skip_limit, grow, ctx->n_rows, lo_i, (int)hi, ctx->d_hist_cc,
+                               ctx->d_hist_np, ctx->d_sums);
+        else
+            hipLaunchKernelGGL((k1_classify_hist<K1_THREADS, false, false>), dim3(blocks), dim3(K1_THREADS), lds, ctx->stream, ctx->d_loc1,
+                               ctx->d_loc2, ctx->d_count, key, skip, ctx->skip_limit, grow, ctx->n_rows, lo_i, (int)hi, ctx->d_hist_cc,
+                               ctx->d_hist_np, ctx->d_sums);
     }
     FHX_HIP(hipGetLastError());
     FHX_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
@@ -1074,3 +1132,8 @@ int fhx_pass_stats(fhx_ctx* ctx, fhx_stats* out) {
     return FHX_OK;
 }
 
+int fhx_debug_k1_wide(fhx_ctx* ctx, int on) {
+    if (!ctx || on < 0 || on > 1) return FHX_ERR_ARG;
+    ctx->k1_force_wide = on != 0;
+    return FHX_OK;
+}

@@ -57,13 +57,15 @@ __host__ __device__ inline bool bin_saturates(int b, unsigned long long cum_incl
 }
 
 // (dense_flag: 1 when at least dense_min values lie below the cutoff - the pass then takes q through the dense array, k3_compact<true>)
+// (sparse_flag: 1 when at most sparse_max do - k3_compact_sparse then runs in place of k3_compact<false>)
 // (host: the engine's own pass - the survivors' number goes straight to the host's pinned words, followed by the ticket the host
 // waits for (fhx_ctx::h_flags: no copy dispatched behind this kernel), and the compaction's counter is zeroed here (no fill before it):
 // CutoffToHost, fhx_ctx.hpp)
 __global__ __launch_bounds__(1024) void k3_cutoff(const unsigned long long* __restrict__ hist, double n_tests,
                                                   unsigned long long* __restrict__ cutoff_key, unsigned long long* __restrict__ n_below,
                                                   unsigned long long dense_min, unsigned long long* __restrict__ dense_flag,
-                                                  CutoffToHost host) {
+                                                  CutoffToHost host, unsigned long long sparse_max,
+                                                  unsigned long long* __restrict__ sparse_flag) {
     __shared__ unsigned long long part[1024];
     __shared__ unsigned long long below;
     __shared__ unsigned int best;
@@ -110,6 +112,7 @@ __global__ __launch_bounds__(1024) void k3_cutoff(const unsigned long long* __re
         if (threadIdx.x == 0) {
             *n_below = below;
             if (dense_flag) *dense_flag = below >= dense_min ? 1ull : 0ull;
+            if (sparse_flag) *sparse_flag = below <= sparse_max ? 1ull : 0ull;
             if (host.words) const_cast<unsigned long long*>(host.words)[1] = below;
             if (host.zero_me) *host.zero_me = 0ull;
         }
@@ -132,6 +135,7 @@ struct DenseQ {
     unsigned long long* mask = nullptr;      // per wave chunk (1024 rows) and step h: keep even rows, keep odd rows, NaN even, NaN odd
     unsigned long long* wave_slot = nullptr; // per wave chunk: compact index of its first survivor
     const unsigned long long* flag = nullptr; // the device's decision (k3_cutoff): non-zero = this pass goes through the dense array
+    const unsigned long long* sparse = nullptr; // the device's other decision: non-zero = k3_compact_sparse does the compaction
 };
 
 template <bool DENSE>
@@ -156,6 +160,7 @@ __global__ __launch_bounds__(CP_THREADS) void k3_compact(const double* __restric
     const unsigned long long lane_lt = (1ull << lane) - 1ull;
     const int64_t tiles = (n + CP_TILE - 1) / CP_TILE;
     if (dq.flag && (*dq.flag != 0ull) != DENSE) return;          // both variants are launched; the one the device chose runs
+    if (dq.sparse && *dq.sparse != 0ull) return;                 // ... or the third one, k3_compact_sparse
     const unsigned long long cutoff = *cutoff_key;
     const double2* p2 = reinterpret_cast<const double2*>(p);
     double2* q2 = reinterpret_cast<double2*>(q);
@@ -262,6 +267,149 @@ __global__ __launch_bounds__(CP_THREADS) void k3_compact(const double* __restric
                 if (threadIdx.x == 0) strip_n = 0u;
                 __syncthreads();
             }
+        }
+    }
+}
+
+// SPARSE (the rule on a Hi-C map: 76 768 survivors in 1.48e8 rows on C3, eight per tile): the variant for a q column that already
+// holds 1.0 (k1_prezero) and a survivor bound of at most K3_SPARSE_PER_GROUP per workgroup (k3_cutoff: `sparse`).  The kernel above
+// pays three block barriers and a serial prefix by thread 0 per tile to hand out slots that nearly no wave needs - a workgroup
+// loads, waits, loads again: 3.9 TB/s where the column could be read at the HBM rate.  Here a wave works alone: it loads its 1024
+// rows, takes the ballots, stores the q of NaN rows, and goes on to its next chunk if it keeps nothing.  A wave that keeps rows
+// reserves slots in the workgroup's strip with one LDS atomic; the strip goes out once, behind the last chunk, with one atomic on
+// the survivors' counter.  A wave whose reservation passes the end of the strip - the flag makes that rare - asks the counter for
+// slots of its own, and so does every wave of the workgroup after it (strip_n stays beyond the end); what the strip held when that
+// happened is the reservation that wave was given (strip_held).  Same tiles, wave chunks and lane-to-row layout as k3_compact; the
+// order of the survivors among themselves is free.
+// A workgroup's expected survivors - the bound shared out evenly over the groups of tiles - fill half its strip at the most: evenly
+// spread survivors then never pass its end (their number per group scatters by some tens), clustered ones take the global slots.
+// With the library's four tiles per workgroup that is 1.56 % of the rows (C3: 0.05 %), with the one tile of a small row set 6.25 %
+// (the k3_stress columns: 12 % and more).
+constexpr int K3_SPARSE_PER_GROUP = CP_STRIP / 2;
+// Eight waves per workgroup, each taking two of a tile's sixteen chunks: at this kernel's 73 registers a CU holds three workgroups,
+// so one reads while another ends and writes its strip out.  (Measured and dropped, profiles/r10/narrow_streams_ab.txt: sixteen
+// waves per workgroup, and the next chunk's loads issued in front of this chunk's ballots - 222 to 229 us on C3 either way.)
+constexpr int SP_THREADS = 512;
+constexpr int SP_WAVES = SP_THREADS / 64;
+constexpr int SP_STEPS = CP_WAVES / SP_WAVES;                 // chunks of one tile that a wave takes
+static_assert(CP_WAVES % SP_WAVES == 0, "a tile's chunks are shared out evenly");
+
+__global__ __launch_bounds__(SP_THREADS) void k3_compact_sparse(const double* __restrict__ p, int64_t n,
+                                                                 unsigned long long* __restrict__ keys, unsigned int* __restrict__ vals,
+                                                                 double* __restrict__ q, unsigned long long* __restrict__ counter,
+                                                                 const unsigned long long* __restrict__ cutoff_key,
+                                                                 const unsigned long long* __restrict__ dense_flag,
+                                                                 const unsigned long long* __restrict__ sparse_flag, int tiles_per_wg) {
+    __shared__ unsigned long long strip_k[CP_STRIP];
+    __shared__ unsigned int strip_v[CP_STRIP];
+    __shared__ unsigned int strip_n, strip_held;                 // slots reserved so far; entries when the first reservation failed
+    __shared__ unsigned long long block_base;
+    if (*sparse_flag == 0ull || (dense_flag && *dense_flag != 0ull)) return;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned long long lane_lt = (1ull << lane) - 1ull;
+    const int64_t tiles = (n + CP_TILE - 1) / CP_TILE;
+    const unsigned long long cutoff = *cutoff_key;
+    const double2* p2 = reinterpret_cast<const double2*>(p);
+    double2* q2 = reinterpret_cast<double2*>(q);
+    if (threadIdx.x == 0) strip_n = strip_held = 0u;
+    __syncthreads();
+    const int64_t t0 = (int64_t)blockIdx.x * tiles_per_wg, t_end = min(tiles, t0 + tiles_per_wg);
+    // Kept: not NaN and key below the cutoff key.  Every NaN pattern lies at or above KEY_KEEP_ALL as an unsigned number, every other
+    // value of either sign that is below the cutoff key lies below KEY_KEEP_ALL too: with the cutoff clamped there one unsigned compare
+    // of the bits says both, and -0.0 (key 0) is the one pattern to name.  The compare masks of a full wave are the ballots.
+    const unsigned long long cut = min(cutoff, KEY_KEEP_ALL);
+    const bool zero_kept = cut != 0ull;
+    const double past_end = __longlong_as_double(0x7FF8000000000000ll);       // rows past the end read as NaN: never kept, never stored
+    const int64_t steps = (t_end - t0) * SP_STEPS;
+    for (int64_t k = 0; k < steps; ++k) {
+        // step k of a workgroup: chunk (k % SP_STEPS) * SP_WAVES + wave of tile t0 + k / SP_STEPS
+        const int64_t wave_base = (t0 + k / SP_STEPS) * CP_TILE + ((k % SP_STEPS) * SP_WAVES + wave) * (int64_t)(64 * CP_ITEMS);
+        if (wave_base >= n) continue;
+        double v[CP_ITEMS];
+        if (wave_base + 64 * CP_ITEMS <= n) {     // a whole chunk: eight 16-byte loads per lane, all issued before a value is looked at
+#pragma unroll
+            for (int h = 0; h < CP_ITEMS / 2; ++h) {
+                const double2 w = p2[(wave_base >> 1) + h * 64 + lane];
+                v[2 * h] = w.x;
+                v[2 * h + 1] = w.y;
+            }
+        } else {
+#pragma unroll
+            for (int h = 0; h < CP_ITEMS / 2; ++h) {
+                const int64_t i = wave_base + (int64_t)(h * 64 + lane) * 2;
+                v[2 * h] = v[2 * h + 1] = past_end;
+                if (i + 1 < n) {
+                    const double2 w = p2[i >> 1];
+                    v[2 * h] = w.x;
+                    v[2 * h + 1] = w.y;
+                } else if (i < n) {               // the last row of an odd count
+                    v[2 * h] = p[i];
+                }
+            }
+        }
+        unsigned long long m[CP_ITEMS];           // which lanes keep item r (wave-uniform: scalar registers)
+        unsigned long long nan = 0;               // lanes that hold a NaN
+        unsigned int run = 0;
+#pragma unroll
+        for (int r = 0; r < CP_ITEMS; ++r) {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(v[r]);
+            m[r] = __ballot(bits < cut || (zero_kept && bits == 0x8000000000000000ull));
+            nan |= __ballot(v[r] != v[r]);
+            run += __popcll(m[r]);
+        }
+        // the column holds 1.0: only a NaN is left to store (the pair in one 16-byte store, as k3_compact does)
+        if (nan) {
+#pragma unroll
+            for (int h = 0; h < CP_ITEMS / 2; ++h) {
+                const int64_t i = wave_base + (int64_t)(h * 64 + lane) * 2;
+                const double x = v[2 * h], y = v[2 * h + 1];
+                if (x != x || y != y) {
+                    if (i + 1 < n)
+                        q2[i >> 1] = make_double2((x == x) ? 1.0 : x, (y == y) ? 1.0 : y);
+                    else if (i < n && x != x)     // (y is the NaN of the row past the end)
+                        q[i] = x;
+                }
+            }
+        }
+        if (run == 0) continue;                   // (wave-uniform)
+        unsigned int at = 0;
+        if (lane == 0) {
+            at = atomicAdd(&strip_n, run);
+            if (at <= (unsigned int)CP_STRIP && at + run > (unsigned int)CP_STRIP) strip_held = at;      // exactly one wave can see this
+        }
+        at = __shfl(at, 0, 64);
+        const bool in_strip = at + run <= (unsigned int)CP_STRIP;
+        unsigned long long base = 0;
+        if (!in_strip) {
+            if (lane == 0) base = atomicAdd(counter, (unsigned long long)run);
+            base = __shfl(base, 0, 64);
+        }
+        unsigned int before = 0;                  // survivors of the items in front of r
+#pragma unroll
+        for (int r = 0; r < CP_ITEMS; ++r) {
+            if ((m[r] >> lane) & 1ull) {
+                const unsigned int slot = before + __popcll(m[r] & lane_lt);
+                const unsigned int row = (unsigned int)(wave_base + (int64_t)((r >> 1) * 64 + lane) * 2 + (r & 1));
+                if (in_strip) {
+                    strip_k[at + slot] = pvalue_key(v[r]);
+                    strip_v[at + slot] = row;
+                } else {
+                    keys[base + slot] = pvalue_key(v[r]);
+                    vals[base + slot] = row;
+                }
+            }
+            before += __popcll(m[r]);
+        }
+    }
+    // the strip: one atomic, then out
+    __syncthreads();
+    const unsigned int held = strip_n <= (unsigned int)CP_STRIP ? strip_n : strip_held;
+    if (held) {
+        if (threadIdx.x == 0) block_base = atomicAdd(counter, (unsigned long long)held);
+        __syncthreads();
+        for (unsigned int i = threadIdx.x; i < held; i += SP_THREADS) {
+            keys[block_base + i] = strip_k[i];
+            vals[block_base + i] = strip_v[i];
         }
     }
 }
@@ -1109,8 +1257,10 @@ void launch_rs_scan(fhx_ctx* ctx, int nblk) {
     hipLaunchKernelGGL(rs_scan, dim3(RADIX), dim3((nblk + 63) / 64 * 64), 0, ctx->stream, ctx->d_block_hist, ctx->d_digit_total, nblk);
 }
 void launch_k3_cutoff(fhx_ctx* ctx, const unsigned long long* hist, double n_tests, unsigned long long* d_cutoff,
-                      unsigned long long* n_below, unsigned long long dense_min, unsigned long long* dense_flag, const CutoffToHost& host) {
-    hipLaunchKernelGGL(k3_cutoff, dim3(1), dim3(1024), 0, ctx->stream, hist, n_tests, d_cutoff, n_below, dense_min, dense_flag, host);
+                      unsigned long long* n_below, unsigned long long dense_min, unsigned long long* dense_flag, const CutoffToHost& host,
+                      unsigned long long sparse_max, unsigned long long* sparse_flag) {
+    hipLaunchKernelGGL(k3_cutoff, dim3(1), dim3(1024), 0, ctx->stream, hist, n_tests, d_cutoff, n_below, dense_min, dense_flag, host,
+                       sparse_max, sparse_flag);
 }
 void launch_bh_tile_max(fhx_ctx* ctx, int tiles, const unsigned long long* keys, const unsigned long long* n_ptr, int64_t n_fixed,
                         double n_tests, double rank0, double* tile_max) {
@@ -1171,6 +1321,7 @@ struct K3Pass {
     hipEvent_t wait_ev = nullptr;                 // ... behind this event, recorded in front of k3_cutoff (K2's end): the host sleeps on it
     unsigned long long ticket = 0;
     bool counter_zeroed = false;                  // k3_cutoff zeroes the counter: no fill in front of k3_compact
+    const unsigned long long* sparse = nullptr;   // k3_cutoff's word for k3_compact_sparse (set when the q column holds 1.0), or none
     // compact_pvalues -> sort_kept -> bh_from_sorted, the entry point
     int64_t n_kept = 0;
     bool n_is_bound = false;                      // n_kept is the histogram's upper bound: the exact number is in *counter
@@ -1178,9 +1329,18 @@ struct K3Pass {
     OsPending pend;                               // the one-sweep sort's second half, when sort_kept left it to its caller
     // what the steps chose, for fhx_k3_pass_info
     int tiles_per_wg = 0;                         // of k3_compact<false> (0: not launched)
+    bool sparse_enqueued = false;                 // k3_compact_sparse was launched beside it
     bool q_is_ones = false;                       // k3_compact<false> was told the q column holds 1.0 already
     int sort_taken = 0;                           // 0: nothing to sort, 1: LDS tile sorts, 2: one-sweep, 3: radix_passes
 };
+
+// tiles per workgroup of the scattered compaction (k3_compact<false>, k3_compact_sparse)
+static int compact_tiles_per_wg(const fhx_ctx* ctx, const K3Pass& pass) {
+    const int64_t n_tiles = (pass.n + CP_TILE - 1) / CP_TILE;
+    int per = (int)std::max<int64_t>(1, std::min<int64_t>(4, n_tiles / 2048));
+    if (ctx->k3_force_per && pass.p == ctx->d_p) per = ctx->k3_force_per;      // fhx_debug_k3_tiles_per_group (tests)
+    return per;
+}
 
 // the cutoff key from this GPU's own histogram of pass.p, and the survivors' number on its way to the host
 // (dense_min: k3_cutoff sets DeviceWords::k3_dense from that many survivors on, ~0: never.  k2_done: an event the caller has just
@@ -1210,7 +1370,15 @@ static int auto_cutoff(fhx_ctx* ctx, K3Pass& pass, unsigned long long dense_min,
         k2_done = ctx->ev_k3;
     }
     const CutoffToHost host{ctx->h_flags + FLAG_K3, ++ctx->ticket, ctx->d_done + 1, pass.counter};      // (zero_me: the compaction's counter)
-    launch_k3_cutoff(ctx, hist, pass.n_total_tests, pass.cutoff, &ctx->d_words->bh_below, dense_min, &ctx->d_words->k3_dense, host);
+    // the sparse compaction needs the q column that k1_prezero filled (what compact_pvalues calls `ones`) and a workspace word per
+    // four rows for its values: the engine's own pass.  Without the prefill the word is cleared and nobody is handed it.
+    const bool ones = ctx->q_prefilled && pass.q == ctx->d_q && pass.p == ctx->d_p;
+    const int64_t n_tiles = (pass.n + CP_TILE - 1) / CP_TILE;
+    const int per = compact_tiles_per_wg(ctx, pass);
+    const unsigned long long sparse_max = ones ? (unsigned long long)((n_tiles + per - 1) / per) * K3_SPARSE_PER_GROUP : 0ull;
+    launch_k3_cutoff(ctx, hist, pass.n_total_tests, pass.cutoff, &ctx->d_words->bh_below, dense_min, &ctx->d_words->k3_dense, host, sparse_max,
+                     &ctx->d_words->k3_sparse);
+    pass.sparse = ones ? &ctx->d_words->k3_sparse : nullptr;
     FHX_HIP(hipGetLastError());
     pass.wait_ev = k2_done;
     pass.ticket = host.ticket;
@@ -1234,14 +1402,19 @@ static int compact_pvalues(fhx_ctx* ctx, K3Pass& pass) {
         DenseQ off;
         if (dq) off.flag = dq->flag;
         const bool ones = ctx->q_prefilled && pass.q == ctx->d_q && pass.p == ctx->d_p;
+        off.sparse = ones ? pass.sparse : nullptr;
         // tiles per workgroup: as many as leave every CU its two workgroups several times over (a shard keeps one tile per workgroup)
         const int64_t n_tiles = (pass.n + CP_TILE - 1) / CP_TILE;
-        int per = (int)std::max<int64_t>(1, std::min<int64_t>(4, n_tiles / 2048));
-        if (ctx->k3_force_per && pass.p == ctx->d_p) per = ctx->k3_force_per;      // fhx_debug_k3_tiles_per_group (tests)
+        const int per = compact_tiles_per_wg(ctx, pass);
         pass.tiles_per_wg = per;
         pass.q_is_ones = ones;
         hipLaunchKernelGGL(k3_compact<false>, dim3(grid_for((n_tiles + per - 1) / per, 1, 1 << 30)), dim3(CP_THREADS), 0, ctx->stream, pass.p,
                            pass.n, pass.keys[0], pass.vals[0], pass.q, pass.counter, pass.cutoff, off, ones, per);
+        // the same groups of tiles, one workgroup each; the device runs this one or the one above (k3_cutoff: DeviceWords::k3_sparse)
+        if (off.sparse)
+            hipLaunchKernelGGL(k3_compact_sparse, dim3(grid_for((n_tiles + per - 1) / per, 1, 1 << 30)), dim3(SP_THREADS), 0, ctx->stream, pass.p,
+                               pass.n, pass.keys[0], pass.vals[0], pass.q, pass.counter, pass.cutoff, off.flag, off.sparse, per);
+        pass.sparse_enqueued = off.sparse != nullptr;
     }
     if (pass.q == ctx->d_q) ctx->q_prefilled = false;      // from here on the column holds this pass's q
     // how many keys survived decides the shape of the sort.  When the cutoff came from this GPU's own histogram (auto_cutoff) the
@@ -1522,6 +1695,7 @@ int fhx_bh(fhx_ctx* ctx, double n_total_tests) {
     ctx->k3_info[4] = pass.sort_taken;
     ctx->k3_info[5] = far_below ? 1 : 0;
     ctx->k3_info[6] = pass.q_is_ones ? 1 : 0;
+    ctx->k3_sparse_enqueued = pass.sparse_enqueued;
     ctx->have_k3_info = true;
     FHX_HIP(hipEventRecord(ctx->ev[5], ctx->stream));
     ctx->ev_valid[2] = true;
@@ -1544,6 +1718,20 @@ int fhx_k3_pass_info(fhx_ctx* ctx, int64_t* out8) {
     if (out8[0]) out8[0] = dense ? 2 : 1;              // enqueued: the variant the device chose (DeviceWords::k3_dense)
     out8[2] = (int64_t)kept;
     out8[7] = 0;
+    return FHX_OK;
+}
+
+int fhx_k3_compact_variant(fhx_ctx* ctx, int32_t* out) {
+    if (!ctx || !out) return FHX_ERR_ARG;
+    if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
+    if (!ctx->have_k3_info) return fail(ctx, FHX_ERR_ARG, "fhx_bh must run first");
+    FHX_HIP(hipSetDevice(ctx->device));
+    *out = 0;
+    if (!ctx->k3_sparse_enqueued) return FHX_OK;
+    unsigned long long sparse = 0;
+    FHX_HIP(hipMemcpyAsync(&sparse, &ctx->d_words->k3_sparse, sizeof(sparse), hipMemcpyDeviceToHost, ctx->stream));
+    FHX_HIP(hipStreamSynchronize(ctx->stream));
+    *out = sparse ? 2 : 1;
     return FHX_OK;
 }
 

@@ -304,10 +304,20 @@ int fhx_bh_sort_stats(fhx_ctx* ctx, int64_t* out8);
  * last pass's survivor count (under a tenth of the rows) kept the dense launches from being enqueued; [6] 1 when the compaction
  * relied on a q column filled with 1.0 behind fhx_pass_stats; [7] 0.  FHX_ERR_ARG before the first fhx_bh. */
 int fhx_k3_pass_info(fhx_ctx* ctx, int64_t* out8);
+/* One more slot of the same report, read the same way (the call waits for the stream): which kernel compacted the rows below the
+ * cutoff in the last fhx_bh when the scattered variant did.  *out = 0: the sparse compaction (k3_compact_sparse) was not enqueued -
+ * the q column was not filled with 1.0 behind fhx_pass_stats, or the pass was not the engine's own; 1: enqueued, and the device
+ * chose k3_compact<false> (by the key histogram more rows lie below the cutoff than 1024 per workgroup of the compaction); 2: the device chose the
+ * sparse compaction.  FHX_ERR_ARG before the first fhx_bh. */
+int fhx_k3_compact_variant(fhx_ctx* ctx, int32_t* out);
 /* Test hook: per = 1..4 replaces the library's choice of tiles per workgroup in the scattered compaction of this context's later
  * fhx_bh and fhx_bh_local_sort calls (the library itself goes beyond 1 only from 6.7e7 rows on), 0 gives the choice back;
  * anything else is FHX_ERR_ARG.  Results do not depend on it.  Not for production callers. */
 int fhx_debug_k3_tiles_per_group(fhx_ctx* ctx, int per);
+/* Test hook: on = 1 makes this context's later fhx_pass_stats calls classify the rows from their three int32 columns (12 bytes a
+ * row) instead of the 32-bit key column written at load; 0 gives the key column back; anything else is FHX_ERR_ARG.  Results do
+ * not depend on it.  Not for production callers. */
+int fhx_debug_k1_wide(fhx_ctx* ctx, int on);
 /* Seconds the kernels of the last pass took on the context's stream (HIP events): k1, k2, k3. */
 int fhx_kernel_seconds(fhx_ctx* ctx, double* k1, double* k2, double* k3);
 /* The same summed over the passes since the last reset, without stopping the stream after each of them: sums4 = seconds of K1, K2,
