@@ -34,6 +34,7 @@ from . import fitpack_oracle
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+_NUDGED = None
 
 INTRA_ONLY, INTER_ONLY, ALL = "intraOnly", "interOnly", "All"
 
@@ -45,7 +46,22 @@ def build(force=False):
     if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
         subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared",
                                "-o", so, src, "-lm"])
+    build_nudged(force)
     return so
+
+
+def build_nudged(force=False):
+    """Compile cephes_libm_nudge.c twice, with build()'s flags: liboracle_cephes_up.so (-DFHO_NUDGE=+1: every log, exp and pow of
+    the restatement returns the next double above libm's) and liboracle_cephes_down.so (-DFHO_NUDGE=-1: the next one below)."""
+    srcs = [os.path.join(_HERE, "cephes_libm_nudge.c"), os.path.join(_HERE, "cephes_oracle.c")]
+    out = []
+    for tag, d in (("up", "+1"), ("down", "-1")):
+        so = os.path.join(_HERE, "liboracle_cephes_%s.so" % tag)
+        if force or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
+            subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-DFHO_NUDGE=" + d,
+                                   "-Wl,-Bsymbolic", "-o", so, srcs[0], "-lm"])
+        out.append(so)
+    return tuple(out)
 
 
 def _lib():
@@ -53,6 +69,13 @@ def _lib():
     if _LIB is None:
         _LIB = ctypes.CDLL(build())
     return _LIB
+
+
+def _nudged_libs():
+    global _NUDGED
+    if _NUDGED is None:
+        _NUDGED = tuple(ctypes.CDLL(so) for so in build_nudged())
+    return _NUDGED
 
 
 def _dptr(a):
@@ -77,10 +100,36 @@ def bdtrc(k, n, p, totals=TOTALS_REFERENCE):
     k = np.ascontiguousarray(np.broadcast_to(np.asarray(k, np.float64), np.broadcast(k, n, p).shape))
     n = np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.float64), k.shape))
     p = np.ascontiguousarray(np.broadcast_to(np.asarray(p, np.float64), k.shape))
+    return _bdtrc_with(_lib(), k, n, p, totals)
+
+
+def _bdtrc_with(lib, k, n, p, totals):
     out = np.empty(k.shape, np.float64)
-    f = _lib().fho_bdtrc_vec if totals == TOTALS_REFERENCE else _lib().fho_bdtrc_wide_vec
+    f = lib.fho_bdtrc_vec if totals == TOTALS_REFERENCE else lib.fho_bdtrc_wide_vec
     f(_dptr(k), _dptr(n), _dptr(p), _dptr(out), ctypes.c_int64(k.size))
     return out
+
+
+def bdtrc_nudged(k, n, p, totals=TOTALS_REFERENCE):
+    """(up, down): bdtrc() of the two builds of cephes_libm_nudge.c - a libm whose log, exp and pow are one ulp high / low"""
+    if totals not in (TOTALS_REFERENCE, TOTALS_WIDE):
+        raise ValueError("totals must be 'reference' or 'wide'")
+    k = np.ascontiguousarray(np.broadcast_to(np.asarray(k, np.float64), np.broadcast(k, n, p).shape))
+    n = np.ascontiguousarray(np.broadcast_to(np.asarray(n, np.float64), k.shape))
+    p = np.ascontiguousarray(np.broadcast_to(np.asarray(p, np.float64), k.shape))
+    return tuple(_bdtrc_with(lib, k, n, p, totals) for lib in _nudged_libs())
+
+
+def bdtrc_libm_spread(k, n, p, totals=TOTALS_REFERENCE):
+    """(o, S): the oracle's bdtrc and, per row, how far a libm that is one ulp off in log, exp and pow moves it - the larger of
+    |up - o| and |down - o|, absolute; a difference that is NaN (the row is NaN in every build, or only in a nudged one) counts 0.
+    The engine's route calls no libm function besides these three (see cephes_libm_nudge.c), and each is nudged by ONE ulp: no
+    documentation of the device's math library that ships with the toolchain states a larger error for them."""
+    o = bdtrc(k, n, p, totals)
+    up, down = bdtrc_nudged(k, n, p, totals)
+    with np.errstate(invalid="ignore"):
+        S = np.fmax(np.nan_to_num(np.abs(up - o), nan=0.0), np.nan_to_num(np.abs(down - o), nan=0.0))
+    return o, S
 
 
 def bdtrc_stats(k, n, p):
@@ -637,6 +686,8 @@ def fit_spline(pairs, dist_keys, x, y, b1, b2, mode, L, U, tL, tU, sums, frag, u
     rng = ~inter & in_range(d, L, U)
     p = np.ones(n, np.float64)
     expcc = np.zeros(n, np.float64)
+    row_prior = np.full(n, np.nan, np.float64)           # per row, the prior and the total that went into bdtrc (NaN: the row
+    row_n = np.full(n, np.nan, np.float64)               # never reaches bdtrc and keeps p = 1)
     discard = ((b1 < 0) | (b2 < 0)) & ~inter                                     # branch 1
     within = (b1 >= tL) & (b1 <= tU) & (b2 >= tL) & (b2 <= tU)
     cnt = pairs.count.astype(np.float64)
@@ -649,6 +700,7 @@ def fit_spline(pairs, dist_keys, x, y, b1, b2, mode, L, U, tL, tU, sums, frag, u
             idx = np.minimum(np.searchsorted(R.splineX.astype(np.float64), look, side="left"), len(R.splineX) - 1)
             prior = R.newSplineY[idx] * (b1[sel] * b2[sel])
             p[sel] = bdtrc(cnt[sel] - 1, float(in_range_sum), prior, totals)
+            row_prior[sel], row_n[sel] = prior, float(in_range_sum)
             expcc[sel] = np.where(within[sel], in_range_sum * prior, 0.0)
         rest = ~discard & inter                      # branches 3, 4 keep p = 1; inter falls to 5/6
     else:
@@ -658,6 +710,7 @@ def fit_spline(pairs, dist_keys, x, y, b1, b2, mode, L, U, tL, tU, sums, frag, u
         if len(sel):
             prior = frag["inter_prob"] * (b1[sel] * b2[sel])
             p[sel] = bdtrc(cnt[sel] - 1, float(inter_sum), prior, totals)
+            row_prior[sel], row_n[sel] = prior, float(inter_sum)
             expcc[sel] = np.where(within[sel], inter_sum * prior, 0.0)
     # ---- BH dispatch (fithic.py:1126-1164) ------------------------------------------------------
     if all_reg:
@@ -669,6 +722,7 @@ def fit_spline(pairs, dist_keys, x, y, b1, b2, mode, L, U, tL, tU, sums, frag, u
     R.N = N
     R.outlier_thres = 1.0 / N
     R.p = p
+    R.prior, R.bdtrc_n = row_prior, row_n
     R.q = benjamini_hochberg(p, N)
     R.expcc = expcc
     # ---- which rows the writer emits (fithic.py:1197-1213) and the outliers (:1215-1217) --------

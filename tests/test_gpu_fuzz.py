@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from p_relative import assert_pass_p_faithful
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
 
@@ -158,6 +160,9 @@ def test_random_small_runs_match_the_oracle(seed, tmp_path):
                 assert np.array_equal(np.isnan(got), np.isnan(want)), (key, pi)
                 ok = ~np.isnan(want)
                 assert not ok.any() or np.max(np.abs(got[ok] - want[ok])) <= tol, (key, pi)
+            # p, row by row, within what a libm one ulp off moves the oracle's own value (tests/p_relative.py): that bar scales with
+            # the count by itself, so the scaled-up seeds need no special case
+            assert_pass_p_faithful(v["p"], con.count, r, what=(seed, pi))
             assert eng.next_pass() == r.n_outlier_lines_total
     finally:
         eng.close()

@@ -3,7 +3,8 @@
 fhx_pvalues on caller-supplied rows; tests/k2_rows.py builds the rows, tests/test_k2_pass_inputs.py checks that they reach every path).
 
 Bars: NaN pattern identical and |p - reference| <= 1e-10 against scipy's values (f3_bdtrc.npz) and the oracle; counts stay <= 1e4,
-so the last bit of libm's log times the count stays below 1e-11 (see test_gpu_fuzz.py).  And p must equal Context.bdtrc_array - one
+so the last bit of libm's log times the count stays below 1e-11 (see test_gpu_fuzz.py).  Beside it the relative bar of
+tests/p_relative.py against the oracle, row by row: 2 S + 4 ulp, S = what a libm one ulp off moves the oracle's own value.  And p must equal Context.bdtrc_array - one
 lane per row through bdtrc_count -> incbet - BIT FOR BIT: the class kernels claim the same operations in the same order.
 
 The last test is an Engine run: the third exit of the no-bias table path (k2_memo_overflow scanning for its -1.0 marks)."""
@@ -14,6 +15,7 @@ import pytest
 
 import k2_rows as kr
 from conftest import bits_equal, max_abs_diff
+from p_relative import assert_p_faithful
 
 pytestmark = pytest.mark.gpu
 
@@ -60,6 +62,7 @@ def run_and_check(c, r, nonfixed=False, ref=None, totals="reference", what=""):
     diff = np.flatnonzero(~((p.view(np.int64) == lane.view(np.int64)) | (np.isnan(p) & np.isnan(lane))))
     assert len(diff) == 0, (what, len(diff), [(int(r.count[i]), float(r.prior[i]), int(r.is_inter[i]), float(p[i]), float(lane[i])) for i in diff[:5]])
     assert max_abs_diff(p, oracle_p(r, totals)) <= TOL, what
+    assert_p_faithful(p, r.count, r.totals(), r.prior, totals=totals, what=what)          # ... and within the relative bar, row by row
     if ref is not None:
         assert max_abs_diff(p, ref) <= TOL, what
     assert by_class == kr.class_rows(r.outcomes()), what

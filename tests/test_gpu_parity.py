@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import load_case, case_args, ALL_CASES, SMALL_CASES, WRAP_CASES, bits_equal, max_abs_diff, GOLDEN
+from p_relative import assert_p_faithful, assert_pass_p_faithful
 
 pytestmark = pytest.mark.gpu
 
@@ -43,6 +44,7 @@ def test_bdtrc_known_answers_on_gpu(ctx):
         sel = integral & (n == nt)
         out = ctx.bdtrc_array(float(nt), (k[sel] + 1).astype(np.int32), p[sel])
         worst = max(worst, max_abs_diff(out, ref[sel]))
+        assert_p_faithful(out, (k[sel] + 1).astype(np.int32), float(nt), p[sel], what=nt)
         same = (out.view(np.int64) == ref[sel].view(np.int64)) | (np.isnan(out) & np.isnan(ref[sel]))
         n_bits += int(same.sum())
         total += int(sel.sum())
@@ -87,6 +89,7 @@ def test_bdtrc_against_oracle_random(ctx):
         out = ctx.bdtrc_array(float(nt), cnt, prior)
         ref = fo.bdtrc(cnt.astype(np.float64) - 1, float(nt), prior)
         assert max_abs_diff(out, ref) <= TOL, nt
+        assert_p_faithful(out, cnt, float(nt), prior, what=nt)
 
 
 @pytest.mark.parametrize("kind", [0, 1])
@@ -390,9 +393,11 @@ def test_pipeline_matches_oracle_every_row(name):
     meta, g, kw, passes = _run_case(name)
     ref = fo.run(**kw)
     assert len(ref) == len(passes)
-    for out, r in zip(passes, ref):
+    count = fo.read_contacts_file(kw["contacts"]).count
+    for pi, (out, r) in enumerate(zip(passes, ref), 1):
         v = out.values
         assert max_abs_diff(v["p"], r.p) <= TOL
+        assert_pass_p_faithful(v["p"], count, r, what=(name, pi))              # real maps, real priors: every row of every pass
         assert max_abs_diff(v["q"], r.q) <= TOL
         assert bits_equal(v["expcc"], r.expcc) and bits_equal(v["b1"], r.b1) and bits_equal(v["b2"], r.b2)
         # q is exactly BH of OUR p (the sort/scan path is bit-exact on its own input)
