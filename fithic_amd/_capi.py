@@ -127,6 +127,7 @@ SYMBOLS = {
     "fhx_debug_format": (ctypes.c_int, [_P, _F64P, ctypes.c_int64, ctypes.c_int32, ctypes.c_char_p, _I32P]),
     "fhx_debug_contfrac": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _F64P, _F64P, _F64P, ctypes.c_int64, _F64P]),
     "fhx_debug_lean_div": (ctypes.c_int, [_P, _F64P, _F64P, ctypes.c_int64, _F64P]),
+    "fhx_debug_table_div": (ctypes.c_int, [_P, ctypes.c_int, _F64P, ctypes.c_int64, _F64P, _I32P]),
     "fhx_debug_classify": (ctypes.c_int, [_P, ctypes.c_double, _I32P, _F64P, ctypes.c_int64, _I32P, _I32P, _F64P]),
     "fhx_debug_k2_rows": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_double, _I32P, _F64P, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int64,
                                          ctypes.c_int32, _F64P, _I64P, _I64P, _I64P, ctypes.c_int64]),
@@ -941,6 +942,18 @@ class Context:
         n, d = (np.ascontiguousarray(v, np.float64) for v in (n, d))
         out = np.empty(len(n), np.float64)
         self._check(self._L.fhx_debug_lean_div(self._h, _ptr(n, ctypes.c_double), _ptr(d, ctypes.c_double), len(n), _ptr(out, ctypes.c_double)))
+        return out
+
+    def debug_table_div(self, kind, num):
+        """num[i] / j (j + 1) (kind 0) or num[i] / j (kind 1) by the class kernels' tabulated reciprocals: (J - 1, len(num)) for j = 1 .. J - 1"""
+        num = np.ascontiguousarray(num, np.float64)
+        length = ctypes.c_int32(0)
+        dummy = np.empty(1, np.float64)
+        self._check(self._L.fhx_debug_table_div(self._h, int(kind), _ptr(dummy, ctypes.c_double), 0, _ptr(dummy, ctypes.c_double), ctypes.byref(length)))
+        out = np.empty((length.value - 1, len(num)), np.float64)
+        if len(num):
+            self._check(self._L.fhx_debug_table_div(self._h, int(kind), _ptr(num, ctypes.c_double), len(num), _ptr(out, ctypes.c_double),
+                                                    ctypes.byref(length)))
         return out
 
     def bh_array(self, p, n_total_tests):

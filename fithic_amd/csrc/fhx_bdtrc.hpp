@@ -77,23 +77,70 @@ __device__ __forceinline__ double cephes_expm1(double x) {
 // exponentiating a sum of logarithms.  No Hi-C run gets there, but pow() costs ~90 VGPRs wherever it is compiled in: the class
 // kernels exist in both forms and the host launches the one the pass's totals call for (false: the pow statements are not
 // compiled; their condition (a + b) < MAXGAM is false for such totals anyway).
-template <bool SMALL_N = true>
-__device__ __forceinline__ double pseries(double a, double b, double x, double lbeta_ab, double inv_beta_ab) {
-    const double ai = 1.0 / a;
-    double u = (1.0 - b) * x;
-    double v = u / (a + 1.0);
-    const double t1 = v;
-    double t = u;
-    double n = 2.0;
-    double s = 0.0;
-    const double z = kMachEp * ai;
-    while (fabs(v) > z) {
-        u = (n - b) * x / n;
-        t *= u;
-        v = t / (a + n);
-        s += v;
-        n += 1.0;
+//
+// LEAN (the pass's class kernels only; bdtrc_count keeps the statements as Cephes has them): the same divisions as lean_div does
+// them (lean_rcp, lean_quot: defined below), their reciprocals read from rtab (div_table_build<false>, kPsTabJ entries of lean_rcp(j)) where the divisor is
+// a small integer - the term number n, and a + n when a is the contact count.  hipcc's `/` is the same v_rcp_f64, Newton steps,
+// quotient and fused residual step inside v_div_scale / v_div_fmas / v_div_fixup, which only act on extreme exponents; lean_div
+// equals it bit for bit for divisors in (1e-200, 1e200) and numerators that are 0 or in that window.  The window, under the
+// predicate checked at entry (b an integer, 1 <= a, b < 4.5e15, 1e-150 < x, b x <= 1 and x <= 0.95 as for every caller):
+//   * divisors: a, a + 1, n and a + n are in [1, 2^53 + 2^53) - n counts terms, every term is at most 0.95 times the last or
+//     below 1 / n of it, so the loop ends long before n reaches 2^53;
+//   * 1 / a: the numerator is 1;
+//   * (1 - b) x and (n - b) x: b and n are integers, so 1 - b and n - b are exact and either 0 - then the numerator is +0 in both
+//     forms, and so are the quotient, t and every later v: the loop ends - or at least 1 in magnitude: |numerator| in [1e-150, 4.5e15];
+//   * t: |u| <= max(x, b x / n) <= 1 in every term, so |t| <= |(1 - b) x| <= 1; and the loop goes on only while
+//     |v| = |t / (a + n)| > MACHEP / a, i.e. |t| > 1.1e-16, so the next t = t u is 0 or above 1.1e-16 x / n > 1e-182.
+//   A zero quotient: the only zero numerator is +0 over a positive divisor, +0 both ways (lean_quot keeps a zero's sign in any
+//   case) - and the sign would be unobservable anyway (t *= u; s += v with s = +0 or nonzero).
+__device__ __forceinline__ double lean_rcp(double d);
+__device__ __forceinline__ double lean_quot(double n, double d, double y);
+constexpr int kPsTabJ = 512;
+template <bool SMALL_N = true, bool LEAN = false>
+__device__ __forceinline__ double pseries(double a, double b, double x, double lbeta_ab, double inv_beta_ab, const double* rtab = nullptr) {
+    double ai, t1, s = 0.0;
+    if (LEAN && x > 1e-150 && x <= 0.95 && b * x <= 1.0 && a >= 1.0 && a < 4.5e15 && b >= 1.0 && b < 4.5e15 && b == __builtin_rint(b)) {
+        // ja: a as a table index when it is a small integer, else kPsTabJ ("compute"): ja + ni < kPsTabJ fails from then on
+        int ja = kPsTabJ;
+        if (a < (double)kPsTabJ) {
+            const int ia = (int)a;
+            if ((double)ia == a) ja = ia;
+        }
+        const double a1 = a + 1.0;
+        ai = lean_quot(1.0, a, ja < kPsTabJ ? rtab[ja] : lean_rcp(a));
+        double u = (1.0 - b) * x;
+        double v = lean_quot(u, a1, ja + 1 < kPsTabJ ? rtab[ja + 1] : lean_rcp(a1));
+        t1 = v;
+        double t = u;
+        double n = 2.0;
+        int ni = 2;                                       // n as an integer: the same in every lane that is still in the loop
+        const double z = kMachEp * ai;
+        while (fabs(v) > z) {
+            u = lean_quot((n - b) * x, n, ni < kPsTabJ ? rtab[ni] : lean_rcp(n));
+            t *= u;
+            const double an = a + n;
+            v = lean_quot(t, an, ja + ni < kPsTabJ ? rtab[ja + ni] : lean_rcp(an));
+            s += v;
+            n += 1.0;
+            ni += 1;
+        }
+    } else {
+        ai = 1.0 / a;
+        double u = (1.0 - b) * x;
+        double v = u / (a + 1.0);
+        t1 = v;
+        double t = u;
+        double n = 2.0;
+        const double z = kMachEp * ai;
+        while (fabs(v) > z) {
+            u = (n - b) * x / n;
+            t *= u;
+            v = t / (a + n);
+            s += v;
+            n += 1.0;
+        }
     }
+    double u, t;
     s += t1;
     s += ai;
     u = a * log(x);
@@ -177,15 +224,45 @@ __device__ __forceinline__ double contfrac(double a, double b, double x) {
 // exponents and non-finite inputs.  Bit-identical to `n / d` for finite d with 1e-200 < |d| < 1e200 and |n| = 0 or in the
 // same window (checked on 10^8 random operand pairs by tests/test_gpu_parity.py::test_lean_division_matches_ieee);
 // the sign of a zero quotient may differ, which no caller below can observe.
-__device__ __forceinline__ double lean_div(double n, double d) {
+__device__ __forceinline__ double lean_rcp(double d) {                  // the refined reciprocal: v_rcp_f64, two Newton steps
     const double y0 = __builtin_amdgcn_rcp(d);
     const double e0 = __builtin_fma(-d, y0, 1.0);
     const double y1 = __builtin_fma(y0, e0, y0);
     const double e1 = __builtin_fma(-d, y1, 1.0);
-    const double y2 = __builtin_fma(y1, e1, y1);
+    return __builtin_fma(y1, e1, y1);
+}
+__device__ __forceinline__ double lean_div(double n, double d) {
+    const double y2 = lean_rcp(d);
     const double q0 = n * y2;
     const double r0 = __builtin_fma(-d, q0, n);
     return __builtin_fma(r0, y2, q0);
+}
+// lean_div's quotient and fused residual step for a reciprocal y = lean_rcp(d) that the caller holds (the tables below).  The
+// residual is formed as -(d q0 - n) instead of (-d) q0 + n: one rounding of the same exact value, negated - the same bits whenever
+// it is not zero - and a quotient of zero keeps the numerator's sign as `/` does (n = -0: q0 = -0, d q0 - n = -0 + 0 = +0,
+// -(+0) y + (-0) = -0; with (-d) q0 + n the residual is +0 and the sum +0).  Both negations are operand modifiers.
+__device__ __forceinline__ double lean_quot(double n, double d, double y) {
+    const double q0 = n * y;
+    const double r0 = __builtin_fma(d, q0, -n);
+    return __builtin_fma(-r0, y, q0);
+}
+
+// Reciprocal tables by integer, in LDS, for the pass's per-lane loops.  lean_rcp(d) is a pure function of d, and the divisors of
+// those loops are small exact integers whenever the row's a is its contact count: D = j (j + 1) with j = a + 2 i (then j + 1) in
+// the continued fractions, the term number n and a + n in the power series.  Every workgroup tabulates lean_rcp of them once, with
+// the statements above, so lean_quot(n, D, table[j]) is lean_div(n, D) with the same reciprocal, product and two fused steps: the
+// v_rcp_f64 and the four Newton fma per division leave the loop, the quotient's three instructions stay.  Entry 0 is never read.
+//   kCfTabJ: 448 doubles are what the LDS of k2_queue_by_count leaves at four workgroups per CU (16 KB tile, 16 KB histogram, 4 KB
+//            queue prefix: 37 152 of 40 960 bytes).  A row uses the table while j + 1 < kCfTabJ, i.e. up to count 400 for 23
+//            iterations; Hi-C counts of the converging classes are far below that.  Past the table a lane computes lean_rcp itself.
+//   kPsTabJ (above, at pseries): the power-series kernel holds no tile: 512.
+constexpr int kCfTabJ = 448;
+template <bool PRODUCT>          // true: lean_rcp(j (j + 1)), false: lean_rcp(j); all threads of the workgroup, the caller synchronises
+__device__ __forceinline__ void div_table_build(double* tab, int len) {
+    for (int j = (int)threadIdx.x; j < len; j += (int)blockDim.x) {
+        const double fj = (double)j;
+        tab[j] = j == 0 ? 0.0 : lean_rcp(PRODUCT ? fj * (fj + 1.0) : fj);
+    }
 }
 
 // Division modes of the continued-fraction loop: 0 = hipcc's `/`, 1 = lean_div, 2 / 3 = lean_div whose reciprocal seed is
@@ -216,8 +293,29 @@ __device__ __forceinline__ double cf_div(double n, double d, double& y) {
     return __builtin_fma(r0, y, q0);
 }
 
-template <int KIND, int MODE>
-__device__ __forceinline__ double contfrac_lazy_impl(double a, double b, double arg) {
+// TAB (MODE 1 only, the pass's class kernels): the reciprocals of both denominators come from ytab (div_table_build<true>,
+// kCfTabJ entries) while the lane's j = a + 2 i is an integer with j + 1 < kCfTabJ.  Decided per lane and iteration: a lane that
+// leaves the table, or whose a is no integer, computes lean_rcp as MODE 1 does - the same value either way, so the quotients are
+// MODE 1's bit for bit.  The address does not depend on the recurrence: the pair of the NEXT iteration is requested before this
+// one's divisions, one LDS instruction for both half steps.
+//
+// LEAN (MODE 1 to 3, the pass's class kernels; LEAN with MODE 1 is TAB): the divisions of the exact block by lean_div.  A wave runs
+// that block in several of its iterations - its lanes converge at different steps, and each passes through 1e-13 > t > 3 MACHEP
+// on the way - so its three `/` are not rare in a wave's instruction stream.  Window: LEAN narrows the fast test's window from
+// 1e-100 / 1e100 to 1e-30 / 1e30 (Cephes' own rescaling keeps |pk| + |qk| below 2^52 times one iteration's growth and both above
+// 2^-52 over it, so this sends nothing on Hi-C rows to the exact block that did not go there; and which iterations run the exact
+// statements never changes a bit).  Inside the block `win` says pk, qk are in (1e-30, 1e30); `lean_live` says every exact block so far
+// took the lean form, so the pending (rp, rq) is (1, 1), a (pk, qk) that passed the fast test - same window - or (ans, 1) with
+// ans = r of a lean block, a quotient of two such values: in (1e-60, 1e60).  Then rp / rq and pk / qk have operands in lean_div's
+// window and values in (1e-60, 1e60), both nonzero - Cephes' `qk != 0` and `r != 0` hold - and ans - r is 0 or at least 2^-53 of
+// 1e-60, over r: 0 or within (1e-136, 1e120).  Anything else (win false, fast_ok false) runs Cephes' statements with `/`, and clears lean_live.
+// x / 1.0 is x: the pending quotient is not divided when rq is 1 (every block after a lane's first, and the loop's exit).
+template <int KIND, int MODE, bool LEAN = false>
+__device__ __forceinline__ double contfrac_lazy_impl(double a, double b, double arg, const double* ytab = nullptr) {
+    static_assert(!LEAN || MODE >= 1, "MODE 0 is the loop for operands outside lean_div's window");
+    constexpr bool TAB = LEAN && MODE == 1;
+    constexpr double kWinLo = LEAN ? 1e-30 : 1e-100, kWinHi = LEAN ? 1e30 : 1e100;
+    bool lean_live = true;
     double k1, k2, k3, k4, k5, k6, k8;
     if (KIND == 0) {
         k1 = a; k2 = a + b; k3 = a; k4 = a + 1.0; k5 = 1.0; k6 = b - 1.0; k8 = a + 2.0;
@@ -241,14 +339,42 @@ __device__ __forceinline__ double contfrac_lazy_impl(double a, double b, double 
             yrec = __builtin_fma(yrec, e0, yrec);
         }
     }
+    // TAB: the lane's j = k3 as an int while it can read the table (tj <= kCfTabJ - 2: entries j and j + 1 exist); any value above
+    // that means "compute".  It steps by 2 with k3 either way: at most kCfTabJ + 600, no wrap.  ty0 / ty1: the requested pair.
+    int tj = kCfTabJ;
+    double ty0 = 0.0, ty1 = 0.0;
+    if (TAB) {
+        if (a < (double)(kCfTabJ - 1)) {                 // a >= 1 (contfrac_lazy): the conversion is in range
+            const int ia = (int)a;
+            if ((double)ia == a) tj = ia;
+        }
+        const int jc = tj < kCfTabJ - 2 ? tj : kCfTabJ - 2;
+        ty0 = ytab[jc];
+        ty1 = ytab[jc + 1];
+    }
     int n = 0;
     do {
-        double xk = -cf_div<MODE>(arg * k1 * k2, k3 * k4, yrec);
+        double y0 = ty0, y1 = ty1;
+        double xk;
+        if (TAB) {
+            const double d0 = k3 * k4;
+            if (__builtin_expect(tj > kCfTabJ - 2, 0)) {
+                y0 = lean_rcp(d0);
+                y1 = lean_rcp(k4 * k8);
+            }
+            tj += 2;
+            const int jc = tj < kCfTabJ - 2 ? tj : kCfTabJ - 2;      // clamped: a lane outside reads an entry it does not use
+            ty0 = ytab[jc];
+            ty1 = ytab[jc + 1];
+            xk = -lean_quot(arg * k1 * k2, d0, y0);
+        } else {
+            xk = -cf_div<MODE>(arg * k1 * k2, k3 * k4, yrec);
+        }
         double pk = pkm1 + pkm2 * xk;
         double qk = qkm1 + qkm2 * xk;
         pkm2 = pkm1; pkm1 = pk; qkm2 = qkm1; qkm1 = qk;
 
-        xk = cf_div<MODE>(arg * k5 * k6, k4 * k8, yrec);
+        xk = TAB ? lean_quot(arg * k5 * k6, k4 * k8, y1) : cf_div<MODE>(arg * k5 * k6, k4 * k8, yrec);
         pk = pkm1 + pkm2 * xk;
         qk = qkm1 + qkm2 * xk;
         pkm2 = pkm1; pkm1 = pk; qkm2 = qkm1; qkm1 = qk;
@@ -257,7 +383,8 @@ __device__ __forceinline__ double contfrac_lazy_impl(double a, double b, double 
         const double mag_sum = aqk + apk;
         const double mag_min = fmin(apk, aqk);
         bool exact = true;
-        if (__builtin_expect(fast_ok && mag_min > 1e-100 && mag_sum < 1e100, 1)) {
+        const bool win = fast_ok && mag_min > kWinLo && mag_sum < kWinHi;
+        if (__builtin_expect(win, 1)) {
             const double c1 = rp * qk;
             const double c2 = pk * rq;
             if (__builtin_expect(fabs(c1 - c2) > 1e-13 * fabs(c2), 1)) {        // certainly t > thresh: Cephes would set ans = r = pk/qk and go on
@@ -267,19 +394,28 @@ __device__ __forceinline__ double contfrac_lazy_impl(double a, double b, double 
             }
         }
         if (__builtin_expect(exact, 0)) {
-            if (fast_ok) {
-                ans = rp / rq;                               // materialise the pending quotient (x / 1.0 is exact)
-                r = ans;
-            }
             double t;
-            if (qk != 0) r = pk / qk;
-            if (r != 0) {
-                t = fabs((ans - r) / r);
+            if (LEAN && win && lean_live) {                  // Cephes' statements with qk != 0 and r != 0 known (above)
+                ans = rp;
+                if (rq != 1.0) ans = lean_div(rp, rq);
+                r = lean_div(pk, qk);
+                t = fabs(lean_div(ans - r, r));
                 ans = r;
             } else {
-                t = 1.0;
+                lean_live = false;
+                if (fast_ok) {
+                    ans = rp / rq;                           // materialise the pending quotient (x / 1.0 is exact)
+                    r = ans;
+                }
+                if (qk != 0) r = pk / qk;
+                if (r != 0) {
+                    t = fabs((ans - r) / r);
+                    ans = r;
+                } else {
+                    t = 1.0;
+                }
+                if (ans != r) fast_ok = false;
             }
-            if (ans != r) fast_ok = false;
             rp = ans;
             rq = 1.0;
             if (t < thresh) break;
@@ -300,19 +436,23 @@ __device__ __forceinline__ double contfrac_lazy_impl(double a, double b, double 
             pkm2 *= kBig; pkm1 *= kBig; qkm2 *= kBig; qkm1 *= kBig;
         }
     } while (++n < 300);
+    if (LEAN && fast_ok) {
+        if (rq == 1.0) return rp;
+        if (lean_live) return lean_div(rp, rq);
+    }
     return fast_ok ? rp / rq : ans;
 }
 
-template <int KIND>
-__device__ __forceinline__ double contfrac_lazy(double a, double b, double x) {
+template <int KIND, bool LEAN = false>
+__device__ __forceinline__ double contfrac_lazy(double a, double b, double x, const double* ytab = nullptr) {
     const double arg = (KIND == 0) ? x : x / (1.0 - x);
     // operand window of lean_div: denominators are (a+2n)(a+2n+1) with 1 <= a < 2^53 (exact integers), numerators are
     // arg * k * k' with |k k'| < 1e20, so |arg| in [1e-150, 1e150] keeps every operand inside [1e-200, 1e200] or exactly 0
     const double aa = fabs(arg);
     if (aa > 1e-150 && aa < 1e150 && a >= 1.0 && a < 4.5e15 && b < 4.5e15) {
-        if (a >= 2e8) return contfrac_lazy_impl<KIND, 3>(a, b, arg);
-        if (a >= 1e6) return contfrac_lazy_impl<KIND, 2>(a, b, arg);
-        return contfrac_lazy_impl<KIND, 1>(a, b, arg);
+        if (a >= 2e8) return contfrac_lazy_impl<KIND, 3, LEAN>(a, b, arg);
+        if (a >= 1e6) return contfrac_lazy_impl<KIND, 2, LEAN>(a, b, arg);
+        return contfrac_lazy_impl<KIND, 1, LEAN>(a, b, arg, ytab);
     }
     return contfrac_lazy_impl<KIND, 0>(a, b, arg);
 }
@@ -929,25 +1069,35 @@ __device__ __forceinline__ double incbet_finish(double a, double b, double x, do
 // bdtrc_count for a row whose class (bdtrc_class) is known at compile time: only that class's code path is
 // instantiated, so the long-running kernels carry neither the other loops' registers nor their branches.
 // Same operations in the same order as incbet() above.
-template <int CLS, bool SMALL_N = true>
-__device__ __forceinline__ double bdtrc_count_class(int count, const BinomTables& T, double p) {
+// LEAN (the pass's class kernels): `tab` is the workgroup's LDS table of reciprocals by integer - div_table_build<false> for
+// BC_PSERIES (pseries<.., true>), div_table_build<true> for BC_CF_BCF and BC_CF_BD (contfrac_lazy<.., true>).  Same bits.
+template <int CLS, bool SMALL_N = true, bool LEAN = false>
+__device__ __forceinline__ double bdtrc_count_class(int count, const BinomTables& T, double p, const double* tab = nullptr) {
+    static_assert(!LEAN || CLS == BC_PSERIES || CLS == BC_CF_BCF || CLS == BC_CF_BD, "the swapped class has no small divisors");
     const double fk = (double)count - 1.0;
     const double aa = fk + 1.0, bb = T.n - fk, xx = p;
     const double lb = T.lbeta[count];
     const double ib = (SMALL_N && T.small_n) ? T.inv_beta[count] : 0.0;
     if (CLS == BC_PSERIES) {
-        if (bb * xx <= 1.0 && xx <= 0.95) return pseries<SMALL_N>(aa, bb, xx, lb, ib);
+        if (LEAN) {                                       // one inlined series for both orientations: a wave that mixes them runs one loop
+            const bool direct = bb * xx <= 1.0 && xx <= 0.95;
+            const double w = 1.0 - xx;
+            const double t = pseries<SMALL_N, true>(direct ? aa : bb, direct ? bb : aa, direct ? xx : w, lb, ib, tab);
+            if (direct) return t;
+            return (t <= kMachEp) ? 1.0 - kMachEp : 1.0 - t;
+        }
+        if (bb * xx <= 1.0 && xx <= 0.95) return pseries<SMALL_N, LEAN>(aa, bb, xx, lb, ib, tab);
         const double w = 1.0 - xx;                       // otherwise the swapped orientation (flag = 1)
-        double t = pseries<SMALL_N>(bb, aa, w, lb, ib);
+        double t = pseries<SMALL_N, LEAN>(bb, aa, w, lb, ib, tab);
         return (t <= kMachEp) ? 1.0 - kMachEp : 1.0 - t;
     }
     const double w1 = 1.0 - xx;
-    if (CLS == BC_CF_BCF) return incbet_finish<SMALL_N>(aa, bb, xx, w1, contfrac_lazy<0>(aa, bb, xx), 0, lb, ib);
+    if (CLS == BC_CF_BCF) return incbet_finish<SMALL_N>(aa, bb, xx, w1, contfrac_lazy<0, LEAN>(aa, bb, xx, tab), 0, lb, ib);
     if (CLS == BC_CF_SWAPPED) return incbet_finish<SMALL_N>(bb, aa, w1, xx, contfrac_lazy<0>(bb, aa, w1), 1, lb, ib);
     // BC_CF_BD: either orientation
     const int flag = (xx > aa / (aa + bb)) ? 1 : 0;
     const double a = flag ? bb : aa, b = flag ? aa : bb, x = flag ? w1 : xx, xc = flag ? xx : w1;
-    return incbet_finish<SMALL_N>(a, b, x, xc, contfrac_lazy<1>(a, b, x) / xc, flag, lb, ib);
+    return incbet_finish<SMALL_N>(a, b, x, xc, contfrac_lazy<1, LEAN>(a, b, x, tab) / xc, flag, lb, ib);
 }
 
 }  // namespace dev

@@ -479,6 +479,10 @@ template <int CLS, bool SMALL_N>
 __global__ __launch_bounds__(K2_THREADS) void k2_queue(K2Params P, QSpan q) {
     __shared__ unsigned int hist_lds[K2_HIST_BINS];
     __shared__ unsigned int prefix_lds[QDense::PAIRS + 1], wave_tot[K2_WAVES];
+    // the power series divides by small integers: their refined reciprocals, once per workgroup (fhx_bdtrc.hpp, pseries<.., LEAN>)
+    constexpr bool LEAN = CLS == dev::BC_PSERIES;
+    __shared__ double rtab[LEAN ? dev::kPsTabJ : 1];
+    if (LEAN) dev::div_table_build<false>(rtab, dev::kPsTabJ);          // D.build's barriers stand between this and the first read
     FusedHist H;
     H.init(hist_lds, P.top_hist);
     QDense D;
@@ -496,7 +500,7 @@ __global__ __launch_bounds__(K2_THREADS) void k2_queue(K2Params P, QSpan q) {
         const QEntry e = *D.at(q, cur, (unsigned int)v);
         const bool is_inter = e.count < 0;
         const int c = is_inter ? -e.count : e.count;
-        const double pv = dev::bdtrc_count_class<CLS, SMALL_N>(c, is_inter ? P.inter : P.intra, e.prior);
+        const double pv = dev::bdtrc_count_class<CLS, SMALL_N, LEAN>(c, is_inter ? P.inter : P.intra, e.prior, rtab);
         store_p<false>(P.p + e.row, pv);
         H.add(pv);
     }
@@ -519,6 +523,10 @@ __global__ __launch_bounds__(K2_THREADS) __attribute__((amdgpu_waves_per_eu(WPE)
     __shared__ unsigned int bucket_cnt[K2_SORT_BUCKETS], bucket_off[K2_SORT_BUCKETS];
     __shared__ unsigned int hist_lds[K2_HIST_BINS];
     __shared__ unsigned int prefix_lds[QDense::PAIRS + 1], wave_tot[K2_WAVES], tile_lds;
+    // both fractions divide by j (j + 1), j = count + 2 i: the refined reciprocals by j, once per workgroup (fhx_bdtrc.hpp,
+    // contfrac_lazy_impl<.., TAB>; kCfTabJ is what the LDS leaves at four workgroups per CU)
+    __shared__ double ytab[dev::kCfTabJ];
+    dev::div_table_build<true>(ytab, dev::kCfTabJ);                      // D.build's barriers stand between this and the first read
     FusedHist H;
     H.init(hist_lds, P.top_hist);
     QDense D;
@@ -574,7 +582,7 @@ __global__ __launch_bounds__(K2_THREADS) __attribute__((amdgpu_waves_per_eu(WPE)
                 const QEntry x = tile[idx];
                 const bool is_inter = x.count < 0;
                 const int c = is_inter ? -x.count : x.count;
-                const double pv = dev::bdtrc_count_class<CLS, SMALL_N>(c, is_inter ? P.inter : P.intra, x.prior);
+                const double pv = dev::bdtrc_count_class<CLS, SMALL_N, true>(c, is_inter ? P.inter : P.intra, x.prior, ytab);
                 store_p<false>(P.p + x.row, pv);
                 H.add(pv);
             }
@@ -849,6 +857,20 @@ __global__ void k_debug_contfrac(const double* __restrict__ a, const double* __r
 __global__ void k_debug_lean_div(const double* __restrict__ n, const double* __restrict__ d, int64_t len, double* __restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += stride) out[i] = dev::lean_div(n[i], d[i]);
+}
+
+// the class kernels' division by a tabulated reciprocal: workgroup j - 1 builds the whole LDS table as they do and divides every
+// numerator by the table's j-th divisor - j (j + 1) or j - with the statement their loops use
+template <bool PRODUCT, int LEN>
+__global__ __launch_bounds__(256) void k_debug_table_div(const double* __restrict__ num, int64_t m, double* __restrict__ out) {
+    __shared__ double tab[LEN];
+    dev::div_table_build<PRODUCT>(tab, LEN);
+    __syncthreads();
+    const int j = (int)blockIdx.x + 1;
+    if (j >= LEN) return;
+    const double fj = (double)j;
+    const double d = PRODUCT ? fj * (fj + 1.0) : fj;
+    for (int64_t i = threadIdx.x; i < m; i += blockDim.x) out[(int64_t)(j - 1) * m + i] = dev::lean_quot(num[i], d, tab[j]);
 }
 
 // ---- no bias file: p depends on (distance index, count) only ------------------------------------------------------
@@ -1152,7 +1174,8 @@ static void launch_k2_queue(fhx_ctx* ctx, const K2Params& P, const K2Queues& Q) 
 }
 template <int CLS, bool SMALL_N>
 static void launch_k2_queue_by_count(fhx_ctx* ctx, const K2Params& P, const K2Queues& Q) {
-    constexpr int PIECE = SMALL_N ? 4 : 5;
+    // waves per SIMD the compiler aims at: LDS admits four workgroups per CU; BD carries both orientations' loops and only fits 128 VGPRs when asked to
+    constexpr int PIECE = (SMALL_N || CLS == dev::BC_CF_BD) ? 4 : 5;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k2_queue_by_count<CLS, SMALL_N, PIECE>), dim3(resident_grid(ctx, k2_queue_by_count<CLS, SMALL_N, PIECE>)),
                        dim3(K2_THREADS), 0, ctx->stream, P, Q.q[CLS - 1], (unsigned int*)(ctx->d_words->k2_next + CLS));
 }
@@ -1514,6 +1537,30 @@ int fhx_debug_lean_div(fhx_ctx* ctx, const double* n, const double* d, int64_t l
     FHX_HIP(hipMemcpyAsync(out, dv[2], bytes, hipMemcpyDeviceToHost, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
     for (int k = 0; k < 3; ++k) dev_free(dv[k]);
+    return FHX_OK;
+}
+
+int fhx_debug_table_div(fhx_ctx* ctx, int kind, const double* num, int64_t m, double* out, int32_t* table_len) {
+    if (!ctx || (kind != 0 && kind != 1) || !num || !out || !table_len || m < 0) return FHX_ERR_ARG;
+    if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
+    const int len = kind == 0 ? dev::kCfTabJ : dev::kPsTabJ;
+    *table_len = len;
+    if (m == 0) return FHX_OK;
+    FHX_HIP(hipSetDevice(ctx->device));
+    double *d_num = nullptr, *d_out = nullptr;
+    const size_t out_bytes = (size_t)(len - 1) * (size_t)m * sizeof(double);
+    FHX_HIP(hipMalloc(&d_num, (size_t)m * sizeof(double)));
+    FHX_HIP(hipMalloc(&d_out, out_bytes));
+    FHX_HIP(hipMemcpyAsync(d_num, num, (size_t)m * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (kind == 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_debug_table_div<true, dev::kCfTabJ>), dim3(len - 1), dim3(256), 0, ctx->stream, d_num, m, d_out);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_debug_table_div<false, dev::kPsTabJ>), dim3(len - 1), dim3(256), 0, ctx->stream, d_num, m, d_out);
+    FHX_HIP(hipGetLastError());
+    FHX_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    FHX_HIP(hipStreamSynchronize(ctx->stream));
+    dev_free(d_num);
+    dev_free(d_out);
     return FHX_OK;
 }
 

@@ -381,6 +381,11 @@ int fhx_debug_classify(fhx_ctx* ctx, double n_total, const int32_t* count, const
                        int32_t* by_arith, double* thr5);
 /* Test hook: out[i] = K2's lean division of n[i] / d[i] (must equal IEEE n/d inside the operand window it is used in). */
 int fhx_debug_lean_div(fhx_ctx* ctx, const double* n, const double* d, int64_t len, double* out);
+/* Test hook: K2's division by a tabulated reciprocal, as the class kernels do it (an LDS table of refined reciprocals by integer j,
+ * built per workgroup).  kind 0: the divisor is j (j + 1), the continued fractions' table; kind 1: the divisor is j, the power
+ * series' table.  table_len receives the table's length J; out[(j - 1) * m + i] = num[i] / divisor(j) for 1 <= j < J, so out holds
+ * (J - 1) * m doubles (call with m = 0 to learn J).  Must equal IEEE division for numerators that are 0 or in [1e-200, 1e200]. */
+int fhx_debug_table_div(fhx_ctx* ctx, int kind, const double* num, int64_t m, double* out, int32_t* table_len);
 /* Test hook: the device writer's number formatting on arbitrary doubles - kind 0 "%e", 1 "%f"; text32 receives 32 bytes per value
  * (zero padded), len the character count, or -1 where the device formatter hands the row to the host (|v| >= 2^64 / 2^63). */
 int fhx_debug_format(fhx_ctx* ctx, const double* values, int64_t n, int32_t kind, char* text32, int32_t* len);
