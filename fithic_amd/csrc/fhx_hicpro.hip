@@ -140,16 +140,14 @@ __global__ __launch_bounds__(WG) void hp_parse(const unsigned char* __restrict__
                                                int32_t* __restrict__ mid2, int32_t* __restrict__ count, unsigned long long* __restrict__ totals,
                                                unsigned long long* __restrict__ first_error, unsigned long long* __restrict__ absent_index) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
-    for (int base = 0; base < n_lines; base += WG) {        // n_lines is the same for every lane: the shuffles below see whole waves
+    const BlockLines B = block_lines(text, T, block_off, lstart);
+    for (int base = 0; base < B.n_lines; base += WG) {      // n_lines is the same for every lane: the shuffles below see whole waves
         const int e = base + threadIdx.x;
         long long si = -1, sj = -1;
         int cnt = 0;
-        if (e < n_lines) {
-            const int64_t r = row0 + e;
-            Cursor c{text, T, b0 + lstart[e], 0, 0};
+        if (e < B.n_lines) {
+            const int64_t r = B.row0 + e;
+            Cursor c{text, T, B.b0 + lstart[e], 0, 0};
             c.limit = c.p + MAX_LINE;
             long long i = 0, j = 0, absent = 0;
             bool ok = (c.next_token() && c.integer(&i) && c.next_token() && c.integer(&j) && c.next_token() && c.count(&cnt)) ||
@@ -330,25 +328,26 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
     if (timing)
         std::fprintf(stderr, "hicpro matrix on the device (%s): %lld lines, %lld bytes: upload %.6f s; scan %.6f s; parse + accumulate %.6f s\n",
                      path, (long long)n, (long long)T, t_stage[0], t_stage[1], t_stage[2]);
-    auto refuse = [&](int rc, int32_t w, int64_t line, int64_t index, const std::string& msg) {
+    const fhx::Refusal refused{hp, why, bad_line};
+    auto forget = [&] {                                                       // nothing stays loaded
         drop_rows(hp);
         (void)hipMemsetAsync(hp->d_totals, 0, slots * sizeof(unsigned long long), hp->stream);
         (void)hipStreamSynchronize(hp->stream);
-        *why = w;
-        *bad_line = line;
+    };
+    auto refuse = [&](int rc, int32_t w, int64_t line, int64_t index, const std::string& msg) {
+        forget();
         *bad_index = index;
-        return hp->fail(rc, msg);
+        return refused(rc, w, line, msg);
     };
     if (words[1] != NO_ERROR) {
-        const int32_t w = error_why(words[1]);
         const int64_t line = error_line(words[1]);
-        if (w == FHX_HP_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, 0, "the line count of the scan and the parse kernel disagree");
-        if (w == FHX_HP_ABSENT) {
-            if ((int64_t)(words[2] >> 32) != line) return refuse(FHX_ERR_INTERNAL, FHX_HP_INTERNAL, line, 0, "error words disagree about the first bad line");
-            const int64_t index = (int64_t)(int32_t)(unsigned int)(words[2] & 0xFFFFFFFFull);
-            return refuse(FHX_ERR_REFERENCE_EXIT, w, line, index, "line " + std::to_string(line) + ": index " + std::to_string(index) + " is not in the bed file");
+        if (error_why(words[1]) != FHX_HP_ABSENT) {
+            forget();
+            return refused.word(words[1], FHX_HP_INTERNAL);
         }
-        return refuse(FHX_ERR_UNSUPPORTED, w, line, 0, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
+        if ((int64_t)(words[2] >> 32) != line) return refuse(FHX_ERR_INTERNAL, FHX_HP_INTERNAL, line, 0, "error words disagree about the first bad line");
+        const int64_t index = (int64_t)(int32_t)(unsigned int)(words[2] & 0xFFFFFFFFull);
+        return refuse(FHX_ERR_REFERENCE_EXIT, FHX_HP_ABSENT, line, index, "line " + std::to_string(line) + ": index " + std::to_string(index) + " is not in the bed file");
     }
     if (words[4]) return refuse(FHX_ERR_INTERNAL, FHX_HP_INTERNAL, 0, 0, "the scan saw a byte this path does not take, the parse kernel did not");
     if (words[3] >= TOTAL_LIMIT)

@@ -46,8 +46,6 @@ constexpr int BIN_DIGITS = 10, COUNT_DIGITS = 15;
 constexpr long long COUNT_MAX = 1ll << 24;     // hicstraw's records are binary32: every whole number up to here is one
 
 struct Words {
-    unsigned long long newlines;               // scan_tiles' total of the current batch
-    unsigned long long bad_bytes;              // scan_text's flag word
     unsigned long long first_error;            // smallest (line << 8 | reason)
     unsigned long long out_bytes;              // scan_tiles' total of the block bytes
 };
@@ -163,13 +161,11 @@ __global__ __launch_bounds__(WG) void jc_parse(const unsigned char* __restrict__
                                                unsigned short* __restrict__ info, unsigned int* __restrict__ block_bytes,
                                                Words* __restrict__ words) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     unsigned int my_bytes = 0;
-    for (int e = threadIdx.x; e < n_lines; e += WG) {
-        const int64_t r = row0 + e;
-        const int64_t start = b0 + lstart[e];
+    for (int e = threadIdx.x; e < B.n_lines; e += WG) {
+        const int64_t r = B.row0 + e;
+        const int64_t start = B.b0 + lstart[e];
         Line L;
         walk(text, T, start, check_bytes, L);
         int why = L.why;
@@ -229,23 +225,21 @@ __global__ __launch_bounds__(WG) void jc_format(const unsigned char* __restrict_
                                                 int64_t out_capacity, Words* __restrict__ words) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
     __shared__ __attribute__((aligned(16))) unsigned char window[WINDOW];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     int64_t at = (int64_t)out_off[blockIdx.x];
-    for (int base = 0; base < n_lines; base += WG) {        // n_lines is the same for every lane
+    for (int base = 0; base < B.n_lines; base += WG) {      // n_lines is the same for every lane
         const int e = base + (int)threadIdx.x;
-        const int64_t r = row0 + e;
-        const bool valid = e < n_lines && r < n_lines_batch;
+        const int64_t r = B.row0 + e;
+        const bool valid = e < B.n_lines && r < n_lines_batch;
         const unsigned int len = valid ? (unsigned int)info[r] : 0u;
         unsigned int total;
         const unsigned int pre = fhxscan::block_exclusive_scan(len, &total);
         // the line's pieces, once for all its windows
-        const unsigned char* line = text + b0 + (len ? (int64_t)lstart[e] : 0);
+        const unsigned char* line = text + B.b0 + (len ? (int64_t)lstart[e] : 0);
         Line L;
         L.b1 = L.n1 = L.b2 = L.n2 = L.b3 = L.n3 = 0;
         long long m1 = 0, m2 = 0, c = 0;
-        if (len && res == 0) walk(text, T, b0 + lstart[e], 0, L);
+        if (len && res == 0) walk(text, T, B.b0 + lstart[e], 0, L);
         else if (len) {
             m1 = mid1[r];
             m2 = mid2[r];
@@ -318,18 +312,6 @@ void drop_all(fhx_jc* jc) {
     std::vector<char>().swap(jc->text);
 }
 
-// a device array of one call that grows to what a batch needs
-template <typename T>
-hipError_t grow(fhx::Scratch& tmp, T** p, int64_t* capacity, int64_t need) {
-    if (need <= *capacity) return hipSuccess;
-    if (*p) tmp.drop(*p);
-    *p = nullptr;
-    *capacity = 0;
-    const hipError_t e = tmp.get(p, (size_t)need);
-    if (e == hipSuccess) *capacity = need;
-    return e;
-}
-
 // room for `need` rows in the five columns, the first `keep` of them kept
 hipError_t grow_columns(fhx_jc* jc, int64_t keep, int64_t need) {
     if (need <= jc->col_capacity) return hipSuccess;
@@ -386,6 +368,82 @@ int copy_out(fhx_jc* jc, const unsigned char* d_out, int64_t bytes) {
     return FHX_OK;
 }
 
+// fhx_jc_convert_file behind its argument checks; whatever it returns but FHX_OK, the caller drops everything
+int convert_file(fhx_jc* jc, const char* path, const char* name1, const char* name2, int64_t resolution, int32_t id1, int32_t id2,
+                 int32_t keep_text, int32_t keep_rows, int64_t* n_lines, int32_t* why, int64_t* bad_line) {
+    using namespace jcd;
+    TH_HIP(jc, hipSetDevice(jc->device));
+    TH_HIP(jc, hipStreamSynchronize(jc->stream));
+    fhx::StageClock clock{jc->seconds};
+    fhx::Scratch tmp;
+    fhx::TextBatches in;
+    if (const int rc = in.open(jc, &tmp, &clock, path, "dump", "FHX_JC_BATCH_BYTES", (int64_t)1 << 31)) return rc;
+    const int len1 = (int)std::strlen(name1), len2 = (int)std::strlen(name2);
+    unsigned char *d_out = nullptr, *d_names = nullptr;
+    unsigned int* d_block_bytes = nullptr;
+    unsigned long long* d_out_off = nullptr;
+    unsigned short* d_info = nullptr;
+    int64_t info_capacity = 0, out_capacity = 0;
+    Words* d_words = nullptr;
+    TH_HIP(jc, tmp.get(&d_block_bytes, (size_t)in.max_blocks));
+    TH_HIP(jc, tmp.get(&d_out_off, (size_t)in.max_blocks));
+    TH_HIP(jc, tmp.get(&d_names, (size_t)2 * NAME_SLOT));
+    TH_HIP(jc, tmp.get(&d_words, 1));
+    unsigned char names[2 * NAME_SLOT];
+    std::memset(names, 0, sizeof(names));
+    std::memcpy(names, name1, (size_t)len1);
+    std::memcpy(names + NAME_SLOT, name2, (size_t)len2);
+    TH_HIP(jc, hipMemcpyAsync(d_names, names, sizeof(names), hipMemcpyHostToDevice, jc->stream));
+    TH_HIP(jc, hipStreamSynchronize(jc->stream));
+    Words words;
+    const fhx::Refusal refuse{jc, why, bad_line};
+    for (; in.more(); in.advance()) {
+        std::memset(&words, 0, sizeof(words));
+        words.first_error = NO_ERROR;
+        TH_HIP(jc, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, jc->stream));
+        if (const int rc = in.next<JcBytes>()) return rc;
+        const int64_t n = in.lines;
+        const int64_t row_base = jc->n_rows;                                  // a call that keeps no rows writes every batch over the last
+        TH_HIP(jc, tmp.grow(&d_info, &info_capacity, n));
+        if (resolution != 0) TH_HIP(jc, grow_columns(jc, row_base, row_base + n));
+        int32_t* col[5];
+        for (int k = 0; k < 5; ++k) col[k] = jc->d_col[k] ? jc->d_col[k] + row_base : nullptr;
+        hipLaunchKernelGGL(jc_parse, dim3((unsigned)in.n_blocks), dim3(WG), 0, jc->stream, (const unsigned char*)in.d_text, in.len,
+                           (const unsigned long long*)in.d_block_off, n, in.line_base, (long long)resolution, len1 + len2, (int)id1, (int)id2,
+                           (int)in.refused_bytes, col[0], col[1], col[2], col[3], col[4], d_info, d_block_bytes, d_words);
+        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, jc->stream, (const unsigned int*)d_block_bytes, in.n_blocks,
+                           d_out_off, &d_words->out_bytes);
+        TH_HIP(jc, hipGetLastError());
+        TH_HIP(jc, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, jc->stream));
+        TH_HIP(jc, hipStreamSynchronize(jc->stream));
+        clock.mark(2);
+        if (words.first_error != NO_ERROR) return refuse.word(words.first_error, FHX_JC_INTERNAL);      // earlier batches hold the smaller line numbers
+        const int64_t bytes = (int64_t)words.out_bytes;
+        if (keep_text && bytes > 0) {
+            TH_HIP(jc, tmp.grow(&d_out, &out_capacity, (bytes + 15) / 16 * 16));
+            hipLaunchKernelGGL(jc_format, dim3((unsigned)in.n_blocks), dim3(WG), 0, jc->stream, (const unsigned char*)in.d_text, in.len,
+                               (const unsigned long long*)in.d_block_off, n, in.line_base, (long long)resolution, (const unsigned char*)d_names, len1,
+                               len2, (const int32_t*)col[1], (const int32_t*)col[3], (const int32_t*)col[4], (const unsigned short*)d_info,
+                               (const unsigned long long*)d_out_off, d_out, bytes, d_words);
+            TH_HIP(jc, hipGetLastError());
+            TH_HIP(jc, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, jc->stream));
+            TH_HIP(jc, hipStreamSynchronize(jc->stream));
+            clock.mark(3);
+            if (words.first_error != NO_ERROR) return refuse.word(words.first_error, FHX_JC_INTERNAL);
+            if (const int rc = copy_out(jc, d_out, bytes)) return rc;
+            clock.mark(4);
+        }
+        if (keep_rows) jc->n_rows += n;
+    }
+    jc->n_lines += in.line_base;
+    *n_lines = in.line_base;
+    if (std::getenv("FHX_TIMING"))
+        std::fprintf(stderr, "juicer dump on the device (%s): %lld lines, %lld bytes of output so far: read + upload %.6f s; scan %.6f s; parse %.6f s; "
+                     "format %.6f s; copy out %.6f s\n", path, (long long)in.line_base, (long long)jc->text.size(), jc->seconds[0], jc->seconds[1],
+                     jc->seconds[2], jc->seconds[3], jc->seconds[4]);
+    return FHX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -409,7 +467,6 @@ int fhx_jc_reset(fhx_jc* jc) {
 
 int fhx_jc_convert_file(fhx_jc* jc, const char* path, const char* name1, const char* name2, int64_t resolution, int32_t id1, int32_t id2,
                         int32_t keep_text, int32_t keep_rows, int64_t* n_lines, int32_t* why, int64_t* bad_line) {
-    using namespace jcd;
     if (!jc || !path || !n_lines || !why || !bad_line) return FHX_ERR_ARG;
     *n_lines = 0;
     *why = FHX_JC_OK;
@@ -417,112 +474,9 @@ int fhx_jc_convert_file(fhx_jc* jc, const char* path, const char* name1, const c
     if (!name_ok(name1) || !name_ok(name2)) return jc->fail(FHX_ERR_ARG, "a chromosome name must be 1 to 66 bytes of [A-Za-z0-9_.-]");
     if (resolution < 0 || resolution > 0x7fffffffll) return jc->fail(FHX_ERR_ARG, "the resolution must be 1 to 2^31 - 1 (0: verbatim mode)");
     if (keep_rows && resolution == 0) return jc->fail(FHX_ERR_ARG, "verbatim mode has no rows to keep");
-    TH_HIP(jc, hipSetDevice(jc->device));
-    TH_HIP(jc, hipStreamSynchronize(jc->stream));
-    fhx::StageClock clock{jc->seconds};
-    fhx::TextFile src;
-    if (const int rc = src.open(path, /*allow_gzip=*/true, &jc->err)) return rc;
-    const int64_t batch_bytes = fhx::batch_bytes_for("FHX_JC_BATCH_BYTES", (int64_t)1 << 31, src.size());
-    const int64_t max_blocks = (batch_bytes + BLOCK_BYTES - 1) / BLOCK_BYTES;
-    const int len1 = (int)std::strlen(name1), len2 = (int)std::strlen(name2);
-    fhx::Scratch tmp;
-    unsigned char *d_text = nullptr, *d_out = nullptr, *d_names = nullptr;
-    unsigned int *d_block_nl = nullptr, *d_block_bytes = nullptr;
-    unsigned long long *d_block_off = nullptr, *d_out_off = nullptr;
-    unsigned short* d_info = nullptr;
-    int64_t info_capacity = 0, out_capacity = 0;
-    Words* d_words = nullptr;
-    TH_HIP(jc, tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
-    TH_HIP(jc, tmp.get(&d_block_nl, (size_t)max_blocks));
-    TH_HIP(jc, tmp.get(&d_block_bytes, (size_t)max_blocks));
-    TH_HIP(jc, tmp.get(&d_block_off, (size_t)max_blocks));
-    TH_HIP(jc, tmp.get(&d_out_off, (size_t)max_blocks));
-    TH_HIP(jc, tmp.get(&d_names, (size_t)2 * NAME_SLOT));
-    TH_HIP(jc, tmp.get(&d_words, 1));
-    unsigned char names[2 * NAME_SLOT];
-    std::memset(names, 0, sizeof(names));
-    std::memcpy(names, name1, (size_t)len1);
-    std::memcpy(names + NAME_SLOT, name2, (size_t)len2);
-    TH_HIP(jc, hipMemcpyAsync(d_names, names, sizeof(names), hipMemcpyHostToDevice, jc->stream));
-    TH_HIP(jc, hipStreamSynchronize(jc->stream));
-    Words words;
-    auto refuse = [&](int rc, int32_t w, int64_t line, const std::string& msg) {
-        drop_all(jc);
-        *why = w;
-        *bad_line = line;
-        return jc->fail(rc, msg);
-    };
-    auto refuse_word = [&](unsigned long long word) {
-        const int32_t w = error_why(word);
-        const int64_t line = error_line(word);
-        if (w == FHX_JC_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, "the kernels of the conversion disagree about line " + std::to_string(line));
-        return refuse(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
-    };
-    int64_t lines = 0;
-    for (int64_t off = 0; off < src.size();) {
-        std::memset(&words, 0, sizeof(words));
-        words.first_error = NO_ERROR;
-        TH_HIP(jc, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, jc->stream));
-        fhx::TextBatch b;
-        if (const int rc = fhx::upload_batch(jc, src, "dump", off, std::min(batch_bytes, src.size() - off), d_text, &b)) {
-            drop_all(jc);
-            return rc;
-        }
-        const int64_t len = b.len, n_blocks = b.n_blocks;
-        clock.mark(0);
-        hipLaunchKernelGGL(scan_text<JcBytes>, dim3((unsigned)n_blocks), dim3(WG), 0, jc->stream, (const unsigned char*)d_text, len, d_block_nl,
-                           (unsigned int*)&d_words->bad_bytes);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, jc->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
-                           &d_words->newlines);
-        TH_HIP(jc, hipGetLastError());
-        TH_HIP(jc, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, jc->stream));
-        TH_HIP(jc, hipStreamSynchronize(jc->stream));
-        clock.mark(1);
-        const int64_t n = b.lines(words.newlines);
-        const int64_t row_base = jc->n_rows;                                  // a call that keeps no rows writes every batch over the last
-        TH_HIP(jc, grow(tmp, &d_info, &info_capacity, n));
-        if (resolution != 0) TH_HIP(jc, grow_columns(jc, row_base, row_base + n));
-        int32_t* col[5];
-        for (int k = 0; k < 5; ++k) col[k] = jc->d_col[k] ? jc->d_col[k] + row_base : nullptr;
-        hipLaunchKernelGGL(jc_parse, dim3((unsigned)n_blocks), dim3(WG), 0, jc->stream, (const unsigned char*)d_text, len,
-                           (const unsigned long long*)d_block_off, n, lines, (long long)resolution, len1 + len2, (int)id1, (int)id2,
-                           (int)(words.bad_bytes != 0), col[0], col[1], col[2], col[3], col[4], d_info, d_block_bytes, d_words);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, jc->stream, (const unsigned int*)d_block_bytes, n_blocks, d_out_off,
-                           &d_words->out_bytes);
-        TH_HIP(jc, hipGetLastError());
-        TH_HIP(jc, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, jc->stream));
-        TH_HIP(jc, hipStreamSynchronize(jc->stream));
-        clock.mark(2);
-        if (words.first_error != NO_ERROR) return refuse_word(words.first_error);          // earlier batches hold the smaller line numbers
-        const int64_t bytes = (int64_t)words.out_bytes;
-        if (keep_text && bytes > 0) {
-            TH_HIP(jc, grow(tmp, &d_out, &out_capacity, (bytes + 15) / 16 * 16));
-            hipLaunchKernelGGL(jc_format, dim3((unsigned)n_blocks), dim3(WG), 0, jc->stream, (const unsigned char*)d_text, len,
-                               (const unsigned long long*)d_block_off, n, lines, (long long)resolution, (const unsigned char*)d_names, len1, len2,
-                               (const int32_t*)col[1], (const int32_t*)col[3], (const int32_t*)col[4], (const unsigned short*)d_info,
-                               (const unsigned long long*)d_out_off, d_out, bytes, d_words);
-            TH_HIP(jc, hipGetLastError());
-            TH_HIP(jc, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, jc->stream));
-            TH_HIP(jc, hipStreamSynchronize(jc->stream));
-            clock.mark(3);
-            if (words.first_error != NO_ERROR) return refuse_word(words.first_error);
-            if (const int rc = copy_out(jc, d_out, bytes)) {
-                drop_all(jc);
-                return rc;
-            }
-            clock.mark(4);
-        }
-        if (keep_rows) jc->n_rows += n;
-        lines += n;
-        off += len;
-    }
-    jc->n_lines += lines;
-    *n_lines = lines;
-    if (std::getenv("FHX_TIMING"))
-        std::fprintf(stderr, "juicer dump on the device (%s): %lld lines, %lld bytes of output so far: read + upload %.6f s; scan %.6f s; parse %.6f s; "
-                     "format %.6f s; copy out %.6f s\n", path, (long long)lines, (long long)jc->text.size(), jc->seconds[0], jc->seconds[1],
-                     jc->seconds[2], jc->seconds[3], jc->seconds[4]);
-    return FHX_OK;
+    const int rc = convert_file(jc, path, name1, name2, resolution, id1, id2, keep_text, keep_rows, n_lines, why, bad_line);
+    if (rc != FHX_OK) drop_all(jc);                                           // the one exit of a failed conversion, whatever failed
+    return rc;
 }
 
 int fhx_jc_counts(const fhx_jc* jc, int64_t* n_lines, int64_t* n_rows, int64_t* n_bytes) {

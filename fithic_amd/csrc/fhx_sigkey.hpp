@@ -1,6 +1,7 @@
 // fhx_sigkey.hpp - the decision merge-filter.sh makes on the TEXT of field 7 (`$7 <= q` under mawk 1.3.4, LC_ALL=C), shared by the
-// file route (fhx_sigselect.hip: ms_select reads the field from the file's bytes) and the resident route (fhx_sigresident.inc:
-// sr_decide formats q with fmt_e6 and reads the field from registers), so the two cannot drift apart.
+// file route (fhx_sigselect.hip, fhx_sigtrack.inc, fhx_sigsplit.inc: ms_select, ut_select and mp_select read the field from the
+// file's bytes and share decide()) and the resident route (fhx_sigresident.inc: sr_decide formats q with fmt_e6 and reads the
+// field from registers), so the two cannot drift apart.
 //
 // A field in the shape C's %e writes, D.DDDDDDe[+-]XX[X], is
 //   zero     every digit 0: the number 0, kept when 0 <= fdr (0 < fdr when strict) - the host says which
@@ -64,6 +65,20 @@ __device__ inline int compare_text(const unsigned char* __restrict__ text, int64
         if (a != q) return a < q ? -1 : 1;
     }
     return len < fdr.len ? -1 : (len > fdr.len ? 1 : 0);
+}
+
+// The decision on the field at text[b, b + len) that classify put into class cls with `key`: *keep set and 0, or FHX_MS_FIELD for
+// class 0.  strict: `$7 < q` (the track) instead of `$7 <= q`; the host has made key_bound and zero_kept for the same operator.
+__device__ inline int decide(int cls, unsigned long long key, unsigned long long key_bound, int zero_kept, int strict,
+                             const unsigned char* __restrict__ text, int64_t b, int len, const Fdr& fdr, bool* keep) {
+    if (cls == 0) return FHX_MS_FIELD;
+    if (cls == 1) *keep = zero_kept != 0;
+    else if (cls == 2) *keep = key <= key_bound;
+    else {
+        const int cmp = compare_text(text, b, len, fdr);
+        *keep = strict ? cmp < 0 : cmp <= 0;
+    }
+    return 0;
 }
 
 }  // namespace msd

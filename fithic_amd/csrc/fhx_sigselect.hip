@@ -7,7 +7,7 @@
 //   scan_text, scan_tiles    the newline layer (fhx_textlines.hpp) with this grammar's byte policy: the line number of every
 //                  block's first line, and one flag for the batch when a byte outside the grammar is seen (ms_select looks at
 //                  bytes one by one only then)
-//   ms_select      the lines that begin in a block, one per lane.  One walk along the line splits it on blanks and finds field 7;
+//   ms_select      the lines that begin in a block, one per lane.  One walk along the line (fhx_sigline.hpp) splits it on blanks and finds field 7;
 //                  the field is taken only in the shape C's %e writes, D.DDDDDDe[+-]XX[X], and is then
 //                    zero     every digit 0: the number 0, kept when 0 <= fdr (0 < fdr when strict) - the host says which
 //                    numeric  [2.225074e-308, 9.999999e+307]: awk compares numbers, and strtod is monotone in the integer key
@@ -18,8 +18,8 @@
 //                  block: kept bytes and kept lines.
 //   scan_tiles     kept bytes per block -> the block's offset in the subset
 //   ms_gather      the kept lines, verbatim and in file order, into a dense buffer: 256 lines per round, their lengths scanned
-//                  into LDS, lanes assigned by OUTPUT byte (a binary search in the 256 prefixes), so stores are coalesced at
-//                  1 % kept and at 100 %.  A final line without its newline gets one, as awk's print gives it.
+//                  into LDS, lanes assigned by OUTPUT byte (gather_round: a binary search in the 256 prefixes), so stores are
+//                  coalesced at 1 % kept and at 100 %.  A final line without its newline gets one, as awk's print gives it.
 //
 // The subset of each batch is copied to the host and appended.  The UCSC interact track of the same selection (strict, no line
 // skipped) is made by the kernels of fhx_sigtrack.inc, the per-chromosome subsets of merge-filter-parallelized.sh by those of
@@ -39,6 +39,7 @@
 #include "fhx_namerule.hpp"
 #include "fhx_score.hpp"
 #include "fhx_sigkey.hpp"
+#include "fhx_sigline.hpp"
 #include "fhx_textupload.hpp"
 #include "fhx_trackline.hpp"
 
@@ -48,18 +49,9 @@ using namespace fhxlines;
 
 // the words the kernels of one call share
 struct Words {
-    unsigned long long newlines;               // scan_tiles' total of the current batch
-    unsigned long long bad_bytes;              // not 0: scan_text saw a byte outside the grammar in the current batch (it ORs
-                                               // REFUSED_BYTES into the word's low half)
     unsigned long long first_error;            // smallest (line << 8 | reason)
     unsigned long long kept_bytes;             // scan_tiles' total of the current batch
     unsigned long long kept_lines;             // of the current batch
-};
-
-__device__ inline bool refused_byte(unsigned int c) { return c < 0x20u ? (c != '\t' && c != '\n') : c >= 0x7fu; }
-
-struct GrammarBytes {                          // scan_text's policy
-    static __device__ void check(bool& bad, unsigned int c, const unsigned char*, int64_t, int64_t) { bad |= refused_byte(c); }
 };
 
 // ---- pass 2: keep or drop every line --------------------------------------------------------------------------------------------
@@ -68,57 +60,27 @@ __global__ __launch_bounds__(WG) void ms_select(const unsigned char* __restrict_
                                                 int strict, int skip_first_line, int check_bytes, unsigned short* __restrict__ keep_len,
                                                 unsigned int* __restrict__ block_bytes, Words* __restrict__ words) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     unsigned int my_bytes = 0, my_lines = 0;
-    for (int e = threadIdx.x; e < n_lines; e += WG) {
-        const int64_t r = row0 + e;
-        const int64_t start = b0 + lstart[e];
+    for (int e = threadIdx.x; e < B.n_lines; e += WG) {
+        const int64_t r = B.row0 + e;
+        const int64_t start = B.b0 + lstart[e];
         const bool header = skip_first_line && line_base + r == 0;
-        int why = 0, tok = 0;
-        bool in_tok = false;
-        int64_t fb = 0, fe = 0;                                               // field 7
-        int64_t p = start;
-        for (;; ++p) {
-            const int c = p < T ? (int)text[p] : '\n';                        // the end of the text ends the line
-            if (c == '\n') break;
-            if (p - start >= MAX_LINE) {
-                why = FHX_MS_LONG_LINE;
-                break;
-            }
-            if (check_bytes && refused_byte((unsigned int)c)) {
-                why = FHX_MS_BYTES;
-                break;
-            }
-            const bool blank = c == ' ' || c == '\t';
-            if (!blank && !in_tok) {
-                in_tok = true;
-                if (++tok == 7) fb = p;
-            } else if (blank && in_tok) {
-                in_tok = false;
-                if (tok == 7) fe = p;
-            }
-        }
-        if (in_tok && tok == 7) fe = p;
+        Line L;
+        walk</*Tokens=*/false>(text, T, start, check_bytes, L);
+        int why = L.why;
         bool keep = false;
         if (!why && r >= n_lines_batch) why = FHX_MS_INTERNAL;                // the scan and this kernel disagree about the lines
         if (!why && !header) {
-            if (tok < 7) why = FHX_MS_TOKENS;
+            if (L.tok < 7) why = FHX_MS_TOKENS;
             else {
                 unsigned long long key = 0;
-                const int cls = classify(text, fb, (int)(fe - fb), &key);
-                if (cls == 0) why = FHX_MS_FIELD;
-                else if (cls == 1) keep = zero_kept != 0;
-                else if (cls == 2) keep = key <= key_bound;
-                else {
-                    const int cmp = compare_text(text, fb, (int)(fe - fb), fdr);
-                    keep = strict ? cmp < 0 : cmp <= 0;
-                }
+                const int cls = classify(text, start + L.fb, L.fn, &key);
+                why = decide(cls, key, key_bound, zero_kept, strict, text, start + L.fb, L.fn, fdr, &keep);
             }
         }
         if (why) atomicMin(&words->first_error, error_word(line_base + r + 1, why));
-        const unsigned int len = (keep && !why) ? (unsigned int)(p - start) + 1u : 0u;      // with its newline, present or not
+        const unsigned int len = (keep && !why) ? (unsigned int)L.len + 1u : 0u;            // with its newline, present or not
         if (r < n_lines_batch) keep_len[r] = (unsigned short)len;             // at most MAX_LINE + 1
         my_bytes += len;
         my_lines += len ? 1u : 0u;
@@ -138,29 +100,16 @@ __global__ __launch_bounds__(WG) void ms_gather(const unsigned char* __restrict_
                                                 const unsigned long long* __restrict__ out_off, unsigned char* __restrict__ out, int64_t out_capacity) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
     __shared__ unsigned int pre[WG + 1];                    // round-local exclusive prefix of the kept lengths; pre[WG] = their sum
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     int64_t at = (int64_t)out_off[blockIdx.x];
-    for (int base = 0; base < n_lines; base += WG) {        // n_lines is the same for every lane: the scan sees whole blocks
-        const int e = base + threadIdx.x;
-        const int64_t r = row0 + e;
-        const unsigned int len = (e < n_lines && r < n_lines_batch) ? (unsigned int)keep_len[r] : 0u;
+    for (int base = 0; base < B.n_lines; base += WG) {      // n_lines is the same for every lane: the scan sees whole blocks
+        const Round q = round_of(base, B.n_lines, B.row0, n_lines_batch);
+        const unsigned int len = q.valid ? (unsigned int)keep_len[q.r] : 0u;
         unsigned int total;
         pre[threadIdx.x] = fhxscan::block_exclusive_scan(len, &total);
         if (threadIdx.x == 0) pre[WG] = total;
         __syncthreads();
-        for (unsigned int j = threadIdx.x; j < total; j += WG) {
-            int lo = 0, hi = WG;                            // the last t with pre[t] <= j: a dropped line shares its prefix with the
-            while (hi - lo > 1) {                           // next one, so the last of equals is the line that holds byte j
-                const int mid = (lo + hi) >> 1;
-                if (pre[mid] <= j) lo = mid;
-                else hi = mid;
-            }
-            const int64_t src = b0 + lstart[base + lo] + (int64_t)(j - pre[lo]);
-            const unsigned char c = src < T ? text[src] : (unsigned char)'\n';       // the newline the last line lacked
-            if (at + j < out_capacity) out[at + j] = c;
-        }
+        gather_round<WG>(text, T, pre, total, [&](int t) { return B.b0 + lstart[base + t]; }, at, out, out_capacity);
         at += total;
         __syncthreads();                                    // pre is written again in the next round
     }
@@ -197,6 +146,92 @@ void drop_subset(fhx_ms* ms) {
     ms->n_lines = ms->n_kept = 0;
 }
 
+// the threshold as the kernels take it; `noun` is what the message calls it
+int make_fdr(fhx_ms* ms, const char* fdr_text, int32_t fdr_len, const char* noun, msd::Fdr* fdr, int32_t* why) {
+    if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) {
+        *why = FHX_MS_FDR;
+        return ms->fail(FHX_ERR_UNSUPPORTED, std::string("the text of ") + noun + " must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
+    }
+    std::memset(fdr, 0, sizeof(*fdr));
+    std::memcpy(fdr->text, fdr_text, (size_t)fdr_len);
+    fdr->len = fdr_len;
+    return FHX_OK;
+}
+
+// fhx_ms_select_file behind its argument check; whatever it returns but FHX_OK, the caller drops the subset
+int select_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept, int32_t strict,
+                int32_t skip_first_line, int64_t* n_bytes, int32_t* why, int64_t* bad_line) {
+    using namespace msd;
+    TH_HIP(ms, hipSetDevice(ms->device));
+    TH_HIP(ms, hipStreamSynchronize(ms->stream));
+    drop_subset(ms);
+    for (double& s : ms->seconds) s = 0;
+    Fdr fdr;
+    if (const int rc = make_fdr(ms, fdr_text, fdr_len, "fdr", &fdr, why)) return rc;
+    fhx::StageClock clock{ms->seconds};
+    fhx::Scratch tmp;
+    fhx::TextBatches in;
+    if (const int rc = in.open(ms, &tmp, &clock, path, "significances", "FHX_MS_BATCH_BYTES", (int64_t)1 << 31)) return rc;
+    const int64_t out_capacity = in.batch_bytes + 1;                          // every line kept, and the newline the last one lacked
+    unsigned char* d_out = nullptr;
+    unsigned int* d_block_bytes = nullptr;
+    unsigned long long* d_out_off = nullptr;
+    unsigned short* d_keep_len = nullptr;
+    int64_t keep_capacity = 0;
+    Words* d_words = nullptr;
+    TH_HIP(ms, tmp.get(&d_out, (size_t)out_capacity));
+    TH_HIP(ms, tmp.get(&d_block_bytes, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get(&d_out_off, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get(&d_words, 1));
+    Words words;
+    const fhx::Refusal refuse{ms, why, bad_line};
+    int64_t kept = 0;
+    for (; in.more(); in.advance()) {
+        std::memset(&words, 0, sizeof(words));
+        words.first_error = NO_ERROR;
+        TH_HIP(ms, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, ms->stream));
+        if (const int rc = in.next<GrammarBytes>()) return rc;
+        const int64_t n = in.lines;
+        TH_HIP(ms, tmp.grow(&d_keep_len, &keep_capacity, n));                 // one length per line of the batch
+        hipLaunchKernelGGL(ms_select, dim3((unsigned)in.n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)in.d_text, in.len,
+                           (const unsigned long long*)in.d_block_off, n, in.line_base, fdr, (unsigned long long)key_bound, (int)zero_kept,
+                           (int)strict, (int)skip_first_line, (int)in.refused_bytes, d_keep_len, d_block_bytes, d_words);
+        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_bytes, in.n_blocks,
+                           d_out_off, &d_words->kept_bytes);
+        TH_HIP(ms, hipGetLastError());
+        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
+        TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        clock.mark(2);
+        if (words.first_error != NO_ERROR) return refuse.word(words.first_error, FHX_MS_INTERNAL);      // earlier batches hold the smaller line numbers
+        const int64_t bytes = (int64_t)words.kept_bytes;
+        if (bytes > out_capacity || (int64_t)words.kept_lines > n) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "more kept bytes than text");
+        if (bytes > 0) {
+            hipLaunchKernelGGL(ms_gather, dim3((unsigned)in.n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)in.d_text, in.len,
+                               (const unsigned long long*)in.d_block_off, n, (const unsigned short*)d_keep_len, (const unsigned long long*)d_out_off,
+                               d_out, out_capacity);
+            TH_HIP(ms, hipGetLastError());
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        }
+        clock.mark(3);
+        if (bytes > 0) {
+            const size_t had = ms->subset.size();
+            ms->subset.resize(had + (size_t)bytes);
+            TH_HIP(ms, hipMemcpyAsync(ms->subset.data() + had, d_out, (size_t)bytes, hipMemcpyDeviceToHost, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        }
+        clock.mark(4);
+        kept += (int64_t)words.kept_lines;
+    }
+    ms->n_lines = in.line_base;
+    ms->n_kept = kept;
+    *n_bytes = (int64_t)ms->subset.size();
+    if (std::getenv("FHX_TIMING"))
+        std::fprintf(stderr, "FDR subset on the device (%s): %lld lines, %lld kept (%lld bytes): read + upload %.6f s; scan %.6f s; select %.6f s; "
+                     "gather %.6f s; copy out %.6f s\n", path, (long long)in.line_base, (long long)kept, (long long)ms->subset.size(), ms->seconds[0],
+                     ms->seconds[1], ms->seconds[2], ms->seconds[3], ms->seconds[4]);
+    return FHX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -213,119 +248,13 @@ const char* fhx_ms_last_error(const fhx_ms* ms) { return ms ? ms->err.c_str() : 
 
 int fhx_ms_select_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept, int32_t strict,
                        int32_t skip_first_line, int64_t* n_bytes, int32_t* why, int64_t* bad_line) {
-    using namespace msd;
     if (!ms || !path || !fdr_text || !n_bytes || !why || !bad_line) return FHX_ERR_ARG;
     *n_bytes = 0;
     *why = FHX_MS_OK;
     *bad_line = 0;
-    TH_HIP(ms, hipSetDevice(ms->device));
-    TH_HIP(ms, hipStreamSynchronize(ms->stream));
-    drop_subset(ms);
-    for (double& s : ms->seconds) s = 0;
-    if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) {
-        *why = FHX_MS_FDR;
-        return ms->fail(FHX_ERR_UNSUPPORTED, "the text of fdr must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
-    }
-    Fdr fdr;
-    std::memset(&fdr, 0, sizeof(fdr));
-    std::memcpy(fdr.text, fdr_text, (size_t)fdr_len);
-    fdr.len = fdr_len;
-    fhx::StageClock clock{ms->seconds};
-    // the file itself, or its inflated bytes when it starts with the gzip magic
-    fhx::TextFile src;
-    if (const int rc = src.open(path, /*allow_gzip=*/true, &ms->err)) return rc;
-    const int64_t batch_bytes = fhx::batch_bytes_for("FHX_MS_BATCH_BYTES", (int64_t)1 << 31, src.size());
-    const int64_t max_blocks = (batch_bytes + BLOCK_BYTES - 1) / BLOCK_BYTES;
-    const int64_t out_capacity = batch_bytes + 1;                             // every line kept, and the newline the last one lacked
-    fhx::Scratch tmp;
-    unsigned char *d_text = nullptr, *d_out = nullptr;
-    unsigned int *d_block_nl = nullptr, *d_block_bytes = nullptr;
-    unsigned long long *d_block_off = nullptr, *d_out_off = nullptr;
-    unsigned short* d_keep_len = nullptr;
-    int64_t keep_capacity = 0;
-    Words* d_words = nullptr;
-    TH_HIP(ms, tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
-    TH_HIP(ms, tmp.get(&d_out, (size_t)out_capacity));
-    TH_HIP(ms, tmp.get(&d_block_nl, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_block_bytes, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_block_off, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_out_off, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_words, 1));
-    Words words;
-    auto refuse = [&](int rc, int32_t w, int64_t line, const std::string& msg) {
-        drop_subset(ms);
-        *why = w;
-        *bad_line = line;
-        return ms->fail(rc, msg);
-    };
-    int64_t lines = 0, kept = 0;
-    for (int64_t off = 0; off < src.size();) {
-        std::memset(&words, 0, sizeof(words));
-        words.first_error = NO_ERROR;
-        TH_HIP(ms, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, ms->stream));
-        fhx::TextBatch b;
-        if (const int rc = fhx::upload_batch(ms, src, "significances", off, std::min(batch_bytes, src.size() - off), d_text, &b)) return rc;
-        const int64_t len = b.len, n_blocks = b.n_blocks;
-        clock.mark(0);
-        hipLaunchKernelGGL(scan_text<GrammarBytes>, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len, d_block_nl,
-                           (unsigned int*)&d_words->bad_bytes);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
-                           &d_words->newlines);
-        TH_HIP(ms, hipGetLastError());
-        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
-        TH_HIP(ms, hipStreamSynchronize(ms->stream));
-        clock.mark(1);
-        const int64_t n = b.lines(words.newlines);
-        if (n > keep_capacity) {                                              // one length per line of the batch
-            if (d_keep_len) tmp.drop(d_keep_len);
-            d_keep_len = nullptr;
-            TH_HIP(ms, tmp.get(&d_keep_len, (size_t)n));
-            keep_capacity = n;
-        }
-        hipLaunchKernelGGL(ms_select, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
-                           (const unsigned long long*)d_block_off, n, lines, fdr, (unsigned long long)key_bound, (int)zero_kept, (int)strict,
-                           (int)skip_first_line, (int)(words.bad_bytes != 0), d_keep_len, d_block_bytes, d_words);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_bytes, n_blocks, d_out_off,
-                           &d_words->kept_bytes);
-        TH_HIP(ms, hipGetLastError());
-        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
-        TH_HIP(ms, hipStreamSynchronize(ms->stream));
-        clock.mark(2);
-        if (words.first_error != NO_ERROR) {                                  // earlier batches hold the smaller line numbers
-            const int32_t w = error_why(words.first_error);
-            const int64_t line = error_line(words.first_error);
-            if (w == FHX_MS_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, "the line count of the scan and the select kernel disagree");
-            return refuse(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
-        }
-        const int64_t bytes = (int64_t)words.kept_bytes;
-        if (bytes > out_capacity || (int64_t)words.kept_lines > n) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "more kept bytes than text");
-        if (bytes > 0) {
-            hipLaunchKernelGGL(ms_gather, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
-                               (const unsigned long long*)d_block_off, n, (const unsigned short*)d_keep_len, (const unsigned long long*)d_out_off, d_out,
-                               out_capacity);
-            TH_HIP(ms, hipGetLastError());
-            TH_HIP(ms, hipStreamSynchronize(ms->stream));
-        }
-        clock.mark(3);
-        if (bytes > 0) {
-            const size_t had = ms->subset.size();
-            ms->subset.resize(had + (size_t)bytes);
-            TH_HIP(ms, hipMemcpyAsync(ms->subset.data() + had, d_out, (size_t)bytes, hipMemcpyDeviceToHost, ms->stream));
-            TH_HIP(ms, hipStreamSynchronize(ms->stream));
-        }
-        clock.mark(4);
-        lines += n;
-        kept += (int64_t)words.kept_lines;
-        off += len;
-    }
-    ms->n_lines = lines;
-    ms->n_kept = kept;
-    *n_bytes = (int64_t)ms->subset.size();
-    if (std::getenv("FHX_TIMING"))
-        std::fprintf(stderr, "FDR subset on the device (%s): %lld lines, %lld kept (%lld bytes): read + upload %.6f s; scan %.6f s; select %.6f s; "
-                     "gather %.6f s; copy out %.6f s\n", path, (long long)lines, (long long)kept, (long long)ms->subset.size(), ms->seconds[0],
-                     ms->seconds[1], ms->seconds[2], ms->seconds[3], ms->seconds[4]);
-    return FHX_OK;
+    const int rc = select_file(ms, path, fdr_text, fdr_len, key_bound, zero_kept, strict, skip_first_line, n_bytes, why, bad_line);
+    if (rc != FHX_OK) drop_subset(ms);                                        // the one exit of a failed call, whatever failed
+    return rc;
 }
 
 int fhx_ms_counts(const fhx_ms* ms, int64_t* n_lines, int64_t* n_kept, int64_t* n_bytes) {

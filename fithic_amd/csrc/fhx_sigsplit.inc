@@ -12,7 +12,7 @@
 //                  (16 bits); per slot: a flag when it was claimed in this batch.
 //   mp_copy_names  the text of every newly claimed name, from the offset the table holds, into 64 bytes per slot (byte 63: the
 //                  length).  The array outlives the batch; the host reads it once, at the end.
-//   mp_select      one line per lane: ms_select's walk and decision (classify, compare_text, refused_byte are its own), the name
+//   mp_select      one line per lane: ms_select's walk and decision (walk of fhx_sigline.hpp, classify and decide of fhx_sigkey.hpp), the name
 //                  grammar on tokens 1 and 3, token 3 against token 1 byte by byte (a trans row goes nowhere), and token 1 against
 //                  the STORED name of its slot byte by byte - a hash collision is FHX_MS_INTERNAL, never a wrong subset.  Per
 //                  line: its kept length; per block: kept lines.
@@ -20,8 +20,8 @@
 //   mp_emit        one 64-bit record per kept line, in file order: slot << 44 | line start in the batch << 13 | kept length
 //   fhx_sort_u64   the stable radix sort: by slot, then by offset = file order within a chromosome
 //   mp_tile_bytes  bytes of every 256 sorted records; scan_tiles -> where each such round writes
-//   mp_gather      256 sorted records per workgroup, their lengths scanned into LDS, lanes assigned by OUTPUT byte (ms_gather's
-//                  scheme); the record that begins a slot's run notes the byte offset and the record index of the run
+//   mp_gather      256 sorted records per workgroup, their lengths scanned into LDS, lanes assigned by OUTPUT byte (gather_round,
+//                  shared with ms_gather); the record that begins a slot's run notes the byte offset and the record index of the run
 //
 // so the bytes of one chromosome leave the device contiguous and in file order, and the host makes one copy per (batch,
 // chromosome) without looking inside a line.  Atomics: none per good line (mp_names' CAS and atomicMin come once per distinct name
@@ -29,11 +29,7 @@
 namespace mpd {
 
 using namespace fhxlines;
-using namespace msd;
-using utd::Line;
-using utd::Round;
-using utd::round_of;
-using utd::walk;
+using namespace msd;                      // the line and the decision: fhx_sigline.hpp, fhx_sigkey.hpp
 using fhx::namerule::name_grammar;        // what a name may be: fhx_namerule.hpp, shared with the resident route
 
 constexpr int SLOTS = FHX_MS_SPLIT_NAMES;      // 4096 = 2^12: the slot field of a record
@@ -43,8 +39,6 @@ constexpr int LEN_BITS = 13, START_BITS = 31;  // 4097 < 2^13; a batch has at mo
 constexpr int ROUND = 256;                     // sorted records per workgroup of mp_gather
 
 struct SplitWords {
-    unsigned long long newlines;               // scan_tiles' total of the current batch
-    unsigned long long bad_bytes;              // scan_text's flag word
     unsigned long long first_error;            // smallest (line << 8 | reason)
     unsigned long long kept_lines;             // scan_tiles' totals of the current batch
     unsigned long long out_bytes;
@@ -81,17 +75,15 @@ __global__ __launch_bounds__(WG) void mp_names(const unsigned char* __restrict__
                                                unsigned long long* __restrict__ t_hash, unsigned long long* __restrict__ t_off,
                                                unsigned int* __restrict__ claimed, SplitWords* __restrict__ words) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     const int lane = threadIdx.x & 63;
-    for (int base = 0; base < n_lines; base += WG) {        // n_lines is the same for every lane: whole waves reach the votes
-        const Round q = round_of(base, n_lines, row0, n_lines_batch);
+    for (int base = 0; base < B.n_lines; base += WG) {      // n_lines is the same for every lane: whole waves reach the votes
+        const Round q = round_of(base, B.n_lines, B.row0, n_lines_batch);
         unsigned long long h = 0xcbf29ce484222325ull;       // FNV-1a; equal names are confirmed by mp_select
         int64_t start = 0;
         int n = 0;
         if (q.valid) {
-            start = b0 + lstart[q.e];
+            start = B.b0 + lstart[q.e];
             for (; n < NAME_STRIDE; ++n) {
                 const int64_t p = start + n;
                 const int c = p < T ? (int)text[p] : '\n';
@@ -147,13 +139,11 @@ __global__ __launch_bounds__(WG) void mp_select(const unsigned char* __restrict_
                                                 const unsigned char* __restrict__ names, unsigned short* __restrict__ keep_len,
                                                 unsigned int* __restrict__ block_kept, SplitWords* __restrict__ words) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     unsigned int my_kept = 0;
-    for (int e = threadIdx.x; e < n_lines; e += WG) {
-        const int64_t r = row0 + e;
-        const int64_t start = b0 + lstart[e];
+    for (int e = threadIdx.x; e < B.n_lines; e += WG) {
+        const int64_t r = B.row0 + e;
+        const int64_t start = B.b0 + lstart[e];
         const unsigned char* line = text + start;
         const bool header = line_base + r == 0;                               // dropped whatever it holds; cut still lists its field 1
         Line L;
@@ -168,11 +158,8 @@ __global__ __launch_bounds__(WG) void mp_select(const unsigned char* __restrict_
         if (!why && !header) {
             unsigned long long key = 0;
             const int cls = classify(text, start + L.fb, L.fn, &key);
-            if (cls == 0) why = FHX_MS_FIELD;
-            else if (cls == 1) keep = zero_kept != 0;
-            else if (cls == 2) keep = key <= key_bound;
-            else keep = compare_text(text, start + L.fb, L.fn, fdr) <= 0;
-            if (keep) {                                                       // $1 == c && $3 == c for some c: $3 is $1, byte for byte
+            why = decide(cls, key, key_bound, zero_kept, /*strict=*/0, text, start + L.fb, L.fn, fdr, &keep);
+            if (keep) {                                                      // $1 == c && $3 == c for some c: $3 is $1, byte for byte
                 keep = L.n3 == L.n1;
                 for (int k = 0; keep && k < L.n1; ++k) keep = line[L.b3 + k] == line[k];
             }
@@ -207,18 +194,16 @@ __global__ __launch_bounds__(WG) void mp_emit(const unsigned char* __restrict__ 
                                               const unsigned short* __restrict__ keep_len, const unsigned long long* __restrict__ rec_off,
                                               unsigned long long* __restrict__ records, int64_t n_records) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     int64_t at = (int64_t)rec_off[blockIdx.x];
-    for (int base = 0; base < n_lines; base += WG) {
-        const Round q = round_of(base, n_lines, row0, n_lines_batch);
+    for (int base = 0; base < B.n_lines; base += WG) {
+        const Round q = round_of(base, B.n_lines, B.row0, n_lines_batch);
         const unsigned int len = q.valid ? (unsigned int)keep_len[q.r] : 0u;
         unsigned int total;
         const int64_t i = at + fhxscan::block_exclusive_scan(len ? 1u : 0u, &total);
         if (len && i < n_records)
             records[i] = ((unsigned long long)line_slot[q.r] << (START_BITS + LEN_BITS)) |
-                         ((unsigned long long)(b0 + lstart[q.e]) << LEN_BITS) | (unsigned long long)len;
+                         ((unsigned long long)(B.b0 + lstart[q.e]) << LEN_BITS) | (unsigned long long)len;
         at += total;
     }
 }
@@ -257,18 +242,8 @@ __global__ __launch_bounds__(ROUND) void mp_gather(const unsigned char* __restri
             slot_record[slot] = (unsigned int)i;
         }
     }
-    __syncthreads();
-    for (unsigned int j = threadIdx.x; j < total; j += ROUND) {
-        int lo = 0, hi = ROUND;                             // the last t with pre[t] <= j: the absent records of the last round
-        while (hi - lo > 1) {                               // share the sum as their prefix, and j stays below it
-            const int mid = (lo + hi) >> 1;
-            if (pre[mid] <= j) lo = mid;
-            else hi = mid;
-        }
-        const int64_t src = (int64_t)starts[lo] + (int64_t)(j - pre[lo]);
-        const unsigned char c = src < T ? text[src] : (unsigned char)'\n';   // the newline the last line lacked
-        if (at + j < out_capacity) out[at + j] = c;
-    }
+    __syncthreads();                                        // the absent records of the last round share the sum as their prefix
+    gather_round<ROUND>(text, T, pre, total, [&](int t) { return (int64_t)starts[t]; }, at, out, out_capacity);
 }
 
 }  // namespace mpd
@@ -281,55 +256,36 @@ void drop_split(fhx_ms* ms) {
     ms->s_lines = 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int fhx_ms_split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept,
-                      int32_t* n_names, int32_t* why, int64_t* bad_line) {
+// fhx_ms_split_file behind its argument check; whatever it returns but FHX_OK, the caller drops the split
+int split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept, int32_t* n_names,
+               int32_t* why, int64_t* bad_line) {
     using namespace mpd;
-    if (!ms || !path || !fdr_text || !n_names || !why || !bad_line) return FHX_ERR_ARG;
-    *n_names = 0;
-    *why = FHX_MS_OK;
-    *bad_line = 0;
     TH_HIP(ms, hipSetDevice(ms->device));
     TH_HIP(ms, hipStreamSynchronize(ms->stream));
     drop_split(ms);
     for (double& s : ms->s_seconds) s = 0;
-    if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) {
-        *why = FHX_MS_FDR;
-        return ms->fail(FHX_ERR_UNSUPPORTED, "the text of fdr must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
-    }
+    Fdr fdr;
+    if (const int rc = make_fdr(ms, fdr_text, fdr_len, "fdr", &fdr, why)) return rc;
     if (!ms->sorter && fhx_create(ms->device, &ms->sorter) != FHX_OK) {       // only a split pays for it
         ms->sorter = nullptr;
         return ms->fail(FHX_ERR_HIP, "the sort context could not be made");
     }
-    Fdr fdr;
-    std::memset(&fdr, 0, sizeof(fdr));
-    std::memcpy(fdr.text, fdr_text, (size_t)fdr_len);
-    fdr.len = fdr_len;
     fhx::StageClock clock{ms->s_seconds};
-    fhx::TextFile src;
-    if (const int rc = src.open(path, /*allow_gzip=*/true, &ms->err)) return rc;
-    const int64_t batch_bytes = fhx::batch_bytes_for("FHX_MS_BATCH_BYTES", (int64_t)1 << 31, src.size());
-    const int64_t max_blocks = (batch_bytes + BLOCK_BYTES - 1) / BLOCK_BYTES;
-    const int64_t out_capacity = batch_bytes + 1;                             // every line kept, and the newline the last one lacked
     fhx::Scratch tmp;
-    unsigned char *d_text = nullptr, *d_out = nullptr, *d_names = nullptr;
-    unsigned int *d_block_nl = nullptr, *d_block_kept = nullptr, *d_claimed = nullptr, *d_tile_bytes = nullptr, *d_perm = nullptr,
-                 *d_slot_record = nullptr;
-    unsigned long long *d_block_off = nullptr, *d_rec_off = nullptr, *d_hash = nullptr, *d_off = nullptr, *d_records = nullptr,
-                       *d_sorted = nullptr, *d_tile_off = nullptr, *d_slot_byte = nullptr;
+    fhx::TextBatches in;
+    if (const int rc = in.open(ms, &tmp, &clock, path, "significances", "FHX_MS_BATCH_BYTES", (int64_t)1 << 31)) return rc;
+    const int64_t out_capacity = in.batch_bytes + 1;                          // every line kept, and the newline the last one lacked
+    unsigned char *d_out = nullptr, *d_names = nullptr;
+    unsigned int *d_block_kept = nullptr, *d_claimed = nullptr, *d_tile_bytes = nullptr, *d_perm = nullptr, *d_slot_record = nullptr;
+    unsigned long long *d_rec_off = nullptr, *d_hash = nullptr, *d_off = nullptr, *d_records = nullptr, *d_sorted = nullptr, *d_tile_off = nullptr,
+                       *d_slot_byte = nullptr;
     unsigned short *d_keep_len = nullptr, *d_line_slot = nullptr;
     int64_t keep_capacity = 0, slot_capacity = 0, rec_capacity = 0, sorted_capacity = 0, perm_capacity = 0, tile_capacity = 0,
             tile_off_capacity = 0;
     SplitWords* d_words = nullptr;
-    TH_HIP(ms, tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
     TH_HIP(ms, tmp.get(&d_out, (size_t)out_capacity));
-    TH_HIP(ms, tmp.get(&d_block_nl, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_block_kept, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_block_off, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_rec_off, (size_t)max_blocks));
+    TH_HIP(ms, tmp.get(&d_block_kept, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get(&d_rec_off, (size_t)in.max_blocks));
     TH_HIP(ms, tmp.get(&d_hash, (size_t)SLOTS));
     TH_HIP(ms, tmp.get(&d_off, (size_t)SLOTS));
     TH_HIP(ms, tmp.get(&d_claimed, (size_t)SLOTS));
@@ -347,61 +303,39 @@ int fhx_ms_split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_
     std::vector<unsigned long long> slot_byte((size_t)SLOTS);
     std::vector<unsigned int> slot_record((size_t)SLOTS);
     std::vector<int> present;
-    auto refuse = [&](int rc, int32_t w, int64_t line, const std::string& msg) {
-        drop_split(ms);
-        *why = w;
-        *bad_line = line;
-        return ms->fail(rc, msg);
-    };
-    int64_t lines = 0;
+    const fhx::Refusal refuse{ms, why, bad_line};
     bool overflow = false;
-    for (int64_t off = 0; off < src.size();) {
+    for (; in.more(); in.advance()) {
         std::memset(&words, 0, sizeof(words));
         words.first_error = NO_ERROR;
         words.overflow = overflow ? 1ull : 0ull;
         TH_HIP(ms, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, ms->stream));
-        fhx::TextBatch b;
-        if (const int rc = fhx::upload_batch(ms, src, "significances", off, std::min(batch_bytes, src.size() - off), d_text, &b)) return rc;
-        const int64_t len = b.len, n_blocks = b.n_blocks;
-        clock.mark(0);
-        hipLaunchKernelGGL(scan_text<GrammarBytes>, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len, d_block_nl,
-                           (unsigned int*)&d_words->bad_bytes);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
-                           &d_words->newlines);
-        TH_HIP(ms, hipGetLastError());
-        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
-        TH_HIP(ms, hipStreamSynchronize(ms->stream));
-        clock.mark(1);
-        const int64_t n = b.lines(words.newlines);
-        TH_HIP(ms, grow(tmp, &d_keep_len, &keep_capacity, n));                // one length and one slot per line of the batch
-        TH_HIP(ms, grow(tmp, &d_line_slot, &slot_capacity, n));
-        hipLaunchKernelGGL(mp_names, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
-                           (const unsigned long long*)d_block_off, n, off, d_line_slot, d_hash, d_off, d_claimed, d_words);
-        hipLaunchKernelGGL(mp_copy_names, dim3(SLOTS / WG), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len, off,
-                           (const unsigned long long*)d_off, d_claimed, d_names);
-        hipLaunchKernelGGL(mp_select, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
-                           (const unsigned long long*)d_block_off, n, lines, fdr, (unsigned long long)key_bound, (int)zero_kept,
-                           (int)(words.bad_bytes != 0), (const unsigned short*)d_line_slot, (const unsigned char*)d_names, d_keep_len, d_block_kept,
-                           d_words);
+        if (const int rc = in.next<GrammarBytes>()) return rc;
+        const unsigned char* d_text = in.d_text;
+        const unsigned long long* d_block_off = in.d_block_off;
+        const int64_t len = in.len, n_blocks = in.n_blocks, n = in.lines;
+        TH_HIP(ms, tmp.grow(&d_keep_len, &keep_capacity, n));                 // one length and one slot per line of the batch
+        TH_HIP(ms, tmp.grow(&d_line_slot, &slot_capacity, n));
+        hipLaunchKernelGGL(mp_names, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, d_text, len, d_block_off, n, in.off, d_line_slot, d_hash,
+                           d_off, d_claimed, d_words);
+        hipLaunchKernelGGL(mp_copy_names, dim3(SLOTS / WG), dim3(WG), 0, ms->stream, d_text, len, in.off, (const unsigned long long*)d_off, d_claimed,
+                           d_names);
+        hipLaunchKernelGGL(mp_select, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, d_text, len, d_block_off, n, in.line_base, fdr,
+                           (unsigned long long)key_bound, (int)zero_kept, (int)in.refused_bytes, (const unsigned short*)d_line_slot,
+                           (const unsigned char*)d_names, d_keep_len, d_block_kept, d_words);
         hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_kept, n_blocks, d_rec_off,
                            &d_words->kept_lines);
         TH_HIP(ms, hipGetLastError());
         TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
         TH_HIP(ms, hipStreamSynchronize(ms->stream));
-        if (words.first_error != NO_ERROR) {                                  // earlier batches hold the smaller line numbers
-            const int32_t w = error_why(words.first_error);
-            const int64_t line = error_line(words.first_error);
-            if (w == FHX_MS_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, "the kernels of the split disagree about line " + std::to_string(line));
-            return refuse(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
-        }
+        if (words.first_error != NO_ERROR) return refuse.word(words.first_error, FHX_MS_INTERNAL);      // earlier batches hold the smaller line numbers
         overflow = overflow || words.overflow != 0;
         const int64_t n_records = overflow ? 0 : (int64_t)words.kept_lines;   // after an overflow the lines are only checked
         if (n_records > n) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "more kept lines than lines");
         if (n_records > 0) {
-            TH_HIP(ms, grow(tmp, &d_records, &rec_capacity, n_records));
-            hipLaunchKernelGGL(mp_emit, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
-                               (const unsigned long long*)d_block_off, n, (const unsigned short*)d_line_slot, (const unsigned short*)d_keep_len,
-                               (const unsigned long long*)d_rec_off, d_records, n_records);
+            TH_HIP(ms, tmp.grow(&d_records, &rec_capacity, n_records));
+            hipLaunchKernelGGL(mp_emit, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, d_text, len, d_block_off, n, (const unsigned short*)d_line_slot,
+                               (const unsigned short*)d_keep_len, (const unsigned long long*)d_rec_off, d_records, n_records);
             TH_HIP(ms, hipGetLastError());
             TH_HIP(ms, hipStreamSynchronize(ms->stream));                     // the sorter has a stream of its own
         }
@@ -409,10 +343,10 @@ int fhx_ms_split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_
         int64_t bytes = 0;
         if (n_records > 0) {
             const int64_t n_tiles = (n_records + ROUND - 1) / ROUND;
-            TH_HIP(ms, grow(tmp, &d_sorted, &sorted_capacity, n_records));
-            TH_HIP(ms, grow(tmp, &d_perm, &perm_capacity, n_records));
-            TH_HIP(ms, grow(tmp, &d_tile_bytes, &tile_capacity, n_tiles));
-            TH_HIP(ms, grow(tmp, &d_tile_off, &tile_off_capacity, n_tiles));
+            TH_HIP(ms, tmp.grow(&d_sorted, &sorted_capacity, n_records));
+            TH_HIP(ms, tmp.grow(&d_perm, &perm_capacity, n_records));
+            TH_HIP(ms, tmp.grow(&d_tile_bytes, &tile_capacity, n_tiles));
+            TH_HIP(ms, tmp.grow(&d_tile_off, &tile_off_capacity, n_tiles));
             const int rc = fhx_sort_u64(ms->sorter, d_records, n_records, d_sorted, d_perm);
             if (rc != FHX_OK) return refuse(rc, FHX_MS_INTERNAL, 0, std::string("sort: ") + fhx_last_error(ms->sorter));
             TH_HIP(ms, hipMemsetAsync(d_slot_record, 0xFF, sizeof(unsigned int) * SLOTS, ms->stream));
@@ -420,9 +354,8 @@ int fhx_ms_split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_
                                d_tile_bytes);
             hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_tile_bytes, n_tiles,
                                d_tile_off, &d_words->out_bytes);
-            hipLaunchKernelGGL(mp_gather, dim3((unsigned)n_tiles), dim3(ROUND), 0, ms->stream, (const unsigned char*)d_text, len,
-                               (const unsigned long long*)d_sorted, n_records, (const unsigned long long*)d_tile_off, d_out, out_capacity,
-                               d_slot_byte, d_slot_record);
+            hipLaunchKernelGGL(mp_gather, dim3((unsigned)n_tiles), dim3(ROUND), 0, ms->stream, d_text, len, (const unsigned long long*)d_sorted,
+                               n_records, (const unsigned long long*)d_tile_off, d_out, out_capacity, d_slot_byte, d_slot_record);
             TH_HIP(ms, hipGetLastError());
             TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
             TH_HIP(ms, hipMemcpyAsync(slot_byte.data(), d_slot_byte, sizeof(unsigned long long) * SLOTS, hipMemcpyDeviceToHost, ms->stream));
@@ -452,8 +385,6 @@ int fhx_ms_split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_
             TH_HIP(ms, hipStreamSynchronize(ms->stream));
         }
         clock.mark(4);
-        lines += n;
-        off += len;
     }
     if (overflow)
         return refuse(FHX_ERR_UNSUPPORTED, FHX_MS_NAMES, 0, "more than " + std::to_string(SLOTS) + " distinct names in field 1");
@@ -473,13 +404,28 @@ int fhx_ms_split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_
         ms->split.push_back(std::move(one));
     }
     clock.mark(4);
-    ms->s_lines = lines;
+    ms->s_lines = in.line_base;
     *n_names = (int32_t)ms->split.size();
     if (std::getenv("FHX_TIMING"))
         std::fprintf(stderr, "per-chromosome FDR subsets on the device (%s): %lld lines, %d names: read + upload %.6f s; scan %.6f s; names + select "
-                     "%.6f s; sort + gather %.6f s; copy out %.6f s\n", path, (long long)lines, (int)ms->split.size(), ms->s_seconds[0],
+                     "%.6f s; sort + gather %.6f s; copy out %.6f s\n", path, (long long)in.line_base, (int)ms->split.size(), ms->s_seconds[0],
                      ms->s_seconds[1], ms->s_seconds[2], ms->s_seconds[3], ms->s_seconds[4]);
     return FHX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhx_ms_split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept,
+                      int32_t* n_names, int32_t* why, int64_t* bad_line) {
+    if (!ms || !path || !fdr_text || !n_names || !why || !bad_line) return FHX_ERR_ARG;
+    *n_names = 0;
+    *why = FHX_MS_OK;
+    *bad_line = 0;
+    const int rc = split_file(ms, path, fdr_text, fdr_len, key_bound, zero_kept, n_names, why, bad_line);
+    if (rc != FHX_OK) drop_split(ms);                                         // the one exit of a failed call, whatever failed
+    return rc;
 }
 
 int fhx_ms_split_counts(const fhx_ms* ms, int64_t* n_lines, int32_t* n_names, int64_t* kept_lines, int64_t* kept_bytes, int32_t capacity) {

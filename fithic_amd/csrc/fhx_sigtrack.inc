@@ -30,73 +30,11 @@ using namespace fhx::trackline;           // the line itself: fhx_trackline.hpp,
 constexpr int WINDOW = 16384;                  // LDS bytes of ut_format
 
 struct TrackWords {
-    unsigned long long newlines;
-    unsigned long long bad_bytes;
     unsigned long long first_error;
     unsigned long long kept_lines;             // scan_tiles' totals of the current batch
     unsigned long long deferred;
     unsigned long long out_bytes;
 };
-
-// one line split on blanks: tokens 1 to 4 and field 7, relative to the line's first byte
-struct Line {
-    int why, tok, len;                         // len: without the newline
-    int b1, n1, b2, n2, b3, n3, b4, n4, fb, fn;
-};
-
-__device__ inline void walk(const unsigned char* __restrict__ text, int64_t T, int64_t start, int check_bytes, Line& L) {
-    L.why = 0;
-    L.b1 = L.n1 = L.b2 = L.n2 = L.b3 = L.n3 = L.b4 = L.n4 = L.fb = L.fn = 0;
-    int tok = 0, begin = 0, k = 0;
-    bool in_tok = false;
-    auto close = [&](int end) {
-        const int n = end - begin;
-        if (tok == 1) { L.b1 = begin; L.n1 = n; }
-        else if (tok == 2) { L.b2 = begin; L.n2 = n; }
-        else if (tok == 3) { L.b3 = begin; L.n3 = n; }
-        else if (tok == 4) { L.b4 = begin; L.n4 = n; }
-        else if (tok == 7) { L.fb = begin; L.fn = n; }
-    };
-    for (;; ++k) {
-        const int64_t p = start + k;
-        const int c = p < T ? (int)text[p] : '\n';                            // the end of the text ends the line
-        if (c == '\n') break;
-        if (k >= MAX_LINE) {
-            L.why = FHX_MS_LONG_LINE;
-            break;
-        }
-        if (check_bytes && refused_byte((unsigned int)c)) {
-            L.why = FHX_MS_BYTES;
-            break;
-        }
-        const bool blank = c == ' ' || c == '\t';
-        if (!blank && !in_tok) {
-            in_tok = true;
-            ++tok;
-            begin = k;
-        } else if (blank && in_tok) {
-            in_tok = false;
-            close(k);
-        }
-    }
-    if (in_tok) close(k);
-    L.tok = tok;
-    L.len = k;
-}
-
-// the lines of a block in rounds of WG: entry e of the round's lane, its line number in the batch, whether both exist
-struct Round {
-    int e;
-    int64_t r;
-    bool valid;
-};
-__device__ inline Round round_of(int base, int n_lines, int64_t row0, int64_t n_lines_batch) {
-    Round q;
-    q.e = base + (int)threadIdx.x;
-    q.r = row0 + q.e;
-    q.valid = q.e < n_lines && q.r < n_lines_batch;
-    return q;
-}
 
 // ---- the selection, the grammar and the length of every kept line without NR ---------------------------------------------------
 __global__ __launch_bounds__(WG) void ut_select(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ block_off,
@@ -104,13 +42,11 @@ __global__ __launch_bounds__(WG) void ut_select(const unsigned char* __restrict_
                                                 int check_bytes, unsigned short* __restrict__ info, unsigned int* __restrict__ block_kept,
                                                 unsigned int* __restrict__ block_deferred, TrackWords* __restrict__ words) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     unsigned int my_kept = 0, my_deferred = 0;
-    for (int e = threadIdx.x; e < n_lines; e += WG) {
-        const int64_t r = row0 + e;
-        const int64_t start = b0 + lstart[e];
+    for (int e = threadIdx.x; e < B.n_lines; e += WG) {
+        const int64_t r = B.row0 + e;
+        const int64_t start = B.b0 + lstart[e];
         Line L;
         walk(text, T, start, check_bytes, L);
         int why = L.why, cls = 0, v2 = 0, v4 = 0;
@@ -124,11 +60,8 @@ __global__ __launch_bounds__(WG) void ut_select(const unsigned char* __restrict_
             cls = classify(text, start + L.fb, L.fn, &key);
             v2 = midpoint(text, start + L.b2, L.n2);
             v4 = midpoint(text, start + L.b4, L.n4);
-            why = refusal(cls, v2 >= 0 && v4 >= 0, L.n1, L.n3);
-            if (why) {}                                                       // nothing of the file is kept
-            else if (cls == 1) keep = zero_kept != 0;
-            else if (cls == 2) keep = key <= key_bound;
-            else keep = compare_text(text, start + L.fb, L.fn, fdr) < 0;
+            why = refusal(cls, v2 >= 0 && v4 >= 0, L.n1, L.n3);                 // class 0 first; with a reason nothing of the file is kept
+            if (!why) why = decide(cls, key, key_bound, zero_kept, /*strict=*/1, text, start + L.fb, L.fn, fdr, &keep);
         }
         if (why) atomicMin(&words->first_error, error_word(line_base + r + 1, why));
         unsigned int word = 0;
@@ -155,17 +88,15 @@ __global__ __launch_bounds__(WG) void ut_defer(const unsigned char* __restrict__
                                                const unsigned long long* __restrict__ deferred_off, unsigned char* __restrict__ fields,
                                                int64_t n_slots) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     int64_t slot0 = (int64_t)deferred_off[blockIdx.x];
-    for (int base = 0; base < n_lines; base += WG) {
-        const Round q = round_of(base, n_lines, row0, n_lines_batch);
+    for (int base = 0; base < B.n_lines; base += WG) {
+        const Round q = round_of(base, B.n_lines, B.row0, n_lines_batch);
         const bool mine = q.valid && (info[q.r] & DEFERRED);
         unsigned int total;
         const int64_t slot = slot0 + fhxscan::block_exclusive_scan(mine ? 1u : 0u, &total);
         if (mine && slot < n_slots) {
-            const int64_t start = b0 + lstart[q.e];
+            const int64_t start = B.b0 + lstart[q.e];
             Line L;
             walk(text, T, start, 0, L);
             defer_field(fields, slot, text + start + L.fb, L.fn);
@@ -181,12 +112,11 @@ __global__ __launch_bounds__(WG) void ut_measure(const unsigned char* __restrict
                                                  int64_t kept_base, const unsigned char* __restrict__ scores, int64_t n_slots,
                                                  unsigned int* __restrict__ block_bytes) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     int64_t nr0 = kept_base + (int64_t)kept_off[blockIdx.x] + 1, slot0 = (int64_t)deferred_off[blockIdx.x];
     unsigned int my_bytes = 0;
-    for (int base = 0; base < n_lines; base += WG) {
-        const Round q = round_of(base, n_lines, row0, n_lines_batch);
+    for (int base = 0; base < B.n_lines; base += WG) {
+        const Round q = round_of(base, B.n_lines, B.row0, n_lines_batch);
         const unsigned int word = q.valid ? (unsigned int)info[q.r] : 0u;
         const bool kept = word != 0, deferred = (word & DEFERRED) != 0;
         unsigned int total;                                                   // kept lines in the low half, deferred ones in the high half
@@ -224,13 +154,11 @@ __global__ __launch_bounds__(WG) void ut_format(const unsigned char* __restrict_
                                                 TrackWords* __restrict__ words) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
     __shared__ unsigned char window[WINDOW];
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     int64_t nr0 = kept_base + (int64_t)kept_off[blockIdx.x] + 1, slot0 = (int64_t)deferred_off[blockIdx.x];
     int64_t at = (int64_t)out_off[blockIdx.x];
-    for (int base = 0; base < n_lines; base += WG) {        // n_lines is the same for every lane
-        const Round q = round_of(base, n_lines, row0, n_lines_batch);
+    for (int base = 0; base < B.n_lines; base += WG) {      // n_lines is the same for every lane
+        const Round q = round_of(base, B.n_lines, B.row0, n_lines_batch);
         const unsigned int word = q.valid ? (unsigned int)info[q.r] : 0u;
         const unsigned int len = word & ~DEFERRED;
         const bool kept = len != 0, deferred = (word & DEFERRED) != 0;
@@ -238,12 +166,12 @@ __global__ __launch_bounds__(WG) void ut_format(const unsigned char* __restrict_
         const unsigned int rank = fhxscan::block_exclusive_scan((kept ? 1u : 0u) | (deferred ? 0x10000u : 0u), &counts);
         const unsigned int pre = fhxscan::block_exclusive_scan(len, &total);
         // the line's pieces, once for all its windows
-        const unsigned char* line = text + b0 + (kept ? (int64_t)lstart[q.e] : 0);
+        const unsigned char* line = text + B.b0 + (kept ? (int64_t)lstart[q.e] : 0);
         Line L;
         char score[fhx::score::MAX_TEXT];
         int score_len = 0, v2 = 0, v4 = 0;
         if (kept) {
-            walk(text, T, b0 + lstart[q.e], 0, L);
+            walk(text, T, B.b0 + lstart[q.e], 0, L);
             v2 = midpoint(line, L.b2, L.n2);
             v4 = midpoint(line, L.b4, L.n4);
             unsigned long long key = 0;
@@ -279,16 +207,117 @@ void drop_track(fhx_ms* ms) {
     ms->t_lines = ms->t_kept = ms->t_deferred = 0;
 }
 
-// a device array of one call that grows to what a batch needs
-template <typename T>
-hipError_t grow(fhx::Scratch& tmp, T** p, int64_t* capacity, int64_t need) {
-    if (need <= *capacity) return hipSuccess;
-    if (*p) tmp.drop(*p);
-    *p = nullptr;
-    *capacity = 0;
-    const hipError_t e = tmp.get(p, (size_t)need);
-    if (e == hipSuccess) *capacity = need;
-    return e;
+// fhx_ms_track_file behind its argument check; whatever it returns but FHX_OK, the caller drops the track
+int track_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept, int64_t* n_bytes,
+               int32_t* why, int64_t* bad_line) {
+    using namespace utd;
+    TH_HIP(ms, hipSetDevice(ms->device));
+    TH_HIP(ms, hipStreamSynchronize(ms->stream));
+    drop_track(ms);
+    for (double& s : ms->t_seconds) s = 0;
+    Fdr fdr;
+    if (const int rc = make_fdr(ms, fdr_text, fdr_len, "the threshold", &fdr, why)) return rc;
+    fhx::StageClock clock{ms->t_seconds};
+    fhx::Scratch tmp;
+    fhx::TextBatches in;
+    if (const int rc = in.open(ms, &tmp, &clock, path, "significances", "FHX_MS_BATCH_BYTES", (int64_t)1 << 31)) return rc;
+    unsigned char *d_out = nullptr, *d_fields = nullptr, *d_scores = nullptr;
+    unsigned int *d_block_kept = nullptr, *d_block_deferred = nullptr, *d_block_bytes = nullptr;
+    unsigned long long *d_kept_off = nullptr, *d_deferred_off = nullptr, *d_out_off = nullptr;
+    unsigned short* d_info = nullptr;
+    int64_t info_capacity = 0, out_capacity = 0, fields_capacity = 0, scores_capacity = 0;
+    TrackWords* d_words = nullptr;
+    TH_HIP(ms, tmp.get(&d_block_kept, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get(&d_block_deferred, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get(&d_block_bytes, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get(&d_kept_off, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get(&d_deferred_off, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get(&d_out_off, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get(&d_words, 1));
+    TrackWords words;
+    std::vector<unsigned char> fields, scores;
+    const fhx::Refusal refuse{ms, why, bad_line};
+    ms->track.assign(HEAD, HEAD + sizeof(HEAD) - 1);
+    int64_t kept = 0, deferred_lines = 0;
+    for (; in.more(); in.advance()) {
+        std::memset(&words, 0, sizeof(words));
+        words.first_error = NO_ERROR;
+        TH_HIP(ms, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, ms->stream));
+        if (const int rc = in.next<GrammarBytes>()) return rc;
+        const unsigned char* d_text = in.d_text;
+        const unsigned long long* d_block_off = in.d_block_off;
+        const int64_t len = in.len, n_blocks = in.n_blocks, n = in.lines;
+        TH_HIP(ms, tmp.grow(&d_info, &info_capacity, n));
+        hipLaunchKernelGGL(ut_select, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, d_text, len, d_block_off, n, in.line_base, fdr,
+                           (unsigned long long)key_bound, (int)zero_kept, (int)in.refused_bytes, d_info, d_block_kept, d_block_deferred, d_words);
+        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_kept, n_blocks, d_kept_off,
+                           &d_words->kept_lines);
+        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_deferred, n_blocks,
+                           d_deferred_off, &d_words->deferred);
+        TH_HIP(ms, hipGetLastError());
+        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
+        TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        clock.mark(2);
+        if (words.first_error != NO_ERROR) return refuse.word(words.first_error, FHX_MS_INTERNAL);      // earlier batches hold the smaller line numbers
+        const int64_t batch_kept = (int64_t)words.kept_lines, n_slots = (int64_t)words.deferred;
+        if (batch_kept > n || n_slots > batch_kept) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "more kept lines than lines");
+        if (kept + batch_kept > (int64_t)INT32_MAX)
+            return refuse(FHX_ERR_UNSUPPORTED, FHX_MS_KEPT, 0, "more than 2^31 - 1 lines pass: awk prints NR as an integer only below 2^31");
+        if (n_slots > 0) {                                                    // the deferred round trip
+            TH_HIP(ms, tmp.grow(&d_fields, &fields_capacity, n_slots * DEFER_IN));
+            TH_HIP(ms, tmp.grow(&d_scores, &scores_capacity, n_slots * DEFER_OUT));
+            hipLaunchKernelGGL(ut_defer, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, d_text, len, d_block_off, n, (const unsigned short*)d_info,
+                               (const unsigned long long*)d_deferred_off, d_fields, n_slots);
+            TH_HIP(ms, hipGetLastError());
+            fields.resize((size_t)(n_slots * DEFER_IN));
+            TH_HIP(ms, hipMemcpyAsync(fields.data(), d_fields, fields.size(), hipMemcpyDeviceToHost, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+            if (!answer_deferred(fields.data(), n_slots, &scores)) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "a deferred score has no text");
+            TH_HIP(ms, hipMemcpyAsync(d_scores, scores.data(), scores.size(), hipMemcpyHostToDevice, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        }
+        clock.mark(3);
+        int64_t bytes = 0;
+        if (batch_kept > 0) {
+            hipLaunchKernelGGL(ut_measure, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, d_text, len, d_block_off, n, d_info,
+                               (const unsigned long long*)d_kept_off, (const unsigned long long*)d_deferred_off, kept, (const unsigned char*)d_scores,
+                               n_slots, d_block_bytes);
+            hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_bytes, n_blocks, d_out_off,
+                               &d_words->out_bytes);
+            TH_HIP(ms, hipGetLastError());
+            TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+            bytes = (int64_t)words.out_bytes;
+            TH_HIP(ms, tmp.grow(&d_out, &out_capacity, bytes));
+            hipLaunchKernelGGL(ut_format, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, d_text, len, d_block_off, n, in.line_base,
+                               (const unsigned short*)d_info, (const unsigned long long*)d_kept_off, (const unsigned long long*)d_deferred_off, kept,
+                               (const unsigned char*)d_scores, n_slots, (const unsigned long long*)d_out_off, d_out, out_capacity, d_words);
+            TH_HIP(ms, hipGetLastError());
+            TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+            if (words.first_error != NO_ERROR) return refuse.word(words.first_error, FHX_MS_INTERNAL);
+        }
+        clock.mark(4);
+        if (bytes > 0) {
+            const size_t had = ms->track.size();
+            ms->track.resize(had + (size_t)bytes);
+            TH_HIP(ms, hipMemcpyAsync(ms->track.data() + had, d_out, (size_t)bytes, hipMemcpyDeviceToHost, ms->stream));
+            TH_HIP(ms, hipStreamSynchronize(ms->stream));
+        }
+        clock.mark(5);
+        kept += batch_kept;
+        deferred_lines += n_slots;
+    }
+    ms->t_lines = in.line_base;
+    ms->t_kept = kept;
+    ms->t_deferred = deferred_lines;
+    *n_bytes = (int64_t)ms->track.size();
+    if (std::getenv("FHX_TIMING"))
+        std::fprintf(stderr, "interact track on the device (%s): %lld lines, %lld kept, %lld deferred (%lld bytes): read + upload %.6f s; scan %.6f s; "
+                     "select %.6f s; deferred round trip %.6f s; format %.6f s; copy out %.6f s\n", path, (long long)in.line_base, (long long)kept,
+                     (long long)deferred_lines, (long long)ms->track.size(), ms->t_seconds[0], ms->t_seconds[1], ms->t_seconds[2], ms->t_seconds[3],
+                     ms->t_seconds[4], ms->t_seconds[5]);
+    return FHX_OK;
 }
 
 }  // namespace
@@ -317,154 +346,13 @@ int fhx_ms_score_text(const char* field, int32_t len, int32_t certify, char* out
 
 int fhx_ms_track_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept, int64_t* n_bytes,
                       int32_t* why, int64_t* bad_line) {
-    using namespace utd;
     if (!ms || !path || !fdr_text || !n_bytes || !why || !bad_line) return FHX_ERR_ARG;
     *n_bytes = 0;
     *why = FHX_MS_OK;
     *bad_line = 0;
-    TH_HIP(ms, hipSetDevice(ms->device));
-    TH_HIP(ms, hipStreamSynchronize(ms->stream));
-    drop_track(ms);
-    for (double& s : ms->t_seconds) s = 0;
-    if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) {
-        *why = FHX_MS_FDR;
-        return ms->fail(FHX_ERR_UNSUPPORTED, "the text of the threshold must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
-    }
-    Fdr fdr;
-    std::memset(&fdr, 0, sizeof(fdr));
-    std::memcpy(fdr.text, fdr_text, (size_t)fdr_len);
-    fdr.len = fdr_len;
-    fhx::StageClock clock{ms->t_seconds};
-    fhx::TextFile src;
-    if (const int rc = src.open(path, /*allow_gzip=*/true, &ms->err)) return rc;
-    const int64_t batch_bytes = fhx::batch_bytes_for("FHX_MS_BATCH_BYTES", (int64_t)1 << 31, src.size());
-    const int64_t max_blocks = (batch_bytes + BLOCK_BYTES - 1) / BLOCK_BYTES;
-    fhx::Scratch tmp;
-    unsigned char *d_text = nullptr, *d_out = nullptr, *d_fields = nullptr, *d_scores = nullptr;
-    unsigned int *d_block_nl = nullptr, *d_block_kept = nullptr, *d_block_deferred = nullptr, *d_block_bytes = nullptr;
-    unsigned long long *d_block_off = nullptr, *d_kept_off = nullptr, *d_deferred_off = nullptr, *d_out_off = nullptr;
-    unsigned short* d_info = nullptr;
-    int64_t info_capacity = 0, out_capacity = 0, fields_capacity = 0, scores_capacity = 0;
-    TrackWords* d_words = nullptr;
-    TH_HIP(ms, tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
-    TH_HIP(ms, tmp.get(&d_block_nl, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_block_kept, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_block_deferred, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_block_bytes, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_block_off, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_kept_off, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_deferred_off, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_out_off, (size_t)max_blocks));
-    TH_HIP(ms, tmp.get(&d_words, 1));
-    TrackWords words;
-    std::vector<unsigned char> fields, scores;
-    auto refuse = [&](int rc, int32_t w, int64_t line, const std::string& msg) {
-        drop_track(ms);
-        *why = w;
-        *bad_line = line;
-        return ms->fail(rc, msg);
-    };
-    auto refuse_word = [&](unsigned long long word) {
-        const int32_t w = error_why(word);
-        const int64_t line = error_line(word);
-        if (w == FHX_MS_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, "the kernels of the track disagree about line " + std::to_string(line));
-        return refuse(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
-    };
-    ms->track.assign(HEAD, HEAD + sizeof(HEAD) - 1);
-    int64_t lines = 0, kept = 0, deferred_lines = 0;
-    for (int64_t off = 0; off < src.size();) {
-        std::memset(&words, 0, sizeof(words));
-        words.first_error = NO_ERROR;
-        TH_HIP(ms, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, ms->stream));
-        fhx::TextBatch b;
-        if (const int rc = fhx::upload_batch(ms, src, "significances", off, std::min(batch_bytes, src.size() - off), d_text, &b)) return rc;
-        const int64_t len = b.len, n_blocks = b.n_blocks;
-        clock.mark(0);
-        hipLaunchKernelGGL(scan_text<GrammarBytes>, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len, d_block_nl,
-                           (unsigned int*)&d_words->bad_bytes);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
-                           &d_words->newlines);
-        TH_HIP(ms, hipGetLastError());
-        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
-        TH_HIP(ms, hipStreamSynchronize(ms->stream));
-        clock.mark(1);
-        const int64_t n = b.lines(words.newlines);
-        TH_HIP(ms, grow(tmp, &d_info, &info_capacity, n));
-        hipLaunchKernelGGL(ut_select, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
-                           (const unsigned long long*)d_block_off, n, lines, fdr, (unsigned long long)key_bound, (int)zero_kept,
-                           (int)(words.bad_bytes != 0), d_info, d_block_kept, d_block_deferred, d_words);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_kept, n_blocks, d_kept_off,
-                           &d_words->kept_lines);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_deferred, n_blocks,
-                           d_deferred_off, &d_words->deferred);
-        TH_HIP(ms, hipGetLastError());
-        TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
-        TH_HIP(ms, hipStreamSynchronize(ms->stream));
-        clock.mark(2);
-        if (words.first_error != NO_ERROR) return refuse_word(words.first_error);          // earlier batches hold the smaller line numbers
-        const int64_t batch_kept = (int64_t)words.kept_lines, n_slots = (int64_t)words.deferred;
-        if (batch_kept > n || n_slots > batch_kept) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "more kept lines than lines");
-        if (kept + batch_kept > (int64_t)INT32_MAX)
-            return refuse(FHX_ERR_UNSUPPORTED, FHX_MS_KEPT, 0, "more than 2^31 - 1 lines pass: awk prints NR as an integer only below 2^31");
-        if (n_slots > 0) {                                                    // the deferred round trip
-            TH_HIP(ms, grow(tmp, &d_fields, &fields_capacity, n_slots * DEFER_IN));
-            TH_HIP(ms, grow(tmp, &d_scores, &scores_capacity, n_slots * DEFER_OUT));
-            hipLaunchKernelGGL(ut_defer, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
-                               (const unsigned long long*)d_block_off, n, (const unsigned short*)d_info, (const unsigned long long*)d_deferred_off,
-                               d_fields, n_slots);
-            TH_HIP(ms, hipGetLastError());
-            fields.resize((size_t)(n_slots * DEFER_IN));
-            TH_HIP(ms, hipMemcpyAsync(fields.data(), d_fields, fields.size(), hipMemcpyDeviceToHost, ms->stream));
-            TH_HIP(ms, hipStreamSynchronize(ms->stream));
-            if (!answer_deferred(fields.data(), n_slots, &scores)) return refuse(FHX_ERR_INTERNAL, FHX_MS_INTERNAL, 0, "a deferred score has no text");
-            TH_HIP(ms, hipMemcpyAsync(d_scores, scores.data(), scores.size(), hipMemcpyHostToDevice, ms->stream));
-            TH_HIP(ms, hipStreamSynchronize(ms->stream));
-        }
-        clock.mark(3);
-        int64_t bytes = 0;
-        if (batch_kept > 0) {
-            hipLaunchKernelGGL(ut_measure, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
-                               (const unsigned long long*)d_block_off, n, d_info, (const unsigned long long*)d_kept_off,
-                               (const unsigned long long*)d_deferred_off, kept, (const unsigned char*)d_scores, n_slots, d_block_bytes);
-            hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ms->stream, (const unsigned int*)d_block_bytes, n_blocks, d_out_off,
-                               &d_words->out_bytes);
-            TH_HIP(ms, hipGetLastError());
-            TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
-            TH_HIP(ms, hipStreamSynchronize(ms->stream));
-            bytes = (int64_t)words.out_bytes;
-            TH_HIP(ms, grow(tmp, &d_out, &out_capacity, bytes));
-            hipLaunchKernelGGL(ut_format, dim3((unsigned)n_blocks), dim3(WG), 0, ms->stream, (const unsigned char*)d_text, len,
-                               (const unsigned long long*)d_block_off, n, lines, (const unsigned short*)d_info, (const unsigned long long*)d_kept_off,
-                               (const unsigned long long*)d_deferred_off, kept, (const unsigned char*)d_scores, n_slots,
-                               (const unsigned long long*)d_out_off, d_out, out_capacity, d_words);
-            TH_HIP(ms, hipGetLastError());
-            TH_HIP(ms, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ms->stream));
-            TH_HIP(ms, hipStreamSynchronize(ms->stream));
-            if (words.first_error != NO_ERROR) return refuse_word(words.first_error);
-        }
-        clock.mark(4);
-        if (bytes > 0) {
-            const size_t had = ms->track.size();
-            ms->track.resize(had + (size_t)bytes);
-            TH_HIP(ms, hipMemcpyAsync(ms->track.data() + had, d_out, (size_t)bytes, hipMemcpyDeviceToHost, ms->stream));
-            TH_HIP(ms, hipStreamSynchronize(ms->stream));
-        }
-        clock.mark(5);
-        lines += n;
-        kept += batch_kept;
-        deferred_lines += n_slots;
-        off += len;
-    }
-    ms->t_lines = lines;
-    ms->t_kept = kept;
-    ms->t_deferred = deferred_lines;
-    *n_bytes = (int64_t)ms->track.size();
-    if (std::getenv("FHX_TIMING"))
-        std::fprintf(stderr, "interact track on the device (%s): %lld lines, %lld kept, %lld deferred (%lld bytes): read + upload %.6f s; scan %.6f s; "
-                     "select %.6f s; deferred round trip %.6f s; format %.6f s; copy out %.6f s\n", path, (long long)lines, (long long)kept,
-                     (long long)deferred_lines, (long long)ms->track.size(), ms->t_seconds[0], ms->t_seconds[1], ms->t_seconds[2], ms->t_seconds[3],
-                     ms->t_seconds[4], ms->t_seconds[5]);
-    return FHX_OK;
+    const int rc = track_file(ms, path, fdr_text, fdr_len, key_bound, zero_kept, n_bytes, why, bad_line);
+    if (rc != FHX_OK) drop_track(ms);                                         // the one exit of a failed call, whatever failed
+    return rc;
 }
 
 int fhx_ms_track_counts(const fhx_ms* ms, int64_t* n_lines, int64_t* n_kept, int64_t* n_deferred, int64_t* n_bytes) {

@@ -1,11 +1,12 @@
 // fhx_textlines.hpp - the newline layer of every device text path: fhx_ingest.inc (contact counts), fhx_hicpro.hip (HiC-Pro
-// matrix), fhx_validpairs.hip (allValidPairs) and fhx_sigselect.hip (significances).  A text lies in HBM, padded with blanks to
-// whole blocks plus 64 bytes (fhx_textupload.hpp upload_batch); a workgroup of WG lanes owns BLOCK_BYTES of it, SEG bytes per lane
-// read as 16-byte loads.
+// matrix), fhx_validpairs.hip (allValidPairs), fhx_juicer.hip (Juicer dump) and fhx_sigselect.hip with fhx_sigtrack.inc and
+// fhx_sigsplit.inc (significances).  A text lies in HBM, padded with blanks to whole blocks plus 64 bytes (fhx_textupload.hpp
+// upload_batch); a workgroup of WG lanes owns BLOCK_BYTES of it, SEG bytes per lane read as 16-byte loads.
 //
 //   scan_text<Bytes>   newlines per block, and bit REFUSED_BYTES in a flag word when a byte the path's policy refuses is seen
 //   scan_tiles         exclusive scan of the block counts = the line number of every block's first line          (fhx_scan.hpp)
-//   block_lines        called by the path's own parse kernel: where the lines that begin in its block start
+//   block_lines        called by the path's own per-line kernels: where the lines that begin in its block start, and the line
+//                      number of the first of them
 //
 // A refused line is reported as ONE 64-bit word, error_word(line, reason), kept with atomicMin: the smallest offending line
 // whatever the launch order.  The grammars (what a line may hold) stay with the paths.
@@ -72,8 +73,7 @@ __global__ __launch_bounds__(WG) void scan_text(const unsigned char* __restrict_
 }
 
 // The lines that BEGIN after a newline of this block (and line 0 in block 0): their start offsets relative to the block, in
-// order, in LDS (lstart has LSTART_ENTRIES entries).  Line number of entry e within the text: e in block 0,
-// block_off[block] + 1 + e elsewhere.
+// order, in LDS (lstart has LSTART_ENTRIES entries) -> their number.
 __device__ inline int block_lines(const unsigned char* __restrict__ text, int64_t T, unsigned short* lstart) {
     const int64_t p0 = (int64_t)blockIdx.x * BLOCK_BYTES + (int64_t)threadIdx.x * SEG;
     unsigned long long mask = 0;                                              // bit k: byte k of the segment is a newline
@@ -99,6 +99,21 @@ __device__ inline int block_lines(const unsigned char* __restrict__ text, int64_
     }
     __syncthreads();
     return (int)(total + first);
+}
+
+// What a per-line kernel knows of its block: entry e < n_lines begins at text[b0 + lstart[e]] and is line row0 + e of the text
+// (block_off is scan_tiles' exclusive scan of the blocks' newlines: e in block 0, block_off[block] + 1 + e elsewhere).
+struct BlockLines {
+    int n_lines;
+    int64_t b0, row0;
+};
+__device__ inline BlockLines block_lines(const unsigned char* __restrict__ text, int64_t T, const unsigned long long* __restrict__ block_off,
+                                         unsigned short* lstart) {
+    BlockLines B;
+    B.n_lines = block_lines(text, T, lstart);
+    B.b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
+    B.row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    return B;
 }
 
 }  // namespace fhxlines

@@ -1,7 +1,9 @@
-// fhx_textupload.hpp - the host side that the device text paths share (fhx_hicpro.hip, fhx_validpairs.hip, fhx_sigselect.hip):
-// the handle base with its stream and error text, the device temporaries of one call, the stage clock, and the way a text file
-// (fhx_textfile.hpp) reaches HBM: host threads fill one of two pinned buffers while the copy engine drains the other, in batches
-// cut at the last newline and padded with blanks as fhx_textlines.hpp's 16-byte loads need it.
+// fhx_textupload.hpp - the host side that the device text paths share (fhx_hicpro.hip, fhx_validpairs.hip, fhx_juicer.hip,
+// fhx_sigselect.hip with fhx_sigtrack.inc and fhx_sigsplit.inc): the handle base with its stream and error text, the device
+// temporaries of one call, the stage clock, and the way a text file (fhx_textfile.hpp) reaches HBM: host threads fill one of two
+// pinned buffers while the copy engine drains the other, in batches cut at the last newline and padded with blanks as
+// fhx_textlines.hpp's 16-byte loads need it.  TextBatches is the loop over such batches with the newline layer run on each;
+// refused_line turns a kernel's error word into what the caller is told.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,7 +21,7 @@
 
 namespace fhx {
 
-// what fhx_hp, fhx_vp and fhx_ms have in common
+// what fhx_hp, fhx_vp, fhx_jc and fhx_ms have in common
 struct TextHandle {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -92,6 +94,17 @@ struct Scratch {
             ptrs.erase(it);
         }
     }
+    // an array that grows to what a batch needs; its old contents are not kept
+    template <typename T>
+    hipError_t grow(T** p, int64_t* capacity, int64_t need) {
+        if (need <= *capacity) return hipSuccess;
+        if (*p) drop(*p);
+        *p = nullptr;
+        *capacity = 0;
+        const hipError_t e = get(p, (size_t)need);
+        if (e == hipSuccess) *capacity = need;
+        return e;
+    }
 };
 
 // host seconds per stage of a call; the stream is idle at every mark
@@ -157,5 +170,110 @@ inline int upload_batch(TextHandle* h, const TextFile& src, const char* what, in
     TH_HIP(h, hipStreamSynchronize(h->stream));                               // the pinned buffers are free again
     return FHX_OK;
 }
+
+// A text file, batch by batch, with the newline layer run on every batch:
+//
+//     fhx::TextBatches in;
+//     if (const int rc = in.open(h, &tmp, &clock, path, "dump", "FHX_JC_BATCH_BYTES", upper)) return rc;
+//     for (; in.more(); in.advance()) {
+//         if (const int rc = in.next<Bytes>()) return rc;
+//         ... the path's kernels over in.d_text[0, in.len), in.n_blocks blocks, in.d_block_off, in.lines lines ...
+//     }
+//
+// next() leaves the stream idle and has marked slot 0 of the clock after the upload and slot 1 after the scan.
+struct TextBatches {
+    TextFile src;                                 // the file itself, or its inflated bytes when it starts with the gzip magic
+    int64_t batch_bytes = 0, max_blocks = 0;
+    unsigned char* d_text = nullptr;              // max_blocks * BLOCK_BYTES + 64
+    unsigned int* d_block_nl = nullptr;
+    unsigned long long* d_block_off = nullptr;    // scan_tiles' exclusive scan: what fhxlines::block_lines takes
+    // the current batch
+    int64_t off = 0;                              // of its first byte in the text
+    int64_t line_base = 0;                        // lines of the earlier batches
+    int64_t len = 0, n_blocks = 0, lines = 0;
+    bool refused_bytes = false;                   // scan_text<Bytes> saw a byte its policy refuses
+
+    int open(TextHandle* handle, Scratch* scratch, StageClock* stage_clock, const char* path, const char* what_word, const char* env,
+             int64_t upper) {
+        h = handle;
+        tmp = scratch;
+        clock = stage_clock;
+        what = what_word;
+        if (const int rc = src.open(path, /*allow_gzip=*/true, &h->err)) return rc;
+        batch_bytes = batch_bytes_for(env, upper, src.size());
+        max_blocks = (batch_bytes + fhxlines::BLOCK_BYTES - 1) / fhxlines::BLOCK_BYTES;
+        TH_HIP(h, tmp->get(&d_text, (size_t)max_blocks * fhxlines::BLOCK_BYTES + 64));
+        TH_HIP(h, tmp->get(&d_block_nl, (size_t)max_blocks));
+        TH_HIP(h, tmp->get(&d_block_off, (size_t)max_blocks));
+        TH_HIP(h, tmp->get(&d_scan, 1));
+        return FHX_OK;
+    }
+
+    bool more() const { return off < src.size(); }
+
+    template <typename Bytes>
+    int next() {
+        TH_HIP(h, hipMemsetAsync(d_scan, 0, sizeof(ScanWords), h->stream));
+        TextBatch b;
+        if (const int rc = upload_batch(h, src, what, off, std::min(batch_bytes, src.size() - off), d_text, &b)) return rc;
+        len = b.len;
+        n_blocks = b.n_blocks;
+        clock->mark(0);
+        hipLaunchKernelGGL(fhxlines::scan_text<Bytes>, dim3((unsigned)n_blocks), dim3(fhxlines::WG), 0, h->stream, (const unsigned char*)d_text, len,
+                           d_block_nl, &d_scan->flags);
+        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, h->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
+                           &d_scan->newlines);
+        TH_HIP(h, hipGetLastError());
+        ScanWords scan;
+        TH_HIP(h, hipMemcpyAsync(&scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost, h->stream));
+        TH_HIP(h, hipStreamSynchronize(h->stream));
+        clock->mark(1);
+        lines = b.lines(scan.newlines);
+        refused_bytes = scan.flags != 0;
+        return FHX_OK;
+    }
+
+    void advance() {
+        off += len;
+        line_base += lines;
+    }
+
+    // after the last batch: the text leaves HBM and the inflated bytes leave the host
+    void close() {
+        tmp->drop(d_text);
+        d_text = nullptr;
+        src.release();
+    }
+
+  private:
+    struct ScanWords {
+        unsigned long long newlines;              // scan_tiles' total
+        unsigned int flags, pad;                  // scan_text's flag word
+    };
+    TextHandle* h = nullptr;
+    Scratch* tmp = nullptr;
+    StageClock* clock = nullptr;
+    const char* what = "";
+    ScanWords* d_scan = nullptr;
+};
+
+// Where a refusal of a call goes: the caller's why / bad_line, the handle's message, and the code to return.
+struct Refusal {
+    TextHandle* h;
+    int32_t* why;
+    int64_t* bad_line;
+    int operator()(int rc, int32_t w, int64_t line, const std::string& msg) const {
+        *why = w;
+        *bad_line = line;
+        return h->fail(rc, msg);
+    }
+    // a kernel's first_error word (fhxlines::error_word); `internal` is the path's reason for kernels that disagree with each other
+    int word(unsigned long long first_error, int32_t internal) const {
+        const int32_t w = fhxlines::error_why(first_error);
+        const int64_t line = fhxlines::error_line(first_error);
+        if (w == internal) return (*this)(FHX_ERR_INTERNAL, w, line, "the kernels of the call disagree about line " + std::to_string(line));
+        return (*this)(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
+    }
+};
 
 }  // namespace fhx

@@ -49,7 +49,6 @@ constexpr int MAX_NAMES = 1024;
 
 // the words the kernels of one call share
 struct Words {
-    unsigned long long newlines;               // scan_tiles' total of the current batch
     unsigned long long first_error;            // smallest (line << 8 | reason)
     unsigned long long n_records;              // kept pairs so far
     unsigned long long max_bin;                // largest bin index among them
@@ -57,7 +56,6 @@ struct Words {
     unsigned long long n_cells;                // scan_tiles' total of the heads
     unsigned long long max_count;              // largest cell count
     unsigned long long names_overflow;         // 1: a pair named a name the full table could not take
-    unsigned long long scan_flags;             // scan_text's flag word: this path's policy refuses no byte, it stays 0
 };
 
 __device__ inline bool is_digit(int c) { return c >= '0' && c <= '9'; }
@@ -130,17 +128,15 @@ __global__ __launch_bounds__(WG) void vp_parse(const unsigned char* __restrict__
                                                ulonglong2* __restrict__ records, unsigned long long capacity, Words* __restrict__ words) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
     __shared__ unsigned long long out_base;
-    const int n_lines = block_lines(text, T, lstart);
-    const int64_t b0 = (int64_t)blockIdx.x * BLOCK_BYTES;
-    const int64_t row0 = blockIdx.x == 0 ? 0 : (int64_t)block_off[blockIdx.x] + 1;
+    const BlockLines B = block_lines(text, T, block_off, lstart);
     unsigned long long max_bin = 0;
-    for (int base = 0; base < n_lines; base += WG) {        // n_lines is the same for every lane: the scans below see whole blocks
+    for (int base = 0; base < B.n_lines; base += WG) {      // n_lines is the same for every lane: the scans below see whole blocks
         const int e = base + threadIdx.x;
         bool keep = false;
         ulonglong2 rec = make_ulonglong2(0ull, 0ull);
-        if (e < n_lines) {
-            const int64_t r = row0 + e;
-            const int64_t start = b0 + lstart[e];
+        if (e < B.n_lines) {
+            const int64_t r = B.row0 + e;
+            const int64_t start = B.b0 + lstart[e];
             int why = 0, tok = 0, m = 0;
             bool in_tok = false, has_chrM = false;
             int64_t tb[4] = {0, 0, 0, 0}, te[4] = {0, 0, 0, 0};              // tokens 2, 3, 5, 6
@@ -231,7 +227,7 @@ __global__ __launch_bounds__(WG) void vp_parse(const unsigned char* __restrict__
         if (keep) {
             const unsigned long long pos = out_base + at;
             if (pos < capacity) records[pos] = rec;
-            else atomicMin(&words->first_error, error_word(line_base + row0 + e + 1, FHX_VP_INTERNAL));
+            else atomicMin(&words->first_error, error_word(line_base + B.row0 + e + 1, FHX_VP_INTERNAL));
         }
         __syncthreads();                                    // out_base is written again in the next round
     }
@@ -337,35 +333,9 @@ int bits_for(unsigned long long largest) {                                    //
     return b;
 }
 
-}  // namespace
-
-extern "C" {
-
-int fhx_vp_create(int device, fhx_vp** out) {
-    const int rc = fhx::text_handle_create(device, out);
-    if (rc == FHX_OK && fhx_create(device, &(*out)->sorter) != FHX_OK) {
-        fhx_vp_destroy(*out);
-        *out = nullptr;
-        return FHX_ERR_HIP;
-    }
-    return rc;
-}
-
-void fhx_vp_destroy(fhx_vp* vp) {
-    fhx::text_handle_destroy(vp, [&] {
-        drop_cells(vp);
-        if (vp->sorter) fhx_destroy(vp->sorter);
-    });
-}
-
-const char* fhx_vp_last_error(const fhx_vp* vp) { return vp ? vp->err.c_str() : "null context"; }
-
-int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_t* why, int64_t* bad_line) {
+// fhx_vp_bin_file behind its argument check; whatever it returns but FHX_OK, the caller drops the cells
+int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_t* why, int64_t* bad_line) {
     using namespace vpd;
-    if (!vp || !path || !n_cells || !why || !bad_line) return FHX_ERR_ARG;
-    *n_cells = 0;
-    *why = FHX_VP_OK;
-    *bad_line = 0;
     TH_HIP(vp, hipSetDevice(vp->device));
     TH_HIP(vp, hipStreamSynchronize(vp->stream));
     drop_cells(vp);
@@ -375,57 +345,26 @@ int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells,
         return vp->fail(FHX_ERR_UNSUPPORTED, "the resolution must be an even number from 2 to 2^31 - 2");
     }
     fhx::StageClock clock{vp->seconds};
-    // the file itself, or its inflated bytes when it starts with the gzip magic (zcat -f, :33)
-    fhx::TextFile src;
-    if (const int rc = src.open(path, /*allow_gzip=*/true, &vp->err)) return rc;
-    const int64_t batch_bytes = fhx::batch_bytes_for("FHX_VP_BATCH_BYTES", (int64_t)1 << 32, src.size());
-    const int64_t max_blocks = (batch_bytes + BLOCK_BYTES - 1) / BLOCK_BYTES;
     fhx::Scratch tmp;
-    unsigned char* d_text = nullptr;
-    unsigned int* d_block_nl = nullptr;
-    unsigned long long *d_block_off = nullptr, *d_names = nullptr;
+    fhx::TextBatches in;                                                      // a gzip file is read as zcat -f reads it (:33)
+    if (const int rc = in.open(vp, &tmp, &clock, path, "validPairs", "FHX_VP_BATCH_BYTES", (int64_t)1 << 32)) return rc;
+    unsigned long long* d_names = nullptr;
     Words* d_words = nullptr;
     ulonglong2* d_records = nullptr;
     int64_t capacity = 0;
-    TH_HIP(vp, tmp.get(&d_text, (size_t)max_blocks * BLOCK_BYTES + 64));
-    TH_HIP(vp, tmp.get(&d_block_nl, (size_t)max_blocks));
-    TH_HIP(vp, tmp.get(&d_block_off, (size_t)max_blocks));
     TH_HIP(vp, tmp.get(&d_names, (size_t)NAME_SLOTS));
     TH_HIP(vp, tmp.get(&d_words, 1));
     TH_HIP(vp, hipMemsetAsync(d_names, 0, NAME_SLOTS * sizeof(unsigned long long), vp->stream));
-    Words words;
+    Words words;                                                              // running totals: set once, not per batch
     std::memset(&words, 0, sizeof(words));
     words.first_error = NO_ERROR;
     TH_HIP(vp, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, vp->stream));
     TH_HIP(vp, hipStreamSynchronize(vp->stream));
-    auto refuse = [&](int rc, int32_t w, int64_t line, const std::string& msg) {
-        drop_cells(vp);
-        *why = w;
-        *bad_line = line;
-        return vp->fail(rc, msg);
-    };
-    auto refuse_line = [&](unsigned long long word) {
-        const int32_t w = error_why(word);
-        const int64_t line = error_line(word);
-        if (w == FHX_VP_INTERNAL) return refuse(FHX_ERR_INTERNAL, w, line, "the line count of the scan and the parse kernel disagree");
-        return refuse(FHX_ERR_UNSUPPORTED, w, line, "line " + std::to_string(line) + " is outside the device grammar (reason " + std::to_string(w) + ")");
-    };
-    int64_t lines = 0, pairs = 0;
-    for (int64_t off = 0; off < src.size();) {
-        fhx::TextBatch b;
-        if (const int rc = fhx::upload_batch(vp, src, "validPairs", off, std::min(batch_bytes, src.size() - off), d_text, &b)) return rc;
-        const int64_t len = b.len, n_blocks = b.n_blocks;
-        clock.mark(0);
-        hipLaunchKernelGGL(scan_text<AnyByte>, dim3((unsigned)n_blocks), dim3(WG), 0, vp->stream, (const unsigned char*)d_text, len, d_block_nl,
-                           (unsigned int*)&d_words->scan_flags);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned int*)d_block_nl, n_blocks, d_block_off,
-                           &d_words->newlines);
-        TH_HIP(vp, hipGetLastError());
-        unsigned long long n_newlines = 0;
-        TH_HIP(vp, hipMemcpyAsync(&n_newlines, &d_words->newlines, sizeof(n_newlines), hipMemcpyDeviceToHost, vp->stream));
-        TH_HIP(vp, hipStreamSynchronize(vp->stream));
-        clock.mark(1);
-        const int64_t n = b.lines(n_newlines);
+    const fhx::Refusal refuse{vp, why, bad_line};
+    int64_t pairs = 0;
+    for (; in.more(); in.advance()) {
+        if (const int rc = in.next<AnyByte>()) return rc;                     // this path's policy refuses no byte
+        const int64_t n = in.lines;
         if (pairs + n >= ((int64_t)1 << 32)) return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_PAIRS, 0, "2^32 or more pairs may be kept: the sort does not take them");
         if (pairs + n > capacity) {                                           // room for every line of the batch to be kept
             const int64_t want = std::max<int64_t>(pairs + n, capacity * 2);
@@ -437,21 +376,19 @@ int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells,
             d_records = bigger;
             capacity = want;
         }
-        hipLaunchKernelGGL(vp_parse, dim3((unsigned)n_blocks), dim3(WG), 0, vp->stream, (const unsigned char*)d_text, len,
-                           (const unsigned long long*)d_block_off, n, lines, (long long)res, d_names, d_records, (unsigned long long)capacity, d_words);
+        hipLaunchKernelGGL(vp_parse, dim3((unsigned)in.n_blocks), dim3(WG), 0, vp->stream, (const unsigned char*)in.d_text, in.len,
+                           (const unsigned long long*)in.d_block_off, n, in.line_base, (long long)res, d_names, d_records,
+                           (unsigned long long)capacity, d_words);
         TH_HIP(vp, hipGetLastError());
         TH_HIP(vp, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, vp->stream));
         TH_HIP(vp, hipStreamSynchronize(vp->stream));
         clock.mark(2);
-        if (words.first_error != NO_ERROR) return refuse_line(words.first_error);   // earlier batches hold the smaller line numbers
-        lines += n;
+        if (words.first_error != NO_ERROR) return refuse.word(words.first_error, FHX_VP_INTERNAL);      // earlier batches hold the smaller line numbers
         pairs = (int64_t)words.n_records;
         if (pairs > capacity) return refuse(FHX_ERR_INTERNAL, FHX_VP_INTERNAL, 0, "more records than lines");
-        off += len;
     }
-    tmp.drop(d_text);
-    d_text = nullptr;
-    src.release();
+    const int64_t lines = in.line_base;
+    in.close();
     if (words.names_overflow || words.n_names > (unsigned long long)MAX_NAMES)       // after every line has been checked: a line error wins
         return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_NAMES, 0, "more than " + std::to_string(MAX_NAMES) + " distinct chromosome names among the kept pairs");
     vp->n_lines = lines;
@@ -563,6 +500,40 @@ int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells,
                      "names + keys %.6f s; sort %.6f s; cells %.6f s\n", path, (long long)lines, (long long)pairs, (long long)cells, vp->seconds[0],
                      vp->seconds[1], vp->seconds[2], vp->seconds[3], vp->seconds[4], vp->seconds[5]);
     return FHX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhx_vp_create(int device, fhx_vp** out) {
+    const int rc = fhx::text_handle_create(device, out);
+    if (rc == FHX_OK && fhx_create(device, &(*out)->sorter) != FHX_OK) {
+        fhx_vp_destroy(*out);
+        *out = nullptr;
+        return FHX_ERR_HIP;
+    }
+    return rc;
+}
+
+void fhx_vp_destroy(fhx_vp* vp) {
+    fhx::text_handle_destroy(vp, [&] {
+        drop_cells(vp);
+        if (vp->sorter) fhx_destroy(vp->sorter);
+    });
+}
+
+const char* fhx_vp_last_error(const fhx_vp* vp) { return vp ? vp->err.c_str() : "null context"; }
+
+int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_t* why, int64_t* bad_line) {
+    using namespace vpd;
+    if (!vp || !path || !n_cells || !why || !bad_line) return FHX_ERR_ARG;
+    *n_cells = 0;
+    *why = FHX_VP_OK;
+    *bad_line = 0;
+    const int rc = bin_file(vp, path, res, n_cells, why, bad_line);
+    if (rc != FHX_OK) drop_cells(vp);                                         // the one exit of a failed call, whatever failed
+    return rc;
 }
 
 int fhx_vp_counts(const fhx_vp* vp, int64_t* n_lines, int64_t* n_pairs, int64_t* n_cells, int32_t* n_names) {

@@ -3,7 +3,6 @@
 texts built around the 16 KB scan blocks, around batch edges, around the 256-line rounds of the format kernel and at the largest
 amplification, every refusal names the right line and leaves nothing written, two runs give the same bytes, and read() feeds an
 Engine the same rows as the written file does."""
-import contextlib
 import gzip
 import os
 import subprocess
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import juicer_model as jm
+from batch_env import batch_bytes
 from conftest import ROOT, bits_equal
 from test_juicer_host import BAD_BOTH, BAD_MIDPOINT, GOOD, RUNS, _gunzip, run_input, run_output
 
@@ -21,26 +21,13 @@ pytestmark = pytest.mark.gpu
 BLOCK = 16384
 
 
-@contextlib.contextmanager
-def batch_bytes(n):
-    """the batch size of fhx_jc_convert_file for the calls inside (None: the default)"""
-    if n is None:
-        yield
-        return
-    os.environ["FHX_JC_BATCH_BYTES"] = str(n)
-    try:
-        yield
-    finally:
-        del os.environ["FHX_JC_BATCH_BYTES"]
-
-
 def gpu_bytes(data, res, tmp_path, batch=None, chr1="1", chr2="X", out="out.gz"):
     """the (decompressed) bytes convert() writes for the dump text `data`"""
     from fithic_amd import juicer
     src, dst = str(tmp_path / "dump.txt"), str(tmp_path / out)
     with open(src, "wb") as f:
         f.write(data)
-    with batch_bytes(batch):
+    with batch_bytes("FHX_JC_BATCH_BYTES", batch):
         n = juicer.convert(src, chr1, chr2, dst, res)
     with open(dst, "rb") as f:
         raw = f.read()
@@ -191,7 +178,7 @@ def _refusal_of(data, res, tmp_path, batch=None):
         f.write(data)
     jc = _capi.JcContext(0)
     try:
-        with batch_bytes(batch), pytest.raises(_capi.JcRefused) as e:
+        with batch_bytes("FHX_JC_BATCH_BYTES", batch), pytest.raises(_capi.JcRefused) as e:
             jc.convert_file(src, "chr1", "chrX", res or 0, keep_rows=bool(res))
         assert jc.counts() == dict(lines=0, rows=0, bytes=0) and jc.device_ptrs() == [0] * 5 and jc.text() == b""
         return e.value.why, e.value.line
@@ -238,7 +225,7 @@ def test_a_refusal_in_the_second_batch_leaves_nothing_written(tmp_path):
         f.write(GOOD * 900 + b"5000\t10000\t0.5\n" + GOOD * 3)
     for out, res in (("o.gz", None), ("o.txt", 5000), ("o.txt.gz", 5000)):
         dst = str(tmp_path / out)
-        with batch_bytes(8192):
+        with batch_bytes("FHX_JC_BATCH_BYTES", 8192):
             if res is None:
                 assert juicer.convert(src, "1", "1", dst) == 904
                 os.remove(dst)
@@ -251,6 +238,28 @@ def test_a_refusal_in_the_second_batch_leaves_nothing_written(tmp_path):
     assert r.returncode != 0 and "line 901" in r.stderr and not os.path.exists(str(tmp_path / "cli.txt"))
     with pytest.raises(ValueError, match="line 901"):
         juicer.read([(src, "1", "1")], 5000)
+
+
+def test_a_good_call_after_a_refused_one_gives_the_model_s_bytes(tmp_path):
+    from fithic_amd import _capi
+    rows = [b"%d\t%d\t%d\n" % (5000 * (k % 97), 5000 * (k % 89 + 100), 1 + k % 50) for k in range(1500)]
+    good, bad = b"".join(rows), b"".join(rows[:1300]) + b"5000 10000\n" + b"".join(rows[1300:])
+    assert 2 * 8192 < len(b"".join(rows[:1300])) and len(bad) < 4 * 8192     # line 1301 lies in the third batch at the earliest
+    for name, data in (("bad.txt", bad), ("good.txt", good)):
+        with open(str(tmp_path / name), "wb") as f:
+            f.write(data)
+    jc = _capi.JcContext(0)
+    try:
+        with batch_bytes("FHX_JC_BATCH_BYTES", 8192):
+            with pytest.raises(_capi.JcRefused) as e:
+                jc.convert_file(str(tmp_path / "bad.txt"), "chr1", "chrX", 5000, keep_rows=True)
+            assert (e.value.why, e.value.line) == (jm.TOKENS, 1301)
+            assert jc.counts() == dict(lines=0, rows=0, bytes=0) and jc.device_ptrs() == [0] * 5 and jc.text() == b""
+            assert jc.convert_file(str(tmp_path / "good.txt"), "chr1", "chrX", 5000, keep_rows=True) == 1500
+        want = model_bytes(good, 5000, "1", "X")                      # the .py writes `chr` before a name; the handle takes it whole
+        assert jc.text() == want and jc.counts() == dict(lines=1500, rows=1500, bytes=len(want))
+    finally:
+        jc.close()
 
 
 # ---- 4. the direct path -----------------------------------------------------------------------------------------------------------
@@ -293,7 +302,7 @@ def test_read_feeds_an_engine_the_rows_of_the_written_file(tmp_path):
     with open(sizes, "w") as f:
         f.write("chr1\t3000000\nchr2\t3000000\n")
     names, *cols = jm.columns([(text, a.encode(), b.encode()) for _, a, b, text in dumps], 10000)
-    with batch_bytes(32768), juicer.read([(p, a, b) for p, a, b, _ in dumps], 10000) as data:      # every dump takes several batches
+    with batch_bytes("FHX_JC_BATCH_BYTES", 32768), juicer.read([(p, a, b) for p, a, b, _ in dumps], 10000) as data:      # every dump takes several batches
         assert data.names == names == ["chr1", "chr2"] and len(data) == len(cols[0]) > 15000
         for g, w in zip(data.contacts(), cols):
             assert g.dtype == np.int32 and np.array_equal(g, np.asarray(w, np.int32))

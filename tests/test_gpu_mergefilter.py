@@ -2,7 +2,6 @@
 real script's after decompression (tests/golden/mergefilter), the subset equals the model's (tests/mergefilter_model.py) on
 texts built round the 16 KB scan blocks and round batch edges, at 0 % and 100 % kept, for every threshold and class, every
 refusal names the right line, two runs give the same bytes, and combine() equals the combine module on the written subset."""
-import contextlib
 import gzip
 import json
 import os
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import mergefilter_model as mm
+from batch_env import batch_bytes
 from conftest import ROOT
 from test_mergefilter_host import MF, RUNS, THRESHOLDS, _gunzip, run_input
 
@@ -22,26 +22,13 @@ BLOCK = 16384
 HEADER = b"chr1\tfragmentMid1\tchr2\tfragmentMid2\tcontactCount\tp-value\tq-value\tbias1\tbias2\tExpCC\n"
 
 
-@contextlib.contextmanager
-def batch_bytes(n):
-    """the batch size of fhx_ms_select_file for the calls inside (None: the default)"""
-    if n is None:
-        yield
-        return
-    os.environ["FHX_MS_BATCH_BYTES"] = str(n)
-    try:
-        yield
-    finally:
-        del os.environ["FHX_MS_BATCH_BYTES"]
-
-
 def gpu_subset(data, fdr, tmp_path, batch=None, **kw):
     """the subset the device path makes for `data`, after checking its counts against the model"""
     from fithic_amd import mergefilter
     src = str(tmp_path / "sig.txt")
     with open(src, "wb") as f:
         f.write(data)
-    with batch_bytes(batch):
+    with batch_bytes("FHX_MS_BATCH_BYTES", batch):
         got = mergefilter.select(src, fdr, **kw)
     text = got.subset_text()
     assert isinstance(text, bytes) and got.n_kept == text.count(b"\n")
@@ -248,7 +235,7 @@ def _refusal_of(data, tmp_path, batch=None, **kw):
         f.write(data)
     ms = _capi.MsContext(0)
     try:
-        with batch_bytes(batch), pytest.raises(_capi.MsRefused) as e:
+        with batch_bytes("FHX_MS_BATCH_BYTES", batch), pytest.raises(_capi.MsRefused) as e:
             ms.select_file(src, b"0.05", mf.key_bound("0.05"), True, False, kw.get("skip_first_line", True))
         assert ms.counts() == dict(lines=0, kept=0, bytes=0) and ms.subset() == b""
         return e.value.why, e.value.line
@@ -284,6 +271,43 @@ def test_the_smaller_of_two_bad_lines_is_reported_from_a_later_block_and_a_later
     assert _refusal_of(data, tmp_path, 8192) == (mm.TOKENS, 452)
     assert _refusal_of(data, tmp_path, 2 * BLOCK - 100) == (mm.TOKENS, 452)
     assert _refusal_of(HEADER + GOOD * 5 + b"c 1 c 2 3 4 1.000000e-03\r", tmp_path) == (mm.BYTES, 7)       # a \r that ends the text
+
+
+SIX_TOKENS = b"chr1 1 chr1 2 3 1.000000e-09\n"
+
+
+def third_batch_texts():
+    """300 ordinary rows, two in three of them kept, that take three or four batches of 8192 bytes; and the same text with a line
+    of six tokens as line 252, which lies in the third batch at the earliest: 250 rows before it are more than two batches"""
+    rows = [row(k, KEPT if k % 3 else DROPPED) for k in range(300)]
+    good, bad = HEADER + b"".join(rows), HEADER + b"".join(rows[:250]) + SIX_TOKENS + b"".join(rows[250:])
+    assert 2 * 8192 < len(HEADER + b"".join(rows[:250])) and len(bad) < 4 * 8192
+    assert mm.select(HEADER + b"".join(rows[:100]), "0.05")             # the first batch alone keeps lines
+    return good, bad
+
+
+def test_a_refusal_in_the_third_batch_leaves_nothing(tmp_path):
+    _, bad = third_batch_texts()
+    assert _refusal_of(bad, tmp_path, 8192) == (mm.TOKENS, 252)         # counts all 0 and an empty subset: _refusal_of
+
+
+def test_a_good_call_after_a_refused_one_gives_the_model_s_bytes(tmp_path):
+    from fithic_amd import _capi, mergefilter as mf
+    good, bad = third_batch_texts()
+    for name, data in (("bad.txt", bad), ("good.txt", good)):
+        with open(str(tmp_path / name), "wb") as f:
+            f.write(data)
+    ms = _capi.MsContext(0)
+    try:
+        with batch_bytes("FHX_MS_BATCH_BYTES", 8192):
+            with pytest.raises(_capi.MsRefused) as e:
+                ms.select_file(str(tmp_path / "bad.txt"), b"0.05", mf.key_bound("0.05"), True)
+            assert (e.value.why, e.value.line) == (mm.TOKENS, 252)
+            want = mm.select(good, "0.05")
+            assert ms.select_file(str(tmp_path / "good.txt"), b"0.05", mf.key_bound("0.05"), True) == len(want)
+        assert ms.subset() == want and ms.counts() == dict(lines=301, kept=200, bytes=len(want))
+    finally:
+        ms.close()
 
 
 def test_a_refused_file_leaves_no_output_file(tmp_path):

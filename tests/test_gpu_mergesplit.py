@@ -13,8 +13,9 @@ import pytest
 
 import mergefilter_model as mm
 import mergesplit_model as sm
+from batch_env import batch_bytes
 from conftest import ROOT
-from test_gpu_mergefilter import BLOCK, batch_bytes
+from test_gpu_mergefilter import BLOCK
 from test_mergesplit_host import GOOD, HEADER, MODEL_REFUSALS, RUNS, run_input, run_tree
 
 pytestmark = pytest.mark.gpu
@@ -36,7 +37,7 @@ def gpu_split(data, fdr, tmp_path, batch=None):
     src = str(tmp_path / "sig.txt")
     with open(src, "wb") as f:
         f.write(data)
-    with batch_bytes(batch):
+    with batch_bytes("FHX_MS_BATCH_BYTES", batch):
         got = mp.split(src, fdr)
     plain = gzip.decompress(data) if data[:2] == b"\x1f\x8b" else data
     assert got.n_lines == len(mm.lines_of(plain)) and list(got.stage_seconds()) == STAGES
@@ -244,7 +245,7 @@ def refusal_of(data, tmp_path, batch=None):
         f.write(data)
     ms = _capi.MsContext(0)
     try:
-        with batch_bytes(batch), pytest.raises(_capi.MsRefused) as e:
+        with batch_bytes("FHX_MS_BATCH_BYTES", batch), pytest.raises(_capi.MsRefused) as e:
             ms.split_file(src, b"0.05", mf.key_bound("0.05"), True)
         assert ms.split_counts() == dict(lines=0, kept=[], bytes=[]) and ms.split_names() == []
         return e.value.why, e.value.line
@@ -278,7 +279,7 @@ def test_a_refusal_in_the_second_batch_leaves_nothing(tmp_path):
     assert len(HEADER + GOOD * 200) > 8192 and sm.split(HEADER + GOOD * 100, "0.05")[b"chr1"]
     assert refusal_of(data, tmp_path, 8192) == (sm.NAME_NUMERIC, 202)
     src, out = str(tmp_path / "bad.txt"), tmp_path / "out"
-    with batch_bytes(8192):
+    with batch_bytes("FHX_MS_BATCH_BYTES", 8192):
         with pytest.raises(ValueError, match="line 202.*compare as a number.*The reference accepts this"):
             mp.split(src, "0.05")
         with pytest.raises(ValueError, match="line 202"):

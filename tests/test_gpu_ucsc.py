@@ -12,8 +12,9 @@ import numpy as np
 import pytest
 
 import ucsc_model as um
+from batch_env import batch_bytes
 from conftest import ROOT
-from test_gpu_mergefilter import BLOCK, DROPPED, EDGE_KINDS, HEADER, KEPT, batch_bytes, edge_text, row
+from test_gpu_mergefilter import BLOCK, DROPPED, EDGE_KINDS, HEADER, KEPT, edge_text, row, third_batch_texts
 from test_ucsc_host import RUNS, random_fields, run_input, run_track
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,7 @@ def gpu_track(data, qval, tmp_path, batch=None):
     src = str(tmp_path / "sig.txt")
     with open(src, "wb") as f:
         f.write(data)
-    with batch_bytes(batch):
+    with batch_bytes("FHX_MS_BATCH_BYTES", batch):
         got = ucsc.track(src, qval)
     text = got.text()
     assert isinstance(text, bytes) and text.startswith(um.HEAD) and got.n_kept == text.count(b"\n") - 2
@@ -187,7 +188,7 @@ def _refusal_of(data, tmp_path, batch=None):
         f.write(data)
     ms = _capi.MsContext(0)
     try:
-        with batch_bytes(batch), pytest.raises(_capi.MsRefused) as e:
+        with batch_bytes("FHX_MS_BATCH_BYTES", batch), pytest.raises(_capi.MsRefused) as e:
             ms.track_file(src, b"0.05", mf.key_bound("0.05", True), True)
         assert ms.track_counts() == dict(lines=0, kept=0, deferred=0, bytes=0) and ms.track() == b""
         return e.value.why, e.value.line
@@ -228,6 +229,33 @@ def test_the_smaller_of_two_bad_lines_is_reported_from_a_later_block_and_a_later
     assert len(HEADER + GOOD * 450) > BLOCK and len(GOOD * 400) > BLOCK
     for batch in (None, 8192, 2 * BLOCK - 100):
         assert _refusal_of(data, tmp_path, batch) == (um.MIDPOINT, 452)
+
+
+def test_a_refusal_in_the_third_batch_leaves_nothing(tmp_path):
+    _, bad = third_batch_texts()
+    assert model(bad[:bad.rindex(b"\n", 0, 8192) + 1], "0.05") != um.HEAD       # the first batch alone keeps lines
+    assert _refusal_of(bad, tmp_path, 8192) == (um.TOKENS, 252)         # counts all 0 and an empty track: _refusal_of
+
+
+def test_a_good_call_after_a_refused_one_gives_the_model_s_bytes(tmp_path):
+    from fithic_amd import _capi, mergefilter as mf
+    good, bad = third_batch_texts()
+    for name, data in (("bad.txt", bad), ("good.txt", good)):
+        with open(str(tmp_path / name), "wb") as f:
+            f.write(data)
+    ms = _capi.MsContext(0)
+    try:
+        with batch_bytes("FHX_MS_BATCH_BYTES", 8192):
+            with pytest.raises(_capi.MsRefused) as e:
+                ms.track_file(str(tmp_path / "bad.txt"), b"0.05", mf.key_bound("0.05", True), True)
+            assert (e.value.why, e.value.line) == (um.TOKENS, 252)
+            want = model(good, "0.05")
+            assert ms.track_file(str(tmp_path / "good.txt"), b"0.05", mf.key_bound("0.05", True), True) == len(want)
+        assert ms.track() == want
+        counts = ms.track_counts()
+        assert (counts["lines"], counts["kept"], counts["bytes"]) == (301, 200, len(want))
+    finally:
+        ms.close()
 
 
 def test_a_refused_file_leaves_no_output_file(tmp_path):

@@ -2,7 +2,6 @@
 after decompression (tests/golden/validpairs), the cells equal the model's (tests/validpairs_model.py) on texts built around
 the 16 KB scan blocks and around batch edges, on one long run and on all-different lines, every refusal names the right line,
 two runs give the same bytes, and the direct path feeds an Engine the same rows as the written files do."""
-import contextlib
 import gzip
 import os
 import subprocess
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import validpairs_model as vm
+from batch_env import batch_bytes
 from conftest import ROOT, bits_equal
 from test_validpairs_host import RUNS, VP, _gunzip, run_input
 
@@ -21,26 +21,13 @@ BLOCK = 16384
 GOOD = b"r\tchr1\t5\t+\tchr2\t9\t-\n"
 
 
-@contextlib.contextmanager
-def batch_bytes(n):
-    """the batch size of fhx_vp_bin_file for the calls inside (None: the default)"""
-    if n is None:
-        yield
-        return
-    os.environ["FHX_VP_BATCH_BYTES"] = str(n)
-    try:
-        yield
-    finally:
-        del os.environ["FHX_VP_BATCH_BYTES"]
-
-
 def gpu_bytes(data, res, tmp_path, batch=None):
     """the decompressed bytes the device path writes for `data`, after checking the fetched columns against the model"""
     from fithic_amd import validpairs
     src, out = str(tmp_path / "in.validPairs"), str(tmp_path / "out.gz")
     with open(src, "wb") as f:
         f.write(data)
-    with batch_bytes(batch), validpairs.read(src, res) as got:
+    with batch_bytes("FHX_VP_BATCH_BYTES", batch), validpairs.read(src, res) as got:
         names, *cols = vm.columns(data, res)
         assert got.names == names and len(got) == len(cols[0])
         for g, w in zip(got.contacts(), cols):
@@ -166,7 +153,7 @@ def _refusal_of(data, res, tmp_path, batch=None):
         f.write(data)
     vp = _capi.VpContext(0)
     try:
-        with batch_bytes(batch), pytest.raises(_capi.VpRefused) as e:
+        with batch_bytes("FHX_VP_BATCH_BYTES", batch), pytest.raises(_capi.VpRefused) as e:
             vp.bin_file(src, res)
         assert vp.n_cells == 0 and vp.device_ptrs() == [0] * 5
         return e.value.why, e.value.line
@@ -189,6 +176,31 @@ def test_the_smaller_of_two_bad_lines_is_reported_in_a_later_batch_too(tmp_path)
     assert _refusal_of(data, 10000, tmp_path) == (vm.TOKENS, 1001)
     assert _refusal_of(data, 10000, tmp_path, 8192) == (vm.TOKENS, 1001)
     assert _refusal_of(GOOD * 5 + b"r chr1 5 + chr2 9\r", 10000, tmp_path) == (vm.BYTES, 6)       # a \r that ends the text
+
+
+def test_a_good_call_after_a_refused_one_gives_the_model_s_cells(tmp_path):
+    from fithic_amd import _capi
+    rows = [b"r\tchr%d\t%d\t+\tchr%d\t%d\t-\n" % (1 + k % 3, 1000 * k, 1 + k % 2, 700 * k + 5) for k in range(900)]
+    good, bad = b"".join(rows), b"".join(rows[:700]) + b"r chr1 5 + chr2\n" + b"".join(rows[700:])
+    assert 2 * 8192 < len(b"".join(rows[:700])) and len(bad) < 4 * 8192      # line 701 lies in the third batch at the earliest
+    for name, data in (("bad.validPairs", bad), ("good.validPairs", good)):
+        with open(str(tmp_path / name), "wb") as f:
+            f.write(data)
+    vp = _capi.VpContext(0)
+    try:
+        with batch_bytes("FHX_VP_BATCH_BYTES", 8192):
+            with pytest.raises(_capi.VpRefused) as e:
+                vp.bin_file(str(tmp_path / "bad.validPairs"), 10000)
+            assert (e.value.why, e.value.line) == (vm.TOKENS, 701)
+            assert vp.counts() == dict(lines=0, pairs=0, cells=0, names=0) and vp.device_ptrs() == [0] * 5
+            names, *cols = vm.columns(good, 10000)
+            assert vp.bin_file(str(tmp_path / "good.validPairs"), 10000) == len(cols[0])
+        assert vp.names() == names
+        for g, w in zip(vp.fetch_cells(), cols):
+            assert np.array_equal(g, np.asarray(w, np.int32))
+        assert vp.counts() == dict(lines=900, pairs=sum(cols[4]), cells=len(cols[0]), names=len(names))
+    finally:
+        vp.close()
 
 
 def test_lines_the_first_filters_drop_are_not_read_further(tmp_path):
