@@ -115,6 +115,7 @@ SYMBOLS = {
     "fhx_bh_sort_stats": (ctypes.c_int, [_P, _I64P]),
     "fhx_k3_pass_info": (ctypes.c_int, [_P, _I64P]),
     "fhx_debug_k3_tiles_per_group": (ctypes.c_int, [_P, ctypes.c_int]),
+    "fhx_debug_device_blocks": (ctypes.c_int, [_I64P, _I64P]),
     "fhx_debug_k1_wide": (ctypes.c_int, [_P, ctypes.c_int]),
     "fhx_k3_compact_variant": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int32)]),
     "fhx_kernel_seconds": (ctypes.c_int, [_P, _F64P, _F64P, _F64P]),
@@ -403,6 +404,13 @@ class FhxError(RuntimeError):
     def __init__(self, code, message):
         super().__init__("fhx error %d: %s" % (code, message))
         self.code = code
+
+
+def device_blocks():
+    """test hook (fhx_debug_device_blocks): (live device blocks, their bytes) of this process, over every handle"""
+    blocks, nbytes = ctypes.c_int64(0), ctypes.c_int64(0)
+    lib().fhx_debug_device_blocks(ctypes.byref(blocks), ctypes.byref(nbytes))
+    return blocks.value, nbytes.value
 
 
 def _ptr(a, ctype):

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
+#include "fhx_devmem.hpp"
 #include "fhx_scan.hpp"
 
 namespace cnd {
@@ -394,10 +395,7 @@ __global__ __launch_bounds__(THREADS) void cn_records(const unsigned int* out_no
 }  // namespace cnd
 
 // ===================================================================================================================
-struct fhx_cni {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct fhx_cni : fhx::Handle {
     fhx_ctx* sorter = nullptr;
     int64_t rows = 0, res = 0, lattice_r = 0;
     int64_t* d_cc = nullptr;
@@ -413,85 +411,45 @@ struct fhx_cni {
 
 namespace {
 
-int cfail(fhx_cni* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
-}
-
-#define CN_HIP(call)                                                                                      \
-    do {                                                                                                  \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess) return cfail(cn, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <typename T>
-void cfree(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 inline int grid_of(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + cnd::THREADS - 1) / cnd::THREADS, 256 * 16)); }
 
-// RAII for the many device temporaries of one call
-struct DevPool {
-    std::vector<void*> ptrs;
-    ~DevPool() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t get(T** p, size_t count) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
+void free_rows(fhx_cni* cn) {
+    fhx::dev_free(cn->d_cc);
+    fhx::dev_free(cn->d_q);
+    fhx::dev_free(cn->d_p);
+    fhx::dev_free(cn->d_node_key);
+    fhx::dev_free(cn->d_node_row);
+}
 
 }  // namespace
 
 extern "C" {
 
 int fhx_cni_create(int device, fhx_cni** out) {
-    if (!out) return FHX_ERR_ARG;
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return FHX_ERR_NO_DEVICE;
-    fhx_cni* cn = new fhx_cni();
-    cn->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&cn->stream, hipStreamNonBlocking) != hipSuccess ||
-        fhx_create(device, &cn->sorter) != FHX_OK) {
-        delete cn;
+    const int rc = fhx::handle_create(device, out);
+    if (rc == FHX_OK && fhx_create(device, &(*out)->sorter) != FHX_OK) {
+        fhx_cni_destroy(*out);
+        *out = nullptr;
         return FHX_ERR_HIP;
     }
-    *out = cn;
-    return FHX_OK;
+    return rc;
 }
 
 void fhx_cni_destroy(fhx_cni* cn) {
-    if (!cn) return;
-    (void)hipSetDevice(cn->device);
-    if (cn->stream) (void)hipStreamSynchronize(cn->stream);
-    cfree(cn->d_cc);
-    cfree(cn->d_q);
-    cfree(cn->d_p);
-    cfree(cn->d_node_key);
-    cfree(cn->d_node_row);
-    if (cn->sorter) fhx_destroy(cn->sorter);
-    if (cn->stream) (void)hipStreamDestroy(cn->stream);
-    delete cn;
+    fhx::handle_destroy(cn, [&] {
+        free_rows(cn);
+        if (cn->sorter) fhx_destroy(cn->sorter);
+    });
 }
 
-const char* fhx_cni_last_error(const fhx_cni* cn) { return cn ? cn->err.c_str() : "null context"; }
+const char* fhx_cni_last_error(const fhx_cni* cn) { return fhx::handle_last_error(cn); }
 
 int fhx_cni_load(fhx_cni* cn, const int32_t* chr, const int64_t* n1, const int64_t* n2, const int64_t* cc, const double* p,
                  const double* q, int64_t rows, int64_t bin_size, int64_t* n_nodes) {
     if (!cn || rows < 0 || bin_size <= 0 || (rows > 0 && (!chr || !n1 || !n2 || !cc || !p || !q))) return FHX_ERR_ARG;
-    if (rows >= (1ll << 32)) return cfail(cn, FHX_ERR_UNSUPPORTED, "more than 2^32 rows");
+    if (rows >= (1ll << 32)) return fhx::fail(cn, FHX_ERR_UNSUPPORTED, "more than 2^32 rows");
     CN_HIP(hipSetDevice(cn->device));
-    cfree(cn->d_cc);
-    cfree(cn->d_q);
-    cfree(cn->d_p);
-    cfree(cn->d_node_key);
-    cfree(cn->d_node_row);
+    free_rows(cn);
     cn->out.clear();
     cn->rows = rows;
     cn->res = bin_size;
@@ -502,21 +460,21 @@ int fhx_cni_load(fhx_cni* cn, const int32_t* chr, const int64_t* n1, const int64
     int64_t r = n1[0] % bin_size;
     if (r < 0) r += bin_size;
     cn->lattice_r = r;
-    DevPool pool;
+    fhx::DeviceScratch pool;
     int32_t* d_chr = nullptr;
     int64_t *d_n1 = nullptr, *d_n2 = nullptr;
     unsigned long long *keys = nullptr, *skeys = nullptr, *tile_off = nullptr;
     unsigned int *perm = nullptr, *tile_cnt = nullptr, *d_bad = nullptr;
-    CN_HIP(pool.get(&d_chr, rows));
-    CN_HIP(pool.get(&d_n1, rows));
-    CN_HIP(pool.get(&d_n2, rows));
-    CN_HIP(pool.get(&keys, rows));
-    CN_HIP(pool.get(&skeys, rows));
-    CN_HIP(pool.get(&perm, rows));
-    CN_HIP(pool.get(&d_bad, 4));
-    CN_HIP(hipMalloc(&cn->d_cc, (size_t)rows * 8));
-    CN_HIP(hipMalloc(&cn->d_q, (size_t)rows * 8));
-    CN_HIP(hipMalloc(&cn->d_p, (size_t)rows * 8));
+    CN_HIP(pool.get_n(&d_chr, rows));
+    CN_HIP(pool.get_n(&d_n1, rows));
+    CN_HIP(pool.get_n(&d_n2, rows));
+    CN_HIP(pool.get_n(&keys, rows));
+    CN_HIP(pool.get_n(&skeys, rows));
+    CN_HIP(pool.get_n(&perm, rows));
+    CN_HIP(pool.get_n(&d_bad, 4));
+    CN_HIP(fhx::dev_malloc(&cn->d_cc, (size_t)rows * 8));
+    CN_HIP(fhx::dev_malloc(&cn->d_q, (size_t)rows * 8));
+    CN_HIP(fhx::dev_malloc(&cn->d_p, (size_t)rows * 8));
     CN_HIP(hipMemcpyAsync(d_chr, chr, (size_t)rows * 4, hipMemcpyHostToDevice, cn->stream));
     CN_HIP(hipMemcpyAsync(d_n1, n1, (size_t)rows * 8, hipMemcpyHostToDevice, cn->stream));
     CN_HIP(hipMemcpyAsync(d_n2, n2, (size_t)rows * 8, hipMemcpyHostToDevice, cn->stream));
@@ -530,21 +488,21 @@ int fhx_cni_load(fhx_cni* cn, const int32_t* chr, const int64_t* n1, const int64
     CN_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, cn->stream));
     CN_HIP(hipStreamSynchronize(cn->stream));
     if (bad)
-        return cfail(cn, FHX_ERR_UNSUPPORTED, std::to_string(bad) + " rows are off the bin lattice (int(mid + res/2) must be congruent to " +
-                     std::to_string(r) + " modulo the resolution, bins < 2^24, chromosome ids < 65536)");
+        return fhx::fail(cn, FHX_ERR_UNSUPPORTED, std::to_string(bad) + " rows are off the bin lattice (int(mid + res/2) must be congruent to " +
+                         std::to_string(r) + " modulo the resolution, bins < 2^24, chromosome ids < 65536)");
     int rc = fhx_sort_u64(cn->sorter, keys, rows, skeys, perm);
-    if (rc != FHX_OK) return cfail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
+    if (rc != FHX_OK) return fhx::fail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
     const int64_t tiles = (rows + fhxscan::TILE - 1) / fhxscan::TILE;
-    CN_HIP(pool.get(&tile_cnt, tiles));
-    CN_HIP(pool.get(&tile_off, tiles + 1));
+    CN_HIP(pool.get_n(&tile_cnt, tiles));
+    CN_HIP(pool.get_n(&tile_off, tiles + 1));
     hipLaunchKernelGGL(fhxscan::count_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, cn->stream, skeys, rows, tile_cnt);
     hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, cn->stream, tile_cnt, tiles, tile_off, tile_off + tiles);
     CN_HIP(hipGetLastError());
     unsigned long long n = 0;
     CN_HIP(hipMemcpyAsync(&n, tile_off + tiles, 8, hipMemcpyDeviceToHost, cn->stream));
     CN_HIP(hipStreamSynchronize(cn->stream));
-    CN_HIP(hipMalloc(&cn->d_node_key, (size_t)n * 8));
-    CN_HIP(hipMalloc(&cn->d_node_row, (size_t)n * 4));
+    CN_HIP(fhx::dev_malloc(&cn->d_node_key, (size_t)n * 8));
+    CN_HIP(fhx::dev_malloc(&cn->d_node_row, (size_t)n * 4));
     hipLaunchKernelGGL(cnd::cn_emit_nodes, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, cn->stream, skeys, perm, rows, tile_off,
                        cn->d_node_key, cn->d_node_row);
     CN_HIP(hipGetLastError());
@@ -557,8 +515,8 @@ int fhx_cni_load(fhx_cni* cn, const int32_t* chr, const int64_t* n1, const int64
 int fhx_cni_run(fhx_cni* cn, int32_t connectivity, int32_t top_percent, int32_t neighborhood, int32_t sort_order, fhx_cni_info* info_out) {
     if (!cn || (connectivity != 8 && connectivity != 4) || neighborhood < 0 || (sort_order != 0 && sort_order != 1)) return FHX_ERR_ARG;
     if (top_percent <= 0)
-        return cfail(cn, FHX_ERR_UNSUPPORTED, "-p 0 depends on CPython's set iteration order (CombineNearbyInteraction.py:417-437); "
-                                              "-p must be in 1..100 (values > 100 select nothing in the reference)");
+        return fhx::fail(cn, FHX_ERR_UNSUPPORTED, "-p 0 depends on CPython's set iteration order (CombineNearbyInteraction.py:417-437); "
+                                                  "-p must be in 1..100 (values > 100 select nothing in the reference)");
     CN_HIP(hipSetDevice(cn->device));
     cn->out.clear();
     fhx_cni_info info{};
@@ -570,24 +528,24 @@ int fhx_cni_run(fhx_cni* cn, int32_t connectivity, int32_t top_percent, int32_t 
         if (info_out) *info_out = info;
         return FHX_OK;
     }
-    DevPool pool;
+    fhx::DeviceScratch pool;
     unsigned int *parent = nullptr, *uf_parent = nullptr, *order_a = nullptr, *order_b = nullptr, *perm = nullptr, *pos = nullptr, *d_seg = nullptr, *d_limit = nullptr;
     unsigned long long *k_in = nullptr, *k_out = nullptr, *d_counter = nullptr;
     cnd::CompStats* st = nullptr;
     unsigned char* state = nullptr;
-    CN_HIP(pool.get(&parent, n));                         // root of every node, after cn_flatten
-    CN_HIP(pool.get(&uf_parent, n));
-    CN_HIP(pool.get(&st, n));
-    CN_HIP(pool.get(&order_a, n));
-    CN_HIP(pool.get(&order_b, n));
-    CN_HIP(pool.get(&perm, n));
-    CN_HIP(pool.get(&pos, n));
-    CN_HIP(pool.get(&d_seg, n));
-    CN_HIP(pool.get(&d_limit, n));
-    CN_HIP(pool.get(&k_in, n));
-    CN_HIP(pool.get(&k_out, n));
-    CN_HIP(pool.get(&d_counter, 4));
-    CN_HIP(pool.get(&state, n));
+    CN_HIP(pool.get_n(&parent, n));                         // root of every node, after cn_flatten
+    CN_HIP(pool.get_n(&uf_parent, n));
+    CN_HIP(pool.get_n(&st, n));
+    CN_HIP(pool.get_n(&order_a, n));
+    CN_HIP(pool.get_n(&order_b, n));
+    CN_HIP(pool.get_n(&perm, n));
+    CN_HIP(pool.get_n(&pos, n));
+    CN_HIP(pool.get_n(&d_seg, n));
+    CN_HIP(pool.get_n(&d_limit, n));
+    CN_HIP(pool.get_n(&k_in, n));
+    CN_HIP(pool.get_n(&k_out, n));
+    CN_HIP(pool.get_n(&d_counter, 4));
+    CN_HIP(pool.get_n(&state, n));
     const dim3 g(grid_of(n)), b(cnd::THREADS);
     // components
     hipLaunchKernelGGL(cnd::cn_init_stats, g, b, 0, cn->stream, st, uf_parent, n);
@@ -601,17 +559,17 @@ int fhx_cni_run(fhx_cni* cn, int32_t connectivity, int32_t top_percent, int32_t 
     hipLaunchKernelGGL(cnd::cn_key_cc, g, b, 0, cn->stream, cn->d_node_row, cn->d_cc, n, k_in);
     CN_HIP(hipStreamSynchronize(cn->stream));
     int rc = fhx_sort_u64(cn->sorter, k_in, n, k_out, perm);
-    if (rc != FHX_OK) return cfail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
+    if (rc != FHX_OK) return fhx::fail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
     hipLaunchKernelGGL(cnd::cn_compose, g, b, 0, cn->stream, (const unsigned int*)nullptr, perm, n, order_a);
     hipLaunchKernelGGL(cnd::cn_key_q, g, b, 0, cn->stream, order_a, cn->d_node_row, cn->d_q, (int)sort_order, n, k_in);
     CN_HIP(hipStreamSynchronize(cn->stream));
     rc = fhx_sort_u64(cn->sorter, k_in, n, k_out, perm);
-    if (rc != FHX_OK) return cfail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
+    if (rc != FHX_OK) return fhx::fail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
     hipLaunchKernelGGL(cnd::cn_compose, g, b, 0, cn->stream, order_a, perm, n, order_b);
     hipLaunchKernelGGL(cnd::cn_key_root, g, b, 0, cn->stream, order_b, parent, n, k_in);
     CN_HIP(hipStreamSynchronize(cn->stream));
     rc = fhx_sort_u64(cn->sorter, k_in, n, k_out, perm);
-    if (rc != FHX_OK) return cfail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
+    if (rc != FHX_OK) return fhx::fail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
     hipLaunchKernelGGL(cnd::cn_compose, g, b, 0, cn->stream, order_b, perm, n, order_a);       // final order
     hipLaunchKernelGGL(cnd::cn_positions, g, b, 0, cn->stream, order_a, n, pos);
     CN_HIP(hipGetLastError());
@@ -631,18 +589,18 @@ int fhx_cni_run(fhx_cni* cn, int32_t connectivity, int32_t top_percent, int32_t 
         CN_HIP(hipStreamSynchronize(cn->stream));
         ++rounds;
         if (left == 0) break;
-        if (rounds > 1000000) return cfail(cn, FHX_ERR_HIP, "pick rounds do not converge");
+        if (rounds > 1000000) return fhx::fail(cn, FHX_ERR_HIP, "pick rounds do not converge");
     }
     // output order of the components: first row, then (chromosome, size descending) - two stable sorts over the roots
     hipLaunchKernelGGL(cnd::cn_key_first_row, g, b, 0, cn->stream, parent, st, n, k_in);
     CN_HIP(hipStreamSynchronize(cn->stream));
     rc = fhx_sort_u64(cn->sorter, k_in, n, k_out, perm);
-    if (rc != FHX_OK) return cfail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
+    if (rc != FHX_OK) return fhx::fail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
     hipLaunchKernelGGL(cnd::cn_compose, g, b, 0, cn->stream, (const unsigned int*)nullptr, perm, n, order_b);
     hipLaunchKernelGGL(cnd::cn_key_chr_size, g, b, 0, cn->stream, order_b, cn->d_node_key, parent, st, n, k_in);
     CN_HIP(hipStreamSynchronize(cn->stream));
     rc = fhx_sort_u64(cn->sorter, k_in, n, k_out, perm);
-    if (rc != FHX_OK) return cfail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
+    if (rc != FHX_OK) return fhx::fail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
     unsigned long long h_counts[3] = {0, 0, 0};
     CN_HIP(hipMemcpy(h_counts, d_counter, 16, hipMemcpyDeviceToHost));
     const int64_t n_comp = (int64_t)h_counts[0];
@@ -658,11 +616,11 @@ int fhx_cni_run(fhx_cni* cn, int32_t connectivity, int32_t top_percent, int32_t 
     CN_HIP(hipMemcpyAsync(&n_sel, d_counter + 3, 8, hipMemcpyDeviceToHost, cn->stream));
     CN_HIP(hipStreamSynchronize(cn->stream));
     rc = fhx_sort_u64(cn->sorter, k_in, n, k_out, perm);
-    if (rc != FHX_OK) return cfail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
+    if (rc != FHX_OK) return fhx::fail(cn, rc, std::string("sort: ") + fhx_last_error(cn->sorter));
     cn->out.resize((size_t)n_sel);
     if (n_sel) {
         fhx_cni_record* d_rec = nullptr;
-        CN_HIP(pool.get(&d_rec, (size_t)n_sel));
+        CN_HIP(pool.get_n(&d_rec, (size_t)n_sel));
         hipLaunchKernelGGL(cnd::cn_records, dim3(grid_of((int64_t)n_sel)), b, 0, cn->stream, perm, (int64_t)n_sel, cn->d_node_key,
                            cn->d_node_row, parent, st, cn->d_cc, cn->d_p, cn->d_q, cn->res, cn->lattice_r, d_rec);
         CN_HIP(hipGetLastError());

@@ -33,6 +33,7 @@
 
 #include "../../include/fithic_mi355x.h"
 #include "fhx_bdtrc.hpp"
+#include "fhx_devmem.hpp"
 #include "fhx_host.hpp"
 #include "fhx_io_internal.hpp"
 #include "fhx_scan.hpp"
@@ -519,18 +520,6 @@ inline double bdtrc_total(const fhx_params& prm, long long sum) {
     return (double)(int32_t)(uint32_t)(unsigned long long)sum;
 }
 
-inline int fail(fhx_ctx* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
-}
-
-#define FHX_HIP(call)                                                                                     \
-    do {                                                                                                  \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess)                                                                             \
-            return fail(ctx, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));            \
-    } while (0)
-
 // ---- tickets: a kernel's results read by the host without a stream synchronisation (fhx_ctx::h_flags) -------------------
 constexpr int FLAG_K1 = 0, FLAG_K3 = 8, FLAG_FAULT = 16;   // words of h_flags, a cache line apart
 inline int ensure_flags(fhx_ctx* ctx) {
@@ -539,7 +528,7 @@ inline int ensure_flags(fhx_ctx* ctx) {
     FHX_HIP(hipHostMalloc(&h, 64 * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped));
     std::memset(h, 0, 64 * sizeof(unsigned long long));
     ctx->h_flags = reinterpret_cast<volatile unsigned long long*>(h);
-    FHX_HIP(hipMalloc(&ctx->d_done, 16 * sizeof(unsigned int)));
+    FHX_HIP(dev_malloc(&ctx->d_done, 16 * sizeof(unsigned int)));
     FHX_HIP(hipMemsetAsync(ctx->d_done, 0, 16 * sizeof(unsigned int), ctx->stream));
     return FHX_OK;
 }
@@ -585,69 +574,6 @@ inline int check_fault(fhx_ctx* ctx) {
     return fail(ctx, FHX_ERR_INTERNAL, "K3: " + std::to_string(seen) + " p-values survived the cutoff, more than the key histogram announced - the "
                                        "ranking would be truncated (was p rewritten after fhx_pvalues?)");
 }
-
-template <typename T>
-inline void dev_free(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-// temporary device allocations of one call: freed on every return path (FHX_HIP returns early on errors)
-// Device blocks kept between the batches of one call: allocating and freeing GBs per batch stalls behind the other thread's
-// hipFree (a batch of the device writer waited up to 0.5 s in its allocations); a block goes back here instead and the next
-// batch, which asks for the same sizes in the same order, takes it again.  Freed when the pool goes out of scope.
-struct ScratchPool {
-    std::mutex mu;
-    std::vector<std::pair<void*, size_t>> idle;
-    ~ScratchPool() {
-        for (auto& b : idle) (void)hipFree(b.first);
-    }
-    void* take(size_t bytes, size_t* real) {           // the smallest idle block that is large enough, or nullptr
-        std::lock_guard<std::mutex> g(mu);
-        size_t best = idle.size();
-        for (size_t i = 0; i < idle.size(); ++i)
-            if (idle[i].second >= bytes && (best == idle.size() || idle[i].second < idle[best].second)) best = i;
-        if (best == idle.size()) return nullptr;
-        void* p = idle[best].first;
-        *real = idle[best].second;
-        idle.erase(idle.begin() + (long)best);
-        return p;
-    }
-    void give(void* p, size_t bytes) {
-        std::lock_guard<std::mutex> g(mu);
-        idle.emplace_back(p, bytes);
-    }
-};
-
-struct DeviceScratch {
-    std::vector<std::pair<void*, size_t>> v;
-    ScratchPool* pool = nullptr;                       // where the blocks go at the end instead of hipFree
-    DeviceScratch() = default;
-    explicit DeviceScratch(ScratchPool* p) : pool(p) {}
-    ~DeviceScratch() {
-        for (auto& b : v) {
-            if (pool)
-                pool->give(b.first, b.second);
-            else
-                (void)hipFree(b.first);
-        }
-    }
-    template <typename T>
-    hipError_t get(T** p, size_t bytes) {
-        bytes = std::max<size_t>(bytes, 16);
-        if (pool) {
-            size_t real = 0;
-            if (void* q = pool->take(bytes, &real)) {
-                *p = (T*)q;
-                v.emplace_back(q, real);
-                return hipSuccess;
-            }
-        }
-        const hipError_t e = hipMalloc((void**)p, bytes);
-        if (e == hipSuccess) v.emplace_back((void*)*p, bytes);
-        return e;
-    }
-};
 
 inline int grid_for(int64_t n, int threads, int max_blocks = 256 * 8) {
     const int64_t b = (n + threads - 1) / threads;

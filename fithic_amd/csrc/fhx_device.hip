@@ -35,7 +35,7 @@ int fhx_create(int device, fhx_ctx** out) {
                 fhx_destroy(ctx);                // (the stream and the events made so far go with it)
                 return FHX_ERR_HIP;
             }
-        if (hipMalloc(&ctx->d_words, sizeof(DeviceWords)) != hipSuccess) {
+        if (dev_malloc(&ctx->d_words, sizeof(DeviceWords)) != hipSuccess) {
             fhx_destroy(ctx);
             return FHX_ERR_HIP;
         }
@@ -48,6 +48,12 @@ int fhx_warmup(int device) {
     if (device < 0) return FHX_ERR_ARG;
     if (hipSetDevice(device) != hipSuccess) return FHX_ERR_NO_DEVICE;
     return hipFree(nullptr) == hipSuccess ? FHX_OK : FHX_ERR_HIP;
+}
+
+int fhx_debug_device_blocks(int64_t* blocks, int64_t* bytes) {
+    if (blocks) *blocks = dev_live().blocks.load();
+    if (bytes) *bytes = dev_live().bytes.load();
+    return FHX_OK;
 }
 
 void fhx_destroy(fhx_ctx* ctx) {
@@ -382,7 +388,7 @@ int fhx_fit(fhx_ctx* ctx, fhx_fit_info* out) {
             if (ctx->h_fit_stage) (void)hipHostFree(ctx->h_fit_stage);
             ctx->h_fit_stage = nullptr;
             ctx->fit_tables_cap = need + need / 2 + 1024;
-            FHX_HIP(hipMalloc(&ctx->d_fit_tables, ctx->fit_tables_cap * sizeof(double)));
+            FHX_HIP(dev_malloc(&ctx->d_fit_tables, ctx->fit_tables_cap * sizeof(double)));
             FHX_HIP(hipHostMalloc((void**)&ctx->h_fit_stage, ctx->fit_tables_cap * sizeof(double), hipHostMallocDefault));
         }
         if (!ctx->ev_fit_copy) FHX_HIP(hipEventCreateWithFlags(&ctx->ev_fit_copy, hipEventDisableTiming));
@@ -497,7 +503,7 @@ int fhx_set_global_rows(fhx_ctx* ctx, const int64_t* rows, int64_t n) {
     FHX_HIP(hipSetDevice(ctx->device));
     dev_free(ctx->d_grow);
     const size_t cap = std::max<size_t>(4, ((size_t)n + 3) / 4 * 4);
-    FHX_HIP(hipMalloc(&ctx->d_grow, cap * sizeof(long long)));
+    FHX_HIP(dev_malloc(&ctx->d_grow, cap * sizeof(long long)));
     FHX_HIP(hipMemsetAsync(ctx->d_grow, 0, cap * sizeof(long long), ctx->stream));
     if (n) FHX_HIP(hipMemcpyAsync(ctx->d_grow, rows, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));

@@ -238,27 +238,6 @@ static RcclApi* rccl_api() {
     return &api;
 }
 
-template <typename T>
-struct GrowBuf {                       // grow-only device buffer: steady-state passes allocate nothing
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = n + n / 8 + 64;
-        const hipError_t e = hipMalloc(&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 // the rows of fhx_dist_schedule.def: every collective names the one it is
 enum DistStep : int {
 #define FHX_DIST_STEP(id, kind, size, phase) DS_##id,
@@ -442,7 +421,7 @@ int dist_agree_n_dist(fhx_ctx* ctx) {
     }
     if (global > ctx->n_dist) {
         unsigned long long* grown[3] = {nullptr, nullptr, nullptr};
-        for (auto& g : grown) FHX_HIP(hipMalloc(&g, (size_t)global * sizeof(unsigned long long)));
+        for (auto& g : grown) FHX_HIP(dev_malloc(&g, (size_t)global * sizeof(unsigned long long)));
         FHX_HIP(hipMemsetAsync(grown[2], 0, (size_t)global * sizeof(unsigned long long), ctx->stream));
         FHX_HIP(hipMemcpyAsync(grown[2], ctx->d_out_hist, (size_t)ctx->n_dist * sizeof(unsigned long long), hipMemcpyDeviceToDevice,
                                ctx->stream));
@@ -485,15 +464,7 @@ int fhx_comm_destroy(fhx_ctx* ctx) {
         if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     }
     if (D->comm && D->api) (void)D->api->CommDestroy(D->comm);
-    D->pack.release(); D->counts.release(); D->matrix.release(); D->samples.release(); D->all_samples.release();
-    D->splitters.release(); D->misc.release(); D->q_arrival.release(); D->q_back.release(); D->tile_max.release();
-    D->slice_max.release(); D->all_max.release(); D->carry.release(); D->out_hist.release();
-    D->run_off.release(); D->nf_send.release(); D->nf_recv.release();
-    for (int b = 0; b < 2; ++b) {
-        D->xkeys[b].release();
-        D->xvals[b].release();
-    }
-    delete D;
+    delete D;                                             // its GrowBufs go with it
     ctx->dist = nullptr;
     return FHX_OK;
 }
@@ -634,7 +605,7 @@ static int dist_convert_to_nonfixed(fhx_ctx* ctx) {
     if (rc != FHX_OK) {
         // the row arrays were freed (and perhaps half re-allocated) on the way: the context holds no rows any more and says so -
         // every later stage call fails with "no contact rows loaded" until the caller loads them again
-        if (saved_rows) (void)hipFree(saved_rows);
+        dev_free(saved_rows);
         const std::string why = ctx->err;
         dev_free(ctx->d_loc1);
         dev_free(ctx->d_loc2);

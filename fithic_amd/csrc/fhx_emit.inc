@@ -726,7 +726,7 @@ static int write_significances_batch(fhx_ctx* ctx, std::FILE* f, const std::vect
             out_cap = real;
         } else {
             out_cap += out_cap / 16;                                       // the next batch's output may be a little larger
-            FHX_HIP(hipMalloc((void**)&d_out, out_cap));
+            FHX_HIP(dev_malloc(&d_out, out_cap));
         }
     }
     struct OutGuard {

@@ -206,14 +206,8 @@ struct fhx_hp : fhx::TextHandle {
 
 namespace {
 
-template <typename T>
-void hfree(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 void drop_rows(fhx_hp* hp) {
-    hfree(hp->d_cols);
+    fhx::dev_free(hp->d_cols);
     hp->n_rows = 0;
     hp->col_stride = 0;
 }
@@ -222,34 +216,34 @@ void drop_rows(fhx_hp* hp) {
 
 extern "C" {
 
-int fhx_hp_create(int device, fhx_hp** out) { return fhx::text_handle_create(device, out); }
+int fhx_hp_create(int device, fhx_hp** out) { return fhx::handle_create(device, out); }
 
 void fhx_hp_destroy(fhx_hp* hp) {
     fhx::text_handle_destroy(hp, [&] {
         drop_rows(hp);
-        hfree(hp->d_bins);
-        hfree(hp->d_totals);
+        fhx::dev_free(hp->d_bins);
+        fhx::dev_free(hp->d_totals);
     });
 }
 
-const char* fhx_hp_last_error(const fhx_hp* hp) { return hp ? hp->err.c_str() : "null context"; }
+const char* fhx_hp_last_error(const fhx_hp* hp) { return fhx::handle_last_error(hp); }
 
 int fhx_hp_load_bins(fhx_hp* hp, int64_t index_base, const int32_t* chr_id, const int32_t* mid, int64_t n_slots) {
     if (!hp || n_slots < 0 || (n_slots > 0 && (!chr_id || !mid))) return FHX_ERR_ARG;
-    if (n_slots > ((int64_t)1 << 27)) return hp->fail(FHX_ERR_UNSUPPORTED, "a bin table of more than 2^27 slots");
+    if (n_slots > ((int64_t)1 << 27)) return fhx::fail(hp, FHX_ERR_UNSUPPORTED, "a bin table of more than 2^27 slots");
     if (index_base < -((int64_t)1 << 31) || index_base + n_slots > ((int64_t)1 << 31))
-        return hp->fail(FHX_ERR_UNSUPPORTED, "bin indices outside int32");
+        return fhx::fail(hp, FHX_ERR_UNSUPPORTED, "bin indices outside int32");
     TH_HIP(hp, hipSetDevice(hp->device));
     TH_HIP(hp, hipStreamSynchronize(hp->stream));
     drop_rows(hp);
-    hfree(hp->d_bins);
-    hfree(hp->d_totals);
+    fhx::dev_free(hp->d_bins);
+    fhx::dev_free(hp->d_totals);
     hp->have_bins = false;
     std::vector<int2> table((size_t)n_slots);
     for (int64_t s = 0; s < n_slots; ++s) table[(size_t)s] = make_int2(chr_id[s] < 0 ? -1 : chr_id[s], mid[s]);
     const size_t slots = (size_t)std::max<int64_t>(n_slots, 1);
-    TH_HIP(hp, hipMalloc((void**)&hp->d_bins, slots * sizeof(int2)));
-    TH_HIP(hp, hipMalloc((void**)&hp->d_totals, slots * sizeof(unsigned long long)));
+    TH_HIP(hp, fhx::dev_malloc(&hp->d_bins, slots * sizeof(int2)));
+    TH_HIP(hp, fhx::dev_malloc(&hp->d_totals, slots * sizeof(unsigned long long)));
     if (n_slots) TH_HIP(hp, hipMemcpyAsync(hp->d_bins, table.data(), (size_t)n_slots * sizeof(int2), hipMemcpyHostToDevice, hp->stream));
     TH_HIP(hp, hipMemsetAsync(hp->d_totals, 0, slots * sizeof(unsigned long long), hp->stream));
     TH_HIP(hp, hipStreamSynchronize(hp->stream));                                 // `table` goes out of scope
@@ -266,7 +260,7 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
     *why = FHX_HP_OK;
     *bad_line = 0;
     *bad_index = 0;
-    if (!hp->have_bins) return hp->fail(FHX_ERR_ARG, "fhx_hp_load_bins has not been called");
+    if (!hp->have_bins) return fhx::fail(hp, FHX_ERR_ARG, "fhx_hp_load_bins has not been called");
     TH_HIP(hp, hipSetDevice(hp->device));
     TH_HIP(hp, hipStreamSynchronize(hp->stream));
     drop_rows(hp);
@@ -280,20 +274,20 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
         return FHX_OK;
     }
     const int64_t n_blocks = (T + BLOCK_BYTES - 1) / BLOCK_BYTES;
-    if (n_blocks > 0x7fffffffll) return hp->fail(FHX_ERR_UNSUPPORTED, "a matrix file of more than 32 TB");
+    if (n_blocks > 0x7fffffffll) return fhx::fail(hp, FHX_ERR_UNSUPPORTED, "a matrix file of more than 32 TB");
     const bool timing = std::getenv("FHX_TIMING") != nullptr;
     double t_stage[3] = {0, 0, 0};
     fhx::StageClock clock{t_stage};
-    fhx::Scratch tmp;
+    fhx::DeviceScratch tmp;
     unsigned char* d_text = nullptr;
     unsigned int* d_block_nl = nullptr;
     unsigned long long *d_block_off = nullptr, *d_words = nullptr;
-    TH_HIP(hp, tmp.get(&d_text, (size_t)n_blocks * BLOCK_BYTES + 64));
-    TH_HIP(hp, tmp.get(&d_block_nl, (size_t)n_blocks));
-    TH_HIP(hp, tmp.get(&d_block_off, (size_t)n_blocks));
+    TH_HIP(hp, tmp.get_n(&d_text, (size_t)n_blocks * BLOCK_BYTES + 64));
+    TH_HIP(hp, tmp.get_n(&d_block_nl, (size_t)n_blocks));
+    TH_HIP(hp, tmp.get_n(&d_block_off, (size_t)n_blocks));
     // d_words: [0] newlines in all, [1] smallest (line << 8 | reason), [2] smallest (line << 32 | index) among the absent-index
     // lines, [3] the largest total, [4] bytes-not-taken flag of the scan
-    TH_HIP(hp, tmp.get(&d_words, 5));
+    TH_HIP(hp, tmp.get_n(&d_words, 5));
     fhx::TextBatch whole;                                                     // the whole file is resident: one batch
     if (const int rc = fhx::upload_batch(hp, src, "matrix", 0, T, d_text, &whole)) return rc;
     const unsigned long long init[5] = {0ull, NO_ERROR, NO_ERROR, 0ull, 0ull};
@@ -310,9 +304,9 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
     TH_HIP(hp, hipStreamSynchronize(hp->stream));
     clock.mark(1);
     const int64_t n = whole.lines(n_newlines);
-    if (n > 0x7fffffffll) return hp->fail(FHX_ERR_UNSUPPORTED, "a matrix of more than 2^31 - 1 lines");
+    if (n > 0x7fffffffll) return fhx::fail(hp, FHX_ERR_UNSUPPORTED, "a matrix of more than 2^31 - 1 lines");
     const int64_t stride = (n + 63) / 64 * 64;                                // every column starts on a 256-byte boundary
-    TH_HIP(hp, hipMalloc((void**)&hp->d_cols, (size_t)std::max<int64_t>(stride, 64) * 5 * sizeof(int32_t)));
+    TH_HIP(hp, fhx::dev_malloc(&hp->d_cols, (size_t)std::max<int64_t>(stride, 64) * 5 * sizeof(int32_t)));
     hp->col_stride = stride;
     int32_t* c = hp->d_cols;
     hipLaunchKernelGGL(hp_parse, dim3((unsigned)n_blocks), dim3(WG), 0, hp->stream, (const unsigned char*)d_text, T,
@@ -359,7 +353,7 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
 
 int fhx_hp_totals(fhx_hp* hp, int64_t* tcc) {
     if (!hp || (hp->n_slots > 0 && !tcc)) return FHX_ERR_ARG;
-    if (!hp->have_bins) return hp->fail(FHX_ERR_ARG, "fhx_hp_load_bins has not been called");
+    if (!hp->have_bins) return fhx::fail(hp, FHX_ERR_ARG, "fhx_hp_load_bins has not been called");
     TH_HIP(hp, hipSetDevice(hp->device));
     if (hp->n_slots) TH_HIP(hp, hipMemcpyAsync(tcc, hp->d_totals, (size_t)hp->n_slots * sizeof(int64_t), hipMemcpyDeviceToHost, hp->stream));
     TH_HIP(hp, hipStreamSynchronize(hp->stream));

@@ -290,11 +290,11 @@ struct fhx_ctx::TextIngest {
     bool fraction = false;                     // F_FRACTION: d_count holds the integer part of some count that had more
     std::vector<std::string> names;            // order of first appearance
     std::vector<int> name_slot;                // table slot of each
-    ~TextIngest() {
-        (void)hipFree(d_mid1);
-        (void)hipFree(d_mid2);
-        (void)hipFree(d_count);
-        (void)hipFree(d_slots);
+    ~TextIngest() {                            // the only place the four columns go, but for d_slots once the rows are mapped
+        dev_free(d_mid1);
+        dev_free(d_mid2);
+        dev_free(d_count);
+        dev_free(d_slots);
     }
 };
 
@@ -358,10 +358,10 @@ static int ingest_parse_resident(fhx_ctx* ctx, DeviceScratch& tmp, unsigned char
     if (flags & F_BYTES) return refuse("a NUL, a non-ASCII byte or a \\r that is not part of \\r\\n");
     const int64_t n = (int64_t)n_newlines + (last == '\n' ? 0 : 1);
     st->n_rows = n;
-    FHX_HIP(hipMalloc((void**)&st->d_mid1, (size_t)n * sizeof(int32_t)));
-    FHX_HIP(hipMalloc((void**)&st->d_mid2, (size_t)n * sizeof(int32_t)));
-    FHX_HIP(hipMalloc((void**)&st->d_count, (size_t)n * sizeof(int32_t)));
-    FHX_HIP(hipMalloc((void**)&st->d_slots, (size_t)n * sizeof(unsigned int)));
+    FHX_HIP(dev_malloc(&st->d_mid1, (size_t)n * sizeof(int32_t)));
+    FHX_HIP(dev_malloc(&st->d_mid2, (size_t)n * sizeof(int32_t)));
+    FHX_HIP(dev_malloc(&st->d_count, (size_t)n * sizeof(int32_t)));
+    FHX_HIP(dev_malloc(&st->d_slots, (size_t)n * sizeof(unsigned int)));
     hipLaunchKernelGGL(ti_parse, dim3((unsigned)n_blocks), dim3(WG), 0, ctx->stream, (const unsigned char*)d_text, T,
                        (const unsigned long long*)d_block_off, st->d_mid1, st->d_mid2, st->d_count, st->d_slots, d_t_hash, d_t_off, d_flags);
     std::vector<unsigned long long> t_hash(TABLE_SLOTS), t_off(TABLE_SLOTS);
@@ -678,8 +678,7 @@ static int ingest_contacts_commit_timed(fhx_ctx* ctx, const int32_t* ids, int32_
         hipLaunchKernelGGL(ti_map_rows, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, (const unsigned int*)st->d_slots,
                            (const int32_t*)d_slot_id, n, d_c1, d_c2);
     FHX_HIP(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(st->d_slots);
-    st->d_slots = nullptr;
+    dev_free(st->d_slots);
     *t_map = since();
     // an empty text holds no columns: any valid pointer stands in for them
     const int rc = fhx_load_pairs_device(ctx, d_c1, n ? st->d_mid1 : d_c1, d_c2, n ? st->d_mid2 : d_c1, n ? st->d_count : d_c1, n, nullptr);
@@ -852,19 +851,14 @@ int fhx_ingest_contacts_commit_shard(fhx_ctx* ctx, const int32_t* ids, const uin
     FHX_HIP(hipGetLastError());
     FHX_HIP(hipStreamSynchronize(ctx->stream));
     // the parsed text's columns are no longer needed: give them back before the engine allocates its row arrays
-    (void)hipFree(st->d_slots);
-    (void)hipFree(st->d_mid1);
-    (void)hipFree(st->d_mid2);
-    (void)hipFree(st->d_count);
-    st->d_slots = nullptr;
-    st->d_mid1 = st->d_mid2 = st->d_count = nullptr;
+    ingest_drop(ctx);
     int rc = fhx_load_pairs_device(ctx, o[0], o[1], o[2], o[3], o[4], (int64_t)total, nullptr);
     if (rc != FHX_OK) return rc;
     ctx->counts_integral = !fraction;
     // file positions: the -p >= 3 semantics (fhx_set_global_rows), the order of the significances file, the outlier line numbers
     dev_free(ctx->d_grow);
     const size_t gcap = std::max<size_t>(4, ((size_t)total + 3) / 4 * 4);
-    FHX_HIP(hipMalloc(&ctx->d_grow, gcap * sizeof(long long)));
+    FHX_HIP(dev_malloc(&ctx->d_grow, gcap * sizeof(long long)));
     FHX_HIP(hipMemsetAsync(ctx->d_grow, 0, gcap * sizeof(long long), ctx->stream));
     if (total) FHX_HIP(hipMemcpyAsync(ctx->d_grow, d_pos, (size_t)total * sizeof(long long), hipMemcpyDeviceToDevice, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
@@ -889,7 +883,7 @@ int fhx_set_global_rows_range(fhx_ctx* ctx, int64_t first) {
     dev_free(ctx->d_grow);
     const int64_t n = ctx->n_rows;
     const size_t cap = std::max<size_t>(4, ((size_t)n + 3) / 4 * 4);
-    FHX_HIP(hipMalloc(&ctx->d_grow, cap * sizeof(long long)));
+    FHX_HIP(dev_malloc(&ctx->d_grow, cap * sizeof(long long)));
     FHX_HIP(hipMemsetAsync(ctx->d_grow, 0, cap * sizeof(long long), ctx->stream));
     if (n) hipLaunchKernelGGL(ti_iota_i64, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, ctx->d_grow, n, (long long)first);
     FHX_HIP(hipGetLastError());

@@ -304,10 +304,7 @@ struct fhx_jc : fhx::TextHandle {
 namespace {
 
 void drop_all(fhx_jc* jc) {
-    for (int32_t*& p : jc->d_col) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
+    for (int32_t*& p : jc->d_col) fhx::dev_free(p);
     jc->col_capacity = jc->n_rows = jc->n_lines = 0;
     std::vector<char>().swap(jc->text);
 }
@@ -318,11 +315,11 @@ hipError_t grow_columns(fhx_jc* jc, int64_t keep, int64_t need) {
     const int64_t want = std::max<int64_t>(need, jc->col_capacity * 2);
     for (int32_t*& p : jc->d_col) {
         int32_t* bigger = nullptr;
-        hipError_t e = hipMalloc((void**)&bigger, (size_t)want * sizeof(int32_t));
+        hipError_t e = fhx::dev_malloc(&bigger, (size_t)want * sizeof(int32_t));
         if (e != hipSuccess) return e;
         if (keep > 0) e = hipMemcpyAsync(bigger, p, (size_t)keep * sizeof(int32_t), hipMemcpyDeviceToDevice, jc->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(jc->stream);
-        if (p) (void)hipFree(p);
+        fhx::dev_free(p);
         p = bigger;                               // a failed copy leaves the handle consistent: the caller drops everything
         if (e != hipSuccess) return e;
     }
@@ -375,7 +372,7 @@ int convert_file(fhx_jc* jc, const char* path, const char* name1, const char* na
     TH_HIP(jc, hipSetDevice(jc->device));
     TH_HIP(jc, hipStreamSynchronize(jc->stream));
     fhx::StageClock clock{jc->seconds};
-    fhx::Scratch tmp;
+    fhx::DeviceScratch tmp;
     fhx::TextBatches in;
     if (const int rc = in.open(jc, &tmp, &clock, path, "dump", "FHX_JC_BATCH_BYTES", (int64_t)1 << 31)) return rc;
     const int len1 = (int)std::strlen(name1), len2 = (int)std::strlen(name2);
@@ -385,10 +382,10 @@ int convert_file(fhx_jc* jc, const char* path, const char* name1, const char* na
     unsigned short* d_info = nullptr;
     int64_t info_capacity = 0, out_capacity = 0;
     Words* d_words = nullptr;
-    TH_HIP(jc, tmp.get(&d_block_bytes, (size_t)in.max_blocks));
-    TH_HIP(jc, tmp.get(&d_out_off, (size_t)in.max_blocks));
-    TH_HIP(jc, tmp.get(&d_names, (size_t)2 * NAME_SLOT));
-    TH_HIP(jc, tmp.get(&d_words, 1));
+    TH_HIP(jc, tmp.get_n(&d_block_bytes, (size_t)in.max_blocks));
+    TH_HIP(jc, tmp.get_n(&d_out_off, (size_t)in.max_blocks));
+    TH_HIP(jc, tmp.get_n(&d_names, (size_t)2 * NAME_SLOT));
+    TH_HIP(jc, tmp.get_n(&d_words, 1));
     unsigned char names[2 * NAME_SLOT];
     std::memset(names, 0, sizeof(names));
     std::memcpy(names, name1, (size_t)len1);
@@ -448,13 +445,13 @@ int convert_file(fhx_jc* jc, const char* path, const char* name1, const char* na
 
 extern "C" {
 
-int fhx_jc_create(int device, fhx_jc** out) { return fhx::text_handle_create(device, out); }
+int fhx_jc_create(int device, fhx_jc** out) { return fhx::handle_create(device, out); }
 
 void fhx_jc_destroy(fhx_jc* jc) {
     fhx::text_handle_destroy(jc, [&] { drop_all(jc); });
 }
 
-const char* fhx_jc_last_error(const fhx_jc* jc) { return jc ? jc->err.c_str() : "null context"; }
+const char* fhx_jc_last_error(const fhx_jc* jc) { return fhx::handle_last_error(jc); }
 
 int fhx_jc_reset(fhx_jc* jc) {
     if (!jc) return FHX_ERR_ARG;
@@ -471,9 +468,9 @@ int fhx_jc_convert_file(fhx_jc* jc, const char* path, const char* name1, const c
     *n_lines = 0;
     *why = FHX_JC_OK;
     *bad_line = 0;
-    if (!name_ok(name1) || !name_ok(name2)) return jc->fail(FHX_ERR_ARG, "a chromosome name must be 1 to 66 bytes of [A-Za-z0-9_.-]");
-    if (resolution < 0 || resolution > 0x7fffffffll) return jc->fail(FHX_ERR_ARG, "the resolution must be 1 to 2^31 - 1 (0: verbatim mode)");
-    if (keep_rows && resolution == 0) return jc->fail(FHX_ERR_ARG, "verbatim mode has no rows to keep");
+    if (!name_ok(name1) || !name_ok(name2)) return fhx::fail(jc, FHX_ERR_ARG, "a chromosome name must be 1 to 66 bytes of [A-Za-z0-9_.-]");
+    if (resolution < 0 || resolution > 0x7fffffffll) return fhx::fail(jc, FHX_ERR_ARG, "the resolution must be 1 to 2^31 - 1 (0: verbatim mode)");
+    if (keep_rows && resolution == 0) return fhx::fail(jc, FHX_ERR_ARG, "verbatim mode has no rows to keep");
     const int rc = convert_file(jc, path, name1, name2, resolution, id1, id2, keep_text, keep_rows, n_lines, why, bad_line);
     if (rc != FHX_OK) drop_all(jc);                                           // the one exit of a failed conversion, whatever failed
     return rc;

@@ -570,7 +570,7 @@ int build_slot_tables_nonfixed(fhx_ctx* ctx) {
         }
     }
     dev_free(ctx->d_slot_bias);
-    FHX_HIP(hipMalloc(&ctx->d_slot_bias, bias.size() * sizeof(double)));
+    FHX_HIP(dev_malloc(&ctx->d_slot_bias, bias.size() * sizeof(double)));
     FHX_HIP(hipMemcpyAsync(ctx->d_slot_bias, bias.data(), bias.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
     ctx->tables_dirty = false;
@@ -606,8 +606,8 @@ int build_slot_tables(fhx_ctx* ctx) {
     }
     dev_free(ctx->d_slot_bias);
     dev_free(ctx->d_slot_chr);
-    FHX_HIP(hipMalloc(&ctx->d_slot_bias, bias.size() * sizeof(double)));
-    FHX_HIP(hipMalloc(&ctx->d_slot_chr, slot_chr.size() * sizeof(int16_t)));
+    FHX_HIP(dev_malloc(&ctx->d_slot_bias, bias.size() * sizeof(double)));
+    FHX_HIP(dev_malloc(&ctx->d_slot_chr, slot_chr.size() * sizeof(int16_t)));
     FHX_HIP(hipMemcpyAsync(ctx->d_slot_bias, bias.data(), bias.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     FHX_HIP(hipMemcpyAsync(ctx->d_slot_chr, slot_chr.data(), slot_chr.size() * sizeof(int16_t), hipMemcpyHostToDevice,
                            ctx->stream));
@@ -692,8 +692,8 @@ int ingest_device_rows_nonfixed(fhx_ctx* ctx, const int32_t* c1, const int32_t* 
         dev_free(ctx->d_slot_mid);
         dev_free(ctx->d_slot_chr);
         const size_t ns = (size_t)std::max<int64_t>(n_slots, 1);
-        FHX_HIP(hipMalloc(&ctx->d_slot_mid, ns * sizeof(int32_t)));
-        FHX_HIP(hipMalloc(&ctx->d_slot_chr, ns * sizeof(int16_t)));
+        FHX_HIP(dev_malloc(&ctx->d_slot_mid, ns * sizeof(int32_t)));
+        FHX_HIP(dev_malloc(&ctx->d_slot_chr, ns * sizeof(int16_t)));
         hipLaunchKernelGGL(nf_slot_tables, dim3(grid_for(n_slots, 256)), dim3(256), 0, ctx->stream,
                            (const unsigned long long*)slot_key, n_slots, ctx->d_slot_mid, ctx->d_slot_chr);
         ctx->h_slot_keys.assign((size_t)n_slots, 0ull);
@@ -703,8 +703,8 @@ int ingest_device_rows_nonfixed(fhx_ctx* ctx, const int32_t* c1, const int32_t* 
         dev_free(ctx->d_seg_ids);
         dev_free(ctx->d_seg_tiles);
         const size_t cap = std::max<size_t>(4, (size_t)n);
-        FHX_HIP(hipMalloc(&ctx->d_seg_ids, cap * sizeof(unsigned int)));
-        FHX_HIP(hipMalloc(&ctx->d_seg_tiles, (cap / SEG_TILE + 2) * sizeof(unsigned int)));
+        FHX_HIP(dev_malloc(&ctx->d_seg_ids, cap * sizeof(unsigned int)));
+        FHX_HIP(dev_malloc(&ctx->d_seg_tiles, (cap / SEG_TILE + 2) * sizeof(unsigned int)));
         FHX_HIP(hipGetLastError());
         FHX_HIP(hipStreamSynchronize(ctx->stream));
         ctx->h_outlier_dists.clear();
@@ -788,7 +788,7 @@ int ingest_device_rows(fhx_ctx* ctx, const int32_t* c1, const int32_t* m1, const
     ctx->n_slots = base;
     ctx->n_dist = n_dist;
     dev_free(ctx->d_grid);
-    FHX_HIP(hipMalloc(&ctx->d_grid, std::max<size_t>(1, ctx->grid.size()) * sizeof(ChrGrid)));
+    FHX_HIP(dev_malloc(&ctx->d_grid, std::max<size_t>(1, ctx->grid.size()) * sizeof(ChrGrid)));
     FHX_HIP(hipMemcpyAsync(ctx->d_grid, ctx->grid.data(), ctx->grid.size() * sizeof(ChrGrid), hipMemcpyHostToDevice,
                            ctx->stream));
     {
@@ -820,14 +820,14 @@ int alloc_row_arrays(fhx_ctx* ctx, int64_t n, int64_t n_dist) {
     dev_free(ctx->d_p);
     dev_free(ctx->d_q);
     dev_free(ctx->d_grow);
-    FHX_HIP(hipMalloc(&ctx->d_loc1, cap * sizeof(int32_t)));
-    FHX_HIP(hipMalloc(&ctx->d_loc2, cap * sizeof(int32_t)));
-    FHX_HIP(hipMalloc(&ctx->d_count, cap * sizeof(int32_t)));
-    if (!ctx->nonfixed) FHX_HIP(hipMalloc(&ctx->d_k1key, cap * sizeof(uint32_t)));      // K1's key column: written by k0_slots alone
-    FHX_HIP(hipMalloc(&ctx->d_skip, cap));
-    FHX_HIP(hipMalloc(&ctx->d_outlier, cap));
-    FHX_HIP(hipMalloc(&ctx->d_p, cap * sizeof(double)));
-    FHX_HIP(hipMalloc(&ctx->d_q, cap * sizeof(double)));
+    FHX_HIP(dev_malloc(&ctx->d_loc1, cap * sizeof(int32_t)));
+    FHX_HIP(dev_malloc(&ctx->d_loc2, cap * sizeof(int32_t)));
+    FHX_HIP(dev_malloc(&ctx->d_count, cap * sizeof(int32_t)));
+    if (!ctx->nonfixed) FHX_HIP(dev_malloc(&ctx->d_k1key, cap * sizeof(uint32_t)));      // K1's key column: written by k0_slots alone
+    FHX_HIP(dev_malloc(&ctx->d_skip, cap));
+    FHX_HIP(dev_malloc(&ctx->d_outlier, cap));
+    FHX_HIP(dev_malloc(&ctx->d_p, cap * sizeof(double)));
+    FHX_HIP(dev_malloc(&ctx->d_q, cap * sizeof(double)));
     ctx->q_prefilled = false;
     FHX_HIP(hipMemsetAsync(ctx->d_skip, 0, cap, ctx->stream));
     FHX_HIP(hipMemsetAsync(ctx->d_outlier, 0, cap, ctx->stream));
@@ -836,11 +836,11 @@ int alloc_row_arrays(fhx_ctx* ctx, int64_t n, int64_t n_dist) {
     dev_free(ctx->d_hist_np);
     dev_free(ctx->d_out_hist);
     const size_t hist_len = ctx->nonfixed ? cap : (size_t)n_dist;       // -r 0: at most one distinct distance per row
-    FHX_HIP(hipMalloc(&ctx->d_hist_cc, hist_len * sizeof(unsigned long long)));
-    FHX_HIP(hipMalloc(&ctx->d_hist_np, hist_len * sizeof(unsigned long long)));
-    FHX_HIP(hipMalloc(&ctx->d_out_hist, hist_len * sizeof(unsigned long long)));
+    FHX_HIP(dev_malloc(&ctx->d_hist_cc, hist_len * sizeof(unsigned long long)));
+    FHX_HIP(dev_malloc(&ctx->d_hist_np, hist_len * sizeof(unsigned long long)));
+    FHX_HIP(dev_malloc(&ctx->d_out_hist, hist_len * sizeof(unsigned long long)));
     FHX_HIP(hipMemsetAsync(ctx->d_out_hist, 0, hist_len * sizeof(unsigned long long), ctx->stream));
-    if (!ctx->d_sums) FHX_HIP(hipMalloc(&ctx->d_sums, sizeof(K1Sums)));
+    if (!ctx->d_sums) FHX_HIP(dev_malloc(&ctx->d_sums, sizeof(K1Sums)));
     // One workspace, two views that are never live together (K2 and K3 run back to back on one stream):
     //   K2: queue[0] (16 B/row) | queue[1] (16 B/row) | the bucketed 300-iteration queue (16 B/row + bucket padding)
     //   K3: keys[0], keys[1] (8 B/row each)            | vals[0], vals[1] (4 B/row each)
@@ -848,7 +848,7 @@ int alloc_row_arrays(fhx_ctx* ctx, int64_t n, int64_t n_dist) {
     dev_free(ctx->d_work);
     const size_t qcap = std::max<size_t>(cap, (size_t)k2_classify_grid((int64_t)cap) * (size_t)k2_shard_capacity((int64_t)cap));   // sharded queues: k2_classify
     const size_t work_bytes = qcap * 32 + std::max(qcap, cap + (size_t)K2H_BUCKETS * 64 * K2H_MAX_ROWS) * sizeof(QEntry);   // queue 0 | queue 1 | sorted heavy queue / closed-form queue
-    FHX_HIP(hipMalloc(&ctx->d_work, work_bytes));
+    FHX_HIP(dev_malloc(&ctx->d_work, work_bytes));
     ctx->work_bytes = work_bytes;
     ctx->queue_cap = (int64_t)qcap;
     ctx->d_queue[0] = reinterpret_cast<QEntry*>(ctx->d_work);
@@ -858,13 +858,13 @@ int alloc_row_arrays(fhx_ctx* ctx, int64_t n, int64_t n_dist) {
     ctx->d_keys[1] = reinterpret_cast<unsigned long long*>(ctx->d_work + cap * 8);
     ctx->d_vals[0] = reinterpret_cast<unsigned int*>(ctx->d_work + cap * 16);
     ctx->d_vals[1] = reinterpret_cast<unsigned int*>(ctx->d_work + cap * 20);
-    if (!ctx->d_block_hist) FHX_HIP(hipMalloc(&ctx->d_block_hist, (size_t)RADIX * SORT_BLOCKS * sizeof(unsigned int)));
-    if (!ctx->d_digit_total) FHX_HIP(hipMalloc(&ctx->d_digit_total, RADIX * sizeof(unsigned int)));
-    if (!ctx->d_top_hist) FHX_HIP(hipMalloc(&ctx->d_top_hist, TOP_BINS * sizeof(unsigned long long)));
-    if (!ctx->d_cf_tab) FHX_HIP(hipMalloc(&ctx->d_cf_tab, (size_t)K2H_GENERIC * dev::kCfIters * sizeof(dev::CfRow)));
-    if (!ctx->d_k2h_off) FHX_HIP(hipMalloc(&ctx->d_k2h_off, (K2H_BUCKETS + 1) * sizeof(unsigned int)));
+    if (!ctx->d_block_hist) FHX_HIP(dev_malloc(&ctx->d_block_hist, (size_t)RADIX * SORT_BLOCKS * sizeof(unsigned int)));
+    if (!ctx->d_digit_total) FHX_HIP(dev_malloc(&ctx->d_digit_total, RADIX * sizeof(unsigned int)));
+    if (!ctx->d_top_hist) FHX_HIP(dev_malloc(&ctx->d_top_hist, TOP_BINS * sizeof(unsigned long long)));
+    if (!ctx->d_cf_tab) FHX_HIP(dev_malloc(&ctx->d_cf_tab, (size_t)K2H_GENERIC * dev::kCfIters * sizeof(dev::CfRow)));
+    if (!ctx->d_k2h_off) FHX_HIP(dev_malloc(&ctx->d_k2h_off, (K2H_BUCKETS + 1) * sizeof(unsigned int)));
     dev_free(ctx->d_tile_max);
-    FHX_HIP(hipMalloc(&ctx->d_tile_max, ((size_t)n / BH_TILE + 2) * sizeof(double)));
+    FHX_HIP(dev_malloc(&ctx->d_tile_max, ((size_t)n / BH_TILE + 2) * sizeof(double)));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
     ctx->n_rows = n;
     ctx->pass_no = 0;

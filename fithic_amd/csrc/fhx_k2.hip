@@ -1125,7 +1125,7 @@ static int k2_table_rows(fhx_ctx* ctx, const K2Plan& plan, K2Memo* M, K2Params* 
     if (need > ctx->memo_bytes) {
         dev_free(ctx->d_memo);
         ctx->memo_bytes = 0;
-        FHX_HIP(hipMalloc(&ctx->d_memo, need));
+        FHX_HIP(dev_malloc(&ctx->d_memo, need));
         ctx->memo_bytes = need;
     }
     M->loc1 = reinterpret_cast<int32_t*>(ctx->d_memo);
@@ -1147,7 +1147,7 @@ static int k2_table_rows(fhx_ctx* ctx, const K2Plan& plan, K2Memo* M, K2Params* 
 // two entry buffers of n_rows each: [swapped CF up | power series down] and [incbcf up | incbd down]
 static int k2_queue_layout(fhx_ctx* ctx, const K2Plan& plan, bool prezeroed, K2Queues* Q) {
     if ((int64_t)plan.n_shards * plan.cap_s > ctx->queue_cap) return fail(ctx, FHX_ERR_HIP, "internal: queue workspace smaller than the shard layout");
-    if (!ctx->d_k2_counts) FHX_HIP(hipMalloc(&ctx->d_k2_counts, (size_t)(K2_QUEUES + 1) * K2_MAX_SHARDS * sizeof(unsigned long long)));
+    if (!ctx->d_k2_counts) FHX_HIP(dev_malloc(&ctx->d_k2_counts, (size_t)(K2_QUEUES + 1) * K2_MAX_SHARDS * sizeof(unsigned long long)));
     Q->count = ctx->d_k2_counts;
     static_assert((K2H_BLOCKS & (K2H_BLOCKS - 1)) == 0, "shard -> column by masking");
     Q->heavy_hist = plan.legacy_heavy ? nullptr : ctx->d_block_hist;   // k2_classify counts the heavy class's buckets while it queues
@@ -1231,7 +1231,7 @@ static int launch_k2(fhx_ctx* ctx, const K2Plan& plan, const K2Params& P, const 
 
 // K2 collects K3's key histogram while it stores p: the context's table, zeroed unless fhx_pass_stats already did
 static int k2_fused_hist(fhx_ctx* ctx, bool prezeroed, K2Params* P) {
-    if (!ctx->d_k2_hist) FHX_HIP(hipMalloc(&ctx->d_k2_hist, TOP_BINS * sizeof(unsigned long long)));
+    if (!ctx->d_k2_hist) FHX_HIP(dev_malloc(&ctx->d_k2_hist, TOP_BINS * sizeof(unsigned long long)));
     if (!prezeroed) FHX_HIP(hipMemsetAsync(ctx->d_k2_hist, 0, TOP_BINS * sizeof(unsigned long long), ctx->stream));
     P->top_hist = ctx->d_k2_hist;
     return FHX_OK;
@@ -1321,11 +1321,12 @@ int fhx_bdtrc_array(fhx_ctx* ctx, double n_total, const int32_t* count, const do
     build_lbeta_table(n_total, mc, lb, ib);
     double *d_lb = nullptr, *d_ib = nullptr, *d_prior = nullptr, *d_out = nullptr;
     int32_t* d_count = nullptr;
-    FHX_HIP(hipMalloc(&d_lb, lb.size() * sizeof(double)));
-    FHX_HIP(hipMalloc(&d_ib, ib.size() * sizeof(double)));
-    FHX_HIP(hipMalloc(&d_prior, (size_t)n * sizeof(double)));
-    FHX_HIP(hipMalloc(&d_out, (size_t)n * sizeof(double)));
-    FHX_HIP(hipMalloc(&d_count, (size_t)n * sizeof(int32_t)));
+    DeviceScratch G;
+    FHX_HIP(G.get(&d_lb, lb.size() * sizeof(double)));
+    FHX_HIP(G.get(&d_ib, ib.size() * sizeof(double)));
+    FHX_HIP(G.get(&d_prior, (size_t)n * sizeof(double)));
+    FHX_HIP(G.get(&d_out, (size_t)n * sizeof(double)));
+    FHX_HIP(G.get(&d_count, (size_t)n * sizeof(int32_t)));
     FHX_HIP(hipMemcpyAsync(d_lb, lb.data(), lb.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     FHX_HIP(hipMemcpyAsync(d_ib, ib.data(), ib.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     FHX_HIP(hipMemcpyAsync(d_prior, prior, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -1335,11 +1336,6 @@ int fhx_bdtrc_array(fhx_ctx* ctx, double n_total, const int32_t* count, const do
     FHX_HIP(hipGetLastError());
     FHX_HIP(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
-    dev_free(d_lb);
-    dev_free(d_ib);
-    dev_free(d_prior);
-    dev_free(d_out);
-    dev_free(d_count);
     return FHX_OK;
 }
 
@@ -1482,7 +1478,8 @@ int fhx_debug_contfrac(fhx_ctx* ctx, int kind, int lazy, const double* a, const 
     double* d[4] = {nullptr, nullptr, nullptr, nullptr};
     const double* h[3] = {a, b, x};
     const size_t bytes = (size_t)n * sizeof(double);
-    for (int k = 0; k < 4; ++k) FHX_HIP(hipMalloc(&d[k], bytes));
+    DeviceScratch G;
+    for (int k = 0; k < 4; ++k) FHX_HIP(G.get(&d[k], bytes));
     for (int k = 0; k < 3; ++k) FHX_HIP(hipMemcpyAsync(d[k], h[k], bytes, hipMemcpyHostToDevice, ctx->stream));
     const dim3 g(grid_for(n, 256)), t(256);
     if (kind == 0 && !lazy) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_debug_contfrac<0, 0>), g, t, 0, ctx->stream, d[0], d[1], d[2], n, d[3]);
@@ -1492,7 +1489,6 @@ int fhx_debug_contfrac(fhx_ctx* ctx, int kind, int lazy, const double* a, const 
     FHX_HIP(hipGetLastError());
     FHX_HIP(hipMemcpyAsync(out, d[3], bytes, hipMemcpyDeviceToHost, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 4; ++k) dev_free(d[k]);
     return FHX_OK;
 }
 
@@ -1529,14 +1525,14 @@ int fhx_debug_lean_div(fhx_ctx* ctx, const double* n, const double* d, int64_t l
     FHX_HIP(hipSetDevice(ctx->device));
     double* dv[3] = {nullptr, nullptr, nullptr};
     const size_t bytes = (size_t)len * sizeof(double);
-    for (int k = 0; k < 3; ++k) FHX_HIP(hipMalloc(&dv[k], bytes));
+    DeviceScratch G;
+    for (int k = 0; k < 3; ++k) FHX_HIP(G.get(&dv[k], bytes));
     FHX_HIP(hipMemcpyAsync(dv[0], n, bytes, hipMemcpyHostToDevice, ctx->stream));
     FHX_HIP(hipMemcpyAsync(dv[1], d, bytes, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_debug_lean_div, dim3(grid_for(len, 256)), dim3(256), 0, ctx->stream, dv[0], dv[1], len, dv[2]);
     FHX_HIP(hipGetLastError());
     FHX_HIP(hipMemcpyAsync(out, dv[2], bytes, hipMemcpyDeviceToHost, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 3; ++k) dev_free(dv[k]);
     return FHX_OK;
 }
 
@@ -1549,8 +1545,9 @@ int fhx_debug_table_div(fhx_ctx* ctx, int kind, const double* num, int64_t m, do
     FHX_HIP(hipSetDevice(ctx->device));
     double *d_num = nullptr, *d_out = nullptr;
     const size_t out_bytes = (size_t)(len - 1) * (size_t)m * sizeof(double);
-    FHX_HIP(hipMalloc(&d_num, (size_t)m * sizeof(double)));
-    FHX_HIP(hipMalloc(&d_out, out_bytes));
+    DeviceScratch G;
+    FHX_HIP(G.get(&d_num, (size_t)m * sizeof(double)));
+    FHX_HIP(G.get(&d_out, out_bytes));
     FHX_HIP(hipMemcpyAsync(d_num, num, (size_t)m * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (kind == 0)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_debug_table_div<true, dev::kCfTabJ>), dim3(len - 1), dim3(256), 0, ctx->stream, d_num, m, d_out);
@@ -1559,8 +1556,6 @@ int fhx_debug_table_div(fhx_ctx* ctx, int kind, const double* num, int64_t m, do
     FHX_HIP(hipGetLastError());
     FHX_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
-    dev_free(d_num);
-    dev_free(d_out);
     return FHX_OK;
 }
 

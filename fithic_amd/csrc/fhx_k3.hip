@@ -1539,9 +1539,9 @@ static int rank_and_adjust(fhx_ctx* ctx, K3Pass& pass) {
 }
 
 int fhx::ensure_sort_scratch(fhx_ctx* ctx) {
-    if (!ctx->d_block_hist) FHX_HIP(hipMalloc(&ctx->d_block_hist, (size_t)RADIX * SORT_BLOCKS * sizeof(unsigned int)));
-    if (!ctx->d_digit_total) FHX_HIP(hipMalloc(&ctx->d_digit_total, RADIX * sizeof(unsigned int)));
-    if (!ctx->d_top_hist) FHX_HIP(hipMalloc(&ctx->d_top_hist, TOP_BINS * sizeof(unsigned long long)));
+    if (!ctx->d_block_hist) FHX_HIP(dev_malloc(&ctx->d_block_hist, (size_t)RADIX * SORT_BLOCKS * sizeof(unsigned int)));
+    if (!ctx->d_digit_total) FHX_HIP(dev_malloc(&ctx->d_digit_total, RADIX * sizeof(unsigned int)));
+    if (!ctx->d_top_hist) FHX_HIP(dev_malloc(&ctx->d_top_hist, TOP_BINS * sizeof(unsigned long long)));
     return FHX_OK;
 }
 
@@ -1751,8 +1751,9 @@ int fhx_bh_apply_sorted(fhx_ctx* ctx, const void* d_sorted_keys, int64_t n, int6
         return FHX_OK;
     }
     const int tiles = (int)((n + BH_TILE - 1) / BH_TILE);
+    DeviceScratch G;
     double* tile_max = nullptr;
-    FHX_HIP(hipMalloc(&tile_max, ((size_t)tiles + 1) * sizeof(double)));
+    FHX_HIP(G.get(&tile_max, ((size_t)tiles + 1) * sizeof(double)));
     const unsigned long long* keys = (const unsigned long long*)d_sorted_keys;
     launch_bh_tile_max(ctx, tiles, keys, nullptr, n, n_total_tests, (double)global_rank0, tile_max);
     launch_bh_scan_tiles(ctx, tile_max, nullptr, n, carry_in, tile_max + tiles, -1, nullptr);
@@ -1762,7 +1763,6 @@ int fhx_bh_apply_sorted(fhx_ctx* ctx, const void* d_sorted_keys, int64_t n, int6
     double total = 0.0;
     FHX_HIP(hipMemcpyAsync(&total, tile_max + tiles, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     FHX_HIP(hipStreamSynchronize(ctx->stream));
-    dev_free(tile_max);
     if (block_max_out) *block_max_out = total;
     return FHX_OK;
 }

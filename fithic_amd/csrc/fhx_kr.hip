@@ -519,10 +519,7 @@ __global__ __launch_bounds__(THREADS) void kr_compact(int64_t n_old, const int64
 // ===================================================================================================================
 // host side
 // ===================================================================================================================
-struct fhx_kr {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    std::string err;
+struct fhx_kr : fhx::Handle {
     fhx_ctx* sorter = nullptr;
     // loci
     std::vector<unsigned long long> locus_keys;      // sorted distinct (chr<<32 | mid)
@@ -546,10 +543,9 @@ struct fhx_kr {
     std::vector<int64_t> removed;
     std::vector<double> row_sums;
     // iteration state
-    double* d_vec = nullptr;                          // 10 vectors of n doubles
-    int64_t vec_cap = 0;
-    double* d_part = nullptr;                         // 3 partial arrays
-    int64_t part_cap = 0;
+    fhx::GrowBuf<double> vec, part;                   // 10 vectors of vec_cap() doubles, 3 partial arrays of part_cap(): exact sizes
+    int64_t vec_cap() const { return (int64_t)vec.cap / 10; }
+    int64_t part_cap() const { return (int64_t)part.cap / 3; }
     double* d_scalars = nullptr;                      // 8 doubles
     unsigned long long* d_counter = nullptr;
     std::vector<double> x_host;
@@ -561,23 +557,6 @@ struct fhx_kr {
 };
 
 namespace {
-
-int kfail(fhx_kr* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
-}
-
-#define KR_HIP(call)                                                                                      \
-    do {                                                                                                  \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess) return kfail(kr, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <typename T>
-void kfree(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
 
 inline int tiles_of(int64_t n) { return (int)std::max<int64_t>(1, (n + krd::TILE - 1) / krd::TILE); }
 
@@ -603,19 +582,10 @@ void launch_spmv(fhx_kr* kr, int64_t n, const int64_t* ptr, const int32_t* col, 
 
 int ensure_vectors(fhx_kr* kr, int64_t n) {
     const int64_t cap = std::max<int64_t>(n, 1);
-    if (cap > kr->vec_cap) {
-        kfree(kr->d_vec);
-        KR_HIP(hipMalloc(&kr->d_vec, (size_t)cap * 10 * sizeof(double)));
-        kr->vec_cap = cap;
-    }
-    const int64_t t = tiles_of(cap);
-    if (t > kr->part_cap) {
-        kfree(kr->d_part);
-        KR_HIP(hipMalloc(&kr->d_part, (size_t)t * 3 * sizeof(double)));
-        kr->part_cap = t;
-    }
-    if (!kr->d_scalars) KR_HIP(hipMalloc(&kr->d_scalars, 8 * sizeof(double)));
-    if (!kr->d_counter) KR_HIP(hipMalloc(&kr->d_counter, 4 * sizeof(unsigned long long)));
+    KR_HIP(kr->vec.need((size_t)cap * 10, /*exact=*/true));
+    KR_HIP(kr->part.need((size_t)tiles_of(cap) * 3, /*exact=*/true));
+    if (!kr->d_scalars) KR_HIP(dev_malloc(&kr->d_scalars, 8 * sizeof(double)));
+    if (!kr->d_counter) KR_HIP(dev_malloc(&kr->d_counter, 4 * sizeof(unsigned long long)));
     return FHX_OK;
 }
 
@@ -623,7 +593,7 @@ int ensure_vectors(fhx_kr* kr, int64_t n) {
 int finish_scalars(fhx_kr* kr, int64_t n, int n_arrays, const int* ops, double* out) {
     const int64_t t = tiles_of(n);
     for (int a = 0; a < n_arrays; ++a) {
-        const double* part = kr->d_part + (int64_t)a * kr->part_cap;
+        const double* part = kr->part.p + (int64_t)a * kr->part_cap();
         if (ops[a] == 0) hipLaunchKernelGGL(krd::kr_finish<0>, dim3(1), dim3(krd::THREADS), 0, kr->stream, part, t, kr->d_scalars + a);
         else if (ops[a] == 1) hipLaunchKernelGGL(krd::kr_finish<1>, dim3(1), dim3(krd::THREADS), 0, kr->stream, part, t, kr->d_scalars + a);
         else hipLaunchKernelGGL(krd::kr_finish<2>, dim3(1), dim3(krd::THREADS), 0, kr->stream, part, t, kr->d_scalars + a);
@@ -635,15 +605,15 @@ int finish_scalars(fhx_kr* kr, int64_t n, int n_arrays, const int* ops, double* 
 }
 
 void free_matrix(fhx_kr* kr) {
-    kfree(kr->d_indptr);
-    kfree(kr->d_col);
-    kfree(kr->d_val);
-    kfree(kr->d_rptr);
-    kfree(kr->d_rcol);
-    kfree(kr->d_rval);
-    kfree(kr->d_val32);
-    kfree(kr->d_pack);
-    kfree(kr->d_rowbase);
+    dev_free(kr->d_indptr);
+    dev_free(kr->d_col);
+    dev_free(kr->d_val);
+    dev_free(kr->d_rptr);
+    dev_free(kr->d_rcol);
+    dev_free(kr->d_rval);
+    dev_free(kr->d_val32);
+    dev_free(kr->d_pack);
+    dev_free(kr->d_rowbase);
     kr->reduced = false;
     kr->balanced = false;
     kr->n = kr->nnz = kr->nnz_full = 0;
@@ -684,54 +654,40 @@ double numpy_sum(const double* a, int64_t n) {
     return acc;
 }
 
-// The 2m cell keys of m rows (row i: keys[i] and keys[m + i]; freed here) -> the CSR of the full matrix: stable sort, run heads,
-// one cell per run with the values z[row] of the run added in row order, row pointers.  kr->d_indptr is allocated by the caller.
+// The 2m cell keys of m rows (row i: keys[i] and keys[m + i]; a block of the caller's `from`, dropped here once they are
+// sorted) -> the CSR of the full matrix: stable sort, run heads, one cell per run with the values z[row] of the run added in row
+// order, row pointers.  kr->d_indptr is allocated by the caller.
 template <typename ZT>
-int assemble_cells(fhx_kr* kr, unsigned long long*& keys, const ZT* z, int64_t m) {
+int assemble_cells(fhx_kr* kr, DeviceScratch& from, unsigned long long* keys, const ZT* z, int64_t m) {
     const int64_t n = kr->n_full, N = 2 * m;
+    DeviceScratch tmp;
     unsigned long long *skeys = nullptr, *tile_off = nullptr, *cell_key = nullptr;
     unsigned int *perm = nullptr, *tile_cnt = nullptr;
-    auto cleanup = [&]() {
-        kfree(keys); kfree(skeys); kfree(tile_off); kfree(cell_key); kfree(perm); kfree(tile_cnt);
-    };
-#define KR_TRY(call)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (call);                                                                              \
-        if (e_ != hipSuccess) {                                                                              \
-            cleanup();                                                                                       \
-            return kfail(kr, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));                \
-        }                                                                                                    \
-    } while (0)
     // stable sort of the 2m cell keys
-    KR_TRY(hipMalloc(&skeys, (size_t)N * 8));
-    KR_TRY(hipMalloc(&perm, (size_t)N * 4));
+    KR_HIP(tmp.get(&skeys, (size_t)N * 8));
+    KR_HIP(tmp.get(&perm, (size_t)N * 4));
     const int rc = fhx_sort_u64(kr->sorter, keys, N, skeys, perm);
-    if (rc != FHX_OK) {
-        cleanup();
-        return kfail(kr, rc, std::string("sort: ") + fhx_last_error(kr->sorter));
-    }
-    kfree(keys);
+    if (rc != FHX_OK) return fail(kr, rc, std::string("sort: ") + fhx_last_error(kr->sorter));
+    from.drop(keys);
     // run heads -> cells
     const int64_t tiles = (N + krd::TILE - 1) / krd::TILE;
-    KR_TRY(hipMalloc(&tile_cnt, (size_t)tiles * 4));
-    KR_TRY(hipMalloc(&tile_off, (size_t)tiles * 8));
+    KR_HIP(tmp.get(&tile_cnt, (size_t)tiles * 4));
+    KR_HIP(tmp.get(&tile_off, (size_t)tiles * 8));
     hipLaunchKernelGGL(fhxscan::count_heads, dim3((unsigned)tiles), dim3(krd::THREADS), 0, kr->stream, skeys, N, tile_cnt);
     hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(krd::THREADS), 0, kr->stream, tile_cnt, tiles, tile_off, kr->d_counter + 1);
-    KR_TRY(hipGetLastError());
+    KR_HIP(hipGetLastError());
     unsigned long long nnz = 0;
-    KR_TRY(hipMemcpyAsync(&nnz, kr->d_counter + 1, 8, hipMemcpyDeviceToHost, kr->stream));
-    KR_TRY(hipStreamSynchronize(kr->stream));
-    KR_TRY(hipMalloc(&cell_key, (size_t)nnz * 8));
-    KR_TRY(hipMalloc(&kr->d_col, (size_t)(nnz + krd::KR_PAD) * 4));
-    KR_TRY(hipMalloc(&kr->d_val, (size_t)(nnz + krd::KR_PAD) * 8));
+    KR_HIP(hipMemcpyAsync(&nnz, kr->d_counter + 1, 8, hipMemcpyDeviceToHost, kr->stream));
+    KR_HIP(hipStreamSynchronize(kr->stream));
+    KR_HIP(tmp.get(&cell_key, (size_t)nnz * 8));
+    KR_HIP(dev_malloc(&kr->d_col, (size_t)(nnz + krd::KR_PAD) * 4));
+    KR_HIP(dev_malloc(&kr->d_val, (size_t)(nnz + krd::KR_PAD) * 8));
     hipLaunchKernelGGL(krd::kr_emit_cells<ZT>, dim3((unsigned)tiles), dim3(krd::THREADS), 0, kr->stream, skeys, perm, z, m, N, n, tile_off,
                        cell_key, kr->d_col, kr->d_val);
     hipLaunchKernelGGL(krd::kr_indptr, dim3((unsigned)std::min<int64_t>((n + 256) / 256, 4096)), dim3(256), 0, kr->stream, cell_key,
                        (int64_t)nnz, n, kr->d_indptr);
-    KR_TRY(hipGetLastError());
-    KR_TRY(hipStreamSynchronize(kr->stream));
-    cleanup();
-#undef KR_TRY
+    KR_HIP(hipGetLastError());
+    KR_HIP(hipStreamSynchronize(kr->stream));
     kr->nnz_full = kr->nnz = (int64_t)nnz;
     kr->n = n;
     return FHX_OK;
@@ -742,42 +698,35 @@ int assemble_cells(fhx_kr* kr, unsigned long long*& keys, const ZT* z, int64_t m
 extern "C" {
 
 int fhx_kr_create(int device, fhx_kr** out) {
-    if (!out) return FHX_ERR_ARG;
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return FHX_ERR_NO_DEVICE;
-    fhx_kr* kr = new fhx_kr();
-    kr->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&kr->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&kr->ev0) != hipSuccess || hipEventCreate(&kr->ev1) != hipSuccess || fhx_create(device, &kr->sorter) != FHX_OK) {
-        delete kr;
+    const int rc = handle_create(device, out);
+    if (rc != FHX_OK) return rc;
+    fhx_kr* kr = *out;
+    if (hipEventCreate(&kr->ev0) != hipSuccess || hipEventCreate(&kr->ev1) != hipSuccess || fhx_create(device, &kr->sorter) != FHX_OK) {
+        fhx_kr_destroy(kr);
+        *out = nullptr;
         return FHX_ERR_HIP;
     }
-    *out = kr;
     return FHX_OK;
 }
 
 void fhx_kr_destroy(fhx_kr* kr) {
-    if (!kr) return;
-    (void)hipSetDevice(kr->device);
-    if (kr->stream) (void)hipStreamSynchronize(kr->stream);
-    free_matrix(kr);
-    kfree(kr->d_vec);
-    kfree(kr->d_part);
-    kfree(kr->d_scalars);
-    kfree(kr->d_counter);
-    if (kr->ev0) (void)hipEventDestroy(kr->ev0);
-    if (kr->ev1) (void)hipEventDestroy(kr->ev1);
-    if (kr->sorter) fhx_destroy(kr->sorter);
-    if (kr->stream) (void)hipStreamDestroy(kr->stream);
-    delete kr;
+    handle_destroy(kr, [&] {
+        free_matrix(kr);
+        kr->vec.release();
+        kr->part.release();
+        dev_free(kr->d_scalars);
+        dev_free(kr->d_counter);
+        if (kr->ev0) (void)hipEventDestroy(kr->ev0);
+        if (kr->ev1) (void)hipEventDestroy(kr->ev1);
+        if (kr->sorter) fhx_destroy(kr->sorter);
+    });
 }
 
-const char* fhx_kr_last_error(const fhx_kr* kr) { return kr ? kr->err.c_str() : "null context"; }
+const char* fhx_kr_last_error(const fhx_kr* kr) { return handle_last_error(kr); }
 
 int fhx_kr_load_loci(fhx_kr* kr, const int32_t* chr, const int32_t* mid, int64_t n) {
     if (!kr || n < 0 || (n > 0 && (!chr || !mid))) return FHX_ERR_ARG;
-    if (n >= (1ll << 31)) return kfail(kr, FHX_ERR_UNSUPPORTED, "more than 2^31 loci");
+    if (n >= (1ll << 31)) return fail(kr, FHX_ERR_UNSUPPORTED, "more than 2^31 loci");
     std::vector<std::pair<unsigned long long, int32_t>> kv((size_t)n);
     for (int64_t i = 0; i < n; ++i)
         kv[(size_t)i] = {((unsigned long long)(unsigned int)chr[i] << 32) | (unsigned int)mid[i], (int32_t)i};
@@ -798,72 +747,58 @@ int fhx_kr_load_pairs(fhx_kr* kr, const int32_t* chr1, const int32_t* mid1, cons
                       const double* value, int64_t m, int64_t* first_unknown_row) {
     if (!kr || m < 0 || (m > 0 && (!chr1 || !mid1 || !chr2 || !mid2 || !value))) return FHX_ERR_ARG;
     if (first_unknown_row) *first_unknown_row = -1;
-    if (2 * m >= (1ll << 32)) return kfail(kr, FHX_ERR_UNSUPPORTED, "more than 2^31 rows");
+    if (2 * m >= (1ll << 32)) return fail(kr, FHX_ERR_UNSUPPORTED, "more than 2^31 rows");
     const int64_t n = kr->n_full;
-    if (n <= 0) return kfail(kr, FHX_ERR_ARG, "fhx_kr_load_loci must be called first");
+    if (n <= 0) return fail(kr, FHX_ERR_ARG, "fhx_kr_load_loci must be called first");
     KR_HIP(hipSetDevice(kr->device));
     free_matrix(kr);
     const int64_t N = 2 * m;
-    KR_HIP(hipMalloc(&kr->d_indptr, (size_t)(n + 1) * sizeof(int64_t)));
+    KR_HIP(dev_malloc(&kr->d_indptr, (size_t)(n + 1) * sizeof(int64_t)));
     if (m == 0) {
         KR_HIP(hipMemsetAsync(kr->d_indptr, 0, (size_t)(n + 1) * sizeof(int64_t), kr->stream));
-        KR_HIP(hipMalloc(&kr->d_col, (size_t)(1 + krd::KR_PAD) * sizeof(int32_t)));
-        KR_HIP(hipMalloc(&kr->d_val, (size_t)(1 + krd::KR_PAD) * sizeof(double)));
+        KR_HIP(dev_malloc(&kr->d_col, (size_t)(1 + krd::KR_PAD) * sizeof(int32_t)));
+        KR_HIP(dev_malloc(&kr->d_val, (size_t)(1 + krd::KR_PAD) * sizeof(double)));
         KR_HIP(hipStreamSynchronize(kr->stream));
         kr->n = n;
         return FHX_OK;
     }
+    DeviceScratch tmp;
     int32_t *c1 = nullptr, *m1 = nullptr, *c2 = nullptr, *m2 = nullptr, *lidx = nullptr;
     double* z = nullptr;
     unsigned long long *keys = nullptr, *lkeys = nullptr;
-    auto cleanup = [&]() {
-        kfree(c1); kfree(m1); kfree(c2); kfree(m2); kfree(lidx); kfree(z); kfree(keys); kfree(lkeys);
-    };
-#define KR_TRY(call)                                                                                         \
-    do {                                                                                                     \
-        hipError_t e_ = (call);                                                                              \
-        if (e_ != hipSuccess) {                                                                              \
-            cleanup();                                                                                       \
-            return kfail(kr, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));                \
-        }                                                                                                    \
-    } while (0)
     const size_t nl = kr->locus_keys.size();
-    KR_TRY(hipMalloc(&c1, (size_t)m * 4));
-    KR_TRY(hipMalloc(&m1, (size_t)m * 4));
-    KR_TRY(hipMalloc(&c2, (size_t)m * 4));
-    KR_TRY(hipMalloc(&m2, (size_t)m * 4));
-    KR_TRY(hipMalloc(&z, (size_t)m * 8));
-    KR_TRY(hipMalloc(&lkeys, std::max<size_t>(1, nl) * 8));
-    KR_TRY(hipMalloc(&lidx, std::max<size_t>(1, nl) * 4));
-    KR_TRY(hipMalloc(&keys, (size_t)N * 8));
-    KR_TRY(hipMemcpyAsync(c1, chr1, (size_t)m * 4, hipMemcpyHostToDevice, kr->stream));
-    KR_TRY(hipMemcpyAsync(m1, mid1, (size_t)m * 4, hipMemcpyHostToDevice, kr->stream));
-    KR_TRY(hipMemcpyAsync(c2, chr2, (size_t)m * 4, hipMemcpyHostToDevice, kr->stream));
-    KR_TRY(hipMemcpyAsync(m2, mid2, (size_t)m * 4, hipMemcpyHostToDevice, kr->stream));
-    KR_TRY(hipMemcpyAsync(z, value, (size_t)m * 8, hipMemcpyHostToDevice, kr->stream));
-    KR_TRY(hipMemcpyAsync(lkeys, kr->locus_keys.data(), nl * 8, hipMemcpyHostToDevice, kr->stream));
-    KR_TRY(hipMemcpyAsync(lidx, kr->locus_index.data(), nl * 4, hipMemcpyHostToDevice, kr->stream));
-    if (!kr->d_counter) KR_TRY(hipMalloc(&kr->d_counter, 4 * sizeof(unsigned long long)));
+    KR_HIP(tmp.get(&c1, (size_t)m * 4));
+    KR_HIP(tmp.get(&m1, (size_t)m * 4));
+    KR_HIP(tmp.get(&c2, (size_t)m * 4));
+    KR_HIP(tmp.get(&m2, (size_t)m * 4));
+    KR_HIP(tmp.get(&z, (size_t)m * 8));
+    KR_HIP(tmp.get(&lkeys, nl * 8));
+    KR_HIP(tmp.get(&lidx, nl * 4));
+    KR_HIP(tmp.get(&keys, (size_t)N * 8));
+    KR_HIP(hipMemcpyAsync(c1, chr1, (size_t)m * 4, hipMemcpyHostToDevice, kr->stream));
+    KR_HIP(hipMemcpyAsync(m1, mid1, (size_t)m * 4, hipMemcpyHostToDevice, kr->stream));
+    KR_HIP(hipMemcpyAsync(c2, chr2, (size_t)m * 4, hipMemcpyHostToDevice, kr->stream));
+    KR_HIP(hipMemcpyAsync(m2, mid2, (size_t)m * 4, hipMemcpyHostToDevice, kr->stream));
+    KR_HIP(hipMemcpyAsync(z, value, (size_t)m * 8, hipMemcpyHostToDevice, kr->stream));
+    KR_HIP(hipMemcpyAsync(lkeys, kr->locus_keys.data(), nl * 8, hipMemcpyHostToDevice, kr->stream));
+    KR_HIP(hipMemcpyAsync(lidx, kr->locus_index.data(), nl * 4, hipMemcpyHostToDevice, kr->stream));
+    if (!kr->d_counter) KR_HIP(dev_malloc(&kr->d_counter, 4 * sizeof(unsigned long long)));
     const unsigned long long none = ~0ull;
-    KR_TRY(hipMemcpyAsync(kr->d_counter, &none, 8, hipMemcpyHostToDevice, kr->stream));
+    KR_HIP(hipMemcpyAsync(kr->d_counter, &none, 8, hipMemcpyHostToDevice, kr->stream));
     const int lgrid = (int)std::min<int64_t>((m + 255) / 256, 256 * 16);
     hipLaunchKernelGGL(krd::kr_lookup, dim3(lgrid), dim3(256), 0, kr->stream, m, c1, m1, c2, m2, lkeys, lidx, (int64_t)nl, n, keys,
                        kr->d_counter);
-    KR_TRY(hipGetLastError());
+    KR_HIP(hipGetLastError());
     unsigned long long missing = none;
-    KR_TRY(hipMemcpyAsync(&missing, kr->d_counter, 8, hipMemcpyDeviceToHost, kr->stream));
-    KR_TRY(hipStreamSynchronize(kr->stream));
-    kfree(c1); kfree(m1); kfree(c2); kfree(m2); kfree(lkeys); kfree(lidx);
+    KR_HIP(hipMemcpyAsync(&missing, kr->d_counter, 8, hipMemcpyDeviceToHost, kr->stream));
+    KR_HIP(hipStreamSynchronize(kr->stream));
+    for (void* done : {(void*)c1, (void*)m1, (void*)c2, (void*)m2, (void*)lkeys, (void*)lidx}) tmp.drop(done);   // before the sort's blocks come
     if (missing != none) {
-        cleanup();
         if (first_unknown_row) *first_unknown_row = (int64_t)missing;
-        return kfail(kr, FHX_ERR_REFERENCE_EXIT, "row " + std::to_string(missing) +
-                     " names a locus that is not in the fragments file (the reference raises KeyError, HiCKRy.py:44-45)");
+        return fail(kr, FHX_ERR_REFERENCE_EXIT, "row " + std::to_string(missing) +
+                    " names a locus that is not in the fragments file (the reference raises KeyError, HiCKRy.py:44-45)");
     }
-#undef KR_TRY
-    const int rc = assemble_cells(kr, keys, (const double*)z, m);       // sort, run heads, cells, row pointers
-    cleanup();
-    return rc;
+    return assemble_cells(kr, tmp, keys, (const double*)z, m);       // sort, run heads, cells, row pointers
 }
 
 int fhx_kr_shape(const fhx_kr* kr, int64_t* n_full, int64_t* nnz_full, int64_t* n_reduced, int64_t* nnz_reduced) {
@@ -877,8 +812,8 @@ int fhx_kr_shape(const fhx_kr* kr, int64_t* n_full, int64_t* nnz_full, int64_t* 
 
 int fhx_kr_get_csr(fhx_kr* kr, int32_t which, int64_t* indptr, int32_t* col, double* val) {
     if (!kr || (which != 0 && which != 1)) return FHX_ERR_ARG;
-    if (!kr->d_indptr) return kfail(kr, FHX_ERR_ARG, "no matrix loaded");
-    if (which == 1 && !kr->reduced) return kfail(kr, FHX_ERR_ARG, "fhx_kr_remove_sparse has not run");
+    if (!kr->d_indptr) return fail(kr, FHX_ERR_ARG, "no matrix loaded");
+    if (which == 1 && !kr->reduced) return fail(kr, FHX_ERR_ARG, "fhx_kr_remove_sparse has not run");
     KR_HIP(hipSetDevice(kr->device));
     const int64_t n = which ? kr->n : kr->n_full, nnz = which ? kr->nnz : kr->nnz_full;
     if (indptr) KR_HIP(hipMemcpyAsync(indptr, which ? kr->d_rptr : kr->d_indptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, kr->stream));
@@ -890,13 +825,13 @@ int fhx_kr_get_csr(fhx_kr* kr, int32_t which, int64_t* indptr, int32_t* col, dou
 
 int fhx_kr_spmv(fhx_kr* kr, int32_t which, const double* x, double* y, int32_t repeats, double* seconds_per_call) {
     if (!kr || !x || !y || (which != 0 && which != 1) || repeats < 1) return FHX_ERR_ARG;
-    if (!kr->d_indptr) return kfail(kr, FHX_ERR_ARG, "no matrix loaded");
-    if (which == 1 && !kr->reduced) return kfail(kr, FHX_ERR_ARG, "fhx_kr_remove_sparse has not run");
+    if (!kr->d_indptr) return fail(kr, FHX_ERR_ARG, "no matrix loaded");
+    if (which == 1 && !kr->reduced) return fail(kr, FHX_ERR_ARG, "fhx_kr_remove_sparse has not run");
     KR_HIP(hipSetDevice(kr->device));
     const int64_t n = which ? kr->n : kr->n_full;
-    int rc = ensure_vectors(kr, std::max(n, kr->vec_cap));
+    int rc = ensure_vectors(kr, std::max(n, kr->vec_cap()));
     if (rc != FHX_OK) return rc;
-    double *dx = kr->d_vec, *dy = kr->d_vec + kr->vec_cap;
+    double *dx = kr->vec.p, *dy = kr->vec.p + kr->vec_cap();
     KR_HIP(hipMemcpyAsync(dx, x, (size_t)n * 8, hipMemcpyHostToDevice, kr->stream));
     KR_HIP(hipEventRecord(kr->ev0, kr->stream));
     for (int r = 0; r < repeats; ++r)
@@ -916,16 +851,16 @@ int fhx_kr_spmv(fhx_kr* kr, int32_t which, const double* x, double* y, int32_t r
 int fhx_kr_dot(fhx_kr* kr, const double* a, const double* b, int64_t n, double* out) {
     if (!kr || !a || !out || n < 0) return FHX_ERR_ARG;
     KR_HIP(hipSetDevice(kr->device));
-    int rc = ensure_vectors(kr, std::max<int64_t>(n, kr->vec_cap));
+    int rc = ensure_vectors(kr, std::max<int64_t>(n, kr->vec_cap()));
     if (rc != FHX_OK) return rc;
     if (n == 0) {
         *out = 0.0;
         return FHX_OK;
     }
-    double *da = kr->d_vec, *db = kr->d_vec + kr->vec_cap;
+    double *da = kr->vec.p, *db = kr->vec.p + kr->vec_cap();
     KR_HIP(hipMemcpyAsync(da, a, (size_t)n * 8, hipMemcpyHostToDevice, kr->stream));
     if (b) KR_HIP(hipMemcpyAsync(db, b, (size_t)n * 8, hipMemcpyHostToDevice, kr->stream));
-    hipLaunchKernelGGL(krd::kr_dot, dim3(tiles_of(n)), dim3(krd::THREADS), 0, kr->stream, da, b ? db : nullptr, n, kr->d_part);
+    hipLaunchKernelGGL(krd::kr_dot, dim3(tiles_of(n)), dim3(krd::THREADS), 0, kr->stream, da, b ? db : nullptr, n, kr->part.p);
     const int op = 0;
     kr->balanced = false;
     return finish_scalars(kr, n, 1, &op, out);
@@ -933,13 +868,13 @@ int fhx_kr_dot(fhx_kr* kr, const double* a, const double* b, int64_t n, double* 
 
 int fhx_kr_row_sums(fhx_kr* kr, double* out) {
     if (!kr) return FHX_ERR_ARG;
-    if (!kr->d_indptr) return kfail(kr, FHX_ERR_ARG, "no matrix loaded");
+    if (!kr->d_indptr) return fail(kr, FHX_ERR_ARG, "no matrix loaded");
     KR_HIP(hipSetDevice(kr->device));
     const int64_t n = kr->n_full;
     if (kr->row_sums.empty() && n > 0) {
-        int rc = ensure_vectors(kr, std::max(n, kr->vec_cap));
+        int rc = ensure_vectors(kr, std::max(n, kr->vec_cap()));
         if (rc != FHX_OK) return rc;
-        double *ones = kr->d_vec, *dy = kr->d_vec + kr->vec_cap;
+        double *ones = kr->vec.p, *dy = kr->vec.p + kr->vec_cap();
         hipLaunchKernelGGL(krd::kr_fill, dim3(tiles_of(n)), dim3(krd::THREADS), 0, kr->stream, ones, 1.0, n);
         launch_spmv<0>(kr, n, kr->d_indptr, kr->d_col, kr->d_val, ones, dy, nullptr, nullptr, nullptr, nullptr);
         KR_HIP(hipGetLastError());
@@ -954,15 +889,15 @@ int fhx_kr_row_sums(fhx_kr* kr, double* out) {
 
 int fhx_kr_remove_sparse(fhx_kr* kr, double perc, int64_t* n_removed, double* val_to_remove, int64_t* rem_rows) {
     if (!kr) return FHX_ERR_ARG;
-    if (!kr->d_indptr) return kfail(kr, FHX_ERR_ARG, "no matrix loaded");
-    if (kr->reduced) return kfail(kr, FHX_ERR_ARG, "rows were already removed; load the pairs again");
+    if (!kr->d_indptr) return fail(kr, FHX_ERR_ARG, "no matrix loaded");
+    if (kr->reduced) return fail(kr, FHX_ERR_ARG, "rows were already removed; load the pairs again");
     int rc = fhx_kr_row_sums(kr, nullptr);
     if (rc != FHX_OK) return rc;
     const int64_t n = kr->n_full;
     const int64_t rem = (int64_t)(perc * (double)n);              // int(perc * size), HiCKRy.py:83
     if (rem_rows) *rem_rows = rem;
     if (rem < 0 || rem >= n)
-        return kfail(kr, FHX_ERR_REFERENCE_EXIT, "percentOfSparseToRemove selects row " + std::to_string(rem) + " of " +
+        return fail(kr, FHX_ERR_REFERENCE_EXIT, "percentOfSparseToRemove selects row " + std::to_string(rem) + " of " +
                      std::to_string(n) + " (the reference raises IndexError, HiCKRy.py:86)");
     std::vector<double> sorted(kr->row_sums);
     std::nth_element(sorted.begin(), sorted.begin() + rem, sorted.end());
@@ -984,16 +919,9 @@ int fhx_kr_remove_sparse(fhx_kr* kr, double perc, int64_t* n_removed, double* va
     KR_HIP(hipSetDevice(kr->device));
     int32_t* d_new = nullptr;
     int64_t* d_cnt = nullptr;
-    struct Scratch {                                   // freed on every return path
-        int32_t*& a;
-        int64_t*& b;
-        ~Scratch() {
-            kfree(a);
-            kfree(b);
-        }
-    } scratch{d_new, d_cnt};
-    KR_HIP(hipMalloc(&d_new, (size_t)n * 4));
-    KR_HIP(hipMalloc(&d_cnt, (size_t)std::max<int64_t>(n2, 1) * 8));
+    DeviceScratch tmp;
+    KR_HIP(tmp.get(&d_new, (size_t)n * 4));
+    KR_HIP(tmp.get(&d_cnt, (size_t)n2 * 8));
     KR_HIP(hipMemcpyAsync(d_new, newidx.data(), (size_t)n * 4, hipMemcpyHostToDevice, kr->stream));
     const unsigned rows_grid = (unsigned)std::max<int64_t>(1, (n + 3) / 4);
     hipLaunchKernelGGL(krd::kr_count_kept, dim3(rows_grid), dim3(krd::THREADS), 0, kr->stream, n, kr->d_indptr, kr->d_col, d_new, d_cnt);
@@ -1003,9 +931,9 @@ int fhx_kr_remove_sparse(fhx_kr* kr, double perc, int64_t* n_removed, double* va
     KR_HIP(hipStreamSynchronize(kr->stream));
     for (int64_t i = 0; i < n2; ++i) rptr[(size_t)i + 1] += rptr[(size_t)i];
     const int64_t nnz2 = rptr[(size_t)n2];
-    KR_HIP(hipMalloc(&kr->d_rptr, (size_t)(n2 + 1) * 8));
-    KR_HIP(hipMalloc(&kr->d_rcol, (size_t)(std::max<int64_t>(nnz2, 1) + krd::KR_PAD) * 4));
-    KR_HIP(hipMalloc(&kr->d_rval, (size_t)(std::max<int64_t>(nnz2, 1) + krd::KR_PAD) * 8));
+    KR_HIP(dev_malloc(&kr->d_rptr, (size_t)(n2 + 1) * 8));
+    KR_HIP(dev_malloc(&kr->d_rcol, (size_t)(std::max<int64_t>(nnz2, 1) + krd::KR_PAD) * 4));
+    KR_HIP(dev_malloc(&kr->d_rval, (size_t)(std::max<int64_t>(nnz2, 1) + krd::KR_PAD) * 8));
     KR_HIP(hipMemcpyAsync(kr->d_rptr, rptr.data(), (size_t)(n2 + 1) * 8, hipMemcpyHostToDevice, kr->stream));
     hipLaunchKernelGGL(krd::kr_compact, dim3(rows_grid), dim3(krd::THREADS), 0, kr->stream, n, kr->d_indptr, kr->d_col, kr->d_val, d_new,
                        kr->d_rptr, kr->d_rcol, kr->d_rval);
@@ -1031,23 +959,23 @@ int fhx_kr_get_removed(const fhx_kr* kr, int64_t* idx, int64_t capacity, int64_t
 // knightRuizAlg (HiCKRy.py:139-243).  Scalars and control flow on the host, vectors on the device.
 int fhx_kr_balance(fhx_kr* kr, double tol, fhx_kr_info* out) {
     if (!kr) return FHX_ERR_ARG;
-    if (!kr->d_indptr) return kfail(kr, FHX_ERR_ARG, "no matrix loaded");
+    if (!kr->d_indptr) return fail(kr, FHX_ERR_ARG, "no matrix loaded");
     KR_HIP(hipSetDevice(kr->device));
     const int64_t n = kr->n;
-    int rc = ensure_vectors(kr, std::max<int64_t>(n, kr->vec_cap));
+    int rc = ensure_vectors(kr, std::max<int64_t>(n, kr->vec_cap()));
     if (rc != FHX_OK) return rc;
-    const int64_t cap = kr->vec_cap;
-    double *x = kr->d_vec, *v = x + cap, *rk = v + cap, *Z = rk + cap, *p = Z + cap, *w = p + cap, *y = w + cap, *ap = y + cap,
+    const int64_t cap = kr->vec_cap();
+    double *x = kr->vec.p, *v = x + cap, *rk = v + cap, *Z = rk + cap, *p = Z + cap, *w = p + cap, *y = w + cap, *ap = y + cap,
            *ynew = ap + cap, *xp = ynew + cap;
-    double *part0 = kr->d_part, *part1 = kr->d_part + kr->part_cap;
+    double *part0 = kr->part.p, *part1 = kr->part.p + kr->part_cap();
     const int64_t* ptr = mat_ptr(kr);
     const int32_t* col = mat_col(kr);
     const double* val = mat_val(kr);
     // binary32 copy of the values when that is exact (integer contact counts): 8 B per cell instead of 12
     if (kr->nnz > 0 && (!kr->d_val32 || kr->val32_reduced != kr->reduced)) {
-        kfree(kr->d_val32);
-        KR_HIP(hipMalloc(&kr->d_val32, (size_t)(kr->nnz + krd::KR_PAD) * sizeof(float)));
-        if (!kr->d_counter) KR_HIP(hipMalloc(&kr->d_counter, 4 * sizeof(unsigned long long)));
+        dev_free(kr->d_val32);
+        KR_HIP(dev_malloc(&kr->d_val32, (size_t)(kr->nnz + krd::KR_PAD) * sizeof(float)));
+        if (!kr->d_counter) KR_HIP(dev_malloc(&kr->d_counter, 4 * sizeof(unsigned long long)));
         unsigned int* flag = reinterpret_cast<unsigned int*>(kr->d_counter + 3);
         KR_HIP(hipMemsetAsync(flag, 0, 4, kr->stream));
         hipLaunchKernelGGL(krd::kr_to_f32, dim3((unsigned)std::min<int64_t>((kr->nnz + 255) / 256, 256 * 16)), dim3(krd::THREADS), 0,
@@ -1056,13 +984,13 @@ int fhx_kr_balance(fhx_kr* kr, double tol, fhx_kr_info* out) {
         KR_HIP(hipMemcpyAsync(&inexact, flag, 4, hipMemcpyDeviceToHost, kr->stream));
         KR_HIP(hipStreamSynchronize(kr->stream));
         kr->val32_reduced = kr->reduced;
-        if (inexact) kfree(kr->d_val32);               // fractional or huge counts: stay with the doubles
+        if (inexact) dev_free(kr->d_val32);               // fractional or huge counts: stay with the doubles
         // 4-byte cells when the rows are narrow and the counts small (kr_pack16)
-        kfree(kr->d_pack);
-        kfree(kr->d_rowbase);
+        dev_free(kr->d_pack);
+        dev_free(kr->d_rowbase);
         if (kr->d_val32 && !std::getenv("FHX_KR_NO_PACK")) {
-            KR_HIP(hipMalloc(&kr->d_pack, (size_t)(kr->nnz + krd::KR_PAD) * sizeof(unsigned int)));
-            KR_HIP(hipMalloc(&kr->d_rowbase, (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t)));
+            KR_HIP(dev_malloc(&kr->d_pack, (size_t)(kr->nnz + krd::KR_PAD) * sizeof(unsigned int)));
+            KR_HIP(dev_malloc(&kr->d_rowbase, (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t)));
             KR_HIP(hipMemsetAsync(kr->d_pack + kr->nnz, 0, (size_t)krd::KR_PAD * sizeof(unsigned int), kr->stream));
             KR_HIP(hipMemsetAsync(flag, 0, 4, kr->stream));
             hipLaunchKernelGGL(krd::kr_pack16, dim3((unsigned)((n + 3) / 4)), dim3(krd::THREADS), 0, kr->stream, n, ptr, col, val, kr->d_pack,
@@ -1071,8 +999,8 @@ int fhx_kr_balance(fhx_kr* kr, double tol, fhx_kr_info* out) {
             KR_HIP(hipMemcpyAsync(&misfit, flag, 4, hipMemcpyDeviceToHost, kr->stream));
             KR_HIP(hipStreamSynchronize(kr->stream));
             if (misfit) {                              // a row wider than 65 535 columns or a count of 65 536 or more
-                kfree(kr->d_pack);
-                kfree(kr->d_rowbase);
+                dev_free(kr->d_pack);
+                dev_free(kr->d_rowbase);
             }
         }
     }
@@ -1173,8 +1101,8 @@ int fhx_kr_balance(fhx_kr* kr, double tol, fhx_kr_info* out) {
                 unsigned long long selected = 0;
                 KR_HIP(hipMemcpy(&selected, kr->d_counter + 2, 8, hipMemcpyDeviceToHost));
                 if (selected == 0)
-                    return kfail(kr, FHX_ERR_REFERENCE_EXIT, "np.amin of an empty selection at the cone boundary (the reference raises "
-                                                              "ValueError, HiCKRy.py:204/210)");
+                    return fail(kr, FHX_ERR_REFERENCE_EXIT, "np.amin of an empty selection at the cone boundary (the reference raises "
+                                                             "ValueError, HiCKRy.py:204/210)");
                 hipLaunchKernelGGL(krd::kr_step_partial, grid, block, 0, kr->stream, y, ap, s[0], n);
                 info.boundary_steps += 1;
                 break;
@@ -1231,7 +1159,7 @@ int fhx_kr_get_x(const fhx_kr* kr, double* x) {
 // computeBiasVector + addZeroBiases (HiCKRy.py:103-115)
 int fhx_kr_bias(fhx_kr* kr, double* bias) {
     if (!kr || !bias) return FHX_ERR_ARG;
-    if (!kr->balanced) return kfail(kr, FHX_ERR_ARG, "fhx_kr_balance has not run");
+    if (!kr->balanced) return fail(kr, FHX_ERR_ARG, "fhx_kr_balance has not run");
     const int64_t n2 = kr->n;
     std::vector<double> inv((size_t)n2);
     for (int64_t i = 0; i < n2; ++i) inv[(size_t)i] = 1.0 / kr->x_host[(size_t)i];

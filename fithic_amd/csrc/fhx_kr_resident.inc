@@ -97,23 +97,23 @@ std::vector<int32_t> line_of_slot_table(const fhx_kr* kr, const fhx_ctx* ctx) {
 extern "C" int fhx_kr_load_pairs_resident(fhx_kr* kr, fhx_ctx* ctx, int64_t* first_unknown_row) {
     if (!kr || !ctx) return FHX_ERR_ARG;
     if (first_unknown_row) *first_unknown_row = -1;
-    if (ctx->device < 0 || ctx->device != kr->device) return kfail(kr, FHX_ERR_ARG, "the engine context is not on this context's device");
-    if (!ctx->d_loc1 || !ctx->d_loc2 || !ctx->d_count || !ctx->have_params) return kfail(kr, FHX_ERR_ARG, "the engine context holds no contact rows");
+    if (ctx->device < 0 || ctx->device != kr->device) return fail(kr, FHX_ERR_ARG, "the engine context is not on this context's device");
+    if (!ctx->d_loc1 || !ctx->d_loc2 || !ctx->d_count || !ctx->have_params) return fail(kr, FHX_ERR_ARG, "the engine context holds no contact rows");
     const int64_t n = kr->n_full, m = ctx->n_rows;
-    if (n <= 0) return kfail(kr, FHX_ERR_ARG, "fhx_kr_load_loci must be called first");
+    if (n <= 0) return fail(kr, FHX_ERR_ARG, "fhx_kr_load_loci must be called first");
     if (!ctx->counts_integral)
-        return kfail(kr, FHX_ERR_UNSUPPORTED, "a contact count of the resident rows was not an integer as written: HiCKRy balances float(count), "
-                                               "the rows hold int(float(count)) - assemble from the file (fhx_kr_load_pairs)");
-    if (2 * m >= (1ll << 32)) return kfail(kr, FHX_ERR_UNSUPPORTED, "more than 2^31 rows");
-    if (ctx->nonfixed && (int64_t)ctx->h_slot_keys.size() != ctx->n_slots) return kfail(kr, FHX_ERR_INTERNAL, "the engine's locus list does not match its slots");
+        return fail(kr, FHX_ERR_UNSUPPORTED, "a contact count of the resident rows was not an integer as written: HiCKRy balances float(count), "
+                                              "the rows hold int(float(count)) - assemble from the file (fhx_kr_load_pairs)");
+    if (2 * m >= (1ll << 32)) return fail(kr, FHX_ERR_UNSUPPORTED, "more than 2^31 rows");
+    if (ctx->nonfixed && (int64_t)ctx->h_slot_keys.size() != ctx->n_slots) return fail(kr, FHX_ERR_INTERNAL, "the engine's locus list does not match its slots");
     KR_HIP(hipSetDevice(kr->device));
     KR_HIP(hipStreamSynchronize(ctx->stream));        // whatever the engine has in flight; its rows are only read here
     free_matrix(kr);
-    KR_HIP(hipMalloc(&kr->d_indptr, (size_t)(n + 1) * sizeof(int64_t)));
+    KR_HIP(dev_malloc(&kr->d_indptr, (size_t)(n + 1) * sizeof(int64_t)));
     if (m == 0) {
         KR_HIP(hipMemsetAsync(kr->d_indptr, 0, (size_t)(n + 1) * sizeof(int64_t), kr->stream));
-        KR_HIP(hipMalloc(&kr->d_col, (size_t)(1 + krd::KR_PAD) * sizeof(int32_t)));
-        KR_HIP(hipMalloc(&kr->d_val, (size_t)(1 + krd::KR_PAD) * sizeof(double)));
+        KR_HIP(dev_malloc(&kr->d_col, (size_t)(1 + krd::KR_PAD) * sizeof(int32_t)));
+        KR_HIP(dev_malloc(&kr->d_val, (size_t)(1 + krd::KR_PAD) * sizeof(double)));
         KR_HIP(hipStreamSynchronize(kr->stream));
         kr->n = n;
         return FHX_OK;
@@ -131,46 +131,32 @@ extern "C" int fhx_kr_load_pairs_resident(fhx_kr* kr, fhx_ctx* ctx, int64_t* fir
     mark(0);
     int32_t* d_line = nullptr;
     unsigned long long* keys = nullptr;
-    auto cleanup = [&]() {
-        kfree(d_line);
-        kfree(keys);
-    };
-#define KRR_TRY(call)                                                                                        \
-    do {                                                                                                     \
-        hipError_t e_ = (call);                                                                              \
-        if (e_ != hipSuccess) {                                                                              \
-            cleanup();                                                                                       \
-            return kfail(kr, FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));                \
-        }                                                                                                    \
-    } while (0)
-    KRR_TRY(hipMalloc(&d_line, line.size() * sizeof(int32_t)));
-    KRR_TRY(hipMalloc(&keys, (size_t)(2 * m) * 8));
-    KRR_TRY(hipMemcpyAsync(d_line, line.data(), line.size() * sizeof(int32_t), hipMemcpyHostToDevice, kr->stream));
-    if (!kr->d_counter) KRR_TRY(hipMalloc(&kr->d_counter, 4 * sizeof(unsigned long long)));
+    DeviceScratch tmp;
+    KR_HIP(tmp.get(&d_line, line.size() * sizeof(int32_t)));
+    KR_HIP(tmp.get(&keys, (size_t)(2 * m) * 8));
+    KR_HIP(hipMemcpyAsync(d_line, line.data(), line.size() * sizeof(int32_t), hipMemcpyHostToDevice, kr->stream));
+    if (!kr->d_counter) KR_HIP(dev_malloc(&kr->d_counter, 4 * sizeof(unsigned long long)));
     const unsigned long long none = ~0ull;
-    KRR_TRY(hipMemcpyAsync(kr->d_counter, &none, 8, hipMemcpyHostToDevice, kr->stream));
+    KR_HIP(hipMemcpyAsync(kr->d_counter, &none, 8, hipMemcpyHostToDevice, kr->stream));
     const int64_t chunks = (m + krd::KRR_CHUNK - 1) / krd::KRR_CHUNK;
-    if (timing) KRR_TRY(hipEventRecord(kr->ev0, kr->stream));
+    if (timing) KR_HIP(hipEventRecord(kr->ev0, kr->stream));
     hipLaunchKernelGGL(krd::krr_keys, dim3((unsigned)chunks), dim3(krd::THREADS), 0, kr->stream, m, (const int32_t*)ctx->d_loc1,
                        (const int32_t*)ctx->d_loc2, (const long long*)ctx->d_grow, (const int32_t*)d_line, ctx->n_slots, n, keys, kr->d_counter);
-    KRR_TRY(hipGetLastError());
-    if (timing) KRR_TRY(hipEventRecord(kr->ev1, kr->stream));
+    KR_HIP(hipGetLastError());
+    if (timing) KR_HIP(hipEventRecord(kr->ev1, kr->stream));
     unsigned long long missing = none;
-    KRR_TRY(hipMemcpyAsync(&missing, kr->d_counter, 8, hipMemcpyDeviceToHost, kr->stream));
-    KRR_TRY(hipStreamSynchronize(kr->stream));
-#undef KRR_TRY
+    KR_HIP(hipMemcpyAsync(&missing, kr->d_counter, 8, hipMemcpyDeviceToHost, kr->stream));
+    KR_HIP(hipStreamSynchronize(kr->stream));
     mark(1);
     float keys_ms = 0;
     if (timing) (void)hipEventElapsedTime(&keys_ms, kr->ev0, kr->ev1);
-    kfree(d_line);
+    tmp.drop(d_line);
     if (missing != none) {
-        cleanup();
         if (first_unknown_row) *first_unknown_row = (int64_t)missing;
-        return kfail(kr, FHX_ERR_REFERENCE_EXIT, "row " + std::to_string(missing) +
-                     " names a locus that is not in the fragments file (the reference raises KeyError, HiCKRy.py:44-45)");
+        return fail(kr, FHX_ERR_REFERENCE_EXIT, "row " + std::to_string(missing) +
+                    " names a locus that is not in the fragments file (the reference raises KeyError, HiCKRy.py:44-45)");
     }
-    const int rc = assemble_cells(kr, keys, (const int32_t*)ctx->d_count, m);     // the counts stay where the engine keeps them
-    cleanup();
+    const int rc = assemble_cells(kr, tmp, keys, (const int32_t*)ctx->d_count, m);     // the counts stay where the engine keeps them
     mark(2);
     if (timing && rc == FHX_OK)
         std::fprintf(stderr, "fhx_kr_load_pairs_resident: %lld rows, %lld loci, %lld cells: slot table (host) %.6f s; allocations + table upload + "

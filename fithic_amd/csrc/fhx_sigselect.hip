@@ -150,7 +150,7 @@ void drop_subset(fhx_ms* ms) {
 int make_fdr(fhx_ms* ms, const char* fdr_text, int32_t fdr_len, const char* noun, msd::Fdr* fdr, int32_t* why) {
     if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) {
         *why = FHX_MS_FDR;
-        return ms->fail(FHX_ERR_UNSUPPORTED, std::string("the text of ") + noun + " must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
+        return fhx::fail(ms, FHX_ERR_UNSUPPORTED, std::string("the text of ") + noun + " must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
     }
     std::memset(fdr, 0, sizeof(*fdr));
     std::memcpy(fdr->text, fdr_text, (size_t)fdr_len);
@@ -169,7 +169,7 @@ int select_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_
     Fdr fdr;
     if (const int rc = make_fdr(ms, fdr_text, fdr_len, "fdr", &fdr, why)) return rc;
     fhx::StageClock clock{ms->seconds};
-    fhx::Scratch tmp;
+    fhx::DeviceScratch tmp;
     fhx::TextBatches in;
     if (const int rc = in.open(ms, &tmp, &clock, path, "significances", "FHX_MS_BATCH_BYTES", (int64_t)1 << 31)) return rc;
     const int64_t out_capacity = in.batch_bytes + 1;                          // every line kept, and the newline the last one lacked
@@ -179,10 +179,10 @@ int select_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_
     unsigned short* d_keep_len = nullptr;
     int64_t keep_capacity = 0;
     Words* d_words = nullptr;
-    TH_HIP(ms, tmp.get(&d_out, (size_t)out_capacity));
-    TH_HIP(ms, tmp.get(&d_block_bytes, (size_t)in.max_blocks));
-    TH_HIP(ms, tmp.get(&d_out_off, (size_t)in.max_blocks));
-    TH_HIP(ms, tmp.get(&d_words, 1));
+    TH_HIP(ms, tmp.get_n(&d_out, (size_t)out_capacity));
+    TH_HIP(ms, tmp.get_n(&d_block_bytes, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get_n(&d_out_off, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get_n(&d_words, 1));
     Words words;
     const fhx::Refusal refuse{ms, why, bad_line};
     int64_t kept = 0;
@@ -236,7 +236,7 @@ int select_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_
 
 extern "C" {
 
-int fhx_ms_create(int device, fhx_ms** out) { return fhx::text_handle_create(device, out); }
+int fhx_ms_create(int device, fhx_ms** out) { return fhx::handle_create(device, out); }
 
 void fhx_ms_destroy(fhx_ms* ms) {
     fhx::text_handle_destroy(ms, [&] {
@@ -244,7 +244,7 @@ void fhx_ms_destroy(fhx_ms* ms) {
     });
 }
 
-const char* fhx_ms_last_error(const fhx_ms* ms) { return ms ? ms->err.c_str() : "null context"; }
+const char* fhx_ms_last_error(const fhx_ms* ms) { return fhx::handle_last_error(ms); }
 
 int fhx_ms_select_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_len, uint64_t key_bound, int32_t zero_kept, int32_t strict,
                        int32_t skip_first_line, int64_t* n_bytes, int32_t* why, int64_t* bad_line) {

@@ -268,10 +268,10 @@ int split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_l
     if (const int rc = make_fdr(ms, fdr_text, fdr_len, "fdr", &fdr, why)) return rc;
     if (!ms->sorter && fhx_create(ms->device, &ms->sorter) != FHX_OK) {       // only a split pays for it
         ms->sorter = nullptr;
-        return ms->fail(FHX_ERR_HIP, "the sort context could not be made");
+        return fhx::fail(ms, FHX_ERR_HIP, "the sort context could not be made");
     }
     fhx::StageClock clock{ms->s_seconds};
-    fhx::Scratch tmp;
+    fhx::DeviceScratch tmp;
     fhx::TextBatches in;
     if (const int rc = in.open(ms, &tmp, &clock, path, "significances", "FHX_MS_BATCH_BYTES", (int64_t)1 << 31)) return rc;
     const int64_t out_capacity = in.batch_bytes + 1;                          // every line kept, and the newline the last one lacked
@@ -283,16 +283,16 @@ int split_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_l
     int64_t keep_capacity = 0, slot_capacity = 0, rec_capacity = 0, sorted_capacity = 0, perm_capacity = 0, tile_capacity = 0,
             tile_off_capacity = 0;
     SplitWords* d_words = nullptr;
-    TH_HIP(ms, tmp.get(&d_out, (size_t)out_capacity));
-    TH_HIP(ms, tmp.get(&d_block_kept, (size_t)in.max_blocks));
-    TH_HIP(ms, tmp.get(&d_rec_off, (size_t)in.max_blocks));
-    TH_HIP(ms, tmp.get(&d_hash, (size_t)SLOTS));
-    TH_HIP(ms, tmp.get(&d_off, (size_t)SLOTS));
-    TH_HIP(ms, tmp.get(&d_claimed, (size_t)SLOTS));
-    TH_HIP(ms, tmp.get(&d_names, (size_t)SLOTS * NAME_STRIDE));
-    TH_HIP(ms, tmp.get(&d_slot_byte, (size_t)SLOTS));
-    TH_HIP(ms, tmp.get(&d_slot_record, (size_t)SLOTS));
-    TH_HIP(ms, tmp.get(&d_words, 1));
+    TH_HIP(ms, tmp.get_n(&d_out, (size_t)out_capacity));
+    TH_HIP(ms, tmp.get_n(&d_block_kept, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get_n(&d_rec_off, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get_n(&d_hash, (size_t)SLOTS));
+    TH_HIP(ms, tmp.get_n(&d_off, (size_t)SLOTS));
+    TH_HIP(ms, tmp.get_n(&d_claimed, (size_t)SLOTS));
+    TH_HIP(ms, tmp.get_n(&d_names, (size_t)SLOTS * NAME_STRIDE));
+    TH_HIP(ms, tmp.get_n(&d_slot_byte, (size_t)SLOTS));
+    TH_HIP(ms, tmp.get_n(&d_slot_record, (size_t)SLOTS));
+    TH_HIP(ms, tmp.get_n(&d_words, 1));
     TH_HIP(ms, hipMemsetAsync(d_hash, 0, sizeof(unsigned long long) * SLOTS, ms->stream));
     TH_HIP(ms, hipMemsetAsync(d_off, 0xFF, sizeof(unsigned long long) * SLOTS, ms->stream));
     TH_HIP(ms, hipMemsetAsync(d_claimed, 0, sizeof(unsigned int) * SLOTS, ms->stream));

@@ -218,7 +218,7 @@ int track_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_l
     Fdr fdr;
     if (const int rc = make_fdr(ms, fdr_text, fdr_len, "the threshold", &fdr, why)) return rc;
     fhx::StageClock clock{ms->t_seconds};
-    fhx::Scratch tmp;
+    fhx::DeviceScratch tmp;
     fhx::TextBatches in;
     if (const int rc = in.open(ms, &tmp, &clock, path, "significances", "FHX_MS_BATCH_BYTES", (int64_t)1 << 31)) return rc;
     unsigned char *d_out = nullptr, *d_fields = nullptr, *d_scores = nullptr;
@@ -227,13 +227,13 @@ int track_file(fhx_ms* ms, const char* path, const char* fdr_text, int32_t fdr_l
     unsigned short* d_info = nullptr;
     int64_t info_capacity = 0, out_capacity = 0, fields_capacity = 0, scores_capacity = 0;
     TrackWords* d_words = nullptr;
-    TH_HIP(ms, tmp.get(&d_block_kept, (size_t)in.max_blocks));
-    TH_HIP(ms, tmp.get(&d_block_deferred, (size_t)in.max_blocks));
-    TH_HIP(ms, tmp.get(&d_block_bytes, (size_t)in.max_blocks));
-    TH_HIP(ms, tmp.get(&d_kept_off, (size_t)in.max_blocks));
-    TH_HIP(ms, tmp.get(&d_deferred_off, (size_t)in.max_blocks));
-    TH_HIP(ms, tmp.get(&d_out_off, (size_t)in.max_blocks));
-    TH_HIP(ms, tmp.get(&d_words, 1));
+    TH_HIP(ms, tmp.get_n(&d_block_kept, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get_n(&d_block_deferred, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get_n(&d_block_bytes, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get_n(&d_kept_off, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get_n(&d_deferred_off, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get_n(&d_out_off, (size_t)in.max_blocks));
+    TH_HIP(ms, tmp.get_n(&d_words, 1));
     TrackWords words;
     std::vector<unsigned char> fields, scores;
     const fhx::Refusal refuse{ms, why, bad_line};

@@ -1,6 +1,6 @@
 // fhx_textupload.hpp - the host side that the device text paths share (fhx_hicpro.hip, fhx_validpairs.hip, fhx_juicer.hip,
-// fhx_sigselect.hip with fhx_sigtrack.inc and fhx_sigsplit.inc): the handle base with its stream and error text, the device
-// temporaries of one call, the stage clock, and the way a text file (fhx_textfile.hpp) reaches HBM: host threads fill one of two
+// fhx_sigselect.hip with fhx_sigtrack.inc and fhx_sigsplit.inc): the text handle (fhx_devmem.hpp's Handle plus the pinned
+// upload buffers), the stage clock, and the way a text file (fhx_textfile.hpp) reaches HBM: host threads fill one of two
 // pinned buffers while the copy engine drains the other, in batches cut at the last newline and padded with blanks as
 // fhx_textlines.hpp's 16-byte loads need it.  TextBatches is the loop over such batches with the newline layer run on each;
 // refused_line turns a kernel's error word into what the caller is told.
@@ -16,96 +16,30 @@
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
+#include "fhx_devmem.hpp"
 #include "fhx_textfile.hpp"
 #include "fhx_textlines.hpp"
 
 namespace fhx {
 
-// what fhx_hp, fhx_vp, fhx_jc and fhx_ms have in common
-struct TextHandle {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    std::string err;
-    // the upload path: made on first use
+// what fhx_hp, fhx_vp, fhx_jc and fhx_ms have in common beyond fhx::Handle: the upload path, made on first use
+struct TextHandle : Handle {
     static constexpr size_t kChunk = (size_t)32 << 20;
     void* pinned[2] = {nullptr, nullptr};
     hipEvent_t ev[2] = {nullptr, nullptr};
-
-    int fail(int code, const std::string& msg) {
-        err = msg;
-        return code;
-    }
 };
 
-#define TH_HIP(h, call)                                                                                          \
-    do {                                                                                                         \
-        hipError_t e_ = (call);                                                                                  \
-        if (e_ != hipSuccess) return (h)->fail(FHX_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// a new H (derived from TextHandle) on `device`, with a non-blocking stream
-template <typename H>
-int text_handle_create(int device, H** out) {
-    if (!out) return FHX_ERR_ARG;
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return FHX_ERR_NO_DEVICE;
-    H* h = new H();
-    h->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete h;
-        return FHX_ERR_HIP;
-    }
-    *out = h;
-    return FHX_OK;
-}
-
-// drop() frees what H owns beyond the base, on the handle's device and with its stream idle
+// drop() frees what H (derived from TextHandle) owns beyond it, on the handle's device and with its stream idle
 template <typename H, typename Drop>
 void text_handle_destroy(H* h, Drop drop) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    drop();
-    for (int k = 0; k < 2; ++k) {
-        if (h->pinned[k]) (void)hipHostFree(h->pinned[k]);
-        if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
-    }
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
-
-// device temporaries of one call
-struct Scratch {
-    std::vector<void*> ptrs;
-    ~Scratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t get(T** p, size_t count) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-    void drop(void* p) {
-        auto it = std::find(ptrs.begin(), ptrs.end(), p);
-        if (it != ptrs.end()) {
-            (void)hipFree(p);
-            ptrs.erase(it);
+    handle_destroy(h, [&] {
+        drop();
+        for (int k = 0; k < 2; ++k) {
+            if (h->pinned[k]) (void)hipHostFree(h->pinned[k]);
+            if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
         }
-    }
-    // an array that grows to what a batch needs; its old contents are not kept
-    template <typename T>
-    hipError_t grow(T** p, int64_t* capacity, int64_t need) {
-        if (need <= *capacity) return hipSuccess;
-        if (*p) drop(*p);
-        *p = nullptr;
-        *capacity = 0;
-        const hipError_t e = get(p, (size_t)need);
-        if (e == hipSuccess) *capacity = need;
-        return e;
-    }
-};
+    });
+}
 
 // host seconds per stage of a call; the stream is idle at every mark
 struct StageClock {
@@ -155,7 +89,7 @@ inline int upload_batch(TextHandle* h, const TextFile& src, const char* what, in
         int64_t nl = -1;
         if (const int io_errno = src.read(off + done, now, dst, &nl)) {
             (void)hipStreamSynchronize(h->stream);
-            return h->fail(FHX_ERR_ARG, std::string("reading the ") + what + " file: " + std::strerror(io_errno));
+            return fail(h, FHX_ERR_ARG, std::string("reading the ") + what + " file: " + std::strerror(io_errno));
         }
         if (nl >= 0) last_newline = done + nl;
         TH_HIP(h, hipMemcpyAsync(d_text + done, dst, (size_t)now, hipMemcpyHostToDevice, h->stream));
@@ -193,7 +127,7 @@ struct TextBatches {
     int64_t len = 0, n_blocks = 0, lines = 0;
     bool refused_bytes = false;                   // scan_text<Bytes> saw a byte its policy refuses
 
-    int open(TextHandle* handle, Scratch* scratch, StageClock* stage_clock, const char* path, const char* what_word, const char* env,
+    int open(TextHandle* handle, DeviceScratch* scratch, StageClock* stage_clock, const char* path, const char* what_word, const char* env,
              int64_t upper) {
         h = handle;
         tmp = scratch;
@@ -202,10 +136,10 @@ struct TextBatches {
         if (const int rc = src.open(path, /*allow_gzip=*/true, &h->err)) return rc;
         batch_bytes = batch_bytes_for(env, upper, src.size());
         max_blocks = (batch_bytes + fhxlines::BLOCK_BYTES - 1) / fhxlines::BLOCK_BYTES;
-        TH_HIP(h, tmp->get(&d_text, (size_t)max_blocks * fhxlines::BLOCK_BYTES + 64));
-        TH_HIP(h, tmp->get(&d_block_nl, (size_t)max_blocks));
-        TH_HIP(h, tmp->get(&d_block_off, (size_t)max_blocks));
-        TH_HIP(h, tmp->get(&d_scan, 1));
+        TH_HIP(h, tmp->get_n(&d_text, (size_t)max_blocks * fhxlines::BLOCK_BYTES + 64));
+        TH_HIP(h, tmp->get_n(&d_block_nl, (size_t)max_blocks));
+        TH_HIP(h, tmp->get_n(&d_block_off, (size_t)max_blocks));
+        TH_HIP(h, tmp->get_n(&d_scan, 1));
         return FHX_OK;
     }
 
@@ -251,7 +185,7 @@ struct TextBatches {
         unsigned int flags, pad;                  // scan_text's flag word
     };
     TextHandle* h = nullptr;
-    Scratch* tmp = nullptr;
+    DeviceScratch* tmp = nullptr;
     StageClock* clock = nullptr;
     const char* what = "";
     ScanWords* d_scan = nullptr;
@@ -265,7 +199,7 @@ struct Refusal {
     int operator()(int rc, int32_t w, int64_t line, const std::string& msg) const {
         *why = w;
         *bad_line = line;
-        return h->fail(rc, msg);
+        return fail(h, rc, msg);
     }
     // a kernel's first_error word (fhxlines::error_word); `internal` is the path's reason for kernels that disagree with each other
     int word(unsigned long long first_error, int32_t internal) const {

@@ -320,8 +320,7 @@ struct fhx_vp : fhx::TextHandle {
 namespace {
 
 void drop_cells(fhx_vp* vp) {
-    if (vp->d_cols) (void)hipFree(vp->d_cols);
-    vp->d_cols = nullptr;
+    fhx::dev_free(vp->d_cols);
     vp->names.clear();
     vp->n_lines = vp->n_pairs = vp->n_cells = 0;
     vp->col_stride = 0;
@@ -342,18 +341,18 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
     for (double& s : vp->seconds) s = 0;
     if (res < 2 || (res & 1) || res > 0x7fffffffll) {
         *why = FHX_VP_RES;
-        return vp->fail(FHX_ERR_UNSUPPORTED, "the resolution must be an even number from 2 to 2^31 - 2");
+        return fhx::fail(vp, FHX_ERR_UNSUPPORTED, "the resolution must be an even number from 2 to 2^31 - 2");
     }
     fhx::StageClock clock{vp->seconds};
-    fhx::Scratch tmp;
+    fhx::DeviceScratch tmp;
     fhx::TextBatches in;                                                      // a gzip file is read as zcat -f reads it (:33)
     if (const int rc = in.open(vp, &tmp, &clock, path, "validPairs", "FHX_VP_BATCH_BYTES", (int64_t)1 << 32)) return rc;
     unsigned long long* d_names = nullptr;
     Words* d_words = nullptr;
     ulonglong2* d_records = nullptr;
     int64_t capacity = 0;
-    TH_HIP(vp, tmp.get(&d_names, (size_t)NAME_SLOTS));
-    TH_HIP(vp, tmp.get(&d_words, 1));
+    TH_HIP(vp, tmp.get_n(&d_names, (size_t)NAME_SLOTS));
+    TH_HIP(vp, tmp.get_n(&d_words, 1));
     TH_HIP(vp, hipMemsetAsync(d_names, 0, NAME_SLOTS * sizeof(unsigned long long), vp->stream));
     Words words;                                                              // running totals: set once, not per batch
     std::memset(&words, 0, sizeof(words));
@@ -369,7 +368,7 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
         if (pairs + n > capacity) {                                           // room for every line of the batch to be kept
             const int64_t want = std::max<int64_t>(pairs + n, capacity * 2);
             ulonglong2* bigger = nullptr;
-            TH_HIP(vp, tmp.get(&bigger, (size_t)want));
+            TH_HIP(vp, tmp.get_n(&bigger, (size_t)want));
             if (pairs) TH_HIP(vp, hipMemcpyAsync(bigger, d_records, (size_t)pairs * sizeof(ulonglong2), hipMemcpyDeviceToDevice, vp->stream));
             TH_HIP(vp, hipStreamSynchronize(vp->stream));
             tmp.drop(d_records);
@@ -421,27 +420,27 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
     int* d_slot_rank = nullptr;
     unsigned int *d_text_rank = nullptr, *d_bin_at_rank = nullptr, *d_perm = nullptr;
     unsigned long long *d_keys = nullptr, *d_sorted = nullptr;
-    TH_HIP(vp, tmp.get(&d_slot_rank, (size_t)NAME_SLOTS));
+    TH_HIP(vp, tmp.get_n(&d_slot_rank, (size_t)NAME_SLOTS));
     TH_HIP(vp, hipMemcpyAsync(d_slot_rank, slot_rank.data(), NAME_SLOTS * sizeof(int), hipMemcpyHostToDevice, vp->stream));
-    TH_HIP(vp, tmp.get(&d_text_rank, (size_t)n_bins));
-    TH_HIP(vp, tmp.get(&d_bin_at_rank, (size_t)n_bins));
+    TH_HIP(vp, tmp.get_n(&d_text_rank, (size_t)n_bins));
+    TH_HIP(vp, tmp.get_n(&d_bin_at_rank, (size_t)n_bins));
     {
         unsigned long long *d_bin_keys = nullptr, *d_bin_sorted = nullptr;
-        TH_HIP(vp, tmp.get(&d_bin_keys, (size_t)n_bins));
-        TH_HIP(vp, tmp.get(&d_bin_sorted, (size_t)n_bins));
+        TH_HIP(vp, tmp.get_n(&d_bin_keys, (size_t)n_bins));
+        TH_HIP(vp, tmp.get_n(&d_bin_sorted, (size_t)n_bins));
         const unsigned grid = (unsigned)std::min<int64_t>((n_bins + WG - 1) / WG, 4096);
         hipLaunchKernelGGL(vp_text_keys, dim3(grid), dim3(WG), 0, vp->stream, (long long)res, n_bins, d_bin_keys);
         TH_HIP(vp, hipGetLastError());
         TH_HIP(vp, hipStreamSynchronize(vp->stream));                             // the sorter has a stream of its own
         const int rc = fhx_sort_u64(vp->sorter, d_bin_keys, n_bins, d_bin_sorted, d_bin_at_rank);
-        if (rc != FHX_OK) return vp->fail(rc, std::string("sort of the bin starts: ") + fhx_last_error(vp->sorter));
+        if (rc != FHX_OK) return fhx::fail(vp, rc, std::string("sort of the bin starts: ") + fhx_last_error(vp->sorter));
         hipLaunchKernelGGL(vp_invert, dim3(grid), dim3(WG), 0, vp->stream, (const unsigned int*)d_bin_at_rank, n_bins, d_text_rank);
         TH_HIP(vp, hipGetLastError());
         TH_HIP(vp, hipStreamSynchronize(vp->stream));
         tmp.drop(d_bin_keys);
         tmp.drop(d_bin_sorted);
     }
-    TH_HIP(vp, tmp.get(&d_keys, (size_t)pairs));
+    TH_HIP(vp, tmp.get_n(&d_keys, (size_t)pairs));
     {
         const unsigned grid = (unsigned)std::min<int64_t>((pairs + WG - 1) / WG, 8192);
         hipLaunchKernelGGL(vp_keys, dim3(grid), dim3(WG), 0, vp->stream, (const ulonglong2*)d_records, pairs, (const int*)d_slot_rank,
@@ -452,11 +451,11 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
     tmp.drop(d_records);
     d_records = nullptr;
     clock.mark(3);
-    TH_HIP(vp, tmp.get(&d_sorted, (size_t)pairs));
-    TH_HIP(vp, tmp.get(&d_perm, (size_t)pairs));
+    TH_HIP(vp, tmp.get_n(&d_sorted, (size_t)pairs));
+    TH_HIP(vp, tmp.get_n(&d_perm, (size_t)pairs));
     {
         const int rc = fhx_sort_u64(vp->sorter, d_keys, pairs, d_sorted, d_perm);
-        if (rc != FHX_OK) return vp->fail(rc, std::string("sort: ") + fhx_last_error(vp->sorter));
+        if (rc != FHX_OK) return fhx::fail(vp, rc, std::string("sort: ") + fhx_last_error(vp->sorter));
     }
     tmp.drop(d_keys);
     tmp.drop(d_perm);
@@ -465,8 +464,8 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
     const int64_t tiles = (pairs + fhxscan::TILE - 1) / fhxscan::TILE;
     unsigned int* d_tile_cnt = nullptr;
     unsigned long long *d_tile_off = nullptr, *d_head_at = nullptr;
-    TH_HIP(vp, tmp.get(&d_tile_cnt, (size_t)tiles));
-    TH_HIP(vp, tmp.get(&d_tile_off, (size_t)tiles));
+    TH_HIP(vp, tmp.get_n(&d_tile_cnt, (size_t)tiles));
+    TH_HIP(vp, tmp.get_n(&d_tile_off, (size_t)tiles));
     hipLaunchKernelGGL(fhxscan::count_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned long long*)d_sorted, pairs,
                        d_tile_cnt);
     hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned int*)d_tile_cnt, tiles, d_tile_off,
@@ -477,8 +476,8 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
     TH_HIP(vp, hipStreamSynchronize(vp->stream));
     if (cells == 0 || cells > (unsigned long long)pairs) return refuse(FHX_ERR_INTERNAL, FHX_VP_INTERNAL, 0, "the run heads do not match the keys");
     const int64_t stride = ((int64_t)cells + 63) / 64 * 64;                   // every column starts on a 256-byte boundary
-    TH_HIP(vp, tmp.get(&d_head_at, (size_t)cells));
-    TH_HIP(vp, hipMalloc((void**)&vp->d_cols, (size_t)stride * 5 * sizeof(int32_t)));
+    TH_HIP(vp, tmp.get_n(&d_head_at, (size_t)cells));
+    TH_HIP(vp, fhx::dev_malloc(&vp->d_cols, (size_t)stride * 5 * sizeof(int32_t)));
     vp->col_stride = stride;
     int32_t* c = vp->d_cols;
     hipLaunchKernelGGL(vp_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned long long*)d_sorted, pairs,
@@ -507,7 +506,7 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
 extern "C" {
 
 int fhx_vp_create(int device, fhx_vp** out) {
-    const int rc = fhx::text_handle_create(device, out);
+    const int rc = fhx::handle_create(device, out);
     if (rc == FHX_OK && fhx_create(device, &(*out)->sorter) != FHX_OK) {
         fhx_vp_destroy(*out);
         *out = nullptr;
@@ -523,7 +522,7 @@ void fhx_vp_destroy(fhx_vp* vp) {
     });
 }
 
-const char* fhx_vp_last_error(const fhx_vp* vp) { return vp ? vp->err.c_str() : "null context"; }
+const char* fhx_vp_last_error(const fhx_vp* vp) { return fhx::handle_last_error(vp); }
 
 int fhx_vp_bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_t* why, int64_t* bad_line) {
     using namespace vpd;

@@ -314,6 +314,9 @@ int fhx_k3_compact_variant(fhx_ctx* ctx, int32_t* out);
  * fhx_bh and fhx_bh_local_sort calls (the library itself goes beyond 1 only from 6.7e7 rows on), 0 gives the choice back;
  * anything else is FHX_ERR_ARG.  Results do not depend on it.  Not for production callers. */
 int fhx_debug_k3_tiles_per_group(fhx_ctx* ctx, int per);
+/* Test hook: the device blocks this process holds through the library, over all handles of every kind, and their bytes as they were
+ * asked for.  Either pointer may be null.  Compare two readings; other handles of the process are in the absolute values. */
+int fhx_debug_device_blocks(int64_t* blocks, int64_t* bytes);
 /* Test hook: on = 1 makes this context's later fhx_pass_stats calls classify the rows from their three int32 columns (12 bytes a
  * row) instead of the 32-bit key column written at load; 0 gives the key column back; anything else is FHX_ERR_ARG.  Results do
  * not depend on it.  Not for production callers. */
