@@ -14,6 +14,7 @@ What fixes the output (reference lines in brackets):
   * -p 100 / 0 < -p < 100: nodes by (q, -CC, bin_lo, bin_hi) (a total order), greedy pick, a pick suppresses later nodes
     of the component within -n bins in both coordinates [470-600]; 0 < -p < 100 stops at the component's percentile
     (custom_percent [36-52]); with -s 1 the stop test compares -q with a positive bound and stops at once [508] (kept)
+  * -p above 100: none of the three branches [421, 470, 608] runs, the file holds the header alone
   * -p 0 depends on CPython's set iteration order (non-total comparisons over list(set)) [417-437]: not reproducible, raises.
 """
 import gzip
@@ -35,9 +36,14 @@ HEADER = "\t".join(["chr1", "mid1", "chr2", "mid2", "CC", "p", "fdr", "bin1_low"
 
 
 def combine_lines(in_path, res, header=1, conn=8, pct=100, neigh=2, order=0):
-    """-> list of output lines (without the header), in the reference's order."""
+    """-> list of output lines (without the header), in the reference's order.
+
+    -p above 100 gives no line: the reference's three branches test TopPctElem == 0 [421], 0 < TopPctElem < 100 [470] and
+    TopPctElem == 100 [608]; none of them runs, so only the header is written."""
     if pct == 0:
         raise NotImplementedError("-p 0 depends on CPython set iteration order (CombineNearbyInteraction.py:417-437)")
+    if pct > 100:
+        return []
     bin_size = int(res)
     thr = int(neigh) * bin_size
     with _open(in_path) as f:

@@ -728,20 +728,46 @@ def make_f10():
              ("c2_combine_synth_s1", "synth_sig_clusters.txt.gz", ["-s", "1"]),
              ("c2_combine_synth_p30_s1", "synth_sig_clusters.txt.gz", ["-p", "30", "-s", "1"]),
              ("c2_combine_synth_nohdr", "synth_sig_clusters_nohdr.txt.gz", ["-H", "0"])]
+    _f10_run_cases(tool, cases, 40000)
+    make_f10_built(tool)
+
+
+def _f10_run_cases(tool, cases, res):
+    """the real script on each (name, input, extra flags): its output file and a small description of the run"""
+    import subprocess
     for name, inp, extra in cases:
         tmp = tempfile.mkdtemp(prefix="cni_golden_")
         out = os.path.join(tmp, "merged.gz")
         env = dict(os.environ, LC_ALL="C")
-        subprocess.run([sys.executable, tool, "-i", os.path.join(DATA, inp), "-o", out, "-r", "40000"] + extra, check=True,
+        subprocess.run([sys.executable, tool, "-i", os.path.join(DATA, inp), "-o", out, "-r", str(res)] + extra, check=True,
                        stdout=subprocess.DEVNULL, env=env)
         with gzip.open(out, "rb") as f:
             text = f.read()
         _write_gz(os.path.join(HERE, name + ".out.gz"), text.decode())
         with open(os.path.join(HERE, name + ".json"), "w") as f:
-            json.dump(dict(name=name, input=inp, argv=["-r", "40000"] + extra, out_md5=hashlib.md5(text).hexdigest(),
+            json.dump(dict(name=name, input=inp, argv=["-r", str(res)] + extra, out_md5=hashlib.md5(text).hexdigest(),
                            out_lines=len(text.decode().split("\n"))), f, indent=1)
         shutil.rmtree(tmp)
         print("  %s: %d lines" % (name, len(text.decode().split("\n"))))
+
+
+def make_f10_built(tool=None):
+    """(c) built: the shapes of tests/cni_shapes.py that random tables do not reach (a chain with rows written (hi, lo), a square
+    of ties, diagonal cells, one lattice under two names, q = 0.0), small because the reference pairs all nodes; the flags include
+    -p 101, for which the real script writes the header alone"""
+    tool = tool or os.path.join(REF_PKG, "utils", "CombineNearbyInteraction.py")
+    sys.path.insert(0, os.path.dirname(HERE))
+    import cni_shapes
+    rows = cni_shapes.golden_built_rows()
+    _write_gz(os.path.join(DATA, "built_sig_shapes.txt.gz"), cni_shapes.text_of(rows))
+    print("  built input: %d rows" % len(rows))
+    inp = "built_sig_shapes.txt.gz"
+    _f10_run_cases(tool, [("c3_combine_built_default", inp, []),
+                          ("c3_combine_built_n0", inp, ["-n", "0"]),
+                          ("c3_combine_built_p101", inp, ["-p", "101"]),
+                          ("c3_combine_built_c4_n1", inp, ["-c", "4", "-n", "1"]),
+                          ("c3_combine_built_s1_p50", inp, ["-s", "1", "-p", "50"]),
+                          ("c3_combine_built_p1", inp, ["-p", "1"])], cni_shapes.RES)
 
 
 def make_f11():
@@ -960,6 +986,6 @@ def make_calib():
 if __name__ == "__main__":
     which = [a.lower() for a in sys.argv[1:]] or ["f1", "f2", "f3", "f4", "f5", "f6", "f7", "f8", "f9", "f10", "f11", "f12", "f13", "f15"]
     jobs = dict(f1=make_f1, f2=make_f2, f3=make_f3, f4=make_f4, f5=make_f5, f6=make_f6, f7=make_f7, f8=make_f8, f9=make_f9,
-                f10=make_f10, f11=make_f11, f12=make_f12, f13=make_f13, f14=make_f14, f15=make_f15, calib=make_calib)
+                f10=make_f10, f10built=make_f10_built, f11=make_f11, f12=make_f12, f13=make_f13, f14=make_f14, f15=make_f15, calib=make_calib)
     for w in which:
         jobs[w]()
