@@ -328,14 +328,18 @@ __global__ __launch_bounds__(64) void gz_inflate(const unsigned char* __restrict
             for (int s = n_lit + lane; s < 288; s += 64) L.lens[s] = 0;
         }
         {
-            // zlib's (and puff.c's) rule: an incomplete code is accepted only when it is a single code of length 1
+            // zlib's (and puff.c's) rule: an incomplete code is accepted only when it is a single code of length 1 - or, for the
+            // distances, no code at all (RFC 1951 3.2.7: a block of literals only; zlib's inflate_table `max == 0`).  The
+            // literal/length set always holds end-of-block.  With no distance code dist_fast is all zeros and decode_slow finds
+            // nothing, so a length symbol in such a block ends in E_SYMBOL.
             const int left_l = construct(L.lens, 288, L.lit_cnt, L.lit_sym, L.offs);
             if (left_l < 0 || (left_l > 0 && !(288 - (int)uni(L.lit_cnt[0]) == 1 && uni(L.lit_cnt[1]) == 1))) {
                 err = E_TABLE;
                 break;
             }
             const int left_d = construct(L.lens + 288, 32, L.dist_cnt, L.dist_sym, L.offs);
-            if (left_d < 0 || (left_d > 0 && !(32 - (int)uni(L.dist_cnt[0]) == 1 && uni(L.dist_cnt[1]) == 1))) {
+            const int used_d = 32 - (int)uni(L.dist_cnt[0]);
+            if (left_d < 0 || (left_d > 0 && !(used_d == 0 || (used_d == 1 && uni(L.dist_cnt[1]) == 1)))) {
                 err = E_TABLE;
                 break;
             }

@@ -2,8 +2,10 @@
 
 fhx_debug_inflate_file inflates a file of size-tagged gzip members on the GPU and returns the text; the checker is Python's
 zlib/gzip (what the reference reads its inputs with, fithic/fithic.py:404).  Every block type of RFC 1951, every zlib strategy,
-the window limits (distance 32 768, length 258), members of all sizes, BGZF containers - and damaged streams, which must come
-back as FHX_ERR_UNSUPPORTED (the caller then lets zlib on the host report the error) and never as different text."""
+length 258, members of all sizes, BGZF containers - and damaged streams, which must come back as FHX_ERR_UNSUPPORTED (the caller
+then lets zlib on the host report the error) and never as different text.  Every stream here comes out of zlib's encoder, which
+looks back 32 506 bytes at the most: the window limit (distance 32 768) and the rest of RFC 1951 that zlib never writes are in
+tests/test_gpu_inflate_streams.py."""
 import gzip
 import os
 import random
@@ -80,8 +82,8 @@ def test_every_block_type_strategy_and_level(tmp_path):
     add(b"x")
     add(b"\0" * 1_000_000)                                   # distance 1, length 258, over and over
     block = bytes(rng.getrandbits(8) for _ in range(32768))
-    add(block * 6, level=9)                                  # matches at the largest distance
-    add((block[:32767] + b"!") * 5 + block[:100], level=9)
+    add(block * 6, level=9)                                  # a repeat at distance 32 768: beyond zlib's reach, twelve stored blocks
+    add((block[:32767] + b"!") * 5 + block[:100], level=9)   # the same: stored blocks and one fixed block of literals, no match
     add(text[:500_000], flushes=[(1000, zlib.Z_SYNC_FLUSH), (70_000, zlib.Z_FULL_FLUSH), (70_001, zlib.Z_SYNC_FLUSH)])
     add(text[:10_000], name=b"contacts.txt")                 # FNAME after the extra field
     add(bytes(range(256)) * 50, strategy=zlib.Z_FIXED)
