@@ -290,12 +290,24 @@ SYMBOLS = {
     "fhx_jc_fetch_rows": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
     "fhx_jc_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
     "fhx_jc_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "fhx_dg_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "fhx_dg_destroy": (None, [ctypes.c_void_p]),
+    "fhx_dg_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
+    "fhx_dg_digest_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, _I32P, _I32P, ctypes.c_int32, _I32P, _I64P]),
+    "fhx_dg_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P, _I64P]),
+    "fhx_dg_name": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_int64]),
+    "fhx_dg_contig_length": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64]),
+    "fhx_dg_fetch_sites": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P]),
+    "fhx_dg_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
+    "fhx_dg_write_fragments": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int64, _I64P, _I32P, _I32P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "fhx_dg_write_bed": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int64, _I64P, _I32P, _I32P, ctypes.c_int64,
+                                        ctypes.c_int32]),
 }
 
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
 # not recompile K1, K3, the Knight-Ruiz path or the host stages.  Flags are the same for every unit - -ffp-contract=off matters
 # for bit-exactness on the host (FITPACK, lgamma tables) as much as on the device (fhx_bdtrc.hpp).
-SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_juicer.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
+SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_juicer.hip", "fhx_digest.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
 COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread"]
 LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-lz", "-ldl"]
 OBJ_DIR = os.path.join(CSRC, "_obj")
@@ -1723,3 +1735,82 @@ class JcContext(_Handle):
 
     def stream(self):
         return self.L.fhx_jc_stream(self.h) or 0
+
+
+# ---- FASTA -> cut sites -> the fragments of `fithic -r 0` (fhx_dg_*) ---------------------------------------------------------
+(DG_OK, DG_BYTES, DG_BLANK, DG_LONG_LINE, DG_CONTIG_LENGTH, DG_EMPTY_NAME, DG_NAME_CHARS, DG_DUPLICATE, DG_NO_HEADER, DG_INTERNAL) = range(10)
+DG_MAX_MOTIF, DG_MAX_MOTIFS = 16, 64
+DG_STAGE_NAMES = ("read_upload", "newline_scan", "class_pass", "sites", "sort", "fetch")
+
+
+class DgRefused(FhxError):
+    """fhx_dg_digest_file refused the file: why = one of DG_*, line = the smallest offending 1-based line"""
+
+    def __init__(self, code, message, why, line):
+        super().__init__(code, message)
+        self.why, self.line = int(why), int(line)
+
+
+class DgContext(_Handle):
+    """One FASTA digested on one GPU (fhx_dg_*): contig names and lengths on the host, the sorted cut sites in HBM.  Raises without
+    the library or a GPU."""
+    PREFIX = "dg"
+    REFUSED = DgRefused
+
+    def digest_file(self, path, motifs):
+        """motifs = [(letters of acgt, offset of the cut), ...], an N of the site expanded.  DgRefused for a file outside the
+        device grammar: the handle is then empty."""
+        buf = np.zeros((len(motifs), DG_MAX_MOTIF), np.uint8)
+        for k, (m, _) in enumerate(motifs):
+            buf[k, :len(m)] = np.frombuffer(m.encode("ascii"), np.uint8)
+        lengths = np.array([len(m) for m, _ in motifs], np.int32)
+        offsets = np.array([o for _, o in motifs], np.int32)
+        why, line = ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self.L.fhx_dg_digest_file(self.h, os.fsencode(path), buf.ctypes.data_as(ctypes.c_char_p), _ptr(lengths, ctypes.c_int32),
+                                       _ptr(offsets, ctypes.c_int32), len(motifs), ctypes.byref(why), ctypes.byref(line))
+        self._chk(rc, why.value, line.value)
+
+    def counts(self):
+        """lines read, contigs, their bases in all, cut sites"""
+        v = [ctypes.c_int64(0) for _ in range(4)]
+        self._chk(self.L.fhx_dg_counts(self.h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("lines", "contigs", "bases", "sites"), [x.value for x in v]))
+
+    def names(self):
+        return [self.L.fhx_dg_name(self.h, k) for k in range(self.counts()["contigs"])]
+
+    def lengths(self):
+        return np.array([self.L.fhx_dg_contig_length(self.h, k) for k in range(self.counts()["contigs"])], np.int64)
+
+    def fetch_sites(self):
+        """(contig, position), int32, ordered by contig, then position; equal sites are kept"""
+        n = self.counts()["sites"]
+        contig, position = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._chk(self.L.fhx_dg_fetch_sites(self.h, _ptr(contig, ctypes.c_int32), _ptr(position, ctypes.c_int32)))
+        return contig, position
+
+    def stage_seconds(self):
+        out = np.zeros(len(DG_STAGE_NAMES), np.float64)
+        self._chk(self.L.fhx_dg_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
+        return dict(zip(DG_STAGE_NAMES, out.tolist()))
+
+
+def dg_write_fragments(path, lengths, site_contig, site_position, gzip_level=6, threads=0):
+    """the fragments file of `fithic -r 0` (gzip): `chr<k> \\t 0 \\t end \\t 1 \\t 1` per fragment of the digest.  Host side, no GPU."""
+    lengths = np.ascontiguousarray(lengths, np.int64)
+    c, p = _i32(site_contig), _i32(site_position)
+    rc = lib().fhx_dg_write_fragments(os.fsencode(path), len(lengths), _ptr(lengths, ctypes.c_int64), _ptr(c, ctypes.c_int32),
+                                      _ptr(p, ctypes.c_int32), len(c), int(gzip_level), int(threads))
+    if rc != FHX_OK:
+        raise FhxError(rc, "fhx_dg_write_fragments(%s)" % path)
+
+
+def dg_write_bed(path, names, lengths, site_contig, site_position, threads=0):
+    """HiC-Pro's fragment bed of the digest (plain text); names are bytes.  Host side, no GPU."""
+    lengths = np.ascontiguousarray(lengths, np.int64)
+    c, p = _i32(site_contig), _i32(site_position)
+    arr = (ctypes.c_char_p * max(len(names), 1))(*names)
+    rc = lib().fhx_dg_write_bed(os.fsencode(path), arr, len(lengths), _ptr(lengths, ctypes.c_int64), _ptr(c, ctypes.c_int32),
+                                _ptr(p, ctypes.c_int32), len(c), int(threads))
+    if rc != FHX_OK:
+        raise FhxError(rc, "fhx_dg_write_bed(%s)" % path)

@@ -1080,6 +1080,81 @@ int fhx_vp_write_contacts(const char* path, const char* const* chr_names, int32_
     return ok ? FHX_OK : FHX_ERR_ARG;
 }
 
+// The two files of a digest (fhx_digest.hip): HiC-Pro's fragment bed and what createFitHiCFragments-nonfixedsize.sh:18-33 makes
+// of it.  A contig of k sites has k + 1 fragments, one row each in either file: rows 0 .. n_sites + n_contigs - 1 are cut into
+// blocks, a block finds its first contig by bisection, and row r of contig c ends at site r - c (or at the contig's length).
+static int write_digest(const char* path, const char* const* names, int64_t n_contigs, const int64_t* lengths, const int32_t* site_contig,
+                        const int32_t* site_position, int64_t n_sites, bool bed, int32_t gzip_level, int32_t n_threads) {
+    if (!path || n_contigs < 1 || !lengths || n_sites < 0 || (bed && !names)) return FHX_ERR_ARG;
+    if (n_sites > 0 && (!site_contig || !site_position)) return FHX_ERR_ARG;
+    if (gzip_level < 0 || gzip_level > 9) gzip_level = 6;
+    if (n_threads <= 0) n_threads = fhx::usable_cpus();
+    std::vector<int64_t> row0((size_t)n_contigs + 1, 0);                      // the first row of every contig
+    {
+        std::vector<int64_t> n_of((size_t)n_contigs, 0);
+        for (int64_t i = 0; i < n_sites; ++i) {
+            if (site_contig[i] < 0 || site_contig[i] >= n_contigs || (i > 0 && site_contig[i] < site_contig[i - 1])) return FHX_ERR_ARG;
+            ++n_of[(size_t)site_contig[i]];
+        }
+        for (int64_t c = 0; c < n_contigs; ++c) row0[(size_t)c + 1] = row0[(size_t)c] + n_of[(size_t)c] + 1;
+    }
+    std::vector<size_t> name_len((size_t)(bed ? n_contigs : 0));
+    for (size_t c = 0; c < name_len.size(); ++c) name_len[c] = std::strlen(names[c]);
+    std::FILE* f = std::fopen(path, "wb");
+    if (!f) return FHX_ERR_ARG;
+    const int64_t n_rows = n_sites + n_contigs, block = 1 << 18;
+    const int64_t n_blocks = (n_rows + block - 1) / block;
+    auto produce = [&](int64_t blk, std::string& text, std::string& out) -> bool {
+        const int64_t lo = blk * block, hi = std::min(n_rows, lo + block);
+        std::string& dst = bed ? out : text;                                  // the bed is plain text
+        dst.clear();
+        int64_t c = (std::upper_bound(row0.begin(), row0.end(), lo) - row0.begin()) - 1;
+        char buf[64];
+        for (int64_t r = lo; r < hi; ++r) {
+            while (r >= row0[(size_t)c + 1]) ++c;
+            const int64_t k = r - row0[(size_t)c];                            // the fragment within the contig, from 0
+            const int64_t s = r - c;                                          // the site that ends it, when it is not the last
+            const long long start = k == 0 ? 0 : site_position[s - 1];
+            const long long end = r + 1 == row0[(size_t)c + 1] ? (long long)lengths[c] : site_position[s];
+            if (bed) {
+                dst.append(names[c], name_len[(size_t)c]);
+                dst.push_back('\t');
+                dst.append(buf, (size_t)put_int(buf, start));
+                dst.push_back('\t');
+                dst.append(buf, (size_t)put_int(buf, end));
+                dst.append("\tHIC_");
+                dst.append(names[c], name_len[(size_t)c]);
+                dst.push_back('_');
+                dst.append(buf, (size_t)put_int(buf, k + 1));
+                dst.append("\t0\t+\n");
+            } else {
+                dst.append("chr");
+                dst.append(buf, (size_t)put_int(buf, c + 1));
+                dst.append("\t0\t");
+                dst.append(buf, (size_t)put_int(buf, end));
+                dst.append("\t1\t1\n");
+            }
+        }
+        if (bed) return true;
+        out.clear();
+        return deflate_member(text, gzip_level, out);
+    };
+    bool ok = ordered_parallel_write(f, n_blocks, n_threads, produce);
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) std::remove(path);
+    return ok ? FHX_OK : FHX_ERR_ARG;
+}
+
+int fhx_dg_write_fragments(const char* path, int64_t n_contigs, const int64_t* lengths, const int32_t* site_contig, const int32_t* site_position,
+                           int64_t n_sites, int32_t gzip_level, int32_t n_threads) {
+    return write_digest(path, nullptr, n_contigs, lengths, site_contig, site_position, n_sites, false, gzip_level, n_threads);
+}
+
+int fhx_dg_write_bed(const char* path, const char* const* names, int64_t n_contigs, const int64_t* lengths, const int32_t* site_contig,
+                     const int32_t* site_position, int64_t n_sites, int32_t n_threads) {
+    return write_digest(path, names, n_contigs, lengths, site_contig, site_position, n_sites, true, 6, n_threads);
+}
+
 int64_t fhx_table_rows(const fhx_table* t) { return t ? (t->row0.empty() ? 0 : (int64_t)t->row0.back()) : -1; }
 int32_t fhx_table_n_names(const fhx_table* t) { return t ? (int32_t)t->names.size() : -1; }
 const char* fhx_table_name(const fhx_table* t, int32_t i) {

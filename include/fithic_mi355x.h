@@ -881,6 +881,52 @@ int fhx_jc_fetch_rows(fhx_jc* jc, int32_t* chr1, int32_t* mid1, int32_t* chr2, i
 void* fhx_jc_device_ptr(fhx_jc* jc, int32_t which);
 void* fhx_jc_stream(fhx_jc* jc);
 
+/* ---- a FASTA cut with restriction enzymes -> the fragments file of `fithic -r 0`
+ * (fithic/utils/createFitHiCFragments-nonfixedsize.sh: HiC-Pro's digest_genome.py, then the script's loop; csrc/fhx_digest.hip).
+ * The FASTA, plain or gzipped, goes through HBM in batches cut at the last newline (FHX_DG_BATCH_BYTES overrides the batch size of
+ * 256 MB; 8192 at least).  A line that begins with `>` starts a contig named by the bytes behind `>` up to the first blank, tab or
+ * \r; every other line adds its bytes to the contig's sequence, case folded; lines before the first header add to nothing.
+ * motifs: n_motifs x FHX_DG_MAX_MOTIF bytes, each motif's lengths[m] letters of acgt in either case first (an N of the site comes
+ * expanded), offsets[m] = where the site cuts (0 .. lengths[m]).  Every start s at which the sequence equals a motif gives the site
+ * s + offset; overlapping matches count, a motif runs across line ends and never across a header.  Per contig the sites come
+ * sorted, equal ones kept.
+ * Anything else is refused and the handle is left empty: *why = one of FHX_DG_*, *bad_line = the smallest offending 1-based line
+ * (of a contig that is too long: its header's).  Return value: FHX_ERR_UNSUPPORTED. */
+#define FHX_DG_OK 0
+#define FHX_DG_BYTES 1             /* a NUL, a control byte other than \n and a \r directly before \n, DEL, a non-ASCII byte */
+#define FHX_DG_BLANK 2             /* a blank or a tab in a line that is no header */
+#define FHX_DG_LONG_LINE 3         /* a line of more than 4096 bytes */
+#define FHX_DG_CONTIG_LENGTH 4     /* a contig of more than 2^31 - 1 bases */
+#define FHX_DG_EMPTY_NAME 5        /* `>` alone, or `>` followed by a blank or a tab */
+#define FHX_DG_NAME_CHARS 6        /* a name that holds one of * ? [ \ */
+#define FHX_DG_DUPLICATE 7         /* a name seen before */
+#define FHX_DG_NO_HEADER 8         /* no header line in the file (bad_line = 1) */
+#define FHX_DG_INTERNAL 9          /* a device-side consistency check failed */
+#define FHX_DG_MAX_MOTIF 16        /* bases per motif */
+#define FHX_DG_MAX_MOTIFS 64
+#define FHX_DG_STAGES 6            /* read + upload, newline scan, class pass, sites, sort, names + fetch: of the last digest */
+typedef struct fhx_dg fhx_dg;
+int fhx_dg_create(int device, fhx_dg** out);
+void fhx_dg_destroy(fhx_dg* dg);
+const char* fhx_dg_last_error(const fhx_dg* dg);
+int fhx_dg_digest_file(fhx_dg* dg, const char* path, const char* motifs, const int32_t* lengths, const int32_t* offsets, int32_t n_motifs,
+                       int32_t* why, int64_t* bad_line);
+/* lines read, contigs, their bases in all, cut sites */
+int fhx_dg_counts(const fhx_dg* dg, int64_t* n_lines, int64_t* n_contigs, int64_t* seq_bytes, int64_t* n_sites);
+const char* fhx_dg_name(const fhx_dg* dg, int64_t contig);         /* NULL outside 0 .. n_contigs - 1; valid until the next digest */
+int64_t fhx_dg_contig_length(const fhx_dg* dg, int64_t contig);    /* -1 outside 0 .. n_contigs - 1 */
+int fhx_dg_fetch_sites(fhx_dg* dg, int32_t* contig, int32_t* position);   /* n_sites each, ordered by contig, then position */
+int fhx_dg_stage_seconds(const fhx_dg* dg, double* seconds);
+/* Host side, no GPU: the two files made of a digest.  sites are ordered by (contig, position); a contig with the sites c1 <= ... <= ck
+ * has the k + 1 fragments [0, c1], [c1, c2], ..., [ck, length], empty ones included.
+ *   fhx_dg_write_fragments: gzip, one line `chr<contig + 1> \t 0 \t end \t 1 \t 1 \n` per fragment - what the script's loop writes
+ *   fhx_dg_write_bed: plain text, HiC-Pro's `name \t start \t end \t HIC_<name>_<k> \t 0 \t + \n`, k from 1 within the contig
+ * gzip_level outside 0-9 means 6; n_threads <= 0 means every usable CPU. */
+int fhx_dg_write_fragments(const char* path, int64_t n_contigs, const int64_t* lengths, const int32_t* site_contig, const int32_t* site_position,
+                           int64_t n_sites, int32_t gzip_level, int32_t n_threads);
+int fhx_dg_write_bed(const char* path, const char* const* names, int64_t n_contigs, const int64_t* lengths, const int32_t* site_contig,
+                     const int32_t* site_position, int64_t n_sites, int32_t n_threads);
+
 #ifdef __cplusplus
 }
 #endif
