@@ -302,12 +302,23 @@ SYMBOLS = {
     "fhx_dg_write_fragments": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int64, _I64P, _I32P, _I32P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     "fhx_dg_write_bed": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int64, _I64P, _I32P, _I32P, ctypes.c_int64,
                                         ctypes.c_int32]),
+    # HiC-Pro allValidPairs -> contact counts between the restriction fragments of a digest (no reference script)
+    "fhx_fp_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "fhx_fp_destroy": (None, [ctypes.c_void_p]),
+    "fhx_fp_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
+    "fhx_fp_load_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, _I32P, ctypes.c_int32, _I64P, ctypes.c_int32, _I32P, ctypes.c_int64]),
+    "fhx_fp_bin_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, _I64P, _I32P, _I64P]),
+    "fhx_fp_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P, _I64P, _I64P]),
+    "fhx_fp_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
+    "fhx_fp_fetch_cells": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
+    "fhx_fp_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
+    "fhx_fp_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
 }
 
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
 # not recompile K1, K3, the Knight-Ruiz path or the host stages.  Flags are the same for every unit - -ffp-contract=off matters
 # for bit-exactness on the host (FITPACK, lgamma tables) as much as on the device (fhx_bdtrc.hpp).
-SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_juicer.hip", "fhx_digest.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
+SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_juicer.hip", "fhx_digest.hip", "fhx_fragpairs.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
 COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread"]
 LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-lz", "-ldl"]
 OBJ_DIR = os.path.join(CSRC, "_obj")
@@ -1814,3 +1825,75 @@ def dg_write_bed(path, names, lengths, site_contig, site_position, threads=0):
                                 _ptr(p, ctypes.c_int32), len(c), int(threads))
     if rc != FHX_OK:
         raise FhxError(rc, "fhx_dg_write_bed(%s)" % path)
+
+
+# ---- allValidPairs -> contact counts between restriction fragments (fhx_fp_*) -------------------------------------------------
+(FP_OK, FP_TOKENS, FP_NAME, FP_POSITION, FP_RANGE, FP_BYTES, FP_LONG_LINE, FP_COUNT, FP_INTERNAL, FP_PAIRS) = range(10)
+FP_MAX_CONTIGS, FP_NAME_BYTES = 4096, 64
+FP_STAGE_NAMES = ("read_upload", "newline_scan", "parse", "sort", "cells", "table")
+
+
+class FpRefused(FhxError):
+    """fhx_fp_bin_file refused the file: why = one of FP_*, line = the smallest offending 1-based line (0: the reason belongs to
+    no line)"""
+
+    def __init__(self, code, message, why, line):
+        super().__init__(code, message)
+        self.why, self.line = int(why), int(line)
+
+
+class FpContext(_Handle):
+    """A validPairs file binned to the fragments of a digest, sorted and counted on one GPU (fhx_fp_*).  Raises without the library
+    or a GPU."""
+    PREFIX = "fp"
+    REFUSED = FpRefused
+
+    def __init__(self, device=0):
+        self.n_cells = 0
+        super().__init__(device)
+
+    def load_table(self, names, name_contig, first, ends):
+        """names: bytes of 1 to 63 bytes each; name_contig[k] = the contig name k stands for, -1 = its lines are dropped; first:
+        n_contigs + 1 row offsets into ends, the ascending fragment ends of every contig"""
+        text = np.zeros((len(names), FP_NAME_BYTES), np.uint8)
+        for k, n in enumerate(names):
+            if not 1 <= len(n) < FP_NAME_BYTES:
+                raise ValueError("name %r: 1 to %d bytes are expected" % (n, FP_NAME_BYTES - 1))
+            text[k, :len(n)] = np.frombuffer(n, np.uint8)
+        which, ends = _i32(name_contig), _i32(ends)
+        first = np.ascontiguousarray(first, np.int64)
+        self.n_cells = 0
+        self._chk(self.L.fhx_fp_load_table(self.h, text.ctypes.data_as(ctypes.c_char_p), _ptr(which, ctypes.c_int32), len(names),
+                                           _ptr(first, ctypes.c_int64), len(first) - 1, _ptr(ends, ctypes.c_int32), len(ends)))
+
+    def bin_file(self, path):
+        """-> number of cells; FpRefused for a file outside the device grammar"""
+        n, why, line = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        self.n_cells = 0
+        rc = self.L.fhx_fp_bin_file(self.h, os.fsencode(path), ctypes.byref(n), ctypes.byref(why), ctypes.byref(line))
+        self._chk(rc, why.value, line.value)
+        self.n_cells = n.value
+        return self.n_cells
+
+    def counts(self):
+        """lines read, pairs kept, lines dropped for a name, lines dropped as same-fragment, cells"""
+        v = [ctypes.c_int64(0) for _ in range(5)]
+        self._chk(self.L.fhx_fp_counts(self.h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("lines", "pairs", "dropped_name", "same_fragment", "cells"), [x.value for x in v]))
+
+    def stage_seconds(self):
+        out = np.zeros(len(FP_STAGE_NAMES), np.float64)
+        self._chk(self.L.fhx_fp_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
+        return dict(zip(FP_STAGE_NAMES, out.tolist()))
+
+    def fetch_cells(self):
+        """(contig1, end1, contig2, end2, count), int32, in ascending (fragment row 1, fragment row 2)"""
+        cols = [np.zeros(self.n_cells, np.int32) for _ in range(5)]
+        self._chk(self.L.fhx_fp_fetch_cells(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
+        return cols
+
+    def device_ptrs(self):
+        return [self.L.fhx_fp_device_ptr(self.h, k) or 0 for k in range(5)]
+
+    def stream(self):
+        return self.L.fhx_fp_stream(self.h) or 0

@@ -32,8 +32,8 @@ inside); a line of more than 4096 bytes (an unwrapped FASTA: re-wrap it, e.g. `f
 would end in a failing gzip).  The grammar of the bytes holds for the lines before the first header too.  Limits, a ValueError
 before any file is opened: a motif of 1 to 16 bases, at most 3 N per site, at most 64 expanded motifs in all.
 Not done: an unwrapped FASTA (lines over 4096 bytes); IUPAC codes other than N; minimum or maximum fragment size filters; a
-midpoint variant of column 3; binning read pairs to the fragments.  There is no CPU implementation here: without the library or
-a GPU `read` raises.
+midpoint variant of column 3.  Read pairs are binned to the fragments by fithic_amd.fragpairs.  There is no CPU implementation here:
+without the library or a GPU `read` raises.
 """
 import argparse
 import itertools

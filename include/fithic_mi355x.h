@@ -927,6 +927,53 @@ int fhx_dg_write_fragments(const char* path, int64_t n_contigs, const int64_t* l
 int fhx_dg_write_bed(const char* path, const char* const* names, int64_t n_contigs, const int64_t* lengths, const int32_t* site_contig,
                      const int32_t* site_position, int64_t n_sites, int32_t n_threads);
 
+/* ---- HiC-Pro allValidPairs -> contact counts between the RESTRICTION FRAGMENTS of a digest, for `fithic -r 0`
+ * (csrc/fhx_fragpairs.hip; the reference has no script for it, the semantics are this project's: INTEGRATION.md).
+ * One handle per GPU, independent of fhx_ctx.  fhx_fp_load_table gives the fragments: per contig c (0-based, file order) the
+ * ascending ends E_c of its fragments - its cut sites with duplicates kept, then its length - as rows first[c] .. first[c + 1] - 1 of
+ * `ends` (first[0] = 0, first[n_contigs] = n_frags, every contig has at least one row), and the names a line may use:
+ * name_text holds n_names x FHX_FP_NAME_BYTES bytes, each name zero-padded (1 to 63 bytes of name, no two equal), name_contig[k]
+ * is the contig that name k stands for or -1 for a name whose lines are dropped.  At most FHX_FP_MAX_CONTIGS contigs, twice as
+ * many names, fewer than 2^31 fragments: FHX_ERR_UNSUPPORTED beyond that, FHX_ERR_ARG for a table that is not as described.
+ * fhx_fp_bin_file takes the file (plain text, or gzip: it is inflated on the host first) through HBM in batches cut at the last
+ * newline (FHX_FP_BATCH_BYTES overrides the batch size of 256 MB; 8192 at least).  A line is split on blanks and tabs; token 2 is
+ * name1, token 3 pos1, token 5 name2, token 6 pos2; nothing else is read.  A line with a dropped name is dropped and counted, its
+ * positions unread.  A position p (1-based) of contig c lies in the fragment bisect_left(E_c, p): start < p <= end, an empty fragment
+ * is never hit.  g = the row of the fragment; the pair is ordered g1 < g2, a pair with g1 == g2 is dropped and counted.  The cells
+ * (contig1, E[g1], contig2, E[g2], count: int32) stay in HBM in ascending (g1, g2).
+ * Taken: printable ASCII and tabs, lines of at most 4096 bytes ending in \n or \r\n (the last one may end with the file), at
+ * least 6 tokens per line, names of the table, positions of 1..10 digits from 1 to the contig's length.  Anything else is refused
+ * with nothing left loaded: *why = one of FHX_FP_*, *bad_line = the smallest offending 1-based line number (0 for the reasons that
+ * belong to no line).  Return value: FHX_ERR_UNSUPPORTED. */
+#define FHX_FP_OK 0
+#define FHX_FP_TOKENS 1            /* fewer than six tokens (an empty line included) */
+#define FHX_FP_NAME 2              /* a name that is neither a contig of the table nor dropped */
+#define FHX_FP_POSITION 3          /* a position that is not 1..10 digits */
+#define FHX_FP_RANGE 4             /* position 0, or one above the contig's length */
+#define FHX_FP_BYTES 5             /* a NUL, another control byte than tab, DEL, a non-ASCII byte, a \r that is not followed by \n */
+#define FHX_FP_LONG_LINE 6         /* a line of more than 4096 bytes */
+#define FHX_FP_COUNT 7             /* a cell hit by more than 2^31 - 1 pairs (no line number) */
+#define FHX_FP_INTERNAL 8          /* a device-side consistency check failed */
+#define FHX_FP_PAIRS 9             /* 2^32 or more pairs could be kept: the sort does not take them (no line number) */
+#define FHX_FP_MAX_CONTIGS 4096
+#define FHX_FP_NAME_BYTES 64
+#define FHX_FP_STAGES 6            /* read + upload, newline scan, parse, sort, cells: of the last file; then the last table's upload */
+typedef struct fhx_fp fhx_fp;
+int fhx_fp_create(int device, fhx_fp** out);
+void fhx_fp_destroy(fhx_fp* fp);
+const char* fhx_fp_last_error(const fhx_fp* fp);
+int fhx_fp_load_table(fhx_fp* fp, const char* name_text, const int32_t* name_contig, int32_t n_names, const int64_t* first, int32_t n_contigs,
+                      const int32_t* ends, int64_t n_frags);
+int fhx_fp_bin_file(fhx_fp* fp, const char* path, int64_t* n_cells, int32_t* why, int64_t* bad_line);
+/* lines read, pairs kept, lines dropped for a name, lines dropped as same-fragment, cells */
+int fhx_fp_counts(const fhx_fp* fp, int64_t* n_lines, int64_t* n_pairs, int64_t* n_dropped_name, int64_t* n_same_fragment, int64_t* n_cells);
+int fhx_fp_stage_seconds(const fhx_fp* fp, double* seconds);       /* FHX_FP_STAGES host clocks */
+int fhx_fp_fetch_cells(fhx_fp* fp, int32_t* chr1, int32_t* end1, int32_t* chr2, int32_t* end2, int32_t* count);   /* n_cells each */
+/* the columns in HBM (which 0..4 = contig1, end1, contig2, end2, count) and the stream they were written on, for
+ * fhx_load_pairs_device; valid until the next fhx_fp_bin_file / fhx_fp_load_table / fhx_fp_destroy */
+void* fhx_fp_device_ptr(fhx_fp* fp, int32_t which);
+void* fhx_fp_stream(fhx_fp* fp);
+
 #ifdef __cplusplus
 }
 #endif
