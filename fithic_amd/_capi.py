@@ -313,12 +313,25 @@ SYMBOLS = {
     "fhx_fp_fetch_cells": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
     "fhx_fp_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
     "fhx_fp_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
+    # contact rows in HBM summed onto N-fold coarser loci (no reference script)
+    "fhx_cz_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "fhx_cz_destroy": (None, [ctypes.c_void_p]),
+    "fhx_cz_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
+    "fhx_cz_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "fhx_cz_load_plan": (ctypes.c_int, [ctypes.c_void_p, _I64P, ctypes.c_int32, _I32P, _I32P, ctypes.c_int64, _I32P, _I32P, ctypes.c_int64]),
+    "fhx_cz_coarsen_device": (ctypes.c_int, [ctypes.c_void_p, _P, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int32, _I64P, _I32P, _I64P]),
+    "fhx_cz_coarsen_host": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P, ctypes.c_int64, ctypes.c_int32, _I64P, _I32P, _I64P]),
+    "fhx_cz_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P]),
+    "fhx_cz_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
+    "fhx_cz_fetch_cells": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
+    "fhx_cz_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
+    "fhx_cz_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
 }
 
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
 # not recompile K1, K3, the Knight-Ruiz path or the host stages.  Flags are the same for every unit - -ffp-contract=off matters
 # for bit-exactness on the host (FITPACK, lgamma tables) as much as on the device (fhx_bdtrc.hpp).
-SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_juicer.hip", "fhx_digest.hip", "fhx_fragpairs.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
+SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_juicer.hip", "fhx_digest.hip", "fhx_fragpairs.hip", "fhx_coarsen.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
 COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread"]
 LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-lz", "-ldl"]
 OBJ_DIR = os.path.join(CSRC, "_obj")
@@ -1897,3 +1910,86 @@ class FpContext(_Handle):
 
     def stream(self):
         return self.L.fhx_fp_stream(self.h) or 0
+
+
+# ---- contact rows in HBM summed onto N-fold coarser loci (fhx_cz_*) -----------------------------------------------------------
+(CZ_OK, CZ_LOCUS, CZ_COUNT, CZ_SUM, CZ_INTERNAL) = range(5)
+CZ_STAGE_NAMES = ("upload", "keys", "sort", "heads_sums", "cells", "plan")
+
+
+class CzRefused(FhxError):
+    """fhx_cz_coarsen_* refused the rows: why = one of CZ_*, row = the smallest offending 0-based row; for CZ_SUM, which belongs to
+    no row, the first cell above 2^31 - 1 as coarse row 1 << 32 | coarse row 2"""
+
+    def __init__(self, code, message, why, row):
+        super().__init__(code, message)
+        self.why, self.row = int(why), int(row)
+
+
+class CzContext(_Handle):
+    """Contact rows re-keyed to the coarse loci of a plan, sorted and summed on one GPU (fhx_cz_*).  Raises without the library or a
+    GPU."""
+    PREFIX = "cz"
+    REFUSED = CzRefused
+
+    def __init__(self, device=0):
+        self.n_cells = 0
+        super().__init__(device)
+
+    def reset(self):
+        self.n_cells = 0
+        self._chk(self.L.fhx_cz_reset(self.h))
+
+    def load_plan(self, first, fine_mid, group_of, coarse_chr, coarse_mid):
+        """first: n_chr + 1 row offsets into fine_mid by chromosome id, the strictly ascending mids of every id; group_of: the coarse
+        row of every fine row; (coarse_chr, coarse_mid): the coarse loci"""
+        first = np.ascontiguousarray(first, np.int64)
+        a = [_i32(v) for v in (fine_mid, group_of, coarse_chr, coarse_mid)]
+        self.n_cells = 0
+        self._chk(self.L.fhx_cz_load_plan(self.h, _ptr(first, ctypes.c_int64), len(first) - 1, _ptr(a[0], ctypes.c_int32), _ptr(a[1], ctypes.c_int32),
+                                          len(a[0]), _ptr(a[2], ctypes.c_int32), _ptr(a[3], ctypes.c_int32), len(a[2])))
+
+    def _done(self, rc, n, why, row):
+        self.n_cells = 0
+        self._chk(rc, why.value, row.value)
+        self.n_cells = n.value
+        return self.n_cells
+
+    def coarsen_device(self, ptrs, n, stream=0, diagonal=True):
+        """five device pointers (chr1, mid1, chr2, mid2, count: int32), n rows, the producer's stream -> number of cells; CzRefused
+        for rows outside the plan"""
+        cells, why, row = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self.L.fhx_cz_coarsen_device(self.h, *[_P(int(p)) if p else None for p in ptrs], int(n), _P(int(stream)) if stream else None,
+                                          int(bool(diagonal)), ctypes.byref(cells), ctypes.byref(why), ctypes.byref(row))
+        return self._done(rc, cells, why, row)
+
+    def coarsen_host(self, chr1, mid1, chr2, mid2, count, diagonal=True):
+        """the same on five host columns, uploaded first"""
+        cols = [_i32(v) for v in (chr1, mid1, chr2, mid2, count)]
+        cells, why, row = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+        rc = self.L.fhx_cz_coarsen_host(self.h, *[_ptr(v, ctypes.c_int32) for v in cols], len(cols[0]), int(bool(diagonal)),
+                                        ctypes.byref(cells), ctypes.byref(why), ctypes.byref(row))
+        return self._done(rc, cells, why, row)
+
+    def counts(self):
+        """rows given, rows dropped as diagonal, cells"""
+        v = [ctypes.c_int64(0) for _ in range(3)]
+        self._chk(self.L.fhx_cz_counts(self.h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("rows", "diagonal", "cells"), [x.value for x in v]))
+
+    def stage_seconds(self):
+        out = np.zeros(len(CZ_STAGE_NAMES), np.float64)
+        self._chk(self.L.fhx_cz_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
+        return dict(zip(CZ_STAGE_NAMES, out.tolist()))
+
+    def fetch_cells(self):
+        """(chr1, mid1, chr2, mid2, count), int32, in ascending (coarse row 1, coarse row 2)"""
+        cols = [np.zeros(self.n_cells, np.int32) for _ in range(5)]
+        self._chk(self.L.fhx_cz_fetch_cells(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
+        return cols
+
+    def device_ptrs(self):
+        return [self.L.fhx_cz_device_ptr(self.h, k) or 0 for k in range(5)]
+
+    def stream(self):
+        return self.L.fhx_cz_stream(self.h) or 0

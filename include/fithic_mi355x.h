@@ -974,6 +974,46 @@ int fhx_fp_fetch_cells(fhx_fp* fp, int32_t* chr1, int32_t* end1, int32_t* chr2, 
 void* fhx_fp_device_ptr(fhx_fp* fp, int32_t which);
 void* fhx_fp_stream(fhx_fp* fp);
 
+/* ---- contact rows in HBM summed onto N-fold coarser loci (csrc/fhx_coarsen.hip; the reference has no script for it, the
+ * semantics are this project's: INTEGRATION.md section 16).  One handle per GPU, independent of fhx_ctx.
+ * fhx_cz_load_plan gives what the host planned (fithic_amd/coarsen.py): the fine loci laid out by chromosome id - rows
+ * first[c] .. first[c + 1] - 1 of fine_mid are the strictly ascending mids of chromosome id c (first[0] = 0, first[n_chr] = n_fine,
+ * an id without loci has an empty range) -, group_of[row] = the coarse row of that fine locus, and the coarse loci
+ * (coarse_chr, coarse_mid), n_coarse <= n_fine of them.  FHX_ERR_ARG for a plan that is not as described.
+ * fhx_cz_coarsen_device takes n rows (chr1, mid1, chr2, mid2, count: int32 columns in HBM) after waiting for `stream`, the
+ * producer's; fhx_cz_coarsen_host uploads them first.  Each end is looked up in the fine table, the two coarse rows are ordered
+ * g1 <= g2, a row with g1 == g2 is kept (keep_diagonal != 0) or dropped and counted, and the counts of the rows with equal
+ * (g1, g2) are summed.  The cells (coarse chr1, mid1, chr2, mid2, sum: int32) stay in HBM in ascending (g1, g2); a cell exists
+ * when any row maps to it, a sum of zero included.
+ * Anything else is refused with nothing left loaded: *why = one of FHX_CZ_*, *bad_row = the smallest offending 0-based row; for
+ * FHX_CZ_SUM, which belongs to no row, *bad_row = g1 << 32 | g2 of the first cell above 2^31 - 1.  Return value:
+ * FHX_ERR_UNSUPPORTED. */
+#define FHX_CZ_OK 0
+#define FHX_CZ_LOCUS 1             /* an end (chr, mid) that is no locus of the fine table */
+#define FHX_CZ_COUNT 2             /* a negative count */
+#define FHX_CZ_SUM 3               /* the counts of a cell sum to more than 2^31 - 1 */
+#define FHX_CZ_INTERNAL 4          /* a device-side consistency check failed */
+#define FHX_CZ_STAGES 6            /* upload (host rows), keys, sort, heads + sums, cells: of the last call; then the last plan's upload */
+typedef struct fhx_cz fhx_cz;
+int fhx_cz_create(int device, fhx_cz** out);
+void fhx_cz_destroy(fhx_cz* cz);
+const char* fhx_cz_last_error(const fhx_cz* cz);
+int fhx_cz_reset(fhx_cz* cz);                                      /* drops the cells and the stage clocks; the plan stays */
+int fhx_cz_load_plan(fhx_cz* cz, const int64_t* first, int32_t n_chr, const int32_t* fine_mid, const int32_t* group_of, int64_t n_fine,
+                     const int32_t* coarse_chr, const int32_t* coarse_mid, int64_t n_coarse);
+int fhx_cz_coarsen_device(fhx_cz* cz, const void* d_chr1, const void* d_mid1, const void* d_chr2, const void* d_mid2, const void* d_count, int64_t n,
+                          void* stream, int32_t keep_diagonal, int64_t* n_cells, int32_t* why, int64_t* bad_row);
+int fhx_cz_coarsen_host(fhx_cz* cz, const int32_t* chr1, const int32_t* mid1, const int32_t* chr2, const int32_t* mid2, const int32_t* count, int64_t n,
+                        int32_t keep_diagonal, int64_t* n_cells, int32_t* why, int64_t* bad_row);
+/* rows given, rows dropped as diagonal, cells */
+int fhx_cz_counts(const fhx_cz* cz, int64_t* n_rows, int64_t* n_diagonal, int64_t* n_cells);
+int fhx_cz_stage_seconds(const fhx_cz* cz, double* seconds);       /* FHX_CZ_STAGES host clocks */
+int fhx_cz_fetch_cells(fhx_cz* cz, int32_t* chr1, int32_t* mid1, int32_t* chr2, int32_t* mid2, int32_t* count);   /* n_cells each */
+/* the columns in HBM (which 0..4 = chr1, mid1, chr2, mid2, count) and the stream they were written on, for
+ * fhx_load_pairs_device; valid until the next fhx_cz_coarsen_* / fhx_cz_reset / fhx_cz_load_plan / fhx_cz_destroy */
+void* fhx_cz_device_ptr(fhx_cz* cz, int32_t which);
+void* fhx_cz_stream(fhx_cz* cz);
+
 #ifdef __cplusplus
 }
 #endif
