@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import pass_state_model as pm
+from k1_windows import numpy_k1            # the count made with numpy: shared with tests/test_gpu_k1_windows.py
 
 pytestmark = pytest.mark.gpu
 
@@ -24,24 +25,6 @@ CHROMS = ((300, 5000), (220, 2500), (100, 5000))            # loci, offset of th
 STAT_FIELDS = ("n_rows", "inter_count", "inter_sum", "intra_all_count", "intra_all_sum", "in_range_count", "in_range_sum", "max_count",
                "n_dist", "n_skipped")
 BIG = 2 ** 31 - 1
-
-
-def numpy_k1(rows, res, low, up):
-    """rows: (chr1, idx1, chr2, idx2, count) with idx = the locus' bin on its chromosome -> (stats dict, sumCC, rows per distance)"""
-    c1, i1, c2, i2, cnt = (np.asarray(v, np.int64) for v in rows)
-    n_dist = int(max(i1.max(), i2.max())) + 2                # slots of the longest chromosome + the spare index
-    inter = c1 != c2
-    d = np.abs(i1 - i2)
-    lo = -(-low // res)
-    hi = n_dist - 1 if up is None else min(up // res, n_dist - 1)
-    rng = ~inter & (d >= lo) & (d <= hi)
-    st = dict(n_rows=len(cnt), inter_count=int(inter.sum()), inter_sum=int(cnt[inter].sum()), intra_all_count=int((~inter).sum()),
-              intra_all_sum=int(cnt[~inter].sum()), in_range_count=int(rng.sum()), in_range_sum=int(cnt[rng].sum()),
-              max_count=int(cnt.max()), n_dist=n_dist, n_skipped=0)
-    cc, npairs = np.zeros(n_dist, np.int64), np.zeros(n_dist, np.int64)
-    np.add.at(cc, d[rng], cnt[rng])
-    np.add.at(npairs, d[rng], 1)
-    return st, cc, npairs
 
 
 def device_k1(c, wide):
