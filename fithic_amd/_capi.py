@@ -208,9 +208,6 @@ SYMBOLS = {
     "fhx_host_pava_decreasing": (ctypes.c_int, [_F64P, ctypes.c_int64, _F64P]),
     "fhx_host_lbeta_table": (ctypes.c_int, [ctypes.c_double, ctypes.c_int64, _F64P, _F64P]),
     # Knight-Ruiz bias vectors (fithic/utils/HiCKRy.py)
-    "fhx_kr_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "fhx_kr_destroy": (None, [ctypes.c_void_p]),
-    "fhx_kr_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "fhx_kr_load_loci": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, ctypes.c_int64]),
     "fhx_kr_load_pairs": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _F64P, ctypes.c_int64, _I64P]),
     "fhx_kr_load_pairs_resident": (ctypes.c_int, [ctypes.c_void_p, _P, _I64P]),
@@ -225,43 +222,25 @@ SYMBOLS = {
     "fhx_kr_spmv": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _F64P, _F64P, ctypes.c_int32, _F64P]),
     "fhx_kr_dot": (ctypes.c_int, [ctypes.c_void_p, _F64P, _F64P, ctypes.c_int64, _F64P]),
     # merging of nearby significant contacts (fithic/utils/CombineNearbyInteraction.py)
-    "fhx_cni_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "fhx_cni_destroy": (None, [ctypes.c_void_p]),
-    "fhx_cni_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "fhx_cni_load": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I64P, _I64P, _I64P, _F64P, _F64P, ctypes.c_int64, ctypes.c_int64, _I64P]),
     "fhx_cni_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "fhx_cni_get_records": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _I64P]),
     # HiC-Pro matrix -> contact columns and per-bin totals (fithic/utils/HiCPro2FitHiC.py)
-    "fhx_hp_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "fhx_hp_destroy": (None, [ctypes.c_void_p]),
-    "fhx_hp_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "fhx_hp_load_bins": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _I32P, _I32P, ctypes.c_int64]),
     "fhx_hp_parse_matrix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, _I64P, _I32P, _I64P, _I64P]),
     "fhx_hp_totals": (ctypes.c_int, [ctypes.c_void_p, _I64P]),
     "fhx_hp_fetch_rows": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
-    "fhx_hp_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
-    "fhx_hp_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     # HiC-Pro allValidPairs -> contact counts (fithic/utils/validPairs2FitHiC-fixedSize.sh)
-    "fhx_vp_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "fhx_vp_destroy": (None, [ctypes.c_void_p]),
-    "fhx_vp_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "fhx_vp_bin_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64, _I64P, _I32P, _I64P]),
     "fhx_vp_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P, _I32P]),
     "fhx_vp_name": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_int32]),
-    "fhx_vp_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
     "fhx_vp_fetch_cells": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
-    "fhx_vp_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
-    "fhx_vp_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     "fhx_vp_write_contacts": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, _I32P, _I32P, _I32P, _I32P,
                                              _I32P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     # the FDR subset of a significances file (fithic/utils/merge-filter.sh)
-    "fhx_ms_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "fhx_ms_destroy": (None, [ctypes.c_void_p]),
-    "fhx_ms_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "fhx_ms_select_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
                                           ctypes.c_int32, ctypes.c_int32, _I64P, _I32P, _I64P]),
     "fhx_ms_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P]),
-    "fhx_ms_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
     "fhx_ms_copy_subset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     # the UCSC interact track of the same selection (fithic/utils/visualize-UCSC.sh)
     "fhx_ms_track_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
@@ -278,55 +257,41 @@ SYMBOLS = {
     "fhx_ms_split_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
     "fhx_ms_copy_split": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64]),
     # Juicer dump text -> contact counts (fithic/utils/createFitHiCContacts-hic_old.sh, createFitHiCContacts-hic.py)
-    "fhx_jc_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "fhx_jc_destroy": (None, [ctypes.c_void_p]),
-    "fhx_jc_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "fhx_jc_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "fhx_jc_convert_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int32,
                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _I64P, _I32P, _I64P]),
     "fhx_jc_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P]),
-    "fhx_jc_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
     "fhx_jc_copy_text": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]),
     "fhx_jc_fetch_rows": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
-    "fhx_jc_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
-    "fhx_jc_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
-    "fhx_dg_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "fhx_dg_destroy": (None, [ctypes.c_void_p]),
-    "fhx_dg_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "fhx_dg_digest_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, _I32P, _I32P, ctypes.c_int32, _I32P, _I64P]),
     "fhx_dg_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P, _I64P]),
     "fhx_dg_name": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_int64]),
     "fhx_dg_contig_length": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64]),
     "fhx_dg_fetch_sites": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P]),
-    "fhx_dg_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
     "fhx_dg_write_fragments": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int64, _I64P, _I32P, _I32P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     "fhx_dg_write_bed": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int64, _I64P, _I32P, _I32P, ctypes.c_int64,
                                         ctypes.c_int32]),
     # HiC-Pro allValidPairs -> contact counts between the restriction fragments of a digest (no reference script)
-    "fhx_fp_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "fhx_fp_destroy": (None, [ctypes.c_void_p]),
-    "fhx_fp_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "fhx_fp_load_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, _I32P, ctypes.c_int32, _I64P, ctypes.c_int32, _I32P, ctypes.c_int64]),
     "fhx_fp_bin_file": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, _I64P, _I32P, _I64P]),
     "fhx_fp_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P, _I64P, _I64P]),
-    "fhx_fp_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
     "fhx_fp_fetch_cells": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
-    "fhx_fp_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
-    "fhx_fp_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     # contact rows in HBM summed onto N-fold coarser loci (no reference script)
-    "fhx_cz_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "fhx_cz_destroy": (None, [ctypes.c_void_p]),
-    "fhx_cz_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "fhx_cz_reset": (ctypes.c_int, [ctypes.c_void_p]),
     "fhx_cz_load_plan": (ctypes.c_int, [ctypes.c_void_p, _I64P, ctypes.c_int32, _I32P, _I32P, ctypes.c_int64, _I32P, _I32P, ctypes.c_int64]),
     "fhx_cz_coarsen_device": (ctypes.c_int, [ctypes.c_void_p, _P, _P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int32, _I64P, _I32P, _I64P]),
     "fhx_cz_coarsen_host": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P, ctypes.c_int64, ctypes.c_int32, _I64P, _I32P, _I64P]),
     "fhx_cz_counts": (ctypes.c_int, [ctypes.c_void_p, _I64P, _I64P, _I64P]),
-    "fhx_cz_stage_seconds": (ctypes.c_int, [ctypes.c_void_p, _F64P]),
     "fhx_cz_fetch_cells": (ctypes.c_int, [ctypes.c_void_p, _I32P, _I32P, _I32P, _I32P, _I32P]),
-    "fhx_cz_device_ptr": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int32]),
-    "fhx_cz_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
 }
+# the rows every handle beside the engine's repeats, per prefix
+for _p in ("kr", "cni", "hp", "vp", "ms", "jc", "dg", "fp", "cz"):
+    SYMBOLS.update({"fhx_%s_create" % _p: (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_P)]), "fhx_%s_destroy" % _p: (None, [_P]),
+                    "fhx_%s_last_error" % _p: (ctypes.c_char_p, [_P])})
+for _p in ("vp", "ms", "jc", "dg", "fp", "cz"):
+    SYMBOLS["fhx_%s_stage_seconds" % _p] = (ctypes.c_int, [_P, _F64P])
+for _p in ("hp", "vp", "jc", "fp", "cz"):
+    SYMBOLS.update({"fhx_%s_device_ptr" % _p: (_P, [_P, ctypes.c_int32]), "fhx_%s_stream" % _p: (_P, [_P])})
 
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
 # not recompile K1, K3, the Knight-Ruiz path or the host stages.  Flags are the same for every unit - -ffp-contract=off matters
@@ -1291,6 +1256,8 @@ class _Handle:
     """A native context on one GPU: fhx_<PREFIX>_create / _destroy / _last_error.  Raises without the built library or a GPU."""
     PREFIX = None
     REFUSED = None                   # the text paths: what _chk raises when the call named a reason
+    STAGE_NAMES = None               # stage_seconds(): the slots of fhx_<PREFIX>_stage_seconds
+    COUNTS = None                    # counts(): ((key, ctype), ...), the outputs of fhx_<PREFIX>_counts
 
     def __init__(self, device=0):
         self.L = lib()
@@ -1319,6 +1286,46 @@ class _Handle:
             raise self.REFUSED(rc, self._last_error(), why, *where)
         if rc != FHX_OK:
             raise FhxError(rc, self._last_error())
+
+    def _stage_seconds(self, names, fn="stage_seconds"):
+        out = np.zeros(len(names), np.float64)
+        self._chk(self._fn(fn)(self.h, _ptr(out, ctypes.c_double)))
+        return dict(zip(names, out.tolist()))
+
+    def stage_seconds(self):
+        return self._stage_seconds(self.STAGE_NAMES)
+
+    def _counts(self, spec, fn="counts"):
+        v = [t(0) for _, t in spec]
+        self._chk(self._fn(fn)(self.h, *[ctypes.byref(x) for x in v]))
+        return {k: x.value for (k, _), x in zip(spec, v)}
+
+    def counts(self):
+        return self._counts(self.COUNTS)
+
+    # the handles that hold five resident int32 columns: fhx_<PREFIX>_fetch_<what>, _device_ptr and _stream
+    def _fetch_columns(self, what, n):
+        cols = [np.zeros(n, np.int32) for _ in range(5)]
+        self._chk(self._fn("fetch_" + what)(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
+        return cols
+
+    def device_ptrs(self):
+        return [self._fn("device_ptr")(self.h, k) or 0 for k in range(5)]
+
+    def stream(self):
+        return self._fn("stream")(self.h) or 0
+
+
+class _LineRefused(FhxError):
+    """a text path refused its file: why = one of the path's reasons, line = the smallest offending 1-based line"""
+
+    def __init__(self, code, message, why, line):
+        super().__init__(code, message)
+        self.why, self.line = int(why), int(line)
+
+
+def _i64s(*keys):
+    return tuple((k, ctypes.c_int64) for k in keys)
 
 
 # ---- Knight-Ruiz (fhx_kr_*) ------------------------------------------------------------------------------------------
@@ -1499,34 +1506,24 @@ class HpContext(_Handle):
 
     def fetch_rows(self):
         """(chr1, mid1, chr2, mid2, count), int32, file order"""
-        cols = [np.zeros(self.n_rows, np.int32) for _ in range(5)]
-        self._chk(self.L.fhx_hp_fetch_rows(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
-        return cols
-
-    def device_ptrs(self):
-        return [self.L.fhx_hp_device_ptr(self.h, k) or 0 for k in range(5)]
-
-    def stream(self):
-        return self.L.fhx_hp_stream(self.h) or 0
+        return self._fetch_columns("rows", self.n_rows)
 
 
 (VP_OK, VP_TOKENS, VP_NAME, VP_POSITION, VP_RANGE, VP_BYTES, VP_LONG_LINE, VP_NAMES, VP_COUNT, VP_RES, VP_INTERNAL, VP_PAIRS) = range(12)
 VP_STAGE_NAMES = ("read_upload", "newline_scan", "parse", "names_keys", "sort", "cells")
 
 
-class VpRefused(FhxError):
+class VpRefused(_LineRefused):
     """fhx_vp_bin_file refused the file: why = one of VP_*, line = the smallest offending 1-based line (0: the reason belongs to
     no line)"""
-
-    def __init__(self, code, message, why, line):
-        super().__init__(code, message)
-        self.why, self.line = int(why), int(line)
 
 
 class VpContext(_Handle):
     """A validPairs file binned, sorted and counted on one GPU (fhx_vp_*).  Raises without the library or a GPU."""
     PREFIX = "vp"
     REFUSED = VpRefused
+    STAGE_NAMES = VP_STAGE_NAMES
+    COUNTS = _i64s("lines", "pairs", "cells") + (("names", ctypes.c_int32),)     # lines read, pairs kept by the filters, cells, distinct names
 
     def __init__(self, device=0):
         self.n_cells = 0
@@ -1541,32 +1538,13 @@ class VpContext(_Handle):
         self.n_cells = n.value
         return self.n_cells
 
-    def counts(self):
-        """lines read, pairs kept by the filters, cells, distinct names"""
-        a, b, c, d = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
-        self._chk(self.L.fhx_vp_counts(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
-        return dict(lines=a.value, pairs=b.value, cells=c.value, names=d.value)
-
     def names(self):
         """the chromosome names in bytewise order: the chr columns index this list"""
         return [self.L.fhx_vp_name(self.h, k).decode() for k in range(self.counts()["names"])]
 
-    def stage_seconds(self):
-        out = np.zeros(len(VP_STAGE_NAMES), np.float64)
-        self._chk(self.L.fhx_vp_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
-        return dict(zip(VP_STAGE_NAMES, out.tolist()))
-
     def fetch_cells(self):
         """(chr1, mid1, chr2, mid2, count), int32, in the script's text order"""
-        cols = [np.zeros(self.n_cells, np.int32) for _ in range(5)]
-        self._chk(self.L.fhx_vp_fetch_cells(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
-        return cols
-
-    def device_ptrs(self):
-        return [self.L.fhx_vp_device_ptr(self.h, k) or 0 for k in range(5)]
-
-    def stream(self):
-        return self.L.fhx_vp_stream(self.h) or 0
+        return self._fetch_columns("cells", self.n_cells)
 
 
 def vp_write_contacts(path, names, chr1, mid1, chr2, mid2, count, gzip_level=1, threads=0):
@@ -1589,19 +1567,17 @@ MS_TRACK_STAGE_NAMES = ("read_upload", "newline_scan", "select", "deferred_round
 MS_SPLIT_STAGE_NAMES = ("read_upload", "newline_scan", "names_select", "sort_gather", "copy_out")
 
 
-class MsRefused(FhxError):
+class MsRefused(_LineRefused):
     """fhx_ms_select_file refused the file: why = one of MS_*, line = the smallest offending 1-based line (0: the reason belongs
     to no line)"""
-
-    def __init__(self, code, message, why, line):
-        super().__init__(code, message)
-        self.why, self.line = int(why), int(line)
 
 
 class MsContext(_Handle):
     """The FDR subset of a significances file made on one GPU (fhx_ms_*).  Raises without the library or a GPU."""
     PREFIX = "ms"
     REFUSED = MsRefused
+    STAGE_NAMES = MS_STAGE_NAMES
+    COUNTS = _i64s("lines", "kept", "bytes")                         # lines read, lines kept, bytes of the subset
 
     def select_file(self, path, fdr_text, key_bound, zero_kept, strict=False, skip_first_line=True):
         """-> bytes of the subset; MsRefused for a file outside the device grammar"""
@@ -1610,17 +1586,6 @@ class MsContext(_Handle):
                                        int(bool(strict)), int(bool(skip_first_line)), ctypes.byref(n), ctypes.byref(why), ctypes.byref(line))
         self._chk(rc, why.value, line.value)
         return n.value
-
-    def counts(self):
-        """lines read, lines kept, bytes of the subset"""
-        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        self._chk(self.L.fhx_ms_counts(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
-        return dict(lines=a.value, kept=b.value, bytes=c.value)
-
-    def stage_seconds(self):
-        out = np.zeros(len(MS_STAGE_NAMES), np.float64)
-        self._chk(self.L.fhx_ms_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
-        return dict(zip(MS_STAGE_NAMES, out.tolist()))
 
     def subset(self):
         """the kept lines, verbatim and in file order, each ending in a newline"""
@@ -1638,14 +1603,10 @@ class MsContext(_Handle):
 
     def track_counts(self):
         """lines read, lines kept, kept lines whose score the host made, bytes of the track"""
-        a, b, c, d = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        self._chk(self.L.fhx_ms_track_counts(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
-        return dict(lines=a.value, kept=b.value, deferred=c.value, bytes=d.value)
+        return self._counts(_i64s("lines", "kept", "deferred", "bytes"), "track_counts")
 
     def track_stage_seconds(self):
-        out = np.zeros(len(MS_TRACK_STAGE_NAMES), np.float64)
-        self._chk(self.L.fhx_ms_track_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
-        return dict(zip(MS_TRACK_STAGE_NAMES, out.tolist()))
+        return self._stage_seconds(MS_TRACK_STAGE_NAMES, "track_stage_seconds")
 
     def track(self):
         """the script's two fixed lines and one line per kept row, in file order"""
@@ -1679,9 +1640,7 @@ class MsContext(_Handle):
         return [raw[k * MS_SPLIT_NAME_BYTES:(k + 1) * MS_SPLIT_NAME_BYTES].rstrip(b"\0") for k in range(n)]
 
     def split_stage_seconds(self):
-        out = np.zeros(len(MS_SPLIT_STAGE_NAMES), np.float64)
-        self._chk(self.L.fhx_ms_split_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
-        return dict(zip(MS_SPLIT_STAGE_NAMES, out.tolist()))
+        return self._stage_seconds(MS_SPLIT_STAGE_NAMES, "split_stage_seconds")
 
     def split_text(self, index, n_bytes):
         """the kept lines of one name, verbatim and in file order, each ending in a newline"""
@@ -1705,12 +1664,8 @@ def ms_score_text(field, certify=False):
 JC_STAGE_NAMES = ("read_upload", "newline_scan", "parse", "format", "copy_out")
 
 
-class JcRefused(FhxError):
+class JcRefused(_LineRefused):
     """fhx_jc_convert_file refused the file: why = one of JC_*, line = the smallest offending 1-based line"""
-
-    def __init__(self, code, message, why, line):
-        super().__init__(code, message)
-        self.why, self.line = int(why), int(line)
 
 
 class JcContext(_Handle):
@@ -1718,6 +1673,8 @@ class JcContext(_Handle):
     without the library or a GPU."""
     PREFIX = "jc"
     REFUSED = JcRefused
+    STAGE_NAMES = JC_STAGE_NAMES
+    COUNTS = _i64s("lines", "rows", "bytes")                         # lines read, rows kept, bytes of text kept
 
     def reset(self):
         self._chk(self.L.fhx_jc_reset(self.h))
@@ -1731,17 +1688,6 @@ class JcContext(_Handle):
         self._chk(rc, why.value, line.value)
         return n.value
 
-    def counts(self):
-        """lines read, rows kept, bytes of text kept"""
-        a, b, c = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        self._chk(self.L.fhx_jc_counts(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
-        return dict(lines=a.value, rows=b.value, bytes=c.value)
-
-    def stage_seconds(self):
-        out = np.zeros(len(JC_STAGE_NAMES), np.float64)
-        self._chk(self.L.fhx_jc_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
-        return dict(zip(JC_STAGE_NAMES, out.tolist()))
-
     def text(self):
         """the output lines kept so far, in the order of the calls and of the lines"""
         buf = np.empty(self.counts()["bytes"], np.uint8)
@@ -1750,15 +1696,7 @@ class JcContext(_Handle):
 
     def fetch_rows(self):
         """(chr1, mid1, chr2, mid2, count), int32, in the order of the calls and of the lines"""
-        cols = [np.zeros(self.counts()["rows"], np.int32) for _ in range(5)]
-        self._chk(self.L.fhx_jc_fetch_rows(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
-        return cols
-
-    def device_ptrs(self):
-        return [self.L.fhx_jc_device_ptr(self.h, k) or 0 for k in range(5)]
-
-    def stream(self):
-        return self.L.fhx_jc_stream(self.h) or 0
+        return self._fetch_columns("rows", self.counts()["rows"])
 
 
 # ---- FASTA -> cut sites -> the fragments of `fithic -r 0` (fhx_dg_*) ---------------------------------------------------------
@@ -1767,12 +1705,8 @@ DG_MAX_MOTIF, DG_MAX_MOTIFS = 16, 64
 DG_STAGE_NAMES = ("read_upload", "newline_scan", "class_pass", "sites", "sort", "fetch")
 
 
-class DgRefused(FhxError):
+class DgRefused(_LineRefused):
     """fhx_dg_digest_file refused the file: why = one of DG_*, line = the smallest offending 1-based line"""
-
-    def __init__(self, code, message, why, line):
-        super().__init__(code, message)
-        self.why, self.line = int(why), int(line)
 
 
 class DgContext(_Handle):
@@ -1780,6 +1714,8 @@ class DgContext(_Handle):
     the library or a GPU."""
     PREFIX = "dg"
     REFUSED = DgRefused
+    STAGE_NAMES = DG_STAGE_NAMES
+    COUNTS = _i64s("lines", "contigs", "bases", "sites")             # lines read, contigs, their bases in all, cut sites
 
     def digest_file(self, path, motifs):
         """motifs = [(letters of acgt, offset of the cut), ...], an N of the site expanded.  DgRefused for a file outside the
@@ -1794,12 +1730,6 @@ class DgContext(_Handle):
                                        _ptr(offsets, ctypes.c_int32), len(motifs), ctypes.byref(why), ctypes.byref(line))
         self._chk(rc, why.value, line.value)
 
-    def counts(self):
-        """lines read, contigs, their bases in all, cut sites"""
-        v = [ctypes.c_int64(0) for _ in range(4)]
-        self._chk(self.L.fhx_dg_counts(self.h, *[ctypes.byref(x) for x in v]))
-        return dict(zip(("lines", "contigs", "bases", "sites"), [x.value for x in v]))
-
     def names(self):
         return [self.L.fhx_dg_name(self.h, k) for k in range(self.counts()["contigs"])]
 
@@ -1812,11 +1742,6 @@ class DgContext(_Handle):
         contig, position = np.zeros(n, np.int32), np.zeros(n, np.int32)
         self._chk(self.L.fhx_dg_fetch_sites(self.h, _ptr(contig, ctypes.c_int32), _ptr(position, ctypes.c_int32)))
         return contig, position
-
-    def stage_seconds(self):
-        out = np.zeros(len(DG_STAGE_NAMES), np.float64)
-        self._chk(self.L.fhx_dg_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
-        return dict(zip(DG_STAGE_NAMES, out.tolist()))
 
 
 def dg_write_fragments(path, lengths, site_contig, site_position, gzip_level=6, threads=0):
@@ -1846,13 +1771,9 @@ FP_MAX_CONTIGS, FP_NAME_BYTES = 4096, 64
 FP_STAGE_NAMES = ("read_upload", "newline_scan", "parse", "sort", "cells", "table")
 
 
-class FpRefused(FhxError):
+class FpRefused(_LineRefused):
     """fhx_fp_bin_file refused the file: why = one of FP_*, line = the smallest offending 1-based line (0: the reason belongs to
     no line)"""
-
-    def __init__(self, code, message, why, line):
-        super().__init__(code, message)
-        self.why, self.line = int(why), int(line)
 
 
 class FpContext(_Handle):
@@ -1860,6 +1781,9 @@ class FpContext(_Handle):
     or a GPU."""
     PREFIX = "fp"
     REFUSED = FpRefused
+    STAGE_NAMES = FP_STAGE_NAMES
+    # lines read, pairs kept, lines dropped for a name, lines dropped as same-fragment, cells
+    COUNTS = _i64s("lines", "pairs", "dropped_name", "same_fragment", "cells")
 
     def __init__(self, device=0):
         self.n_cells = 0
@@ -1888,28 +1812,9 @@ class FpContext(_Handle):
         self.n_cells = n.value
         return self.n_cells
 
-    def counts(self):
-        """lines read, pairs kept, lines dropped for a name, lines dropped as same-fragment, cells"""
-        v = [ctypes.c_int64(0) for _ in range(5)]
-        self._chk(self.L.fhx_fp_counts(self.h, *[ctypes.byref(x) for x in v]))
-        return dict(zip(("lines", "pairs", "dropped_name", "same_fragment", "cells"), [x.value for x in v]))
-
-    def stage_seconds(self):
-        out = np.zeros(len(FP_STAGE_NAMES), np.float64)
-        self._chk(self.L.fhx_fp_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
-        return dict(zip(FP_STAGE_NAMES, out.tolist()))
-
     def fetch_cells(self):
         """(contig1, end1, contig2, end2, count), int32, in ascending (fragment row 1, fragment row 2)"""
-        cols = [np.zeros(self.n_cells, np.int32) for _ in range(5)]
-        self._chk(self.L.fhx_fp_fetch_cells(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
-        return cols
-
-    def device_ptrs(self):
-        return [self.L.fhx_fp_device_ptr(self.h, k) or 0 for k in range(5)]
-
-    def stream(self):
-        return self.L.fhx_fp_stream(self.h) or 0
+        return self._fetch_columns("cells", self.n_cells)
 
 
 # ---- contact rows in HBM summed onto N-fold coarser loci (fhx_cz_*) -----------------------------------------------------------
@@ -1931,6 +1836,8 @@ class CzContext(_Handle):
     GPU."""
     PREFIX = "cz"
     REFUSED = CzRefused
+    STAGE_NAMES = CZ_STAGE_NAMES
+    COUNTS = _i64s("rows", "diagonal", "cells")                      # rows given, rows dropped as diagonal, cells
 
     def __init__(self, device=0):
         self.n_cells = 0
@@ -1971,25 +1878,6 @@ class CzContext(_Handle):
                                         ctypes.byref(cells), ctypes.byref(why), ctypes.byref(row))
         return self._done(rc, cells, why, row)
 
-    def counts(self):
-        """rows given, rows dropped as diagonal, cells"""
-        v = [ctypes.c_int64(0) for _ in range(3)]
-        self._chk(self.L.fhx_cz_counts(self.h, *[ctypes.byref(x) for x in v]))
-        return dict(zip(("rows", "diagonal", "cells"), [x.value for x in v]))
-
-    def stage_seconds(self):
-        out = np.zeros(len(CZ_STAGE_NAMES), np.float64)
-        self._chk(self.L.fhx_cz_stage_seconds(self.h, _ptr(out, ctypes.c_double)))
-        return dict(zip(CZ_STAGE_NAMES, out.tolist()))
-
     def fetch_cells(self):
         """(chr1, mid1, chr2, mid2, count), int32, in ascending (coarse row 1, coarse row 2)"""
-        cols = [np.zeros(self.n_cells, np.int32) for _ in range(5)]
-        self._chk(self.L.fhx_cz_fetch_cells(self.h, *[_ptr(v, ctypes.c_int32) for v in cols]))
-        return cols
-
-    def device_ptrs(self):
-        return [self.L.fhx_cz_device_ptr(self.h, k) or 0 for k in range(5)]
-
-    def stream(self):
-        return self.L.fhx_cz_stream(self.h) or 0
+        return self._fetch_columns("cells", self.n_cells)

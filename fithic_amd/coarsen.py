@@ -43,6 +43,7 @@ import sys
 import numpy as np
 
 from . import _capi, tables
+from ._resident import Resident
 
 _INT32_MAX = (1 << 31) - 1
 _REASONS = {_capi.CZ_LOCUS: "an end that is no locus of the fragments table", _capi.CZ_COUNT: "a negative count"}
@@ -128,10 +129,8 @@ def _handle_of(source):
     reach it)"""
     if hasattr(source, "device_ptrs") and hasattr(source, "stream"):
         return source
-    for attr in ("_vp", "_fp", "_jc", "_hp"):
-        h = getattr(source, attr, None)
-        if h is not None and hasattr(h, "device_ptrs"):
-            return h
+    if isinstance(source, Resident) and not isinstance(source, Coarsened) and source._handle is not None:
+        return source._handle
     raise TypeError("%r: a contacts file, five columns or a resident producer (validpairs, fragpairs, juicer, hicpro) is expected" % (source,))
 
 
@@ -143,38 +142,14 @@ def _locus(names, chr_id, mid):
     return "%s:%d" % (names[chr_id] if 0 <= chr_id < len(names) else "chromosome id %d" % chr_id, mid)
 
 
-class Coarsened:
+class Coarsened(Resident):
     """The coarse cells (chr1, mid1, chr2, mid2, count) resident in HBM in ascending (coarse row 1, coarse row 2), and the coarse
-    fragments table on the host.  The chr columns index `names`; `resolution` is N*R, or 0 for meta-fragments."""
+    fragments table on the host.  The chr columns index `names`; `resolution` is N*R, or 0 for meta-fragments.  counts(): rows
+    (given), diagonal (dropped), cells.  load_into: the coarse fragments and the cells into a configured Engine."""
 
     def __init__(self, cz, n_cells, names, plan_):
-        self._cz, self.n_cells, self.names, self.plan = cz, n_cells, names, plan_
-        self.resolution = plan_.resolution
-
-    def close(self):
-        if self._cz is not None:
-            self._cz.close()
-            self._cz = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return self.n_cells
-
-    def counts(self):
-        """rows (given), diagonal (dropped), cells"""
-        return self._cz.counts()
-
-    def stage_seconds(self):
-        return self._cz.stage_seconds()
-
-    def contacts(self):
-        """(chr1, mid1, chr2, mid2, count) fetched from the device"""
-        return self._cz.fetch_cells()
+        super().__init__(cz, n_cells, names)
+        self.n_cells, self.plan, self.resolution = n_cells, plan_, plan_.resolution
 
     def fragments(self):
         """(chr ids, mids, hits) of the coarse table, as tables.read_fragments returns them for the written file"""
@@ -192,18 +167,8 @@ class Coarsened:
         with gzip.open(path, "wt") as f:
             f.write(self.fragments_text())
 
-    def intern(self, chroms):
-        """these names into the run's ChromIndex: empty (it receives them) or one whose ids agree with them"""
-        for k, name in enumerate(self.names):
-            if chroms.intern(name) != k:
-                raise ValueError("chromosome %r has id %d in the given ChromIndex and %d here" % (name, chroms.intern(name), k))
-
-    def load_into(self, engine, chroms):
-        """The coarse fragments and the cells into a configured Engine; the five columns go from HBM to HBM."""
-        self.intern(chroms)
+    def _load_tables(self, engine, chroms):
         engine.load_fragments(*self.fragments(), chroms.sort_rank())
-        engine.load_contacts_device(self._cz.device_ptrs() if self.n_cells else [0] * 5, self.n_cells, self._cz.stream())
-        engine.ctx.sync()                                            # the engine has its own copy: this object may be closed now
 
 
 def _refusal(e, names, plan_, row_of):

@@ -6,12 +6,12 @@
 //   cz_keys        one row per lane: each end (chr, mid) is found in the fine table by bisection over its chromosome's ascending
 //                  mids (fp_parse's layout: first[n_chr + 1] and one ascending column), group_of gives the coarse rows g1, g2,
 //                  swapped to g1 <= g2.  The row becomes ONE word g1 << 32 | g2 and its count, both stored compacted (a
-//                  diagonal row may be dropped): a block scan of the keep flags and one atomicAdd per 256 rows.  The smallest
-//                  bad row and the diagonal count are reduced per wave first.
+//                  diagonal row may be dropped; fhx::block_append: one atomicAdd per 256 rows).  The smallest bad row and the
+//                  diagonal count are reduced per wave first.
 //   fhx_sort_u64   the stable radix sort; its permutation says which count belongs to a sorted key
-//   count_heads / scan_tiles    run heads of the sorted keys (fhx_scan.hpp, as they are)
-//   cz_tile_sums / cz_scan_sums / cz_heads    the 64-bit ordered scan of the permuted counts: per-tile sums, their exclusive
-//                  scan, then every head's position and the exclusive prefix of the counts in front of it.  No loop over a run:
+//   fhx::run_heads              the number of run heads of the sorted keys (fhx_cells.hpp, up to the count)
+//   cz_tile_sums / scan_tiles / cz_heads    the 64-bit ordered scan of the permuted counts: per-tile sums, their exclusive
+//                  scan (fhx_scan.hpp's, on 64-bit values), then every head's position and the exclusive prefix of the counts in front of it.  No loop over a run:
 //                  one cell may hold every row of the input.  2^31 rows of 2^31 - 1 fit 63 bits.
 //   cz_cells       one cell per lane: its sum is the difference of the prefixes at two heads; five int32 columns, lanes on
 //                  consecutive cells; the largest sum and the first cell above 2^31 - 1 are reduced per wave
@@ -29,7 +29,7 @@
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
-#include "fhx_textupload.hpp"
+#include "fhx_cells.hpp"
 
 namespace czd {
 
@@ -39,13 +39,13 @@ constexpr unsigned long long INT32_TOP = 0x7fffffffull;
 
 // the words the kernels of one call share
 struct Words {
-    unsigned long long first_error;            // smallest (row << 8 | reason)
-    unsigned long long n_records;              // kept rows
-    unsigned long long n_diagonal;             // rows dropped as diagonal
-    unsigned long long n_cells;                // scan_tiles' total of the heads
-    unsigned long long total;                  // cz_scan_sums' total of the counts
-    unsigned long long max_sum;                // largest cell sum
-    unsigned long long first_big;              // smallest (cell << 8 | FHX_CZ_SUM)
+    unsigned long long first_error = NO_ERROR; // smallest (row << 8 | reason)
+    unsigned long long n_records = 0;          // kept rows
+    unsigned long long n_diagonal = 0;         // rows dropped as diagonal
+    unsigned long long n_cells = 0;            // scan_tiles' total of the heads
+    unsigned long long total = 0;              // scan_tiles' total of the counts
+    unsigned long long max_sum = 0;            // largest cell sum
+    unsigned long long first_big = NO_ERROR;   // smallest (cell << 8 | FHX_CZ_SUM)
 };
 
 // what cz_keys reads of the plan, all of it in HBM
@@ -70,31 +70,9 @@ __device__ inline int32_t locus_of(const Plan& p, int32_t chr, int32_t mid) {
     return lo < end && p.mids[lo] == mid ? lo : -1;
 }
 
-// ordered block-wide exclusive scan of one 64-bit sum per thread: fhxscan::block_exclusive_scan's wider form
-__device__ inline unsigned long long block_exclusive_scan64(unsigned long long v, unsigned long long* total) {
-    __shared__ unsigned long long wsum64[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned long long inc = v;
-    for (int s = 1; s < 64; s <<= 1) {
-        const unsigned long long up = __shfl_up(inc, s, 64);
-        if (lane >= s) inc += up;
-    }
-    if (lane == 63) wsum64[w] = inc;
-    __syncthreads();
-    unsigned long long base = 0, all = 0;
-    for (int k = 0; k < 4; ++k) {
-        if (k < w) base += wsum64[k];
-        all += wsum64[k];
-    }
-    __syncthreads();
-    *total = all;
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(WG) void cz_keys(const int32_t* __restrict__ chr1, const int32_t* __restrict__ mid1, const int32_t* __restrict__ chr2,
                                               const int32_t* __restrict__ mid2, const int32_t* __restrict__ count, int64_t n, Plan plan, int keep_diagonal,
                                               unsigned long long* __restrict__ keys, int32_t* __restrict__ kept_count, Words* __restrict__ words) {
-    __shared__ unsigned long long out_base;
     const int64_t r = (int64_t)blockIdx.x * WG + threadIdx.x;
     unsigned long long first_error = NO_ERROR, key = 0;
     unsigned int diagonal = 0;
@@ -114,13 +92,9 @@ __global__ __launch_bounds__(WG) void cz_keys(const int32_t* __restrict__ chr1, 
             }
         }
     }
-    unsigned int total;
-    const unsigned int at = fhxscan::block_exclusive_scan(keep ? 1u : 0u, &total);
-    if (threadIdx.x == 0) out_base = total ? atomicAdd(&words->n_records, (unsigned long long)total) : 0ull;
-    __syncthreads();
+    const unsigned long long pos = fhx::block_append(keep, &words->n_records, (unsigned long long)n);
     if (keep) {
-        const unsigned long long pos = out_base + at;
-        if (pos < (unsigned long long)n) {                   // room for every row: n words were allocated
+        if (pos != fhx::APPEND_OVER) {                       // room for every row: n words were allocated
             keys[pos] = key;
             kept_count[pos] = cnt;
         } else first_error = min(first_error, ((unsigned long long)r << 8) | FHX_CZ_INTERNAL);
@@ -148,26 +122,8 @@ __global__ __launch_bounds__(fhxscan::THREADS) void cz_tile_sums(const unsigned 
             s += (unsigned long long)(unsigned int)v;                              // cz_keys kept no negative count
         }
     unsigned long long total;
-    block_exclusive_scan64(s, &total);
+    fhxscan::block_exclusive_scan(s, &total);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-// exclusive scan of the tile sums (one block, any number of tiles): fhxscan::scan_tiles' wider form
-__global__ __launch_bounds__(fhxscan::THREADS) void cz_scan_sums(const unsigned long long* __restrict__ tile_sums, int64_t n_tiles,
-                                                                 unsigned long long* __restrict__ tile_prefix, unsigned long long* __restrict__ total_out) {
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < n_tiles; base += fhxscan::THREADS) {
-        const int64_t i = base + threadIdx.x;
-        unsigned long long total;
-        const unsigned long long ex = block_exclusive_scan64(i < n_tiles ? tile_sums[i] : 0ull, &total);
-        if (i < n_tiles) tile_prefix[i] = carry + ex;
-        __syncthreads();
-        if (threadIdx.x == 0) carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total_out = carry;
 }
 
 // the run heads of the sorted keys, in order: where each run starts and the sum of the counts in front of it
@@ -190,7 +146,7 @@ __global__ __launch_bounds__(fhxscan::THREADS) void cz_heads(const unsigned long
     unsigned int heads;
     unsigned long long sum;
     unsigned long long pos = tile_offsets[blockIdx.x] + fhxscan::block_exclusive_scan(c, &heads);
-    unsigned long long before = tile_prefix[blockIdx.x] + block_exclusive_scan64(s, &sum);
+    unsigned long long before = tile_prefix[blockIdx.x] + fhxscan::block_exclusive_scan(s, &sum);
     for (int k = 0; k < fhxscan::SCAN_ITEMS; ++k) {
         if (head[k] && (int64_t)pos < n_cells) {
             head_at[pos] = (unsigned long long)(base + k);
@@ -244,18 +200,16 @@ struct fhx_cz : fhx::Handle {
     int32_t *d_first = nullptr, *d_mids = nullptr, *d_group_of = nullptr, *d_coarse_chr = nullptr, *d_coarse_mid = nullptr;
     double plan_seconds = 0;
     // the last coarsened rows
-    int64_t n_rows = 0, n_diagonal = 0, n_cells = 0;
-    int32_t* d_cols = nullptr;                    // five columns of col_stride elements
-    int64_t col_stride = 0;
+    int64_t n_rows = 0, n_diagonal = 0;
+    fhx::CellColumns cols;
     double seconds[FHX_CZ_STAGES] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace {
 
 void drop_cells(fhx_cz* cz) {
-    fhx::dev_free(cz->d_cols);
-    cz->n_rows = cz->n_diagonal = cz->n_cells = 0;
-    cz->col_stride = 0;
+    cz->cols.drop();
+    cz->n_rows = cz->n_diagonal = 0;
 }
 
 void drop_plan(fhx_cz* cz) {
@@ -268,15 +222,10 @@ void drop_plan(fhx_cz* cz) {
     cz->n_fine = cz->n_coarse = 0;
 }
 
-int upload(fhx_cz* cz, int32_t** d, const int32_t* src, size_t n) {
-    TH_HIP(cz, fhx::dev_malloc(d, std::max<size_t>(n, 1) * sizeof(int32_t)));
-    if (n) TH_HIP(cz, hipMemcpyAsync(*d, src, n * sizeof(int32_t), hipMemcpyHostToDevice, cz->stream));
-    return FHX_OK;
-}
-
 // fhx_cz_load_plan behind its argument check; whatever it returns but FHX_OK, the caller drops the plan
 int load_plan(fhx_cz* cz, const int64_t* first, int32_t n_chr, const int32_t* fine_mid, const int32_t* group_of, int64_t n_fine,
               const int32_t* coarse_chr, const int32_t* coarse_mid, int64_t n_coarse) {
+    using fhx::upload;
     if (n_fine > 0x7fffffffll) return fhx::fail(cz, FHX_ERR_UNSUPPORTED, "2^31 or more loci");
     if (n_coarse > n_fine) return fhx::fail(cz, FHX_ERR_ARG, "more coarse loci than fine ones");
     if (first[0] != 0 || first[n_chr] != n_fine) return fhx::fail(cz, FHX_ERR_ARG, "first[0] is not 0, or first[n_chr] is not n_fine");
@@ -303,25 +252,13 @@ int load_plan(fhx_cz* cz, const int64_t* first, int32_t n_chr, const int32_t* fi
     return FHX_OK;
 }
 
-// where a refusal of a call goes
-struct Refuse {
-    fhx_cz* cz;
-    int32_t* why;
-    int64_t* row;
-    int operator()(int rc, int32_t w, int64_t r, const std::string& msg) const {
-        *why = w;
-        *row = r;
-        return fhx::fail(cz, rc, msg);
-    }
-};
-
 // the rows d[0..4][0, n) -> the cells; the stream is idle on entry.  Whatever it returns but FHX_OK, the caller drops the cells.
 int coarsen_rows(fhx_cz* cz, fhx::DeviceScratch& tmp, fhx::StageClock& clock, const int32_t* const* d, int64_t n, int keep_diagonal,
                  int64_t* n_cells, int32_t* why, int64_t* bad_row) {
     using namespace czd;
     if (cz->n_fine < 1) return fhx::fail(cz, FHX_ERR_ARG, "no plan is loaded (fhx_cz_load_plan)");
     if (n > 0x7fffffffll) return fhx::fail(cz, FHX_ERR_UNSUPPORTED, "2^31 or more rows");
-    const Refuse refuse{cz, why, bad_row};
+    const fhx::Refusal refuse{cz, why, bad_row};
     cz->n_rows = n;
     if (n == 0) return FHX_OK;
     const Plan plan{cz->d_first, cz->d_mids, cz->d_group_of, cz->n_chr};
@@ -332,8 +269,6 @@ int coarsen_rows(fhx_cz* cz, fhx::DeviceScratch& tmp, fhx::StageClock& clock, co
     TH_HIP(cz, tmp.get_n(&d_keys, (size_t)n));
     TH_HIP(cz, tmp.get_n(&d_kept_count, (size_t)n));
     Words words;
-    std::memset(&words, 0, sizeof(words));
-    words.first_error = words.first_big = NO_ERROR;
     TH_HIP(cz, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, cz->stream));
     hipLaunchKernelGGL(cz_keys, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, cz->stream, d[0], d[1], d[2], d[3], d[4], n, plan, keep_diagonal,
                        d_keys, d_kept_count, d_words);
@@ -364,45 +299,34 @@ int coarsen_rows(fhx_cz* cz, fhx::DeviceScratch& tmp, fhx::StageClock& clock, co
     clock.mark(2);
     // ---- run heads, and the prefix of the counts at every head ---------------------------------------------------------------------
     const int64_t tiles = (kept + fhxscan::TILE - 1) / fhxscan::TILE;
-    unsigned int* d_tile_cnt = nullptr;
-    unsigned long long *d_tile_off = nullptr, *d_tile_sum = nullptr, *d_tile_prefix = nullptr, *d_head_at = nullptr, *d_prefix_at = nullptr;
+    unsigned long long *d_tile_sum = nullptr, *d_tile_prefix = nullptr, *d_head_at = nullptr, *d_prefix_at = nullptr;
     int32_t* d_sorted_count = nullptr;
-    TH_HIP(cz, tmp.get_n(&d_tile_cnt, (size_t)tiles));
-    TH_HIP(cz, tmp.get_n(&d_tile_off, (size_t)tiles));
     TH_HIP(cz, tmp.get_n(&d_tile_sum, (size_t)tiles));
     TH_HIP(cz, tmp.get_n(&d_tile_prefix, (size_t)tiles));
     TH_HIP(cz, tmp.get_n(&d_sorted_count, (size_t)kept));
-    hipLaunchKernelGGL(fhxscan::count_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, cz->stream, (const unsigned long long*)d_sorted, kept,
-                       d_tile_cnt);
-    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, cz->stream, (const unsigned int*)d_tile_cnt, tiles, d_tile_off,
-                       &d_words->n_cells);
     hipLaunchKernelGGL(cz_tile_sums, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, cz->stream, (const unsigned int*)d_perm,
                        (const int32_t*)d_kept_count, kept, d_sorted_count, d_tile_sum);
-    hipLaunchKernelGGL(cz_scan_sums, dim3(1), dim3(fhxscan::THREADS), 0, cz->stream, (const unsigned long long*)d_tile_sum, tiles, d_tile_prefix,
+    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, cz->stream, (const unsigned long long*)d_tile_sum, tiles, d_tile_prefix,
                        &d_words->total);
-    TH_HIP(cz, hipGetLastError());
-    unsigned long long cells = 0;
-    TH_HIP(cz, hipMemcpyAsync(&cells, &d_words->n_cells, sizeof(cells), hipMemcpyDeviceToHost, cz->stream));
-    TH_HIP(cz, hipStreamSynchronize(cz->stream));
+    fhx::Heads heads;                                                         // its read of the count leaves the stream idle
+    if (const int rc = fhx::run_heads(refuse, FHX_CZ_INTERNAL, tmp, d_sorted, kept, &d_words->n_cells, /*positions=*/false, &heads)) return rc;
+    const int64_t cells = heads.cells;
     tmp.drop(d_perm);
     tmp.drop(d_kept_count);
-    if (cells == 0 || cells > (unsigned long long)kept) return refuse(FHX_ERR_INTERNAL, FHX_CZ_INTERNAL, 0, "the run heads do not match the keys");
     TH_HIP(cz, tmp.get_n(&d_head_at, (size_t)cells));
     TH_HIP(cz, tmp.get_n(&d_prefix_at, (size_t)cells));
     hipLaunchKernelGGL(cz_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, cz->stream, (const unsigned long long*)d_sorted,
-                       (const int32_t*)d_sorted_count, kept, (const unsigned long long*)d_tile_off, (const unsigned long long*)d_tile_prefix,
-                       (int64_t)cells, d_head_at, d_prefix_at);
+                       (const int32_t*)d_sorted_count, kept, (const unsigned long long*)heads.d_tile_off, (const unsigned long long*)d_tile_prefix,
+                       cells, d_head_at, d_prefix_at);
     TH_HIP(cz, hipGetLastError());
     TH_HIP(cz, hipStreamSynchronize(cz->stream));
     clock.mark(3);
     // ---- cells ---------------------------------------------------------------------------------------------------------------------
-    const int64_t stride = ((int64_t)cells + 63) / 64 * 64;                   // every column starts on a 256-byte boundary
-    TH_HIP(cz, fhx::dev_malloc(&cz->d_cols, (size_t)stride * 5 * sizeof(int32_t)));
-    cz->col_stride = stride;
-    int32_t* c = cz->d_cols;
-    hipLaunchKernelGGL(cz_cells, dim3((unsigned)(((int64_t)cells + WG - 1) / WG)), dim3(WG), 0, cz->stream, (const unsigned long long*)d_sorted, kept,
-                       (const unsigned long long*)d_head_at, (const unsigned long long*)d_prefix_at, (int64_t)cells, (const int32_t*)cz->d_coarse_chr,
-                       (const int32_t*)cz->d_coarse_mid, (int32_t)cz->n_coarse, c, c + stride, c + 2 * stride, c + 3 * stride, c + 4 * stride, d_words);
+    TH_HIP(cz, cz->cols.alloc(cells));
+    const fhx::CellColumns& C = cz->cols;
+    hipLaunchKernelGGL(cz_cells, dim3((unsigned)((cells + WG - 1) / WG)), dim3(WG), 0, cz->stream, (const unsigned long long*)d_sorted, kept,
+                       (const unsigned long long*)d_head_at, (const unsigned long long*)d_prefix_at, cells, (const int32_t*)cz->d_coarse_chr,
+                       (const int32_t*)cz->d_coarse_mid, (int32_t)cz->n_coarse, C.col(0), C.col(1), C.col(2), C.col(3), C.col(4), d_words);
     TH_HIP(cz, hipGetLastError());
     TH_HIP(cz, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, cz->stream));
     TH_HIP(cz, hipStreamSynchronize(cz->stream));
@@ -416,8 +340,7 @@ int coarsen_rows(fhx_cz* cz, fhx::DeviceScratch& tmp, fhx::StageClock& clock, co
                       std::to_string(words.max_sum) + "): the count column is int32");
     }
     clock.mark(4);
-    cz->n_cells = (int64_t)cells;
-    *n_cells = cz->n_cells;
+    *n_cells = cells;
     if (std::getenv("FHX_TIMING"))
         std::fprintf(stderr, "coarsen on the device: %lld rows, %lld dropped as diagonal, %lld cells: upload %.6f s; keys %.6f s; sort %.6f s; "
                      "heads + sums %.6f s; cells %.6f s\n", (long long)n, (long long)cz->n_diagonal, (long long)cells, cz->seconds[0], cz->seconds[1],
@@ -439,21 +362,13 @@ int begin_call(fhx_cz* cz) {
 
 extern "C" {
 
-int fhx_cz_create(int device, fhx_cz** out) {
-    const int rc = fhx::handle_create(device, out);
-    if (rc == FHX_OK && fhx_create(device, &(*out)->sorter) != FHX_OK) {
-        fhx_cz_destroy(*out);
-        *out = nullptr;
-        return FHX_ERR_HIP;
-    }
-    return rc;
-}
+int fhx_cz_create(int device, fhx_cz** out) { return fhx::handle_create_with_sorter(device, out); }
 
 void fhx_cz_destroy(fhx_cz* cz) {
     fhx::handle_destroy(cz, [&] {
         drop_cells(cz);
         drop_plan(cz);
-        if (cz->sorter) fhx_destroy(cz->sorter);
+        fhx::drop_sorter(cz);
     });
 }
 
@@ -519,7 +434,7 @@ int fhx_cz_counts(const fhx_cz* cz, int64_t* n_rows, int64_t* n_diagonal, int64_
     if (!cz) return FHX_ERR_ARG;
     if (n_rows) *n_rows = cz->n_rows;
     if (n_diagonal) *n_diagonal = cz->n_diagonal;
-    if (n_cells) *n_cells = cz->n_cells;
+    if (n_cells) *n_cells = cz->cols.n;
     return FHX_OK;
 }
 
@@ -530,20 +445,10 @@ int fhx_cz_stage_seconds(const fhx_cz* cz, double* seconds) {
 }
 
 int fhx_cz_fetch_cells(fhx_cz* cz, int32_t* chr1, int32_t* mid1, int32_t* chr2, int32_t* mid2, int32_t* count) {
-    if (!cz) return FHX_ERR_ARG;
-    if (cz->n_cells > 0 && (!chr1 || !mid1 || !chr2 || !mid2 || !count)) return FHX_ERR_ARG;
-    TH_HIP(cz, hipSetDevice(cz->device));
-    int32_t* out[5] = {chr1, mid1, chr2, mid2, count};
-    for (int k = 0; k < 5 && cz->n_cells > 0; ++k)
-        TH_HIP(cz, hipMemcpyAsync(out[k], cz->d_cols + k * cz->col_stride, (size_t)cz->n_cells * sizeof(int32_t), hipMemcpyDeviceToHost, cz->stream));
-    TH_HIP(cz, hipStreamSynchronize(cz->stream));
-    return FHX_OK;
+    return cz ? cz->cols.fetch(cz, {chr1, mid1, chr2, mid2, count}) : FHX_ERR_ARG;
 }
 
-void* fhx_cz_device_ptr(fhx_cz* cz, int32_t which) {
-    if (!cz || which < 0 || which > 4 || !cz->d_cols) return nullptr;
-    return cz->d_cols + which * cz->col_stride;
-}
+void* fhx_cz_device_ptr(fhx_cz* cz, int32_t which) { return cz ? cz->cols.ptr(which) : nullptr; }
 
 void* fhx_cz_stream(fhx_cz* cz) { return cz ? (void*)cz->stream : nullptr; }
 

@@ -4,9 +4,11 @@
 //   dev_malloc / dev_free   the two doors; they count the live blocks and bytes of the process (fhx_debug_device_blocks)
 //   raw members             a handle's long-lived blocks stay plain pointers: dev_malloc'ed where they are sized, dev_free'd
 //                           (which nulls them) where they are replaced and in the handle's destroy
-//   DeviceScratch           the blocks of one call: freed on every return path, or earlier with drop()
+//   DeviceScratch           the blocks of one call: freed on every return path, or earlier with drop(); grow() for an array
+//                           sized per batch, grow_keep() for one that accumulates over the batches
 //   GrowBuf<T>              a handle's grow-only buffer: steady-state calls allocate nothing
 //   Handle                  device, stream, error text; FHX_HIP_ON / fail() store the message and return the code
+//   upload<T>               a host table -> one of a handle's long-lived blocks
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -168,6 +170,22 @@ struct DeviceScratch {
         if (e == hipSuccess) *capacity = need;
         return e;
     }
+    // an array that grows to `need` elements and KEEPS its first `used` ones (at least doubling, so that a file of many batches
+    // moves its records a logarithmic number of times); the stream is idle afterwards
+    template <typename T>
+    hipError_t grow_keep(T** p, int64_t* capacity, int64_t used, int64_t need, hipStream_t stream) {
+        if (need <= *capacity) return hipSuccess;
+        const int64_t want = std::max<int64_t>(need, *capacity * 2);
+        T* bigger = nullptr;
+        hipError_t e = get_n(&bigger, (size_t)want);
+        if (e == hipSuccess && used > 0) e = hipMemcpyAsync(bigger, *p, (size_t)used * sizeof(T), hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) return e;                 // `bigger` goes with the call's other blocks
+        if (*p) drop(*p);
+        *p = bigger;
+        *capacity = want;
+        return hipSuccess;
+    }
 
   private:
     void release(std::pair<void*, size_t>& b) {
@@ -240,5 +258,14 @@ void handle_destroy(H* h, Drop drop) {
 }
 
 inline const char* handle_last_error(const Handle* h) { return h ? h->err.c_str() : "null context"; }
+
+// a host table of n elements as one of the handle's long-lived blocks (at least one element is allocated); the copy is in
+// flight on the handle's stream when this returns
+template <typename H, typename T>
+int upload(H* h, T** d, const T* src, size_t n) {
+    FHX_HIP_ON(h, dev_malloc(d, std::max<size_t>(n, 1) * sizeof(T)));
+    if (n) FHX_HIP_ON(h, hipMemcpyAsync(*d, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    return FHX_OK;
+}
 
 }  // namespace fhx

@@ -19,8 +19,9 @@
 //                  atomic, and the order of the buffer is the order of the file.
 //
 // A window that runs past the end of its batch matches nothing on the device; the host tests those at most 15 start positions
-// per batch edge against the bytes of the file (stitch_edge).  After the last batch fhx_sort_u64 orders the sites (several
-// motifs interleave, equal sites stay).  Names, their grammar and the duplicate check are the host's: one name per contig.
+// per batch edge against the bytes of the file (stitch_edge).  The sites of the batches so far stay in one array that grows
+// with its contents (DeviceScratch::grow_keep); after the last batch fhx_sort_u64 orders them (several motifs interleave, equal
+// sites stay; the handle owns its sorter through fhx_cells.hpp).  Names, their grammar and the duplicate check are the host's: one name per contig.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,7 +34,7 @@
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
-#include "fhx_textupload.hpp"
+#include "fhx_cells.hpp"
 
 namespace dgd {
 
@@ -393,16 +394,7 @@ int digest_file(fhx_dg* dg, const char* path, const dgd::Motifs& motifs, const i
         TH_HIP(dg, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, dg->stream));
         TH_HIP(dg, hipStreamSynchronize(dg->stream));
         const int64_t batch_hits = first_error != NO_ERROR ? 0 : (int64_t)words.hits;
-        if (n_hits + batch_hits > hit_capacity) {                            // the sites of the earlier batches move to a larger block
-            const int64_t want = std::max<int64_t>(n_hits + batch_hits, hit_capacity * 2);
-            unsigned long long* bigger = nullptr;
-            TH_HIP(dg, tmp.get_n(&bigger, (size_t)want));
-            if (n_hits > 0) TH_HIP(dg, hipMemcpyAsync(bigger, d_hits, (size_t)n_hits * sizeof(unsigned long long), hipMemcpyDeviceToDevice, dg->stream));
-            TH_HIP(dg, hipStreamSynchronize(dg->stream));
-            if (d_hits) tmp.drop(d_hits);
-            d_hits = bigger;
-            hit_capacity = want;
-        }
+        TH_HIP(dg, tmp.grow_keep(&d_hits, &hit_capacity, n_hits, n_hits + batch_hits, dg->stream));       // the earlier batches' sites are kept
         if (batch_hits > 0) {
             hipLaunchKernelGGL(dg_walk<true>, dim3(grid), dim3(WG), 0, dg->stream, text, in.len, block_off, in.line_base,
                                (const unsigned long long*)d_seq_off, (const unsigned long long*)d_hdr_off, seq_base, (long long)hdr_base, carry_S,
@@ -484,20 +476,12 @@ int digest_file(fhx_dg* dg, const char* path, const dgd::Motifs& motifs, const i
 
 extern "C" {
 
-int fhx_dg_create(int device, fhx_dg** out) {
-    const int rc = fhx::handle_create(device, out);
-    if (rc == FHX_OK && fhx_create(device, &(*out)->sorter) != FHX_OK) {
-        fhx_dg_destroy(*out);
-        *out = nullptr;
-        return FHX_ERR_HIP;
-    }
-    return rc;
-}
+int fhx_dg_create(int device, fhx_dg** out) { return fhx::handle_create_with_sorter(device, out); }
 
 void fhx_dg_destroy(fhx_dg* dg) {
     fhx::text_handle_destroy(dg, [&] {
         drop_all(dg);
-        if (dg->sorter) fhx_destroy(dg->sorter);
+        fhx::drop_sorter(dg);
     });
 }
 

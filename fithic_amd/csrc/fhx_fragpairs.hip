@@ -1,18 +1,18 @@
 // fhx_fragpairs.hip - HiC-Pro's allValidPairs (one line per read pair) binned to RESTRICTION FRAGMENTS on MI355X (gfx950): the
 // contact counts that go with the fragments file of fithic_amd.digest for `fithic -r 0`.  The reference ships no script for
-// this; the semantics are the project's own.  The shape is fhx_validpairs.hip's - parse, key, sort, count -
-// with the grid division replaced by a search over the cut sites:
+// this; the semantics are the project's own.  Parse, key, sort, count as in fhx_validpairs.hip, over the same
+// shared layers (fhx_pairline.hpp, fhx_cells.hpp), with the grid division replaced by a search over the cut sites:
 //
 //   scan_text, scan_tiles    the newline layer (fhx_textlines.hpp) over batches cut at the last newline (fhx_textupload.hpp)
-//   fp_parse       the lines that begin in a block, one per lane, one walk along the line: where tokens 2, 3, 5, 6 lie.  A
+//   fp_parse       the lines that begin in a block, one per lane, one walk along the line (fhx_pairline.hpp): tokens 2, 3, 5, 6.  A
 //                  name is hashed (64-bit FNV-1a) and probed in a 16384-slot table the host made of the table's names and the
 //                  dropped ones; a hit counts only when the bytes equal the slot's text.  A position p lies in the fragment
 //                  k = bisect_left(E_c, p) of its contig (the bed is 0-based and half-open, p is 1-based: start < p <= end),
 //                  E_c being the contig's ascending fragment ends in HBM.  The pair becomes ONE word g1 << 32 | g2, g = the
-//                  row of the fragment in the fragments file, g1 < g2, stored compacted: a block scan of the keep flags and one
-//                  atomicAdd per 256 lines.  The two drop counts and the smallest bad line are reduced per wave first.
+//                  row of the fragment in the fragments file, g1 < g2, stored compacted (fhx::block_append: one atomicAdd per
+//                  256 lines).  The two drop counts and the smallest bad line are reduced per wave first.
 //   fhx_sort_u64   the stable radix sort; equal words are the pairs of one cell
-//   count_heads / scan_tiles / fp_heads / fp_cells    run heads -> cells (contig1, end1, contig2, end2, count); the contig of a
+//   fhx::run_heads, fp_cells    run heads (fhx_cells.hpp) -> cells (contig1, end1, contig2, end2, count); the contig of a
 //                  row is found by bisection over the contigs' first rows, a count is the distance between two heads
 //
 // Nothing is approximated: a line outside the grammar (the header lists it) is REFUSED with the smallest offending line number
@@ -29,7 +29,8 @@
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
-#include "fhx_textupload.hpp"
+#include "fhx_cells.hpp"
+#include "fhx_pairline.hpp"
 
 namespace fpd {
 
@@ -42,12 +43,12 @@ constexpr int NOT_FOUND = -2, DROPPED = -1;    // what a name gives when it is n
 
 // the words the kernels of one call share
 struct Words {
-    unsigned long long first_error;            // smallest (line << 8 | reason)
-    unsigned long long n_records;              // kept pairs so far
-    unsigned long long n_dropped_name;         // lines dropped for a name of the drop list
-    unsigned long long n_same_fragment;        // lines whose two ends lie in one fragment
-    unsigned long long n_cells;                // scan_tiles' total of the heads
-    unsigned long long max_count;              // largest cell count
+    unsigned long long first_error = NO_ERROR; // smallest (line << 8 | reason)
+    unsigned long long n_records = 0;          // kept pairs so far
+    unsigned long long n_dropped_name = 0;     // lines dropped for a name of the drop list
+    unsigned long long n_same_fragment = 0;    // lines whose two ends lie in one fragment
+    unsigned long long n_cells = 0;            // scan_tiles' total of the heads
+    unsigned long long max_count = 0;          // largest cell count
 };
 
 // what the kernels read of the fragment table, all of it in HBM
@@ -69,20 +70,7 @@ __host__ __device__ inline unsigned long long fnv1a(const unsigned char* s, int 
 }
 __host__ __device__ inline unsigned int slot_of(unsigned long long h) { return (unsigned int)((h ^ (h >> 32)) & (SLOTS - 1)); }
 
-__device__ inline bool is_digit(int c) { return c >= '0' && c <= '9'; }
-
-// digits (1..10 of them) at text[b, b + len) -> the value; false for anything else
-__device__ inline bool position(const unsigned char* __restrict__ text, int64_t b, int len, long long* out) {
-    if (len < 1 || len > 10) return false;
-    long long v = 0;
-    for (int k = 0; k < len; ++k) {
-        const int c = text[b + k];
-        if (!is_digit(c)) return false;
-        v = v * 10 + (c - '0');
-    }
-    *out = v;
-    return true;
-}
+using fhxpair::position;
 
 // the contig named by text[b, b + len), DROPPED, or NOT_FOUND.  An equal hash is no hit until the bytes are.
 __device__ inline int lookup(const Table& t, const unsigned char* __restrict__ text, int64_t b, int len) {
@@ -118,7 +106,6 @@ __global__ __launch_bounds__(WG) void fp_parse(const unsigned char* __restrict__
                                                int64_t n_lines_batch, int64_t line_base, Table table, unsigned long long* __restrict__ records,
                                                unsigned long long capacity, Words* __restrict__ words) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    __shared__ unsigned long long out_base;
     const BlockLines B = block_lines(text, T, block_off, lstart);
     unsigned long long first_error = NO_ERROR;
     unsigned int dropped_name = 0, same_fragment = 0;
@@ -128,57 +115,20 @@ __global__ __launch_bounds__(WG) void fp_parse(const unsigned char* __restrict__
         unsigned long long rec = 0;
         if (e < B.n_lines) {
             const int64_t r = B.row0 + e;
-            const int64_t start = B.b0 + lstart[e];
-            int why = 0, tok = 0;
-            bool in_tok = false;
-            int64_t tb[4] = {0, 0, 0, 0}, te[4] = {0, 0, 0, 0};              // tokens 2, 3, 5, 6
-            int64_t p = start;
-            for (;; ++p) {
-                const int c = p < T ? (int)text[p] : '\n';                    // the end of the text ends the line
-                if (c == '\n') break;
-                if (p - start >= MAX_LINE) {
-                    why = FHX_FP_LONG_LINE;
-                    break;
-                }
-                if (c == '\r' && p + 1 < T && text[p + 1] == '\n') break;     // \r\n
-                if (c < 0x20 ? c != '\t' : c >= 0x7f) {                       // NUL, controls (a lone \r among them), DEL, non-ASCII
-                    why = FHX_FP_BYTES;
-                    break;
-                }
-                const bool blank = c == ' ' || c == '\t';
-                if (!blank && !in_tok) {
-                    in_tok = true;
-                    ++tok;
-                    if (tok == 2) tb[0] = p;
-                    if (tok == 3) tb[1] = p;
-                    if (tok == 5) tb[2] = p;
-                    if (tok == 6) tb[3] = p;
-                } else if (blank && in_tok) {
-                    in_tok = false;
-                    if (tok == 2) te[0] = p;
-                    if (tok == 3) te[1] = p;
-                    if (tok == 5) te[2] = p;
-                    if (tok == 6) te[3] = p;
-                }
-            }
-            if (in_tok) {
-                if (tok == 2) te[0] = p;
-                if (tok == 3) te[1] = p;
-                if (tok == 5) te[2] = p;
-                if (tok == 6) te[3] = p;
-            }
-            if (!why && tok < 6) why = FHX_FP_TOKENS;
+            const fhxpair::Line L = fhxpair::walk(text, T, B.b0 + lstart[e]);
+            int why = L.stop == fhxpair::STOP_LONG_LINE ? FHX_FP_LONG_LINE : L.stop == fhxpair::STOP_BYTES ? FHX_FP_BYTES : 0;
+            if (!why && L.tok < 6) why = FHX_FP_TOKENS;
             if (!why && r >= n_lines_batch) why = FHX_FP_INTERNAL;           // the scan and this kernel disagree about the lines
             if (!why) {
-                const int l1 = (int)(te[0] - tb[0]), l2 = (int)(te[2] - tb[2]);
+                const int l1 = L.len(0), l2 = L.len(2);
                 bool same_name = l1 == l2;                                    // most pairs are cis: one lookup then
-                for (int k = 0; k < l1 && same_name; ++k) same_name = text[tb[0] + k] == text[tb[2] + k];
-                const int c1 = lookup(table, text, tb[0], l1);
-                const int c2 = same_name ? c1 : lookup(table, text, tb[2], l2);
+                for (int k = 0; k < l1 && same_name; ++k) same_name = text[L.tb[0] + k] == text[L.tb[2] + k];
+                const int c1 = lookup(table, text, L.tb[0], l1);
+                const int c2 = same_name ? c1 : lookup(table, text, L.tb[2], l2);
                 long long p1 = 0, p2 = 0;
                 if (c1 == DROPPED || c2 == DROPPED) ++dropped_name;           // the line is not read further
                 else if (c1 == NOT_FOUND || c2 == NOT_FOUND) why = FHX_FP_NAME;
-                else if (!position(text, tb[1], (int)(te[1] - tb[1]), &p1) || !position(text, tb[3], (int)(te[3] - tb[3]), &p2)) why = FHX_FP_POSITION;
+                else if (!position(text, L.tb[1], L.len(1), &p1) || !position(text, L.tb[3], L.len(3), &p2)) why = FHX_FP_POSITION;
                 else if (p1 < 1 || p2 < 1 || p1 > (long long)table.ends[table.first[c1 + 1] - 1] || p2 > (long long)table.ends[table.first[c2 + 1] - 1])
                     why = FHX_FP_RANGE;
                 else {
@@ -192,16 +142,12 @@ __global__ __launch_bounds__(WG) void fp_parse(const unsigned char* __restrict__
             }
             if (why) first_error = min(first_error, error_word(line_base + r + 1, why));
         }
-        unsigned int total;
-        const unsigned int at = fhxscan::block_exclusive_scan(keep ? 1u : 0u, &total);
-        if (threadIdx.x == 0) out_base = total ? atomicAdd(&words->n_records, (unsigned long long)total) : 0ull;
-        __syncthreads();
+        const unsigned long long pos = fhx::block_append(keep, &words->n_records, capacity);
         if (keep) {
-            const unsigned long long pos = out_base + at;
-            if (pos < capacity) records[pos] = rec;
+            if (pos != fhx::APPEND_OVER) records[pos] = rec;
             else first_error = min(first_error, error_word(line_base + B.row0 + e + 1, FHX_FP_INTERNAL));
         }
-        __syncthreads();                                    // out_base is written again in the next round
+        __syncthreads();                                    // block_append's LDS word is written again in the next round
     }
     for (int s = 32; s >= 1; s >>= 1) {
         first_error = min(first_error, (unsigned long long)__shfl_down(first_error, s, 64));
@@ -213,23 +159,6 @@ __global__ __launch_bounds__(WG) void fp_parse(const unsigned char* __restrict__
         if (dropped_name) atomicAdd(&words->n_dropped_name, (unsigned long long)dropped_name);
         if (same_fragment) atomicAdd(&words->n_same_fragment, (unsigned long long)same_fragment);
     }
-}
-
-// the run heads of the sorted keys, in order: where each run starts
-__global__ __launch_bounds__(fhxscan::THREADS) void fp_heads(const unsigned long long* __restrict__ keys, int64_t n,
-                                                             const unsigned long long* __restrict__ tile_offsets, int64_t n_cells,
-                                                             unsigned long long* __restrict__ head_at) {
-    const int64_t base = (int64_t)blockIdx.x * fhxscan::TILE + (int64_t)threadIdx.x * fhxscan::SCAN_ITEMS;
-    unsigned int c = 0;
-    bool head[fhxscan::SCAN_ITEMS];
-    for (int k = 0; k < fhxscan::SCAN_ITEMS; ++k) {
-        head[k] = base + k < n && fhxscan::is_head(keys, base + k);
-        c += head[k] ? 1u : 0u;
-    }
-    unsigned int total;
-    unsigned long long pos = tile_offsets[blockIdx.x] + fhxscan::block_exclusive_scan(c, &total);
-    for (int k = 0; k < fhxscan::SCAN_ITEMS; ++k)
-        if (head[k] && (int64_t)pos < n_cells) head_at[pos++] = (unsigned long long)(base + k);
 }
 
 // the contig of row g: the last c with first[c] <= g (a contig has at least one fragment: first is strictly ascending)
@@ -280,18 +209,16 @@ struct fhx_fp : fhx::TextHandle {
     unsigned char* d_name_text = nullptr;
     double table_seconds = 0;
     // the last binned file
-    int64_t n_lines = 0, n_pairs = 0, n_dropped_name = 0, n_same_fragment = 0, n_cells = 0;
-    int32_t* d_cols = nullptr;                    // five columns of col_stride elements
-    int64_t col_stride = 0;
+    int64_t n_lines = 0, n_pairs = 0, n_dropped_name = 0, n_same_fragment = 0;
+    fhx::CellColumns cols;
     double seconds[FHX_FP_STAGES] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace {
 
 void drop_cells(fhx_fp* fp) {
-    fhx::dev_free(fp->d_cols);
-    fp->n_lines = fp->n_pairs = fp->n_dropped_name = fp->n_same_fragment = fp->n_cells = 0;
-    fp->col_stride = 0;
+    fp->cols.drop();
+    fp->n_lines = fp->n_pairs = fp->n_dropped_name = fp->n_same_fragment = 0;
 }
 
 void drop_table(fhx_fp* fp) {
@@ -305,17 +232,11 @@ void drop_table(fhx_fp* fp) {
     fp->n_frags = 0;
 }
 
-template <typename T>
-int upload(fhx_fp* fp, T** d, const T* src, size_t n) {
-    TH_HIP(fp, fhx::dev_malloc(d, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n) TH_HIP(fp, hipMemcpyAsync(*d, src, n * sizeof(T), hipMemcpyHostToDevice, fp->stream));
-    return FHX_OK;
-}
-
 // fhx_fp_load_table behind its argument check; whatever it returns but FHX_OK, the caller drops the table
 int load_table(fhx_fp* fp, const char* name_text, const int32_t* name_contig, int32_t n_names, const int64_t* first, int32_t n_contigs,
                const int32_t* ends, int64_t n_frags) {
     using namespace fpd;
+    using fhx::upload;
     if (n_contigs > FHX_FP_MAX_CONTIGS) return fhx::fail(fp, FHX_ERR_UNSUPPORTED, "more than " + std::to_string(FHX_FP_MAX_CONTIGS) + " contigs");
     if (n_names > MAX_NAMES) return fhx::fail(fp, FHX_ERR_UNSUPPORTED, "more than " + std::to_string(MAX_NAMES) + " names, the contigs' and the dropped ones together");
     if (n_frags > 0x7fffffffll) return fhx::fail(fp, FHX_ERR_UNSUPPORTED, "2^31 or more fragments");
@@ -382,8 +303,6 @@ int bin_file(fhx_fp* fp, const char* path, int64_t* n_cells, int32_t* why, int64
     int64_t capacity = 0;
     TH_HIP(fp, tmp.get_n(&d_words, 1));
     Words words;                                                              // running totals: set once, not per batch
-    std::memset(&words, 0, sizeof(words));
-    words.first_error = NO_ERROR;
     TH_HIP(fp, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, fp->stream));
     TH_HIP(fp, hipStreamSynchronize(fp->stream));
     const fhx::Refusal refuse{fp, why, bad_line};
@@ -392,16 +311,7 @@ int bin_file(fhx_fp* fp, const char* path, int64_t* n_cells, int32_t* why, int64
         if (const int rc = in.next<AnyByte>()) return rc;                     // this path's policy refuses no byte: fp_parse names the line
         const int64_t n = in.lines;
         if (pairs + n >= ((int64_t)1 << 32)) return refuse(FHX_ERR_UNSUPPORTED, FHX_FP_PAIRS, 0, "2^32 or more pairs may be kept: the sort does not take them");
-        if (pairs + n > capacity) {                                           // room for every line of the batch to be kept
-            const int64_t want = std::max<int64_t>(pairs + n, capacity * 2);
-            unsigned long long* bigger = nullptr;
-            TH_HIP(fp, tmp.get_n(&bigger, (size_t)want));
-            if (pairs) TH_HIP(fp, hipMemcpyAsync(bigger, d_records, (size_t)pairs * sizeof(unsigned long long), hipMemcpyDeviceToDevice, fp->stream));
-            TH_HIP(fp, hipStreamSynchronize(fp->stream));
-            tmp.drop(d_records);
-            d_records = bigger;
-            capacity = want;
-        }
+        TH_HIP(fp, tmp.grow_keep(&d_records, &capacity, pairs, pairs + n, fp->stream));        // room for every line of the batch to be kept
         hipLaunchKernelGGL(fp_parse, dim3((unsigned)in.n_blocks), dim3(WG), 0, fp->stream, (const unsigned char*)in.d_text, in.len,
                            (const unsigned long long*)in.d_block_off, n, in.line_base, table, d_records, (unsigned long long)capacity, d_words);
         TH_HIP(fp, hipGetLastError());
@@ -434,30 +344,14 @@ int bin_file(fhx_fp* fp, const char* path, int64_t* n_cells, int32_t* why, int64
     tmp.drop(d_perm);
     clock.mark(3);
     // ---- run heads -> cells --------------------------------------------------------------------------------------------------
-    const int64_t tiles = (pairs + fhxscan::TILE - 1) / fhxscan::TILE;
-    unsigned int* d_tile_cnt = nullptr;
-    unsigned long long *d_tile_off = nullptr, *d_head_at = nullptr;
-    TH_HIP(fp, tmp.get_n(&d_tile_cnt, (size_t)tiles));
-    TH_HIP(fp, tmp.get_n(&d_tile_off, (size_t)tiles));
-    hipLaunchKernelGGL(fhxscan::count_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, fp->stream, (const unsigned long long*)d_sorted, pairs,
-                       d_tile_cnt);
-    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, fp->stream, (const unsigned int*)d_tile_cnt, tiles, d_tile_off,
-                       &d_words->n_cells);
-    TH_HIP(fp, hipGetLastError());
-    unsigned long long cells = 0;
-    TH_HIP(fp, hipMemcpyAsync(&cells, &d_words->n_cells, sizeof(cells), hipMemcpyDeviceToHost, fp->stream));
-    TH_HIP(fp, hipStreamSynchronize(fp->stream));
-    if (cells == 0 || cells > (unsigned long long)pairs) return refuse(FHX_ERR_INTERNAL, FHX_FP_INTERNAL, 0, "the run heads do not match the keys");
-    const int64_t stride = ((int64_t)cells + 63) / 64 * 64;                   // every column starts on a 256-byte boundary
-    TH_HIP(fp, tmp.get_n(&d_head_at, (size_t)cells));
-    TH_HIP(fp, fhx::dev_malloc(&fp->d_cols, (size_t)stride * 5 * sizeof(int32_t)));
-    fp->col_stride = stride;
-    int32_t* c = fp->d_cols;
-    hipLaunchKernelGGL(fp_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, fp->stream, (const unsigned long long*)d_sorted, pairs,
-                       (const unsigned long long*)d_tile_off, (int64_t)cells, d_head_at);
-    hipLaunchKernelGGL(fp_cells, dim3((unsigned)std::min<int64_t>(((int64_t)cells + WG - 1) / WG, 8192)), dim3(WG), 0, fp->stream,
-                       (const unsigned long long*)d_sorted, pairs, (const unsigned long long*)d_head_at, (int64_t)cells, (const int32_t*)fp->d_first,
-                       fp->n_contigs, (int32_t)fp->n_frags, (const int32_t*)fp->d_ends, c, c + stride, c + 2 * stride, c + 3 * stride, c + 4 * stride,
+    fhx::Heads heads;
+    if (const int rc = fhx::run_heads(refuse, FHX_FP_INTERNAL, tmp, d_sorted, pairs, &d_words->n_cells, /*positions=*/true, &heads)) return rc;
+    const int64_t cells = heads.cells;
+    TH_HIP(fp, fp->cols.alloc(cells));
+    const fhx::CellColumns& C = fp->cols;
+    hipLaunchKernelGGL(fp_cells, dim3((unsigned)std::min<int64_t>((cells + WG - 1) / WG, 8192)), dim3(WG), 0, fp->stream,
+                       (const unsigned long long*)d_sorted, pairs, (const unsigned long long*)heads.d_head_at, cells, (const int32_t*)fp->d_first,
+                       fp->n_contigs, (int32_t)fp->n_frags, (const int32_t*)fp->d_ends, C.col(0), C.col(1), C.col(2), C.col(3), C.col(4),
                        &d_words->max_count);
     TH_HIP(fp, hipGetLastError());
     unsigned long long max_count = 0;
@@ -465,8 +359,7 @@ int bin_file(fhx_fp* fp, const char* path, int64_t* n_cells, int32_t* why, int64
     TH_HIP(fp, hipStreamSynchronize(fp->stream));
     clock.mark(4);
     if (max_count > 0x7fffffffull) return refuse(FHX_ERR_UNSUPPORTED, FHX_FP_COUNT, 0, "a cell is hit by more than 2^31 - 1 pairs: the count column is int32");
-    fp->n_cells = (int64_t)cells;
-    *n_cells = fp->n_cells;
+    *n_cells = cells;
     if (std::getenv("FHX_TIMING"))
         std::fprintf(stderr, "validPairs to fragments on the device (%s): %lld lines, %lld kept pairs, %lld cells: read + upload %.6f s; scan %.6f s; "
                      "parse %.6f s; sort %.6f s; cells %.6f s\n", path, (long long)lines, (long long)pairs, (long long)cells, fp->seconds[0],
@@ -478,21 +371,13 @@ int bin_file(fhx_fp* fp, const char* path, int64_t* n_cells, int32_t* why, int64
 
 extern "C" {
 
-int fhx_fp_create(int device, fhx_fp** out) {
-    const int rc = fhx::handle_create(device, out);
-    if (rc == FHX_OK && fhx_create(device, &(*out)->sorter) != FHX_OK) {
-        fhx_fp_destroy(*out);
-        *out = nullptr;
-        return FHX_ERR_HIP;
-    }
-    return rc;
-}
+int fhx_fp_create(int device, fhx_fp** out) { return fhx::handle_create_with_sorter(device, out); }
 
 void fhx_fp_destroy(fhx_fp* fp) {
     fhx::text_handle_destroy(fp, [&] {
         drop_cells(fp);
         drop_table(fp);
-        if (fp->sorter) fhx_destroy(fp->sorter);
+        fhx::drop_sorter(fp);
     });
 }
 
@@ -527,7 +412,7 @@ int fhx_fp_counts(const fhx_fp* fp, int64_t* n_lines, int64_t* n_pairs, int64_t*
     if (n_pairs) *n_pairs = fp->n_pairs;
     if (n_dropped_name) *n_dropped_name = fp->n_dropped_name;
     if (n_same_fragment) *n_same_fragment = fp->n_same_fragment;
-    if (n_cells) *n_cells = fp->n_cells;
+    if (n_cells) *n_cells = fp->cols.n;
     return FHX_OK;
 }
 
@@ -538,20 +423,10 @@ int fhx_fp_stage_seconds(const fhx_fp* fp, double* seconds) {
 }
 
 int fhx_fp_fetch_cells(fhx_fp* fp, int32_t* chr1, int32_t* end1, int32_t* chr2, int32_t* end2, int32_t* count) {
-    if (!fp) return FHX_ERR_ARG;
-    if (fp->n_cells > 0 && (!chr1 || !end1 || !chr2 || !end2 || !count)) return FHX_ERR_ARG;
-    TH_HIP(fp, hipSetDevice(fp->device));
-    int32_t* out[5] = {chr1, end1, chr2, end2, count};
-    for (int k = 0; k < 5 && fp->n_cells > 0; ++k)
-        TH_HIP(fp, hipMemcpyAsync(out[k], fp->d_cols + k * fp->col_stride, (size_t)fp->n_cells * sizeof(int32_t), hipMemcpyDeviceToHost, fp->stream));
-    TH_HIP(fp, hipStreamSynchronize(fp->stream));
-    return FHX_OK;
+    return fp ? fp->cols.fetch(fp, {chr1, end1, chr2, end2, count}) : FHX_ERR_ARG;
 }
 
-void* fhx_fp_device_ptr(fhx_fp* fp, int32_t which) {
-    if (!fp || which < 0 || which > 4 || !fp->d_cols) return nullptr;
-    return fp->d_cols + which * fp->col_stride;
-}
+void* fhx_fp_device_ptr(fhx_fp* fp, int32_t which) { return fp ? fp->cols.ptr(which) : nullptr; }
 
 void* fhx_fp_stream(fhx_fp* fp) { return fp ? (void*)fp->stream : nullptr; }
 

@@ -5,6 +5,8 @@
 // fragDic[j][3] += cc`, five str() and a gzip write per line.  Here the file goes to HBM as it is (two pinned buffers filled
 // by pread, drained by the copy engine: fhx_textupload.hpp) and kernels do everything that is per line:
 //
+// The five columns of the result are an fhx::CellColumns (fhx_cells.hpp).
+//
 //   scan_text, scan_tiles    the newline layer (fhx_textlines.hpp) with the text-mode byte policy: the row number of every
 //                  block's first line, and a flag for NUL, non-ASCII and a \r that is not followed by \n
 //   hp_parse       the lines that begin in a block, one per lane: three tokens, (chr, mid) of i and j gathered from the dense
@@ -30,7 +32,7 @@
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
-#include "fhx_textupload.hpp"
+#include "fhx_cells.hpp"
 
 namespace hpd {
 
@@ -199,18 +201,12 @@ struct fhx_hp : fhx::TextHandle {
     int2* d_bins = nullptr;
     unsigned long long* d_totals = nullptr;
     // the last parsed matrix
-    int64_t n_rows = 0;
-    int32_t* d_cols = nullptr;                    // five columns of col_stride elements
-    int64_t col_stride = 0;
+    fhx::CellColumns cols;
 };
 
 namespace {
 
-void drop_rows(fhx_hp* hp) {
-    fhx::dev_free(hp->d_cols);
-    hp->n_rows = 0;
-    hp->col_stride = 0;
-}
+void drop_rows(fhx_hp* hp) { hp->cols.drop(); }
 
 }  // namespace
 
@@ -305,13 +301,11 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
     clock.mark(1);
     const int64_t n = whole.lines(n_newlines);
     if (n > 0x7fffffffll) return fhx::fail(hp, FHX_ERR_UNSUPPORTED, "a matrix of more than 2^31 - 1 lines");
-    const int64_t stride = (n + 63) / 64 * 64;                                // every column starts on a 256-byte boundary
-    TH_HIP(hp, fhx::dev_malloc(&hp->d_cols, (size_t)std::max<int64_t>(stride, 64) * 5 * sizeof(int32_t)));
-    hp->col_stride = stride;
-    int32_t* c = hp->d_cols;
+    TH_HIP(hp, hp->cols.alloc(n));
+    const fhx::CellColumns& C = hp->cols;
     hipLaunchKernelGGL(hp_parse, dim3((unsigned)n_blocks), dim3(WG), 0, hp->stream, (const unsigned char*)d_text, T,
-                       (const unsigned long long*)d_block_off, (const int2*)hp->d_bins, (long long)hp->index_base, (long long)hp->n_slots, n, c,
-                       c + stride, c + 2 * stride, c + 3 * stride, c + 4 * stride, hp->d_totals, d_words + 1, d_words + 2);
+                       (const unsigned long long*)d_block_off, (const int2*)hp->d_bins, (long long)hp->index_base, (long long)hp->n_slots, n, C.col(0),
+                       C.col(1), C.col(2), C.col(3), C.col(4), hp->d_totals, d_words + 1, d_words + 2);
     hipLaunchKernelGGL(hp_max_total, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((hp->n_slots + WG - 1) / WG, 1024))), dim3(WG), 0,
                        hp->stream, (const unsigned long long*)hp->d_totals, (long long)hp->n_slots, d_words + 3);
     TH_HIP(hp, hipGetLastError());
@@ -346,7 +340,6 @@ int fhx_hp_parse_matrix(fhx_hp* hp, const char* path, int64_t* n_rows, int32_t* 
     if (words[4]) return refuse(FHX_ERR_INTERNAL, FHX_HP_INTERNAL, 0, 0, "the scan saw a byte this path does not take, the parse kernel did not");
     if (words[3] >= TOTAL_LIMIT)
         return refuse(FHX_ERR_UNSUPPORTED, FHX_HP_TOTAL, 0, 0, "a bin's total contact count reaches 2^53: the reference's float sum would round");
-    hp->n_rows = n;
     *n_rows = n;
     return FHX_OK;
 }
@@ -361,20 +354,10 @@ int fhx_hp_totals(fhx_hp* hp, int64_t* tcc) {
 }
 
 int fhx_hp_fetch_rows(fhx_hp* hp, int32_t* chr1, int32_t* mid1, int32_t* chr2, int32_t* mid2, int32_t* count) {
-    if (!hp) return FHX_ERR_ARG;
-    if (hp->n_rows > 0 && (!chr1 || !mid1 || !chr2 || !mid2 || !count)) return FHX_ERR_ARG;
-    TH_HIP(hp, hipSetDevice(hp->device));
-    int32_t* out[5] = {chr1, mid1, chr2, mid2, count};
-    for (int k = 0; k < 5 && hp->n_rows > 0; ++k)
-        TH_HIP(hp, hipMemcpyAsync(out[k], hp->d_cols + k * hp->col_stride, (size_t)hp->n_rows * sizeof(int32_t), hipMemcpyDeviceToHost, hp->stream));
-    TH_HIP(hp, hipStreamSynchronize(hp->stream));
-    return FHX_OK;
+    return hp ? hp->cols.fetch(hp, {chr1, mid1, chr2, mid2, count}) : FHX_ERR_ARG;
 }
 
-void* fhx_hp_device_ptr(fhx_hp* hp, int32_t which) {
-    if (!hp || which < 0 || which > 4 || !hp->d_cols) return nullptr;
-    return hp->d_cols + which * hp->col_stride;
-}
+void* fhx_hp_device_ptr(fhx_hp* hp, int32_t which) { return hp ? hp->cols.ptr(which) : nullptr; }
 
 void* fhx_hp_stream(fhx_hp* hp) { return hp ? (void*)hp->stream : nullptr; }
 

@@ -33,6 +33,7 @@
 
 #include "../../include/fithic_mi355x.h"
 #include "fhx_fmt.hpp"
+#include "fhx_pairline.hpp"
 #include "fhx_textupload.hpp"
 
 namespace jcd {
@@ -56,7 +57,7 @@ struct JcBytes {                               // scan_text's policy
     static __device__ void check(bool& bad, unsigned int c, const unsigned char*, int64_t, int64_t) { bad |= refused_byte(c); }
 };
 
-__device__ inline bool is_digit(int c) { return c >= '0' && c <= '9'; }
+using fhxpair::is_digit;
 
 // one line split at runs of blank and tab: tokens 1 to 3 relative to the line's first byte (length 0: the token is missing)
 struct Line {

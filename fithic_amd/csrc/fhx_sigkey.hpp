@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "../../include/fithic_mi355x.h"
+#include "fhx_pairline.hpp"
 
 namespace msd {
 
@@ -26,7 +27,7 @@ struct Fdr {
     int len;
 };
 
-__device__ inline bool is_digit(int c) { return c >= '0' && c <= '9'; }
+using fhxpair::is_digit;
 
 // Field 7 at text[b, b + len): 0 = not the %e shape (or one the classes leave out), 1 = zero, 2 = numeric (*key set), 3 = string.
 __device__ inline int classify(const unsigned char* __restrict__ text, int64_t b, int len, unsigned long long* key) {

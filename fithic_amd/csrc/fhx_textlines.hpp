@@ -1,6 +1,6 @@
 // fhx_textlines.hpp - the newline layer of every device text path: fhx_ingest.inc (contact counts), fhx_hicpro.hip (HiC-Pro
-// matrix), fhx_validpairs.hip (allValidPairs), fhx_juicer.hip (Juicer dump) and fhx_sigselect.hip with fhx_sigtrack.inc and
-// fhx_sigsplit.inc (significances).  A text lies in HBM, padded with blanks to whole blocks plus 64 bytes (fhx_textupload.hpp
+// matrix), fhx_validpairs.hip and fhx_fragpairs.hip (allValidPairs; their line walk is fhx_pairline.hpp), fhx_digest.hip (FASTA),
+// fhx_juicer.hip (Juicer dump) and fhx_sigselect.hip with fhx_sigtrack.inc and fhx_sigsplit.inc (significances).  A text lies in HBM, padded with blanks to whole blocks plus 64 bytes (fhx_textupload.hpp
 // upload_batch); a workgroup of WG lanes owns BLOCK_BYTES of it, SEG bytes per lane read as 16-byte loads.
 //
 //   scan_text<Bytes>   newlines per block, and bit REFUSED_BYTES in a flag word when a byte the path's policy refuses is seen

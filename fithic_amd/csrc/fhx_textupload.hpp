@@ -1,5 +1,5 @@
-// fhx_textupload.hpp - the host side that the device text paths share (fhx_hicpro.hip, fhx_validpairs.hip, fhx_juicer.hip,
-// fhx_sigselect.hip with fhx_sigtrack.inc and fhx_sigsplit.inc): the text handle (fhx_devmem.hpp's Handle plus the pinned
+// fhx_textupload.hpp - the host side that the device text paths share (fhx_hicpro.hip, fhx_validpairs.hip, fhx_fragpairs.hip,
+// fhx_digest.hip, fhx_juicer.hip, fhx_sigselect.hip with fhx_sigtrack.inc and fhx_sigsplit.inc): the text handle (fhx_devmem.hpp's Handle plus the pinned
 // upload buffers), the stage clock, and the way a text file (fhx_textfile.hpp) reaches HBM: host threads fill one of two
 // pinned buffers while the copy engine drains the other, in batches cut at the last newline and padded with blanks as
 // fhx_textlines.hpp's 16-byte loads need it.  TextBatches is the loop over such batches with the newline layer run on each;
@@ -22,7 +22,7 @@
 
 namespace fhx {
 
-// what fhx_hp, fhx_vp, fhx_jc and fhx_ms have in common beyond fhx::Handle: the upload path, made on first use
+// what fhx_hp, fhx_vp, fhx_fp, fhx_dg, fhx_jc and fhx_ms have in common beyond fhx::Handle: the upload path, made on first use
 struct TextHandle : Handle {
     static constexpr size_t kChunk = (size_t)32 << 20;
     void* pinned[2] = {nullptr, nullptr};
@@ -191,9 +191,10 @@ struct TextBatches {
     ScanWords* d_scan = nullptr;
 };
 
-// Where a refusal of a call goes: the caller's why / bad_line, the handle's message, and the code to return.
+// Where a refusal of a call goes: the caller's why / bad_line (fhx_coarsen.hip: bad row), the handle's message, and the code
+// to return.
 struct Refusal {
-    TextHandle* h;
+    Handle* h;
     int32_t* why;
     int64_t* bad_line;
     int operator()(int rc, int32_t w, int64_t line, const std::string& msg) const {

@@ -6,14 +6,14 @@
 //
 //   scan_text, scan_tiles    the newline layer (fhx_textlines.hpp), no byte refused there: the line number of every block's
 //                  first line
-//   vp_parse       the lines that begin in a block, one per lane.  One walk along the line splits it on blanks, keeps where
-//                  tokens 2, 3, 5, 6 lie and looks for `chrM` anywhere (grep -v chrM, :34); then the name-length filter (:34),
+//   vp_parse       the lines that begin in a block, one per lane.  One walk along the line (fhx_pairline.hpp's, in place) splits it on
+//                  blanks, keeps where tokens 2, 3, 5, 6 lie and looks for `chrM` anywhere (grep -v chrM, :34); then the name-length filter (:34),
 //                  the distance filter (pos1-pos2)^2 > 2*res (:35 - the comparison sits INSIDE the sqrt), the bins
 //                  int(pos/res) (:36) and the order of the two ends (:37).  A name of <= 5 bytes is 40 bits, big-endian and
 //                  zero-padded: its integer order is its byte order.  The distinct names go into a 2048-slot table in HBM
 //                  (one load per name once it is there, a compare-and-swap only for a new one); a kept pair becomes the record
-//                  (slot1 << 32 | bin1, slot2 << 32 | bin2), stored compacted: a block scan of the keep flags and ONE atomicAdd
-//                  per 256 lines (r04_w_atomic_rate: same-address atomics run at 0.09e9/s - never one per line).
+//                  (slot1 << 32 | bin1, slot2 << 32 | bin2), stored compacted (fhx::block_append: a block scan of the
+//                  keep flags and ONE atomicAdd per 256 lines; r04_w_atomic_rate: same-address atomics run at 0.09e9/s).
 //
 // After the last batch the host ranks the names bytewise (sort runs under LC_ALL=C, :38) and
 //
@@ -22,8 +22,9 @@
 //                  shorter one is smaller than '0'); fhx_sort_u64 + vp_invert give t[k] = the TEXT rank of bin k
 //   vp_keys        record -> one 64-bit key  rank1 | t[bin1] | rank2 | t[bin2], bit widths fitted to the data
 //   fhx_sort_u64   the stable radix sort; equal keys are the duplicates uniq -c counts
-//   count_heads / scan_tiles / vp_heads / vp_cells    run heads -> cells (chr1, mid1, chr2, mid2, count) in the script's text
-//                  order; a count is the distance between two heads (64-bit), never a walk along the run
+//   fhx::run_heads, vp_cells    run heads (fhx_cells.hpp: count_heads / scan_tiles / head_positions) -> cells (chr1, mid1, chr2,
+//                  mid2, count) in the script's text order; a count is the distance between two heads (64-bit), never a walk
+//                  along the run
 //
 // ONLY THE REGULAR FILE IS TAKEN (the header lists the grammar); anything else is REFUSED with the smallest offending line number
 // (one 64-bit word, atomicMin over line << 8 | reason: the same answer whatever the launch order) and nothing stays loaded.
@@ -38,7 +39,8 @@
 #include <vector>
 
 #include "../../include/fithic_mi355x.h"
-#include "fhx_textupload.hpp"
+#include "fhx_cells.hpp"
+#include "fhx_pairline.hpp"
 
 namespace vpd {
 
@@ -49,16 +51,17 @@ constexpr int MAX_NAMES = 1024;
 
 // the words the kernels of one call share
 struct Words {
-    unsigned long long first_error;            // smallest (line << 8 | reason)
-    unsigned long long n_records;              // kept pairs so far
-    unsigned long long max_bin;                // largest bin index among them
-    unsigned long long n_names;                // distinct names in the table
-    unsigned long long n_cells;                // scan_tiles' total of the heads
-    unsigned long long max_count;              // largest cell count
-    unsigned long long names_overflow;         // 1: a pair named a name the full table could not take
+    unsigned long long first_error = NO_ERROR; // smallest (line << 8 | reason)
+    unsigned long long n_records = 0;          // kept pairs so far
+    unsigned long long max_bin = 0;            // largest bin index among them
+    unsigned long long n_names = 0;            // distinct names in the table
+    unsigned long long n_cells = 0;            // scan_tiles' total of the heads
+    unsigned long long max_count = 0;          // largest cell count
+    unsigned long long names_overflow = 0;     // 1: a pair named a name the full table could not take
 };
 
-__device__ inline bool is_digit(int c) { return c >= '0' && c <= '9'; }
+using fhxpair::is_digit;
+using fhxpair::position;
 __device__ inline bool is_alpha(int c) { return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); }
 
 // A name of 1..5 bytes at text[b, b + len) -> its 40-bit word, or 0 for a name awk would compare as a number (or might): the
@@ -92,19 +95,6 @@ __device__ inline bool name_less(unsigned long long a, int la, unsigned long lon
     return a < b;
 }
 
-// digits (1..10 of them) at text[b, b + len) -> the value; false for anything else
-__device__ inline bool position(const unsigned char* __restrict__ text, int64_t b, int len, long long* out) {
-    if (len < 1 || len > 10) return false;
-    long long v = 0;
-    for (int k = 0; k < len; ++k) {
-        const int c = text[b + k];
-        if (!is_digit(c)) return false;
-        v = v * 10 + (c - '0');
-    }
-    *out = v;
-    return true;
-}
-
 // the slot of `name` in the table, inserting it when it is new; -1 when the table holds MAX_NAMES other names already
 __device__ inline int intern_name(unsigned long long* __restrict__ table, unsigned long long* __restrict__ n_names, unsigned long long name) {
     unsigned int h = (unsigned int)((name * 0x9E3779B97F4A7C15ull) >> 53);    // 11 bits
@@ -127,7 +117,6 @@ __global__ __launch_bounds__(WG) void vp_parse(const unsigned char* __restrict__
                                                int64_t n_lines_batch, int64_t line_base, long long res, unsigned long long* __restrict__ names,
                                                ulonglong2* __restrict__ records, unsigned long long capacity, Words* __restrict__ words) {
     __shared__ unsigned short lstart[LSTART_ENTRIES];
-    __shared__ unsigned long long out_base;
     const BlockLines B = block_lines(text, T, block_off, lstart);
     unsigned long long max_bin = 0;
     for (int base = 0; base < B.n_lines; base += WG) {      // n_lines is the same for every lane: the scans below see whole blocks
@@ -136,10 +125,12 @@ __global__ __launch_bounds__(WG) void vp_parse(const unsigned char* __restrict__
         ulonglong2 rec = make_ulonglong2(0ull, 0ull);
         if (e < B.n_lines) {
             const int64_t r = B.row0 + e;
+            // fhxpair::walk written out in place, with the `chrM` search (grep -v chrM, :34) in the same pass: called as a function
+            // the walk cost this kernel 4 to 5 % of the parse stage (profiles/r14/cells_layer_ab.txt), fp_parse nothing
             const int64_t start = B.b0 + lstart[e];
-            int why = 0, tok = 0, m = 0;
+            int why = 0, m = 0;
             bool in_tok = false, has_chrM = false;
-            int64_t tb[4] = {0, 0, 0, 0}, te[4] = {0, 0, 0, 0};              // tokens 2, 3, 5, 6
+            fhxpair::Line L;
             int64_t p = start;
             for (;; ++p) {
                 const int c = p < T ? (int)text[p] : '\n';                    // the end of the text ends the line
@@ -161,34 +152,34 @@ __global__ __launch_bounds__(WG) void vp_parse(const unsigned char* __restrict__
                 const bool blank = c == ' ' || c == '\t';
                 if (!blank && !in_tok) {
                     in_tok = true;
-                    ++tok;
-                    if (tok == 2) tb[0] = p;
-                    if (tok == 3) tb[1] = p;
-                    if (tok == 5) tb[2] = p;
-                    if (tok == 6) tb[3] = p;
+                    ++L.tok;
+                    if (L.tok == 2) L.tb[0] = p;
+                    if (L.tok == 3) L.tb[1] = p;
+                    if (L.tok == 5) L.tb[2] = p;
+                    if (L.tok == 6) L.tb[3] = p;
                 } else if (blank && in_tok) {
                     in_tok = false;
-                    if (tok == 2) te[0] = p;
-                    if (tok == 3) te[1] = p;
-                    if (tok == 5) te[2] = p;
-                    if (tok == 6) te[3] = p;
+                    if (L.tok == 2) L.te[0] = p;
+                    if (L.tok == 3) L.te[1] = p;
+                    if (L.tok == 5) L.te[2] = p;
+                    if (L.tok == 6) L.te[3] = p;
                 }
             }
             if (in_tok) {
-                if (tok == 2) te[0] = p;
-                if (tok == 3) te[1] = p;
-                if (tok == 5) te[2] = p;
-                if (tok == 6) te[3] = p;
+                if (L.tok == 2) L.te[0] = p;
+                if (L.tok == 3) L.te[1] = p;
+                if (L.tok == 5) L.te[2] = p;
+                if (L.tok == 6) L.te[3] = p;
             }
-            if (!why && tok < 6) why = FHX_VP_TOKENS;
+            if (!why && L.tok < 6) why = FHX_VP_TOKENS;
             if (!why && r >= n_lines_batch) why = FHX_VP_INTERNAL;           // the scan and this kernel disagree about the lines
-            const int l1 = (int)(te[0] - tb[0]), l2 = (int)(te[2] - tb[2]);
+            const int l1 = L.len(0), l2 = L.len(2);
             // :34 - a line with a longer name, or with chrM anywhere, is dropped whatever else it holds
             if (!why && l1 <= 5 && l2 <= 5 && !has_chrM) {
-                unsigned long long n1 = pack_name(text, tb[0], l1), n2 = pack_name(text, tb[2], l2);
+                unsigned long long n1 = pack_name(text, L.tb[0], l1), n2 = pack_name(text, L.tb[2], l2);
                 long long p1 = 0, p2 = 0;
                 if (n1 == 0 || n2 == 0) why = FHX_VP_NAME;
-                else if (!position(text, tb[1], (int)(te[1] - tb[1]), &p1) || !position(text, tb[3], (int)(te[3] - tb[3]), &p2)) why = FHX_VP_POSITION;
+                else if (!position(text, L.tb[1], L.len(1), &p1) || !position(text, L.tb[3], L.len(3), &p2)) why = FHX_VP_POSITION;
                 else {
                     long long k1 = p1 / res, k2 = p2 / res;                   // :36
                     if (k1 * res + res / 2 > 2147483647ll || k2 * res + res / 2 > 2147483647ll) why = FHX_VP_RANGE;
@@ -220,16 +211,12 @@ __global__ __launch_bounds__(WG) void vp_parse(const unsigned char* __restrict__
             }
             if (why) atomicMin(&words->first_error, error_word(line_base + r + 1, why));
         }
-        unsigned int total;
-        const unsigned int at = fhxscan::block_exclusive_scan(keep ? 1u : 0u, &total);
-        if (threadIdx.x == 0) out_base = total ? atomicAdd(&words->n_records, (unsigned long long)total) : 0ull;
-        __syncthreads();
+        const unsigned long long pos = fhx::block_append(keep, &words->n_records, capacity);
         if (keep) {
-            const unsigned long long pos = out_base + at;
-            if (pos < capacity) records[pos] = rec;
+            if (pos != fhx::APPEND_OVER) records[pos] = rec;
             else atomicMin(&words->first_error, error_word(line_base + B.row0 + e + 1, FHX_VP_INTERNAL));
         }
-        __syncthreads();                                    // out_base is written again in the next round
+        __syncthreads();                                    // block_append's LDS word is written again in the next round
     }
     for (int s = 32; s >= 1; s >>= 1) max_bin = max(max_bin, (unsigned long long)__shfl_down(max_bin, s, 64));
     if ((threadIdx.x & 63) == 0 && max_bin) atomicMax(&words->max_bin, max_bin);
@@ -264,23 +251,6 @@ __global__ __launch_bounds__(WG) void vp_keys(const ulonglong2* __restrict__ rec
     }
 }
 
-// the run heads of the sorted keys, in order: where each run starts
-__global__ __launch_bounds__(fhxscan::THREADS) void vp_heads(const unsigned long long* __restrict__ keys, int64_t n,
-                                                             const unsigned long long* __restrict__ tile_offsets, int64_t n_cells,
-                                                             unsigned long long* __restrict__ head_at) {
-    const int64_t base = (int64_t)blockIdx.x * fhxscan::TILE + (int64_t)threadIdx.x * fhxscan::SCAN_ITEMS;
-    unsigned int c = 0;
-    bool head[fhxscan::SCAN_ITEMS];
-    for (int k = 0; k < fhxscan::SCAN_ITEMS; ++k) {
-        head[k] = base + k < n && fhxscan::is_head(keys, base + k);
-        c += head[k] ? 1u : 0u;
-    }
-    unsigned int total;
-    unsigned long long pos = tile_offsets[blockIdx.x] + fhxscan::block_exclusive_scan(c, &total);
-    for (int k = 0; k < fhxscan::SCAN_ITEMS; ++k)
-        if (head[k] && (int64_t)pos < n_cells) head_at[pos++] = (unsigned long long)(base + k);
-}
-
 // cell c = the run that starts at head_at[c]: its key decoded, its count = the distance to the next head
 __global__ __launch_bounds__(WG) void vp_cells(const unsigned long long* __restrict__ keys, int64_t n, const unsigned long long* __restrict__ head_at,
                                                int64_t n_cells, const unsigned int* __restrict__ bin_at_rank, int bin_bits, int name_bits,
@@ -311,19 +281,17 @@ struct fhx_vp : fhx::TextHandle {
     fhx_ctx* sorter = nullptr;
     // the last binned file
     std::vector<std::string> names;               // bytewise order: a cell's chr column is an index into it
-    int64_t n_lines = 0, n_pairs = 0, n_cells = 0;
-    int32_t* d_cols = nullptr;                    // five columns of col_stride elements
-    int64_t col_stride = 0;
+    int64_t n_lines = 0, n_pairs = 0;
+    fhx::CellColumns cols;
     double seconds[FHX_VP_STAGES] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace {
 
 void drop_cells(fhx_vp* vp) {
-    fhx::dev_free(vp->d_cols);
+    vp->cols.drop();
     vp->names.clear();
-    vp->n_lines = vp->n_pairs = vp->n_cells = 0;
-    vp->col_stride = 0;
+    vp->n_lines = vp->n_pairs = 0;
 }
 
 int bits_for(unsigned long long largest) {                                    // bits that hold 0..largest, at least 1
@@ -355,8 +323,6 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
     TH_HIP(vp, tmp.get_n(&d_words, 1));
     TH_HIP(vp, hipMemsetAsync(d_names, 0, NAME_SLOTS * sizeof(unsigned long long), vp->stream));
     Words words;                                                              // running totals: set once, not per batch
-    std::memset(&words, 0, sizeof(words));
-    words.first_error = NO_ERROR;
     TH_HIP(vp, hipMemcpyAsync(d_words, &words, sizeof(words), hipMemcpyHostToDevice, vp->stream));
     TH_HIP(vp, hipStreamSynchronize(vp->stream));
     const fhx::Refusal refuse{vp, why, bad_line};
@@ -365,16 +331,7 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
         if (const int rc = in.next<AnyByte>()) return rc;                     // this path's policy refuses no byte
         const int64_t n = in.lines;
         if (pairs + n >= ((int64_t)1 << 32)) return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_PAIRS, 0, "2^32 or more pairs may be kept: the sort does not take them");
-        if (pairs + n > capacity) {                                           // room for every line of the batch to be kept
-            const int64_t want = std::max<int64_t>(pairs + n, capacity * 2);
-            ulonglong2* bigger = nullptr;
-            TH_HIP(vp, tmp.get_n(&bigger, (size_t)want));
-            if (pairs) TH_HIP(vp, hipMemcpyAsync(bigger, d_records, (size_t)pairs * sizeof(ulonglong2), hipMemcpyDeviceToDevice, vp->stream));
-            TH_HIP(vp, hipStreamSynchronize(vp->stream));
-            tmp.drop(d_records);
-            d_records = bigger;
-            capacity = want;
-        }
+        TH_HIP(vp, tmp.grow_keep(&d_records, &capacity, pairs, pairs + n, vp->stream));        // room for every line of the batch to be kept
         hipLaunchKernelGGL(vp_parse, dim3((unsigned)in.n_blocks), dim3(WG), 0, vp->stream, (const unsigned char*)in.d_text, in.len,
                            (const unsigned long long*)in.d_block_off, n, in.line_base, (long long)res, d_names, d_records,
                            (unsigned long long)capacity, d_words);
@@ -461,39 +418,22 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
     tmp.drop(d_perm);
     clock.mark(4);
     // ---- run heads -> cells --------------------------------------------------------------------------------------------------
-    const int64_t tiles = (pairs + fhxscan::TILE - 1) / fhxscan::TILE;
-    unsigned int* d_tile_cnt = nullptr;
-    unsigned long long *d_tile_off = nullptr, *d_head_at = nullptr;
-    TH_HIP(vp, tmp.get_n(&d_tile_cnt, (size_t)tiles));
-    TH_HIP(vp, tmp.get_n(&d_tile_off, (size_t)tiles));
-    hipLaunchKernelGGL(fhxscan::count_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned long long*)d_sorted, pairs,
-                       d_tile_cnt);
-    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned int*)d_tile_cnt, tiles, d_tile_off,
-                       &d_words->n_cells);
-    TH_HIP(vp, hipGetLastError());
-    unsigned long long cells = 0;
-    TH_HIP(vp, hipMemcpyAsync(&cells, &d_words->n_cells, sizeof(cells), hipMemcpyDeviceToHost, vp->stream));
-    TH_HIP(vp, hipStreamSynchronize(vp->stream));
-    if (cells == 0 || cells > (unsigned long long)pairs) return refuse(FHX_ERR_INTERNAL, FHX_VP_INTERNAL, 0, "the run heads do not match the keys");
-    const int64_t stride = ((int64_t)cells + 63) / 64 * 64;                   // every column starts on a 256-byte boundary
-    TH_HIP(vp, tmp.get_n(&d_head_at, (size_t)cells));
-    TH_HIP(vp, fhx::dev_malloc(&vp->d_cols, (size_t)stride * 5 * sizeof(int32_t)));
-    vp->col_stride = stride;
-    int32_t* c = vp->d_cols;
-    hipLaunchKernelGGL(vp_heads, dim3((unsigned)tiles), dim3(fhxscan::THREADS), 0, vp->stream, (const unsigned long long*)d_sorted, pairs,
-                       (const unsigned long long*)d_tile_off, (int64_t)cells, d_head_at);
-    hipLaunchKernelGGL(vp_cells, dim3((unsigned)std::min<int64_t>(((int64_t)cells + WG - 1) / WG, 8192)), dim3(WG), 0, vp->stream,
-                       (const unsigned long long*)d_sorted, pairs, (const unsigned long long*)d_head_at, (int64_t)cells,
-                       (const unsigned int*)d_bin_at_rank, bin_bits, name_bits, (long long)res, c, c + stride, c + 2 * stride, c + 3 * stride,
-                       c + 4 * stride, &d_words->max_count);
+    fhx::Heads heads;
+    if (const int rc = fhx::run_heads(refuse, FHX_VP_INTERNAL, tmp, d_sorted, pairs, &d_words->n_cells, /*positions=*/true, &heads)) return rc;
+    const int64_t cells = heads.cells;
+    TH_HIP(vp, vp->cols.alloc(cells));
+    const fhx::CellColumns& C = vp->cols;
+    hipLaunchKernelGGL(vp_cells, dim3((unsigned)std::min<int64_t>((cells + WG - 1) / WG, 8192)), dim3(WG), 0, vp->stream,
+                       (const unsigned long long*)d_sorted, pairs, (const unsigned long long*)heads.d_head_at, cells,
+                       (const unsigned int*)d_bin_at_rank, bin_bits, name_bits, (long long)res, C.col(0), C.col(1), C.col(2), C.col(3), C.col(4),
+                       &d_words->max_count);
     TH_HIP(vp, hipGetLastError());
     unsigned long long max_count = 0;
     TH_HIP(vp, hipMemcpyAsync(&max_count, &d_words->max_count, sizeof(max_count), hipMemcpyDeviceToHost, vp->stream));
     TH_HIP(vp, hipStreamSynchronize(vp->stream));
     clock.mark(5);
     if (max_count > 0x7fffffffull) return refuse(FHX_ERR_UNSUPPORTED, FHX_VP_COUNT, 0, "a cell is hit by more than 2^31 - 1 pairs: the count column is int32");
-    vp->n_cells = (int64_t)cells;
-    *n_cells = vp->n_cells;
+    *n_cells = cells;
     if (std::getenv("FHX_TIMING"))
         std::fprintf(stderr, "validPairs on the device (%s): %lld lines, %lld kept pairs, %lld cells: read + upload %.6f s; scan %.6f s; parse %.6f s; "
                      "names + keys %.6f s; sort %.6f s; cells %.6f s\n", path, (long long)lines, (long long)pairs, (long long)cells, vp->seconds[0],
@@ -505,20 +445,12 @@ int bin_file(fhx_vp* vp, const char* path, int64_t res, int64_t* n_cells, int32_
 
 extern "C" {
 
-int fhx_vp_create(int device, fhx_vp** out) {
-    const int rc = fhx::handle_create(device, out);
-    if (rc == FHX_OK && fhx_create(device, &(*out)->sorter) != FHX_OK) {
-        fhx_vp_destroy(*out);
-        *out = nullptr;
-        return FHX_ERR_HIP;
-    }
-    return rc;
-}
+int fhx_vp_create(int device, fhx_vp** out) { return fhx::handle_create_with_sorter(device, out); }
 
 void fhx_vp_destroy(fhx_vp* vp) {
     fhx::text_handle_destroy(vp, [&] {
         drop_cells(vp);
-        if (vp->sorter) fhx_destroy(vp->sorter);
+        fhx::drop_sorter(vp);
     });
 }
 
@@ -539,7 +471,7 @@ int fhx_vp_counts(const fhx_vp* vp, int64_t* n_lines, int64_t* n_pairs, int64_t*
     if (!vp) return FHX_ERR_ARG;
     if (n_lines) *n_lines = vp->n_lines;
     if (n_pairs) *n_pairs = vp->n_pairs;
-    if (n_cells) *n_cells = vp->n_cells;
+    if (n_cells) *n_cells = vp->cols.n;
     if (n_names) *n_names = (int32_t)vp->names.size();
     return FHX_OK;
 }
@@ -553,20 +485,10 @@ int fhx_vp_stage_seconds(const fhx_vp* vp, double* seconds) {
 }
 
 int fhx_vp_fetch_cells(fhx_vp* vp, int32_t* chr1, int32_t* mid1, int32_t* chr2, int32_t* mid2, int32_t* count) {
-    if (!vp) return FHX_ERR_ARG;
-    if (vp->n_cells > 0 && (!chr1 || !mid1 || !chr2 || !mid2 || !count)) return FHX_ERR_ARG;
-    TH_HIP(vp, hipSetDevice(vp->device));
-    int32_t* out[5] = {chr1, mid1, chr2, mid2, count};
-    for (int k = 0; k < 5 && vp->n_cells > 0; ++k)
-        TH_HIP(vp, hipMemcpyAsync(out[k], vp->d_cols + k * vp->col_stride, (size_t)vp->n_cells * sizeof(int32_t), hipMemcpyDeviceToHost, vp->stream));
-    TH_HIP(vp, hipStreamSynchronize(vp->stream));
-    return FHX_OK;
+    return vp ? vp->cols.fetch(vp, {chr1, mid1, chr2, mid2, count}) : FHX_ERR_ARG;
 }
 
-void* fhx_vp_device_ptr(fhx_vp* vp, int32_t which) {
-    if (!vp || which < 0 || which > 4 || !vp->d_cols) return nullptr;
-    return vp->d_cols + which * vp->col_stride;
-}
+void* fhx_vp_device_ptr(fhx_vp* vp, int32_t which) { return vp ? vp->cols.ptr(which) : nullptr; }
 
 void* fhx_vp_stream(fhx_vp* vp) { return vp ? (void*)vp->stream : nullptr; }
 

@@ -41,6 +41,7 @@ import sys
 import numpy as np
 
 from . import _capi
+from ._resident import Resident, _is_gzip
 from .hicpro import _line_of
 
 MAX_CONTIGS, MAX_NAME, MAX_DROP = _capi.FP_MAX_CONTIGS, _capi.FP_NAME_BYTES - 1, _capi.FP_MAX_CONTIGS
@@ -187,11 +188,6 @@ def table_of(table):
     return table_of_bed(table)
 
 
-def _is_gzip(path):
-    with open(path, "rb") as f:
-        return f.read(2) == b"\x1f\x8b"
-
-
 def _refusal(path, e):
     """the exception a refused file is reported with (module docstring, `Known deviations`)"""
     if e.why == _capi.FP_COUNT:
@@ -204,53 +200,18 @@ def _refusal(path, e):
     return ValueError("%s, line %d: %s%s" % (path, e.line, _REASONS[e.why], text))
 
 
-class FragPairs:
+class FragPairs(Resident):
     """One validPairs file binned to fragments: the cells (chr1, end1, chr2, end2, count) resident in HBM, in ascending order of
-    the two fragments' rows in the fragments file.  `names` holds chr1, chr2, ... - one per contig of the table."""
+    the two fragments' rows in the fragments file.  `names` holds chr1, chr2, ... - one per contig of the table, as
+    Digest.fragments leaves them in a ChromIndex.  counts(): lines, pairs (kept), dropped_name, same_fragment, cells.
+    load_into: the cells into a configured Engine whose fragments are loaded."""
 
     def __init__(self, fp, n_cells, names):
-        self._fp, self.n_cells, self.names = fp, n_cells, names
-
-    def close(self):
-        if self._fp is not None:
-            self._fp.close()
-            self._fp = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return self.n_cells
-
-    def counts(self):
-        """lines, pairs (kept), dropped_name, same_fragment, cells"""
-        return self._fp.counts()
-
-    def stage_seconds(self):
-        return self._fp.stage_seconds()
-
-    def contacts(self):
-        """(chr1, end1, chr2, end2, count) fetched from the device; the chr columns index `names`"""
-        return self._fp.fetch_cells()
+        super().__init__(fp, n_cells, names)
+        self.n_cells = n_cells
 
     def write(self, path):
         _capi.host_write_contacts(path, self.names, *self.contacts())
-
-    def intern(self, chroms):
-        """this table's names into the run's ChromIndex: empty (it receives them) or one whose ids agree with them, as
-        Digest.fragments leaves it"""
-        for k, name in enumerate(self.names):
-            if chroms.intern(name) != k:
-                raise ValueError("chromosome %r has id %d in the given ChromIndex and %d here" % (name, chroms.intern(name), k))
-
-    def load_into(self, engine, chroms):
-        """The cells into a configured Engine whose fragments are loaded; the five columns go from HBM to HBM."""
-        self.intern(chroms)
-        engine.load_contacts_device(self._fp.device_ptrs() if self.n_cells else [0] * 5, self.n_cells, self._fp.stream())
-        engine.ctx.sync()                                            # the engine has its own copy: this object may be closed now
 
 
 def read(validpairs_path, table, drop=(), device=0):

@@ -24,6 +24,7 @@ import os
 import numpy as np
 
 from . import _capi, tables
+from ._resident import Resident
 
 MAX_INDEX_SPAN = 1 << 27
 _INT32_MIN, _INT32_MAX = -(1 << 31), (1 << 31) - 1
@@ -162,27 +163,17 @@ def _refusal(path, e):
                       "and does not take it." % (where, what, text[:80]))
 
 
-class HicPro:
-    """One converted HiC-Pro data set: the fragments and bias tables on the host, the contact columns resident in HBM."""
+class HicPro(Resident):
+    """One converted HiC-Pro data set: the fragments and bias tables on the host, the contact columns resident in HBM.
+    load_into: the three tables into a configured Engine; `chroms` is the run's ChromIndex: empty (it receives this data set's
+    names) or one whose ids agree with them."""
+    _FETCH = "fetch_rows"
 
     def __init__(self, bed, hp, n_rows, totals, bias_values):
-        self.bed, self.chroms, self._hp, self.n_rows = bed, bed.chroms, hp, n_rows
+        super().__init__(hp, n_rows, bed.chroms.names)
+        self.bed, self.chroms, self.n_rows = bed, bed.chroms, n_rows
         self.totals = totals                                         # int64 per slot of the dense table
         self.bias_values = bias_values                               # per bias line: value / mean, -1 for NaN; None without -s
-
-    def close(self):
-        if self._hp is not None:
-            self._hp.close()
-            self._hp = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return self.n_rows
 
     @property
     def fragments(self):
@@ -204,22 +195,11 @@ class HicPro:
         slots = np.arange(1, len(self.bias_values) + 1, dtype=np.int64) - self.bed.index_base
         return self.bed.chr_id[slots].copy(), self.bed.mid[slots].copy(), np.asarray(self.bias_values, np.float64)
 
-    def contacts(self):
-        """(chr1, mid1, chr2, mid2, count) fetched from the device"""
-        return self._hp.fetch_rows()
-
-    def load_into(self, engine, chroms):
-        """The three tables into a configured Engine; the contact rows go from HBM to HBM.  `chroms` is the run's ChromIndex:
-        empty (it receives this data set's names) or one whose ids agree with them."""
-        for k, name in enumerate(self.chroms.names):
-            if chroms.intern(name) != k:
-                raise ValueError("chromosome %r has id %d in the given ChromIndex and %d here" % (name, chroms.intern(name), k))
+    def _load_tables(self, engine, chroms):
         engine.load_fragments(*self.fragments, chroms.sort_rank())
         bias = self.bias
         if bias is not None:
             engine.load_bias(*bias)
-        engine.load_contacts_device(self._hp.device_ptrs() if self.n_rows else [0] * 5, self.n_rows, self._hp.stream())
-        engine.ctx.sync()                                            # the engine has its own copy: this object may be closed now
 
 
 def read(bed, matrix, bias=None, res=0, device=0):

@@ -39,6 +39,7 @@ import re
 import sys
 
 from . import _capi
+from ._resident import Resident
 from .hicpro import _line_of
 
 _NAME = re.compile(r"[A-Za-z0-9_.-]{1,63}\Z")
@@ -86,54 +87,22 @@ def _write(path, text, gzipped):
             f.write(text)
 
 
-class JuicerContacts:
-    """The records of one or more dumps: the rows (chr1, mid1, chr2, mid2, count) resident in HBM in the order given, and their text."""
+class JuicerContacts(Resident):
+    """The records of one or more dumps: the rows (chr1, mid1, chr2, mid2, count) resident in HBM in the order given, and their text.
+    load_into: the rows into a configured Engine whose fragments are loaded."""
+    _FETCH = "fetch_rows"
 
     def __init__(self, jc, resolution, names):
-        self._jc, self.resolution, self.names = jc, resolution, names
-        self.n_rows = jc.counts()["rows"]
-
-    def close(self):
-        if self._jc is not None:
-            self._jc.close()
-            self._jc = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return self.n_rows
-
-    def stage_seconds(self):
-        return self._jc.stage_seconds()
-
-    def contacts(self):
-        """(chr1, mid1, chr2, mid2, count) fetched from the device; the chr columns index `names`"""
-        return self._jc.fetch_rows()
+        super().__init__(jc, jc.counts()["rows"], names)
+        self.resolution, self.n_rows = resolution, self._n
 
     def text(self):
         """the lines createFitHiCContacts-hic.py writes for the dumps, one after the other"""
-        return self._jc.text()
+        return self._handle.text()
 
     def write(self, path):
         """the text, gzipped: a contacts file `fithic` reads"""
         _write(path, self.text(), True)
-
-    def intern(self, chroms):
-        """these names into the run's ChromIndex: empty (it receives them) or one whose ids agree with them.  Call it before the
-        fragments are interned when those are loaded first (fragments.bins)."""
-        for k, name in enumerate(self.names):
-            if chroms.intern(name) != k:
-                raise ValueError("chromosome %r has id %d in the given ChromIndex and %d here" % (name, chroms.intern(name), k))
-
-    def load_into(self, engine, chroms):
-        """The rows into a configured Engine whose fragments are loaded; the five columns go from HBM to HBM."""
-        self.intern(chroms)
-        engine.load_contacts_device(self._jc.device_ptrs() if self.n_rows else [0] * 5, self.n_rows, self._jc.stream())
-        engine.ctx.sync()                                            # the engine has its own copy: this object may be closed now
 
 
 def read(dumps, resolution, device=0, keep_text=True):

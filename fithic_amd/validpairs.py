@@ -23,6 +23,7 @@ import os
 import sys
 
 from . import _capi
+from ._resident import Resident, _is_gzip
 from .hicpro import _line_of
 
 
@@ -59,56 +60,16 @@ def _refusal(path, res, e):
     return ValueError("%s: %s: %r" % (where, what, text[:80]) + accepts)
 
 
-def _is_gzip(path):
-    with open(path, "rb") as f:
-        return f.read(2) == b"\x1f\x8b"
-
-
-class ValidPairs:
-    """One binned validPairs file: the cells (chr1, mid1, chr2, mid2, count) resident in HBM, in the script's output order."""
+class ValidPairs(Resident):
+    """One binned validPairs file: the cells (chr1, mid1, chr2, mid2, count) resident in HBM, in the script's output order.
+    load_into: the cells into a configured Engine whose fragments are loaded."""
 
     def __init__(self, vp, res, n_cells, names):
-        self._vp, self.res, self.n_cells, self.names = vp, res, n_cells, names
-
-    def close(self):
-        if self._vp is not None:
-            self._vp.close()
-            self._vp = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return self.n_cells
-
-    def counts(self):
-        return self._vp.counts()
-
-    def stage_seconds(self):
-        return self._vp.stage_seconds()
-
-    def contacts(self):
-        """(chr1, mid1, chr2, mid2, count) fetched from the device; the chr columns index `names`"""
-        return self._vp.fetch_cells()
+        super().__init__(vp, n_cells, names)
+        self.res, self.n_cells = res, n_cells
 
     def write(self, path):
         _capi.vp_write_contacts(path, self.names, *self.contacts())
-
-    def intern(self, chroms):
-        """this file's names into the run's ChromIndex: empty (it receives them) or one whose ids agree with them.  Call it before
-        the fragments are interned when those are loaded first (fragments.bins)."""
-        for k, name in enumerate(self.names):
-            if chroms.intern(name) != k:
-                raise ValueError("chromosome %r has id %d in the given ChromIndex and %d here" % (name, chroms.intern(name), k))
-
-    def load_into(self, engine, chroms):
-        """The cells into a configured Engine whose fragments are loaded; the five columns go from HBM to HBM."""
-        self.intern(chroms)
-        engine.load_contacts_device(self._vp.device_ptrs() if self.n_cells else [0] * 5, self.n_cells, self._vp.stream())
-        engine.ctx.sync()                                            # the engine has its own copy: this object may be closed now
 
 
 def read(path, res, device=0):

@@ -15,6 +15,7 @@ import pytest
 
 import digest_model as dm
 import fragpairs_model as fm
+import tile_edge
 from batch_env import batch_bytes
 from conftest import ROOT, bits_equal
 from test_digest_host import _gunzip
@@ -166,6 +167,27 @@ def test_4096_lines_on_4096_different_cells(tmp_path):
     order = np.random.default_rng(6).permutation(4096).tolist()
     data = b"".join(line(b"B", 50 * (k % 64) + 1 + k % 50, b"A", 50 * (k // 64) + 50 - k % 50) for k in order)
     assert gpu_bytes(data, table, tmp_path).count(b"\n") == 4096
+
+
+TILE_TABLE = [(b"a", [10 * (k + 1) for k in range(1002)]), (b"b", [10])]
+
+
+@pytest.mark.parametrize("n", tile_edge.SIZES)
+def test_runs_that_end_and_start_at_a_1024_key_tile_edge(n, tmp_path):
+    # cell c is fragment c of `a` x the one fragment of `b`: the sort key is row c << 32 | row 1002
+    pairs = [c for c, k in enumerate(tile_edge.hits(n)) for _ in range(k)]
+    data = b"".join(line(b"b", 1 + i % 10, b"a", 10 * pairs[i] + 1 + i % 10) for i in tile_edge.file_order(n))
+    want, counts = fm.cells(data, TILE_TABLE, [])
+    assert counts["pairs"] == n
+    tile_edge.assert_runs_meet_the_edge([c[4] for c in want], n)      # from the model's own cells, in the order of its sorted keys
+    gpu_bytes(data, TILE_TABLE, tmp_path)
+
+
+def test_every_line_kept_over_three_batches_and_more(tmp_path):
+    # the record array grows from batch to batch with the earlier batches' records in it (DeviceScratch::grow_keep)
+    data = b"".join(line(b"chr1", 1 + 523 * k, b"chr2", 349999 - 377 * k) for k in range(900))
+    assert len(data) > 3 * 8192 and fm.cells(data, EDGE_TABLE, [])[1]["pairs"] == 900
+    gpu_bytes(data, EDGE_TABLE, tmp_path, batch=8192)
 
 
 def test_gzipped_input(tmp_path):

@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import tile_edge
 import validpairs_model as vm
 from batch_env import batch_bytes
 from conftest import ROOT, bits_equal
@@ -126,6 +127,22 @@ def test_4096_lines_that_are_all_different(tmp_path):
     want = vm.text(data, 50)
     assert want.count(b"\n") == 4096
     assert gpu_bytes(data, 50, tmp_path) == want
+
+
+@pytest.mark.parametrize("n", tile_edge.SIZES)
+def test_runs_that_end_and_start_at_a_1024_key_tile_edge(n, tmp_path):
+    # cell c is chr1:3 x chr2:10000 + 2 * c: five digits at resolution 2, so the script's text order is the order of c
+    pairs = [c for c, k in enumerate(tile_edge.hits(n)) for _ in range(k)]
+    data = b"".join(b"r\tchr1\t3\t+\tchr2\t%d\t-\n" % (10000 + 2 * pairs[i] + i % 2) for i in tile_edge.file_order(n))
+    tile_edge.assert_runs_meet_the_edge(vm.columns(data, 2)[5], n)   # from the model's own cells, in the order of its sorted keys
+    assert gpu_bytes(data, 2, tmp_path) == vm.text(data, 2)
+
+
+def test_every_line_kept_over_three_batches_and_more(tmp_path):
+    # the record array grows from batch to batch with the earlier batches' records in it (DeviceScratch::grow_keep)
+    data = b"".join(b"read%06d\tchr%d\t%d\t+\tchr%d\t%d\t-\n" % (k, 1 + k % 3, 100 + 37 * k, 4 + k % 2, 900000 - 91 * k) for k in range(900))
+    assert len(data) > 3 * 8192 and sum(vm.columns(data, 10000)[5]) == 900
+    assert gpu_bytes(data, 10000, tmp_path, 8192) == vm.text(data, 10000)
 
 
 def test_two_runs_give_the_same_bytes(tmp_path):
