@@ -123,8 +123,11 @@ def drop(A, removed):
     return Csr(n2, np.cumsum(indptr), np.ascontiguousarray(new[A.indices[sel]].astype(np.int32)), np.ascontiguousarray(A.data[sel]))
 
 
-def knight_ruiz(A, tol=1e-6):
-    """HiCKRy.py:139-243, statement for statement (vectors are 1-D here; the reference's are (n,1))."""
+def knight_ruiz(A, tol=1e-6, trace=None):
+    """HiCKRy.py:139-243, statement for statement (vectors are 1-D here; the reference's are (n,1)).  `trace`: a list that
+    receives the name of every way an inner step ends ("accept", "delta", "Delta", "k>10") and "i>30" at the outer cap; no
+    value depends on it."""
+    note = trace.append if trace is not None else (lambda name: None)
     n = A.n
     e = np.ones(n)
     Delta, delta, g = 3, 0.1, 0.9
@@ -141,6 +144,7 @@ def knight_ruiz(A, tol=1e-6):
     while rout > rt:
         i += 1
         if i > 30:
+            note("i>30")
             break
         k = 0
         y = e.copy()
@@ -155,12 +159,14 @@ def knight_ruiz(A, tol=1e-6):
                 beta = rho_km1 / rho_km2
                 p = Z + beta * p
             if k > 10:
+                note("k>10")
                 break
             w = x * A.dot(x * p) + v * p
             alpha = rho_km1 / dot(p, w)
             ap = alpha * p
             ynew = y + ap
             if np.amin(ynew) <= delta:
+                note("delta")
                 if delta == 0:
                     break
                 ind = np.where(ap < 0.0)[0]
@@ -168,10 +174,12 @@ def knight_ruiz(A, tol=1e-6):
                 y += gamma * ap
                 break
             if np.amax(ynew) >= Delta:
+                note("Delta")
                 ind = np.where(ynew > Delta)[0]
                 gamma = np.amin((Delta - y[ind]) / ap[ind])
                 y += gamma * ap
                 break
+            note("accept")
             y = ynew.copy()
             rk = rk - alpha * w
             rho_km2 = rho_km1
