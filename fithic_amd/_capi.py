@@ -171,12 +171,12 @@ SYMBOLS = {
                                                       _I32P, _I32P, _I32P, ctypes.c_int64, _I64P, _I64P]),
     "fhx_write_significances_device_range": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.c_int64,
                                                             ctypes.c_int64, ctypes.c_int32, _I64P, _I64P]),
-    # the FDR subset of a pass from its resident columns (csrc/fhx_sigresident.inc)
+    # the FDR subset of a pass from its resident columns (csrc/fhx_sigresident.hip)
     "fhx_significant_select": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64,
                                               ctypes.c_int32, ctypes.c_int32, _I64P, _I64P, _I64P, _I32P, _I64P]),
     "fhx_significant_copy_text": (ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_int64]),
     "fhx_significant_copy_rows": (ctypes.c_int, [_P, _I64P, ctypes.c_int64]),
-    # the interact track and the per-chromosome subsets from the same columns (csrc/fhx_sigresident_track.inc, fhx_sigresident_split.inc)
+    # the interact track and the per-chromosome subsets from the same columns (csrc/fhx_sigresident_track.inc, fhx_sigresident_split.inc, both part of that unit)
     "fhx_significant_track": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64,
                                              ctypes.c_int32, _I64P, _I64P, _I64P, _I64P, _I32P, _I64P]),
     "fhx_significant_copy_track": (ctypes.c_int, [_P, ctypes.c_void_p, ctypes.c_int64]),
@@ -296,7 +296,7 @@ for _p in ("hp", "vp", "jc", "fp", "cz"):
 # One object per translation unit (fithic_amd/csrc/_obj/, git-ignored), compiled in parallel, then one link: a change in K2 does
 # not recompile K1, K3, the Knight-Ruiz path or the host stages.  Flags are the same for every unit - -ffp-contract=off matters
 # for bit-exactness on the host (FITPACK, lgamma tables) as much as on the device (fhx_bdtrc.hpp).
-SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_juicer.hip", "fhx_digest.hip", "fhx_fragpairs.hip", "fhx_coarsen.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
+SOURCES = ["fhx_device.hip", "fhx_k1.hip", "fhx_k2.hip", "fhx_k3.hip", "fhx_kr.hip", "fhx_cni.hip", "fhx_hicpro.hip", "fhx_validpairs.hip", "fhx_sigselect.hip", "fhx_sigresident.hip", "fhx_juicer.hip", "fhx_digest.hip", "fhx_fragpairs.hip", "fhx_coarsen.hip", "fhx_host.cpp", "fhx_io.cpp", "fhx_gunzip.cpp"]
 COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-pthread"]
 LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-pthread", "-lz", "-ldl"]
 OBJ_DIR = os.path.join(CSRC, "_obj")

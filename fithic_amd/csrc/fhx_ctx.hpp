@@ -6,6 +6,7 @@
 //   fhx_k3.hip      K3 Benjamini-Hochberg: cutoff, compaction, radix sort, scan (myStats.benjamini_hochberg_correction)
 //   fhx_device.hip  context life cycle, parameters, tables, the host fit, sharded runs (fhx_dist.inc), file I/O on the device
 //                   (fhx_inflate.inc, fhx_ingest.inc, fhx_emit.inc)
+//   fhx_sigresident.hip  the FDR subset, the UCSC track and the per-chromosome subsets from a pass's resident q
 // The whole library is compiled with -ffp-contract=off (fhx_bdtrc.hpp says why).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -430,7 +431,7 @@ struct fhx_ctx {
     double *d_p = nullptr, *d_q = nullptr;
     bool have_p = false, have_q = false;
     bool outliers_folded = false;               // fhx_next_pass has run on this p: the pass is over (fhx_pvalues starts the next one)
-    // the last fhx_significant_select (fhx_sigresident.inc): the kept rows' text and their loaded-row numbers; empty after a refusal
+    // the last fhx_significant_select (fhx_sigresident.hip): the kept rows' text and their loaded-row numbers; empty after a refusal
     std::vector<char> sig_text;
     std::vector<int64_t> sig_rows;
     // the last fhx_significant_split (fhx_sigresident_split.inc): one buffer, and per listed name (bytewise order) its stretch of it;

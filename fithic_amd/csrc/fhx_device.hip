@@ -678,9 +678,6 @@ int fhx_kernel_events_dropped(fhx_ctx* ctx, int64_t* dropped4) {
 
 #include "fhx_dist.inc"
 #include "fhx_emit.inc"
-#include "fhx_sigresident.inc"
-#include "fhx_sigresident_track.inc"
-#include "fhx_sigresident_split.inc"
 #include "fhx_inflate.inc"
 #include "fhx_textlines.hpp"
 #include "fhx_ingest.inc"

@@ -8,12 +8,14 @@
 //                           sized per batch, grow_keep() for one that accumulates over the batches
 //   GrowBuf<T>              a handle's grow-only buffer: steady-state calls allocate nothing
 //   Handle                  device, stream, error text; FHX_HIP_ON / fail() store the message and return the code
+//   StageClock              host seconds per stage of a call
 //   upload<T>               a host table -> one of a handle's long-lived blocks
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <mutex>
 #include <string>
@@ -258,6 +260,17 @@ void handle_destroy(H* h, Drop drop) {
 }
 
 inline const char* handle_last_error(const Handle* h) { return h ? h->err.c_str() : "null context"; }
+
+// host seconds per stage of a call (FHX_TIMING, the *_stage_seconds entry points); the stream is idle at every mark
+struct StageClock {
+    double* seconds;
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    void mark(int k) {
+        const auto now = std::chrono::steady_clock::now();
+        seconds[k] += std::chrono::duration<double>(now - last).count();
+        last = now;
+    }
+};
 
 // a host table of n elements as one of the handle's long-lived blocks (at least one element is allocated); the copy is in
 // flight on the handle's stream when this returns

@@ -18,101 +18,16 @@
 
 #include "fhx_cpus.hpp"
 #include "fhx_deflate.hpp"
+#include "fhx_emitrow.hpp"
 
 namespace fhx {
 namespace emit {
 
-constexpr int ROW_STRIDE = 192;                 // bytes reserved per row in HBM (longer rows -> the host writer takes over): two 24-byte
-                                                // names, 9-digit midpoints and three-digit exponents everywhere are 154
 constexpr int LDS_STRIDE = 196;                 // 49 words (odd): consecutive rows fall into different LDS banks
 constexpr int WG = 256;                         // rows per workgroup
 constexpr int MEMBER_ROWS = 65536;              // rows per gzip member
 constexpr int WG_PER_MEMBER = MEMBER_ROWS / WG;
 constexpr int GZ_HEAD = 24, GZ_TAIL = 8;        // 10 fixed + 2 XLEN + 12 "FH" subfield; CRC32 + ISIZE
-
-struct Cols {
-    const int32_t *chr1, *mid1, *chr2, *mid2, *count;     // chr1 == nullptr: the identity columns are rebuilt from the resident rows
-    const int32_t *loc1, *loc2;                           // slots as ingest stored them (loc2 complemented for inter rows)
-    const int16_t* slot_chr;
-    const int32_t* slot_mid;                              // -r 0 / off-grid: midpoint per slot; nullptr on the fixed grid
-    const fhx::ChrGrid* grid;
-    int32_t res;
-    const double *p, *q, *b1, *b2, *expcc;
-    const char* names;                          // concatenated chromosome names
-    const int32_t* name_off;                    // n_names + 1 offsets
-    int32_t n_names;
-    int64_t n_rows;
-    int32_t mode;
-    int64_t dist_low, dist_up;
-};
-
-// ---- row text ------------------------------------------------------------------------------------------------------
-// The three steps of a row, shared with the selection from resident columns (fhx_sigresident.inc): who the row is, whether the
-// reference's output loop prints it, and its text.
-struct RowId {
-    int c1, c2, m1, m2;
-};
-
-__device__ __forceinline__ RowId row_identity(const Cols& C, int64_t r) {
-    RowId id;
-    if (C.chr1) {
-        id.c1 = C.chr1[r];
-        id.c2 = C.chr2[r];
-        id.m1 = C.mid1[r];
-        id.m2 = C.mid2[r];
-    } else {                                           // invert ingest (k0_slots / nf_finish_rows)
-        const int s1 = C.loc1[r], l2 = C.loc2[r], s2 = l2 < 0 ? ~l2 : l2;
-        id.c1 = C.slot_chr[s1];
-        id.c2 = C.slot_chr[s2];
-        id.m1 = C.slot_mid ? C.slot_mid[s1] : (s1 - C.grid[id.c1].base) * C.res + C.grid[id.c1].off;
-        id.m2 = C.slot_mid ? C.slot_mid[s2] : (s2 - C.grid[id.c2].base) * C.res + C.grid[id.c2].off;
-    }
-    return id;
-}
-
-__device__ __forceinline__ bool row_emitted(const Cols& C, const RowId& id) {
-    if (id.c1 != id.c2) return C.mode == FHX_MODE_ALL || C.mode == FHX_MODE_INTER_ONLY;                       // fithic.py:1197
-    long long d = (long long)id.m1 - (long long)id.m2;
-    d = d < 0 ? -d : d;
-    return (C.mode == FHX_MODE_ALL || C.mode == FHX_MODE_INTRA_ONLY) && d >= C.dist_low && d <= C.dist_up;   // :1205-1207
-}
-
-// the row's text with its newline into buf (288 bytes); its length, or 0 for a row the formatter does not cover
-__device__ __forceinline__ int row_text(const Cols& C, int64_t r, const RowId& id, char* buf) {
-    const int c1 = id.c1, c2 = id.c2;
-    bool ok = c1 >= 0 && c1 < C.n_names && c2 >= 0 && c2 < C.n_names;
-    int n = 0;
-    if (ok) {
-        const int a0 = C.name_off[c1], a1 = C.name_off[c1 + 1], b0 = C.name_off[c2], b1 = C.name_off[c2 + 1];
-        ok = (a1 - a0) <= 24 && (b1 - b0) <= 24;
-        if (ok) {
-            for (int k = a0; k < a1; ++k) buf[n++] = C.names[k];
-            buf[n++] = '\t';
-            n += fmt::put_i64(buf + n, id.m1);
-            buf[n++] = '\t';
-            for (int k = b0; k < b1; ++k) buf[n++] = C.names[k];
-            buf[n++] = '\t';
-            n += fmt::put_i64(buf + n, id.m2);
-            buf[n++] = '\t';
-            n += fmt::put_i64(buf + n, C.count[r]);
-            buf[n++] = '\t';
-            const double vals[4] = {C.p[r], C.q[r], C.b1[r], C.b2[r]};
-            for (int k = 0; k < 4 && ok; ++k) {
-                const int w = fmt::fmt_e6(vals[k], buf + n);
-                ok = w > 0;
-                n += ok ? w : 0;
-                buf[n++] = '\t';
-            }
-            if (ok) {
-                const int w = fmt::fmt_f6(C.expcc[r], buf + n);
-                ok = w > 0 && n + w + 1 < ROW_STRIDE;
-                n += ok ? w : 0;
-                buf[n++] = '\n';
-            }
-        }
-    }
-    return (!ok || n >= ROW_STRIDE) ? 0 : n;
-}
 
 __global__ __launch_bounds__(WG) void em_format(Cols C, unsigned char* __restrict__ rowtext, unsigned char* __restrict__ rowlen,
                                                 unsigned int* __restrict__ wg_len, int* __restrict__ unsupported,
@@ -618,9 +533,21 @@ static int write_significances_batch(fhx_ctx* ctx, std::FILE* f, const std::vect
     P.count += r0;
     P.n = n_rows;
     launch_k2_extras(ctx, P, n_rows, d_e, d_b1, d_b2);
-    Cols C{d_col[0], d_col[1], d_col[2], d_col[3], derive ? ctx->d_count + r0 : d_col[4], ctx->d_loc1 + r0, ctx->d_loc2 + r0, ctx->d_slot_chr,
-           ctx->nonfixed ? ctx->d_slot_mid : nullptr, ctx->d_grid, (int32_t)ctx->prm.resolution, ctx->d_p + r0, ctx->d_q + r0, d_b1, d_b2, d_e, d_names, d_name_off, n_names, n_rows,
-           ctx->prm.mode, ctx->prm.dist_low, ctx->prm.dist_up};
+    // the batch's rows of the resident columns; the five identity columns are the uploaded ones unless they are rebuilt (all null)
+    Cols C = resident_cols(ctx, d_names, d_name_off, n_names);
+    C.chr1 = d_col[0];
+    C.mid1 = d_col[1];
+    C.chr2 = d_col[2];
+    C.mid2 = d_col[3];
+    C.count = derive ? ctx->d_count + r0 : d_col[4];
+    C.loc1 += r0;
+    C.loc2 += r0;
+    C.p += r0;
+    C.q += r0;
+    C.b1 = d_b1;
+    C.b2 = d_b2;
+    C.expcc = d_e;
+    C.n_rows = n_rows;
     hipLaunchKernelGGL(em_format, dim3((unsigned)n_wg), dim3(WG), 0, ctx->stream, C, d_text, d_len, d_wg_a, d_flag, d_rows);
     hipLaunchKernelGGL(em_scan_members, dim3(n_members), dim3(WG_PER_MEMBER), 0, ctx->stream, (const unsigned int*)d_wg_a, n_wg, d_wg_off, d_member_a);
     hipLaunchKernelGGL(em_hist_crc, dim3((unsigned)n_wg), dim3(WG), 0, ctx->stream, (const unsigned char*)d_text, (const unsigned char*)d_len, n_rows,

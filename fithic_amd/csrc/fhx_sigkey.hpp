@@ -1,7 +1,7 @@
 // fhx_sigkey.hpp - the decision merge-filter.sh makes on the TEXT of field 7 (`$7 <= q` under mawk 1.3.4, LC_ALL=C), shared by the
 // file route (fhx_sigselect.hip, fhx_sigtrack.inc, fhx_sigsplit.inc: ms_select, ut_select and mp_select read the field from the
-// file's bytes and share decide()) and the resident route (fhx_sigresident.inc: sr_decide formats q with fmt_e6 and reads the
-// field from registers), so the two cannot drift apart.
+// file's bytes) and the resident route (fhx_sigresident.hip: sr_decide formats q with fmt_e6 and reads the field from registers).
+// All four kernels call classify() and decide(), and both routes make the threshold with fdr_of(), so the two cannot drift apart.
 //
 // A field in the shape C's %e writes, D.DDDDDDe[+-]XX[X], is
 //   zero     every digit 0: the number 0, kept when 0 <= fdr (0 < fdr when strict) - the host says which
@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 
 #include "../../include/fithic_mi355x.h"
 #include "fhx_pairline.hpp"
@@ -26,6 +27,15 @@ struct Fdr {
     unsigned char text[FHX_MS_FDR_BYTES];
     int len;
 };
+
+// fdr_text[0, fdr_len) as the kernels take it; false, and *fdr untouched, unless it has 1 to FHX_MS_FDR_BYTES bytes
+static inline bool fdr_of(const char* fdr_text, int32_t fdr_len, Fdr* fdr) {
+    if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) return false;
+    std::memset(fdr, 0, sizeof(*fdr));
+    std::memcpy(fdr->text, fdr_text, (size_t)fdr_len);
+    fdr->len = fdr_len;
+    return true;
+}
 
 using fhxpair::is_digit;
 

@@ -1,9 +1,9 @@
-// fhx_sigresident.inc - the FDR subset of a pass taken from its RESIDENT columns (included by fhx_device.hip behind fhx_emit.inc,
-// inside its extern "C" block): what fhx_ms_select_file gives for the file fhx_write_significances_device writes, without the
-// file.  The rows merge-filter.sh drops are never formatted, deflated, inflated or uploaded.
+// fhx_sigresident.hip - the FDR subset of a pass taken from its RESIDENT columns: what fhx_ms_select_file gives for the file
+// fhx_write_significances_device writes, without the file.  The rows merge-filter.sh drops are never formatted, deflated,
+// inflated or uploaded.
 //
 // The decision is the script's, made on the %e TEXT of q (fhx_sigkey.hpp, shared with ms_select), and the kept rows' text is
-// the writer's (emit::row_identity / row_emitted / row_text, shared with em_format).  On the context's stream:
+// the writer's (fhx_emitrow.hpp: row_identity / row_emitted / row_text, shared with em_format).  On the context's stream:
 //
 //   sr_decide      one loaded row per lane.  The emit predicate; q -> fmt_e6 -> classify -> zero / numeric key / string compare;
 //                  one flag byte per row (not emitted, emitted and dropped, kept); per workgroup the emitted and the kept count.
@@ -24,17 +24,18 @@
 //                  checked against the scanned total; what a lane wrote is compared with what sr_measure counted.
 //
 // The same front - the state rules, sr_decide, the two rank scans, the refusal with its line, sr_rows - serves the interact track
-// (fhx_sigresident_track.inc) and the per-chromosome subsets (fhx_sigresident_split.inc): sr_decide is a template over the view,
-// and decide_rows<VIEW> / gather_kept below are what the three C calls share.
-}  // extern "C"
-
+// (fhx_sigresident_track.inc) and the per-chromosome subsets (fhx_sigresident_split.inc), both included at the end of this file:
+// sr_decide is a template over the view, and decide_rows<VIEW> / gather_kept below are what the three C calls share; the subset
+// and the split also share what follows the kept rows' columns (kept_extras, format_kept).
 #include <cfloat>
 
+#include "fhx_ctx.hpp"
+#include "fhx_emitrow.hpp"
+#include "fhx_namerule.hpp"
 #include "fhx_sigkey.hpp"
 #include "fhx_trackline.hpp"
 
-namespace fhx {
-namespace sigres {
+namespace fhx::sigres {
 
 using emit::Cols;
 using emit::RowId;
@@ -115,13 +116,7 @@ __global__ __launch_bounds__(WG) void sr_decide(Cols C, Decision D, unsigned cha
                 else {
                     unsigned long long key = 0;
                     const int cls = msd::classify((const unsigned char*)field, 0, w, &key);
-                    if (cls == 0) why = FHX_MS_FIELD;
-                    else if (cls == 1) keep = D.zero_kept != 0;
-                    else if (cls == 2) keep = key <= D.key_bound;             // the host's bound is the strict one when strict
-                    else {
-                        const int cmp = msd::compare_text((const unsigned char*)field, 0, w, D.fdr);
-                        keep = D.strict ? cmp < 0 : cmp <= 0;
-                    }
+                    why = msd::decide(cls, key, D.key_bound, D.zero_kept, D.strict, (const unsigned char*)field, 0, w, D.fdr, &keep);
                 }
             }
             if constexpr (VIEW == TRACK)
@@ -255,49 +250,63 @@ inline double first_e308() {
     return v;
 }
 
-}  // namespace sigres
-}  // namespace fhx
+}  // namespace fhx::sigres
 
 namespace {
 
-void drop_significant(fhx_ctx* ctx) {
-    std::vector<char>().swap(ctx->sig_text);
-    std::vector<int64_t>().swap(ctx->sig_rows);
-}
-
 const char* const kNotCovered = "a row does not fit the device formatter (name longer than 24 bytes, a value of 2^63 or more, or a row of 192 "
                                 "bytes or more): select from the written file";
+const char* const kMoreText = "more text than the kept rows can hold";
 
-// host clocks of one call's stages; every mark() follows a synchronisation of the stream
-struct StageSeconds {
-    double s[6] = {0, 0, 0, 0, 0, 0};
-    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
-    void mark(int stage) {
-        const auto t = std::chrono::steady_clock::now();
-        s[stage] += std::chrono::duration<double>(t - last).count();
-        last = t;
-    }
-};
-
-// What one decision over the loaded rows leaves on the device (sr_decide and the two rank scans), for the subset and for the
-// track; G owns every block until the call returns.
+// One call's state: what the decision over the loaded rows leaves on the device (sr_decide and the two rank scans), what
+// format_kept adds, and the host clocks of the stages the call's FHX_TIMING line names.  G owns every block until the call returns.
 struct Decided {
     DeviceScratch G;
-    fhx::sigres::Words words;
+    fhx::sigres::Words words;                  // the host's copy, as read_words last saw the device's
     fhx::sigres::Words* d_words = nullptr;
     unsigned char* d_flags = nullptr;
     unsigned long long* d_kept_off = nullptr;
     char* d_names = nullptr;
     int32_t* d_name_off = nullptr;
+    int32_t n_names = 0;
     unsigned char* d_listed = nullptr;         // SPLIT: one byte per chromosome id
     int64_t n = 0, n_wg = 0, emitted = 0, kept = 0;
+    // format_kept: the kept rows' text, its bytes, every row's length and every workgroup's first byte
+    unsigned char *d_out = nullptr, *d_len = nullptr;
+    unsigned long long* d_wg_off = nullptr;
+    int64_t bytes = 0;
+    const bool timing = std::getenv("FHX_TIMING") != nullptr;
+    double s[6] = {0, 0, 0, 0, 0, 0};
+    StageClock T{s};
 };
 
-// The kept rows compacted in file order with the columns behind them (sr_rows)
+// the device's words into F.words; the stream is idle afterwards
+int read_words(fhx_ctx* ctx, Decided& F) {
+    FHX_HIP(hipMemcpyAsync(&F.words, F.d_words, sizeof(F.words), hipMemcpyDeviceToHost, ctx->stream));
+    FHX_HIP(hipStreamSynchronize(ctx->stream));
+    return FHX_OK;
+}
+
+// a stage boundary the call pays for only under FHX_TIMING: it synchronises the stream
+int timed_mark(fhx_ctx* ctx, Decided& F, int stage) {
+    if (!F.timing) return FHX_OK;
+    FHX_HIP(hipStreamSynchronize(ctx->stream));
+    F.T.mark(stage);
+    return FHX_OK;
+}
+
+// in front of every walk over the caller's names
+int require_names(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names) {
+    for (int i = 0; i < n_names; ++i)
+        if (!chr_names[i]) return fail(ctx, FHX_ERR_ARG, "a chromosome name is missing");
+    return FHX_OK;
+}
+
+// The kept rows compacted in file order with the columns behind them (sr_rows), and what kept_extras adds
 struct KeptRows {
     int64_t* d_rows = nullptr;
     int32_t *d_loc1 = nullptr, *d_loc2 = nullptr, *d_count = nullptr;
-    double *d_p = nullptr, *d_q = nullptr;
+    double *d_p = nullptr, *d_q = nullptr, *d_b1 = nullptr, *d_b2 = nullptr, *d_e = nullptr;
 };
 
 // The state rules, the decision and its refusals, shared by fhx_significant_select and fhx_significant_track (TRACK: the track's
@@ -305,13 +314,16 @@ struct KeptRows {
 // afterwards which ids the file lists).  F.n == 0: the context holds no rows and nothing was launched.
 template <int VIEW>
 int decide_rows(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, const char* fdr_text, int32_t fdr_len, uint64_t key_bound,
-                int32_t zero_kept, int32_t strict, int32_t* why, int64_t* bad_line, bool timing, Decided& F, StageSeconds& T,
+                int32_t zero_kept, int32_t strict, int32_t* why, int64_t* bad_line, Decided& F,
                 const std::vector<unsigned char>* name_why = nullptr) {
     using namespace fhx::sigres;
+    StageClock& T = F.T;
     if (ctx->device < 0) return fail(ctx, FHX_ERR_NO_DEVICE, "host-only context");
     if (!ctx->have_p || !ctx->have_q) return fail(ctx, FHX_ERR_ARG, "p and q must have been computed (fhx_pvalues, fhx_bh)");
     if (ctx->outliers_folded) return fail(ctx, FHX_ERR_ARG, "fhx_next_pass has closed the pass: select before it");
-    if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) {
+    Decision D;
+    std::memset(&D, 0, sizeof(D));
+    if (!msd::fdr_of(fdr_text, fdr_len, &D.fdr)) {
         *why = FHX_MS_FDR;
         return fail(ctx, FHX_ERR_UNSUPPORTED, "the text of fdr must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
     }
@@ -319,35 +331,26 @@ int decide_rows(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, con
         return fail(ctx, FHX_ERR_ARG, "no resident rows to rebuild the identity columns from");
     FHX_HIP(hipSetDevice(ctx->device));
     FHX_HIP(hipStreamSynchronize(ctx->stream));       // K3 is through: had it seen more survivors than it was sized for, say so
-    {
-        const int rc = check_fault(ctx);
-        if (rc != FHX_OK) return rc;
-    }
+    if (const int rc = check_fault(ctx)) return rc;
     const int64_t n = ctx->n_rows;
     F.n = n;
     if (n == 0) return FHX_OK;
     T.last = std::chrono::steady_clock::now();
-    Decision D;
-    std::memset(&D, 0, sizeof(D));
-    std::memcpy(D.fdr.text, fdr_text, (size_t)fdr_len);
-    D.fdr.len = fdr_len;
     D.key_bound = key_bound;
     D.zero_kept = zero_kept;
     D.strict = strict;
     D.bracket = std::getenv("FHX_SR_NO_BRACKET") ? 0 : 1;
     bracket_of(key_bound, &D.lo, &D.hi);
     D.e308 = first_e308();
-
+    if (const int rc = require_names(ctx, chr_names, n_names)) return rc;
     std::vector<char> blob;
     std::vector<int32_t> name_off(n_names + 1, 0);
     for (int i = 0; i < n_names; ++i) {
-        if (!chr_names[i]) return fail(ctx, FHX_ERR_ARG, "a chromosome name is missing");
         const size_t l = std::strlen(chr_names[i]);
         blob.insert(blob.end(), chr_names[i], chr_names[i] + l);
         name_off[i + 1] = (int32_t)blob.size();
     }
     if (blob.empty()) blob.push_back(0);
-
     const int64_t n_wg = (n + WG - 1) / WG;
     F.n_wg = n_wg;
     DeviceScratch& G = F.G;
@@ -367,10 +370,9 @@ int decide_rows(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, con
     FHX_HIP(hipMemcpyAsync(F.d_words, &words, sizeof(words), hipMemcpyHostToDevice, ctx->stream));
     FHX_HIP(hipMemcpyAsync(F.d_names, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
     FHX_HIP(hipMemcpyAsync(F.d_name_off, name_off.data(), name_off.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    F.n_names = n_names;
     // every loaded row: identity from the resident slots, q resident; p, the biases and ExpCC are not read by sr_decide
-    Cols C{nullptr, nullptr, nullptr, nullptr, ctx->d_count, ctx->d_loc1, ctx->d_loc2, ctx->d_slot_chr, ctx->nonfixed ? ctx->d_slot_mid : nullptr,
-           ctx->d_grid, (int32_t)ctx->prm.resolution, ctx->d_p, ctx->d_q, nullptr, nullptr, nullptr, F.d_names, F.d_name_off, n_names, n,
-           ctx->prm.mode, ctx->prm.dist_low, ctx->prm.dist_up};
+    const Cols C = fhx::emit::resident_cols(ctx, F.d_names, F.d_name_off, n_names);
     SplitTables S{nullptr, nullptr};
     if (VIEW == SPLIT) {
         if (!name_why || (int32_t)name_why->size() != n_names) return fail(ctx, FHX_ERR_INTERNAL, "the split has no reason per chromosome id");
@@ -383,17 +385,13 @@ int decide_rows(fhx_ctx* ctx, const char* const* chr_names, int32_t n_names, con
     }
     hipLaunchKernelGGL(sr_decide<VIEW>, dim3((unsigned)n_wg), dim3(WG), 0, ctx->stream, C, D, F.d_flags, d_wg_emitted, d_wg_kept, F.d_words, S);
     FHX_HIP(hipGetLastError());
-    if (timing) {
-        FHX_HIP(hipStreamSynchronize(ctx->stream));
-        T.mark(0);
-    }
+    if (const int rc = timed_mark(ctx, F, 0)) return rc;
     hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_emitted, n_wg, d_emit_off,
                        &F.d_words->n_emitted);
     hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_kept, n_wg, F.d_kept_off,
                        &F.d_words->n_kept);
     FHX_HIP(hipGetLastError());
-    FHX_HIP(hipMemcpyAsync(&words, F.d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
-    FHX_HIP(hipStreamSynchronize(ctx->stream));
+    if (const int rc = read_words(ctx, F)) return rc;
     T.mark(1);
     if (words.first_bad != NO_BAD_ROW) {
         // the line the row has in the file the pass writes: the header, then the emitted rows before it
@@ -434,6 +432,66 @@ int gather_kept(fhx_ctx* ctx, Decided& F, KeptRows& R) {
     return FHX_OK;
 }
 
+// ExpCC and the biases of the rows R as the writer prints them (fithic.py:1075-1078, :1105-1108); nothing is synchronised
+int kept_extras(fhx_ctx* ctx, Decided& F, KeptRows& R) {
+    FHX_HIP(F.G.get(&R.d_b1, (size_t)F.kept * 8));
+    FHX_HIP(F.G.get(&R.d_b2, (size_t)F.kept * 8));
+    FHX_HIP(F.G.get(&R.d_e, (size_t)F.kept * 8));
+    K2Params P = make_k2_params(ctx);
+    P.loc1 = R.d_loc1;
+    P.loc2 = R.d_loc2;
+    P.count = R.d_count;
+    P.n = F.kept;
+    launch_k2_extras(ctx, P, F.kept, R.d_e, R.d_b1, R.d_b2);
+    FHX_HIP(hipGetLastError());
+    return FHX_OK;
+}
+
+// the kept rows R as a Cols of their own: identity rebuilt from the gathered slots, the biases and ExpCC null without kept_extras
+fhx::emit::Cols kept_cols(const fhx_ctx* ctx, const Decided& F, const KeptRows& R) {
+    fhx::emit::Cols K = fhx::emit::resident_cols(ctx, F.d_names, F.d_name_off, F.n_names);
+    K.count = R.d_count;
+    K.loc1 = R.d_loc1;
+    K.loc2 = R.d_loc2;
+    K.p = R.d_p;
+    K.q = R.d_q;
+    K.b1 = R.d_b1;
+    K.b2 = R.d_b2;
+    K.expcc = R.d_e;
+    K.n_rows = F.kept;
+    return K;
+}
+
+// sr_measure, the byte scan, sr_format: F.d_out, F.bytes, F.d_len, F.d_wg_off.  between() enqueues what a caller wants behind the
+// scan; the first read-back follows it, and `internal_before` is the message for an `internal` word it shows (raised by the
+// caller's own kernels in front of this call; nullptr: there are none).  The stream is idle afterwards.
+template <typename Between>
+int format_kept(fhx_ctx* ctx, Decided& F, const fhx::emit::Cols& K, Between between, const char* internal_before) {
+    using namespace fhx::sigres;
+    const int64_t kept = F.kept, k_wg = (kept + WG - 1) / WG;
+    unsigned int* d_wg_bytes = nullptr;
+    FHX_HIP(F.G.get(&F.d_len, (size_t)kept));
+    FHX_HIP(F.G.get(&d_wg_bytes, (size_t)k_wg * 4));
+    FHX_HIP(F.G.get(&F.d_wg_off, (size_t)k_wg * 8));
+    hipLaunchKernelGGL(sr_measure, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, F.d_len, d_wg_bytes, F.d_words);
+    hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_bytes, k_wg, F.d_wg_off,
+                       &F.d_words->n_bytes);
+    between();
+    FHX_HIP(hipGetLastError());
+    if (const int rc = read_words(ctx, F)) return rc;
+    if (F.words.unsupported) return fail(ctx, FHX_ERR_UNSUPPORTED, kNotCovered);
+    if (internal_before && F.words.internal) return fail(ctx, FHX_ERR_INTERNAL, internal_before);
+    F.bytes = (int64_t)F.words.n_bytes;
+    if (F.bytes <= 0 || F.bytes > kept * (int64_t)fhx::emit::ROW_STRIDE) return fail(ctx, FHX_ERR_INTERNAL, kMoreText);
+    FHX_HIP(F.G.get(&F.d_out, (size_t)F.bytes));
+    hipLaunchKernelGGL(sr_format, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, (const unsigned char*)F.d_len,
+                       (const unsigned long long*)F.d_wg_off, F.d_out, F.bytes, F.d_words);
+    FHX_HIP(hipGetLastError());
+    if (const int rc = read_words(ctx, F)) return rc;
+    if (F.words.internal) return fail(ctx, FHX_ERR_INTERNAL, "the formatter wrote another length than it measured");
+    return FHX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -446,80 +504,36 @@ int fhx_significant_select(fhx_ctx* ctx, const char* const* chr_names, int32_t n
     *n_emitted = *n_kept = *n_bytes = 0;
     *why = FHX_MS_OK;
     *bad_line = 0;
-    drop_significant(ctx);
-    const bool timing = std::getenv("FHX_TIMING") != nullptr;
-    Decided F;
-    StageSeconds T;                                    // decide, rank scans, rows + ExpCC/bias, measure + format, copy out
-    if (const int rc = decide_rows<fhx::sigres::SUBSET>(ctx, chr_names, n_names, fdr_text, fdr_len, key_bound, zero_kept, strict, why, bad_line, timing, F, T))
-        return rc;
+    std::vector<char>().swap(ctx->sig_text);
+    std::vector<int64_t>().swap(ctx->sig_rows);
+    Decided F;                                         // stages: decide, rank scans, rows + ExpCC/bias, measure + format, copy out
+    if (const int rc = decide_rows<SUBSET>(ctx, chr_names, n_names, fdr_text, fdr_len, key_bound, zero_kept, strict, why, bad_line, F)) return rc;
     if (F.n == 0) return FHX_OK;
-    const int64_t n = F.n, emitted = F.emitted, kept = F.kept;
-    DeviceScratch& G = F.G;
-    Words& words = F.words;
-    Words* d_words = F.d_words;
+    const int64_t kept = F.kept;
     std::vector<char> text;
     std::vector<int64_t> rows((size_t)kept);
     if (kept > 0) {
-        const int64_t k_wg = (kept + WG - 1) / WG;
         KeptRows R;
-        double *d_b1 = nullptr, *d_b2 = nullptr, *d_e = nullptr;
-        unsigned char *d_len = nullptr, *d_out = nullptr;
-        unsigned int* d_wg_bytes = nullptr;
-        unsigned long long* d_wg_off = nullptr;
-        FHX_HIP(G.get(&d_b1, (size_t)kept * 8));
-        FHX_HIP(G.get(&d_b2, (size_t)kept * 8));
-        FHX_HIP(G.get(&d_e, (size_t)kept * 8));
-        FHX_HIP(G.get(&d_len, (size_t)kept));
-        FHX_HIP(G.get(&d_wg_bytes, (size_t)k_wg * 4));
-        FHX_HIP(G.get(&d_wg_off, (size_t)k_wg * 8));
         if (const int rc = gather_kept(ctx, F, R)) return rc;
-        // ExpCC and the biases as the writer prints them (fithic.py:1075-1078, :1105-1108), of the kept rows alone
-        K2Params P = make_k2_params(ctx);
-        P.loc1 = R.d_loc1;
-        P.loc2 = R.d_loc2;
-        P.count = R.d_count;
-        P.n = kept;
-        launch_k2_extras(ctx, P, kept, d_e, d_b1, d_b2);
-        FHX_HIP(hipGetLastError());
-        if (timing) {
-            FHX_HIP(hipStreamSynchronize(ctx->stream));
-            T.mark(2);
-        }
-        Cols K{nullptr, nullptr, nullptr, nullptr, R.d_count, R.d_loc1, R.d_loc2, ctx->d_slot_chr, ctx->nonfixed ? ctx->d_slot_mid : nullptr,
-               ctx->d_grid, (int32_t)ctx->prm.resolution, R.d_p, R.d_q, d_b1, d_b2, d_e, F.d_names, F.d_name_off, n_names, kept,
-               ctx->prm.mode, ctx->prm.dist_low, ctx->prm.dist_up};
-        hipLaunchKernelGGL(sr_measure, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, d_len, d_wg_bytes, d_words);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_bytes, k_wg, d_wg_off,
-                           &d_words->n_bytes);
-        FHX_HIP(hipGetLastError());
-        FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
-        FHX_HIP(hipStreamSynchronize(ctx->stream));
-        if (words.unsupported) return fail(ctx, FHX_ERR_UNSUPPORTED, kNotCovered);
-        const int64_t bytes = (int64_t)words.n_bytes;
-        if (bytes <= 0 || bytes > kept * (int64_t)fhx::emit::ROW_STRIDE) return fail(ctx, FHX_ERR_INTERNAL, "more text than the kept rows can hold");
-        FHX_HIP(G.get(&d_out, (size_t)bytes));
-        hipLaunchKernelGGL(sr_format, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, (const unsigned char*)d_len,
-                           (const unsigned long long*)d_wg_off, d_out, bytes, d_words);
-        FHX_HIP(hipGetLastError());
-        FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
-        FHX_HIP(hipStreamSynchronize(ctx->stream));
-        T.mark(3);
-        if (words.internal) return fail(ctx, FHX_ERR_INTERNAL, "the formatter wrote another length than it measured");
-        text.resize((size_t)bytes);
-        FHX_HIP(hipMemcpyAsync(text.data(), d_out, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (const int rc = kept_extras(ctx, F, R)) return rc;
+        if (const int rc = timed_mark(ctx, F, 2)) return rc;
+        if (const int rc = format_kept(ctx, F, kept_cols(ctx, F, R), [] {}, nullptr)) return rc;
+        F.T.mark(3);
+        text.resize((size_t)F.bytes);
+        FHX_HIP(hipMemcpyAsync(text.data(), F.d_out, (size_t)F.bytes, hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipMemcpyAsync(rows.data(), R.d_rows, (size_t)kept * 8, hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipStreamSynchronize(ctx->stream));
-        T.mark(4);
+        F.T.mark(4);
     }
     ctx->sig_text.swap(text);
     ctx->sig_rows.swap(rows);
-    *n_emitted = emitted;
+    *n_emitted = F.emitted;
     *n_kept = kept;
     *n_bytes = (int64_t)ctx->sig_text.size();
-    if (timing)
+    if (F.timing)
         std::fprintf(stderr, "fhx_significant_select: %lld rows, %lld emitted, %lld kept (%lld bytes): decide %.6f s; rank scans %.6f s; "
-                     "rows + ExpCC/bias %.6f s; measure + format %.6f s; copy out %.6f s\n", (long long)n, (long long)emitted, (long long)kept,
-                     (long long)*n_bytes, T.s[0], T.s[1], T.s[2], T.s[3], T.s[4]);
+                     "rows + ExpCC/bias %.6f s; measure + format %.6f s; copy out %.6f s\n", (long long)F.n, (long long)F.emitted, (long long)kept,
+                     (long long)*n_bytes, F.s[0], F.s[1], F.s[2], F.s[3], F.s[4]);
     return FHX_OK;
 }
 
@@ -534,3 +548,8 @@ int fhx_significant_copy_rows(fhx_ctx* ctx, int64_t* rows, int64_t capacity) {
     if (!ctx->sig_rows.empty()) std::memcpy(rows, ctx->sig_rows.data(), ctx->sig_rows.size() * sizeof(int64_t));
     return FHX_OK;
 }
+
+}  // extern "C"
+
+#include "fhx_sigresident_track.inc"
+#include "fhx_sigresident_split.inc"

@@ -1,10 +1,10 @@
-// fhx_sigresident_split.inc - the per-chromosome FDR subsets of a pass taken from its RESIDENT columns (included by fhx_device.hip
-// behind fhx_sigresident_track.inc, inside its extern "C" block): what fhx_ms_split_file gives for the file
-// fhx_write_significances_device writes, without the file.
+// fhx_sigresident_split.inc - the per-chromosome FDR subsets of a pass taken from its RESIDENT columns (included at the end of
+// fhx_sigresident.hip, at file scope): what fhx_ms_split_file gives for the file fhx_write_significances_device writes, without
+// the file.
 //
 // The list is field 1 of every line of that file: the literal `chr1` of fithic's header, and the first chromosome of every EMITTED
 // row (a trans row of an -x All run lists its first chromosome and goes to no subset).  A row is kept for name c when it is
-// emitted, both its chromosomes are c and `$7 <= fdr` holds: sr_decide<SPLIT> (fhx_sigresident.inc) makes that decision, looks
+// emitted, both its chromosomes are c and `$7 <= fdr` holds: sr_decide<SPLIT> (fhx_sigresident.hip) makes that decision, looks
 // the name rules up per chromosome id (fhx_namerule.hpp, applied by the host: the names are known before any kernel runs) and
 // marks the listed ids.  Behind it, the two rank scans and sr_rows:
 //
@@ -14,17 +14,12 @@
 //                  file order whatever the sort does with equal keys, nothing is counted per (workgroup, name), and the cost
 //                  does not depend on how many of the 4096 possible names there are.
 //   srs_permute    the kept rows' columns in sorted order
-//   k2_extras, sr_measure, scan_tiles, sr_format   as for fhx_significant_select, over the permuted rows: ONE output buffer
-//   srs_bounds     the row that begins a name's run notes the run's first row and first byte
+//   kept_extras, format_kept   fhx_significant_select's own, over the permuted rows: ONE output buffer
+//   srs_bounds     behind format_kept's byte scan: the row that begins a name's run notes the run's first row and first byte
 //
 // so a name's subset is one stretch of the output, in file order.  The host ranks the names (at most FHX_MS_SPLIT_NAMES) and cuts
 // the stretches; a listed name without a run has an empty subset.
-}  // extern "C"
-
-#include "fhx_namerule.hpp"
-
-namespace fhx {
-namespace sigres {
+namespace fhx::sigres {
 
 constexpr int RANK_SHIFT = 40;                 // 12 bits of name rank above 40 bits of kept rank
 constexpr unsigned long long RANK_MASK = (1ull << RANK_SHIFT) - 1;
@@ -78,17 +73,7 @@ __global__ __launch_bounds__(WG) void srs_bounds(const unsigned long long* __res
     }
 }
 
-}  // namespace sigres
-}  // namespace fhx
-
-namespace {
-
-void drop_significant_split(fhx_ctx* ctx) {
-    std::vector<char>().swap(ctx->sig_split_text);
-    std::vector<fhx_ctx::SigRun>().swap(ctx->sig_split);
-}
-
-}  // namespace
+}  // namespace fhx::sigres
 
 extern "C" {
 
@@ -100,18 +85,15 @@ int fhx_significant_split(fhx_ctx* ctx, const char* const* chr_names, int32_t n_
     *n_listed = 0;
     *why = FHX_MS_OK;
     *bad_line = 0;
-    drop_significant_split(ctx);
-    const bool timing = std::getenv("FHX_TIMING") != nullptr;
+    std::vector<char>().swap(ctx->sig_split_text);
+    std::vector<fhx_ctx::SigRun>().swap(ctx->sig_split);
+    if (const int rc = require_names(ctx, chr_names, n_names)) return rc;      // here for name_grammar; decide_rows asks again for its own walk
     std::vector<unsigned char> name_why((size_t)n_names, 0);                  // the name rules, once per chromosome id
-    for (int i = 0; i < n_names; ++i) {
-        if (!chr_names[i]) return fail(ctx, FHX_ERR_ARG, "a chromosome name is missing");
+    for (int i = 0; i < n_names; ++i)
         name_why[(size_t)i] = (unsigned char)fhx::namerule::name_grammar((const unsigned char*)chr_names[i], (int)std::min<size_t>(
                                                                              std::strlen(chr_names[i]), (size_t)INT32_MAX));
-    }
-    Decided F;
-    StageSeconds T;                                    // decide, rank scans, rows + keys + sort, ExpCC/bias + measure + format, copy out
-    if (const int rc = decide_rows<SPLIT>(ctx, chr_names, n_names, fdr_text, fdr_len, key_bound, zero_kept, /*strict=*/0, why, bad_line, timing, F, T,
-                                          &name_why))
+    Decided F;                                 // stages: decide, rank scans, rows + keys + sort, ExpCC/bias + measure + format, copy out
+    if (const int rc = decide_rows<SPLIT>(ctx, chr_names, n_names, fdr_text, fdr_len, key_bound, zero_kept, /*strict=*/0, why, bad_line, F, &name_why))
         return rc;
     // the list: `chr1` of the header, and the first chromosome of every emitted row; equal names are one entry
     std::vector<unsigned char> listed((size_t)n_names, 0);
@@ -139,7 +121,6 @@ int fhx_significant_split(fhx_ctx* ctx, const char* const* chr_names, int32_t n_
     const int64_t kept = F.kept;
     if (kept > 0) {
         DeviceScratch& G = F.G;
-        Words& words = F.words;
         Words* d_words = F.d_words;
         const int64_t k_wg = (kept + WG - 1) / WG;
         std::vector<unsigned short> id_rank((size_t)n_names, 0);
@@ -148,10 +129,8 @@ int fhx_significant_split(fhx_ctx* ctx, const char* const* chr_names, int32_t n_
                 id_rank[(size_t)i] = (unsigned short)(std::lower_bound(names.begin(), names.end(), std::string(chr_names[i]), bytewise) - names.begin());
         KeptRows R, P;
         unsigned short* d_id_rank = nullptr;
-        unsigned long long *d_keys = nullptr, *d_sorted = nullptr, *d_run_row = nullptr, *d_run_byte = nullptr, *d_wg_off = nullptr;
-        unsigned int *d_perm = nullptr, *d_wg_bytes = nullptr;
-        double *d_b1 = nullptr, *d_b2 = nullptr, *d_e = nullptr;
-        unsigned char *d_len = nullptr, *d_out = nullptr;
+        unsigned long long *d_keys = nullptr, *d_sorted = nullptr, *d_run_row = nullptr, *d_run_byte = nullptr;
+        unsigned int* d_perm = nullptr;
         FHX_HIP(G.get(&d_id_rank, (size_t)n_names * 2));
         FHX_HIP(G.get(&d_keys, (size_t)kept * 8));
         FHX_HIP(G.get(&d_sorted, (size_t)kept * 8));
@@ -163,12 +142,6 @@ int fhx_significant_split(fhx_ctx* ctx, const char* const* chr_names, int32_t n_
         FHX_HIP(G.get(&P.d_count, (size_t)kept * 4));
         FHX_HIP(G.get(&P.d_p, (size_t)kept * 8));
         FHX_HIP(G.get(&P.d_q, (size_t)kept * 8));
-        FHX_HIP(G.get(&d_b1, (size_t)kept * 8));
-        FHX_HIP(G.get(&d_b2, (size_t)kept * 8));
-        FHX_HIP(G.get(&d_e, (size_t)kept * 8));
-        FHX_HIP(G.get(&d_len, (size_t)kept));
-        FHX_HIP(G.get(&d_wg_bytes, (size_t)k_wg * 4));
-        FHX_HIP(G.get(&d_wg_off, (size_t)k_wg * 8));
         if (!ctx->sig_sorter && fhx_create(ctx->device, &ctx->sig_sorter) != FHX_OK) {      // only a split pays for it
             ctx->sig_sorter = nullptr;
             return fail(ctx, FHX_ERR_HIP, "the sort context could not be made");
@@ -188,46 +161,22 @@ int fhx_significant_split(fhx_ctx* ctx, const char* const* chr_names, int32_t n_
                            (const int32_t*)R.d_loc1, (const int32_t*)R.d_loc2, (const int32_t*)R.d_count, (const double*)R.d_p, (const double*)R.d_q,
                            P.d_loc1, P.d_loc2, P.d_count, P.d_p, P.d_q, d_words);
         FHX_HIP(hipGetLastError());
-        if (timing) {
-            FHX_HIP(hipStreamSynchronize(ctx->stream));
-            T.mark(2);
-        }
-        // ExpCC and the biases as the writer prints them, of the kept rows alone
-        K2Params P2 = make_k2_params(ctx);
-        P2.loc1 = P.d_loc1;
-        P2.loc2 = P.d_loc2;
-        P2.count = P.d_count;
-        P2.n = kept;
-        launch_k2_extras(ctx, P2, kept, d_e, d_b1, d_b2);
-        FHX_HIP(hipGetLastError());
-        Cols K{nullptr, nullptr, nullptr, nullptr, P.d_count, P.d_loc1, P.d_loc2, ctx->d_slot_chr, ctx->nonfixed ? ctx->d_slot_mid : nullptr,
-               ctx->d_grid, (int32_t)ctx->prm.resolution, P.d_p, P.d_q, d_b1, d_b2, d_e, F.d_names, F.d_name_off, n_names, kept,
-               ctx->prm.mode, ctx->prm.dist_low, ctx->prm.dist_up};
-        hipLaunchKernelGGL(sr_measure, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, d_len, d_wg_bytes, d_words);
-        hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_bytes, k_wg, d_wg_off,
-                           &d_words->n_bytes);
-        hipLaunchKernelGGL(srs_bounds, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, (const unsigned long long*)d_sorted, kept,
-                           (const unsigned char*)d_len, (const unsigned long long*)d_wg_off, listed_n, d_run_row, d_run_byte);
-        FHX_HIP(hipGetLastError());
-        FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
-        FHX_HIP(hipStreamSynchronize(ctx->stream));
-        if (words.unsupported) return fail(ctx, FHX_ERR_UNSUPPORTED, kNotCovered);
-        if (words.internal) return fail(ctx, FHX_ERR_INTERNAL, "the sorted keys are not the kept rows");
-        const int64_t bytes = (int64_t)words.n_bytes;
-        if (bytes <= 0 || bytes > kept * (int64_t)fhx::emit::ROW_STRIDE) return fail(ctx, FHX_ERR_INTERNAL, "more text than the kept rows can hold");
-        FHX_HIP(G.get(&d_out, (size_t)bytes));
-        hipLaunchKernelGGL(sr_format, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, (const unsigned char*)d_len,
-                           (const unsigned long long*)d_wg_off, d_out, bytes, d_words);
-        FHX_HIP(hipGetLastError());
+        if (const int rc = timed_mark(ctx, F, 2)) return rc;
+        if (const int rc = kept_extras(ctx, F, P)) return rc;
+        const auto bounds = [&] {
+            hipLaunchKernelGGL(srs_bounds, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, (const unsigned long long*)d_sorted, kept,
+                               (const unsigned char*)F.d_len, (const unsigned long long*)F.d_wg_off, listed_n, d_run_row, d_run_byte);
+        };
+        if (const int rc = format_kept(ctx, F, kept_cols(ctx, F, P), bounds, "the sorted keys are not the kept rows")) return rc;
+        F.T.mark(3);                                                          // the copies of the runs' bounds count as copy out, with the text
         std::vector<unsigned long long> run_row((size_t)listed_n), run_byte((size_t)listed_n);
-        FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
+        text.resize((size_t)F.bytes);
         FHX_HIP(hipMemcpyAsync(run_row.data(), d_run_row, (size_t)listed_n * 8, hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipMemcpyAsync(run_byte.data(), d_run_byte, (size_t)listed_n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        FHX_HIP(hipMemcpyAsync(text.data(), F.d_out, (size_t)F.bytes, hipMemcpyDeviceToHost, ctx->stream));
         FHX_HIP(hipStreamSynchronize(ctx->stream));
-        T.mark(3);
-        if (words.internal) return fail(ctx, FHX_ERR_INTERNAL, "the formatter wrote another length than it measured");
         // ascending ranks are ascending runs: each ends where the next one begins, the last one with the text
-        int64_t row_end = kept, byte_end = bytes;
+        int64_t row_end = kept, byte_end = F.bytes;
         for (int32_t k = listed_n - 1; k >= 0; --k) {
             fhx_ctx::SigRun& run = runs[(size_t)k];
             if (run_row[(size_t)k] == NO_RUN) {
@@ -244,19 +193,16 @@ int fhx_significant_split(fhx_ctx* ctx, const char* const* chr_names, int32_t n_
             byte_end = b_at;
         }
         if (row_end != 0 || byte_end != 0) return fail(ctx, FHX_ERR_INTERNAL, "the runs of the sorted rows do not tile the subsets");
-        text.resize((size_t)bytes);
-        FHX_HIP(hipMemcpyAsync(text.data(), d_out, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
-        FHX_HIP(hipStreamSynchronize(ctx->stream));
-        T.mark(4);
+        F.T.mark(4);
     }
     ctx->sig_split_text.swap(text);
     ctx->sig_split.swap(runs);
     *n_emitted = F.emitted;
     *n_listed = listed_n;
-    if (timing)
+    if (F.timing)
         std::fprintf(stderr, "fhx_significant_split: %lld rows, %lld emitted, %lld kept (%lld bytes) for %d names: decide %.6f s; rank scans "
                      "%.6f s; rows + keys + sort %.6f s; ExpCC/bias + measure + format %.6f s; copy out %.6f s\n", (long long)F.n, (long long)F.emitted,
-                     (long long)kept, (long long)ctx->sig_split_text.size(), (int)listed_n, T.s[0], T.s[1], T.s[2], T.s[3], T.s[4]);
+                     (long long)kept, (long long)ctx->sig_split_text.size(), (int)listed_n, F.s[0], F.s[1], F.s[2], F.s[3], F.s[4]);
     return FHX_OK;
 }
 
@@ -287,3 +233,5 @@ int fhx_significant_copy_split(fhx_ctx* ctx, int32_t index, void* dst, int64_t c
     if (run.bytes > 0) std::memcpy(dst, ctx->sig_split_text.data() + run.offset, (size_t)run.bytes);
     return FHX_OK;
 }
+
+}  // extern "C"

@@ -1,6 +1,6 @@
-// fhx_sigresident_track.inc - the UCSC interact track of a pass taken from its RESIDENT columns (included by fhx_device.hip behind
-// fhx_sigresident.inc, inside its extern "C" block): what fhx_ms_track_file gives for the file fhx_write_significances_device
-// writes, without the file.  The decision is fhx_sigresident.inc's made strict (`$7 < q`), with the track's rules for midpoints
+// fhx_sigresident_track.inc - the UCSC interact track of a pass taken from its RESIDENT columns (included at the end of
+// fhx_sigresident.hip, at file scope): what fhx_ms_track_file gives for the file fhx_write_significances_device
+// writes, without the file.  The decision is fhx_sigresident.hip's made strict (`$7 < q`), with the track's rules for midpoints
 // and names on every emitted row (sr_decide<TRACK>); the line is fhx_trackline.hpp's, shared with the file route.  Line 1 of the
 // pass's file is fithic's header, which the file route drops and counts: here it is only counted.  Behind sr_decide, the two rank
 // scans and sr_rows (the kept rows compacted in file order; ExpCC and the biases are not in a track line, so k2_extras does not run):
@@ -21,10 +21,7 @@
 //                  16-byte boundary of the output and goes out by sr_format's scheme (window_out); what a lane wrote is compared
 //                  with what srt_measure counted.
 // A kept row with a name of 25 to 63 bytes is FHX_ERR_UNSUPPORTED (row_text's cap): the caller takes the file route.
-}  // extern "C"
-
-namespace fhx {
-namespace sigres {
+namespace fhx::sigres {
 
 namespace tl = fhx::trackline;
 
@@ -151,14 +148,7 @@ __global__ __launch_bounds__(WG) void srt_format(Cols K, const unsigned short* _
     window_out(window, mis, total, at, out, out_bytes);
 }
 
-}  // namespace sigres
-}  // namespace fhx
-
-namespace {
-
-void drop_significant_track(fhx_ctx* ctx) { std::vector<char>().swap(ctx->sig_track); }
-
-}  // namespace
+}  // namespace fhx::sigres
 
 extern "C" {
 
@@ -170,12 +160,10 @@ int fhx_significant_track(fhx_ctx* ctx, const char* const* chr_names, int32_t n_
     *n_emitted = *n_kept = *n_deferred = *n_bytes = 0;
     *why = FHX_MS_OK;
     *bad_line = 0;
-    drop_significant_track(ctx);
-    const bool timing = std::getenv("FHX_TIMING") != nullptr;
-    Decided F;
-    StageSeconds T;                                    // decide, rank scans, rows + lines, deferred round trip, measure + format, copy out
-    if (const int rc = decide_rows<TRACK>(ctx, chr_names, n_names, fdr_text, fdr_len, key_bound, zero_kept, /*strict=*/1, why, bad_line, timing, F, T))
-        return rc;
+    std::vector<char>().swap(ctx->sig_track);
+    Decided F;                                 // stages: decide, rank scans, rows + lines, deferred round trip, measure + format, copy out
+    StageClock& T = F.T;
+    if (const int rc = decide_rows<TRACK>(ctx, chr_names, n_names, fdr_text, fdr_len, key_bound, zero_kept, /*strict=*/1, why, bad_line, F)) return rc;
     const int64_t kept = F.kept;
     if (kept > (int64_t)INT32_MAX) {
         *why = FHX_MS_KEPT;
@@ -199,15 +187,12 @@ int fhx_significant_track(fhx_ctx* ctx, const char* const* chr_names, int32_t n_
         FHX_HIP(G.get(&d_deferred_off, (size_t)k_wg * 8));
         FHX_HIP(G.get(&d_wg_off, (size_t)k_wg * 8));
         if (const int rc = gather_kept(ctx, F, R)) return rc;
-        Cols K{nullptr, nullptr, nullptr, nullptr, R.d_count, R.d_loc1, R.d_loc2, ctx->d_slot_chr, ctx->nonfixed ? ctx->d_slot_mid : nullptr,
-               ctx->d_grid, (int32_t)ctx->prm.resolution, R.d_p, R.d_q, nullptr, nullptr, nullptr, F.d_names, F.d_name_off, n_names, kept,
-               ctx->prm.mode, ctx->prm.dist_low, ctx->prm.dist_up};
+        const Cols K = kept_cols(ctx, F, R);
         hipLaunchKernelGGL(srt_line, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, d_info, d_wg_deferred, d_words);
         hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_deferred, k_wg,
                            d_deferred_off, &d_words->n_deferred);
         FHX_HIP(hipGetLastError());
-        FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
-        FHX_HIP(hipStreamSynchronize(ctx->stream));
+        if (const int rc = read_words(ctx, F)) return rc;
         T.mark(2);
         if (words.unsupported) return fail(ctx, FHX_ERR_UNSUPPORTED, kNotCovered);
         if (words.internal) return fail(ctx, FHX_ERR_INTERNAL, "a kept row has no track line");
@@ -233,17 +218,15 @@ int fhx_significant_track(fhx_ctx* ctx, const char* const* chr_names, int32_t n_
         hipLaunchKernelGGL(fhxscan::scan_tiles, dim3(1), dim3(fhxscan::THREADS), 0, ctx->stream, (const unsigned int*)d_wg_bytes, k_wg, d_wg_off,
                            &d_words->n_bytes);
         FHX_HIP(hipGetLastError());
-        FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
-        FHX_HIP(hipStreamSynchronize(ctx->stream));
+        if (const int rc = read_words(ctx, F)) return rc;
         const int64_t bytes = (int64_t)words.n_bytes;
-        if (bytes <= 0 || bytes > kept * (int64_t)TRACK_STRIDE) return fail(ctx, FHX_ERR_INTERNAL, "more text than the kept rows can hold");
+        if (bytes <= 0 || bytes > kept * (int64_t)TRACK_STRIDE) return fail(ctx, FHX_ERR_INTERNAL, kMoreText);
         FHX_HIP(G.get(&d_out, (size_t)bytes));
         hipLaunchKernelGGL(srt_format, dim3((unsigned)k_wg), dim3(WG), 0, ctx->stream, K, (const unsigned short*)d_info,
                            (const unsigned long long*)d_deferred_off, (const unsigned char*)d_scores, n_slots, (const unsigned long long*)d_wg_off,
                            d_out, bytes, d_words);
         FHX_HIP(hipGetLastError());
-        FHX_HIP(hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, ctx->stream));
-        FHX_HIP(hipStreamSynchronize(ctx->stream));
+        if (const int rc = read_words(ctx, F)) return rc;
         T.mark(4);
         if (words.internal) return fail(ctx, FHX_ERR_INTERNAL, "the track formatter wrote another length than it measured");
         const size_t head = text.size();
@@ -257,10 +240,10 @@ int fhx_significant_track(fhx_ctx* ctx, const char* const* chr_names, int32_t n_
     *n_kept = kept;
     *n_deferred = n_slots;
     *n_bytes = (int64_t)ctx->sig_track.size();
-    if (timing)
+    if (F.timing)
         std::fprintf(stderr, "fhx_significant_track: %lld rows, %lld emitted, %lld kept, %lld deferred (%lld bytes): decide %.6f s; rank scans "
                      "%.6f s; rows + lines %.6f s; deferred round trip %.6f s; measure + format %.6f s; copy out %.6f s\n", (long long)F.n,
-                     (long long)F.emitted, (long long)kept, (long long)n_slots, (long long)*n_bytes, T.s[0], T.s[1], T.s[2], T.s[3], T.s[4], T.s[5]);
+                     (long long)F.emitted, (long long)kept, (long long)n_slots, (long long)*n_bytes, F.s[0], F.s[1], F.s[2], F.s[3], F.s[4], F.s[5]);
     return FHX_OK;
 }
 
@@ -269,3 +252,5 @@ int fhx_significant_copy_track(fhx_ctx* ctx, void* dst, int64_t capacity) {
     if (!ctx->sig_track.empty()) std::memcpy(dst, ctx->sig_track.data(), ctx->sig_track.size());
     return FHX_OK;
 }
+
+}  // extern "C"

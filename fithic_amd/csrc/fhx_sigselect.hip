@@ -148,14 +148,9 @@ void drop_subset(fhx_ms* ms) {
 
 // the threshold as the kernels take it; `noun` is what the message calls it
 int make_fdr(fhx_ms* ms, const char* fdr_text, int32_t fdr_len, const char* noun, msd::Fdr* fdr, int32_t* why) {
-    if (fdr_len < 1 || fdr_len > FHX_MS_FDR_BYTES) {
-        *why = FHX_MS_FDR;
-        return fhx::fail(ms, FHX_ERR_UNSUPPORTED, std::string("the text of ") + noun + " must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
-    }
-    std::memset(fdr, 0, sizeof(*fdr));
-    std::memcpy(fdr->text, fdr_text, (size_t)fdr_len);
-    fdr->len = fdr_len;
-    return FHX_OK;
+    if (msd::fdr_of(fdr_text, fdr_len, fdr)) return FHX_OK;
+    *why = FHX_MS_FDR;
+    return fhx::fail(ms, FHX_ERR_UNSUPPORTED, std::string("the text of ") + noun + " must have 1 to " + std::to_string(FHX_MS_FDR_BYTES) + " bytes");
 }
 
 // fhx_ms_select_file behind its argument check; whatever it returns but FHX_OK, the caller drops the subset

@@ -1,6 +1,6 @@
 // fhx_textupload.hpp - the host side that the device text paths share (fhx_hicpro.hip, fhx_validpairs.hip, fhx_fragpairs.hip,
 // fhx_digest.hip, fhx_juicer.hip, fhx_sigselect.hip with fhx_sigtrack.inc and fhx_sigsplit.inc): the text handle (fhx_devmem.hpp's Handle plus the pinned
-// upload buffers), the stage clock, and the way a text file (fhx_textfile.hpp) reaches HBM: host threads fill one of two
+// upload buffers) and the way a text file (fhx_textfile.hpp) reaches HBM: host threads fill one of two
 // pinned buffers while the copy engine drains the other, in batches cut at the last newline and padded with blanks as
 // fhx_textlines.hpp's 16-byte loads need it.  TextBatches is the loop over such batches with the newline layer run on each;
 // refused_line turns a kernel's error word into what the caller is told.
@@ -8,7 +8,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -40,17 +39,6 @@ void text_handle_destroy(H* h, Drop drop) {
         }
     });
 }
-
-// host seconds per stage of a call; the stream is idle at every mark
-struct StageClock {
-    double* seconds;
-    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
-    void mark(int k) {
-        const auto now = std::chrono::steady_clock::now();
-        seconds[k] += std::chrono::duration<double>(now - last).count();
-        last = now;
-    }
-};
 
 // the bytes of a batch: the environment variable `env` overrides 256 MB (tests put a batch edge inside a small file), at least
 // two lines of the longest kind, at most `upper`, and no more than the text has

@@ -1,7 +1,7 @@
 // fhx_trackline.hpp - one line of the UCSC interact track (reference: fithic/utils/visualize-UCSC.sh:18), from its pieces:
 // (name 1, midpoint 1, name 2, midpoint 2, the class and key of field 7, NR) ->
 //   $1 ($2-1) ($4+1) NR int(-log($7)/log(10)) -log($7)/log(10) EXP 0 $1 ($2-1) ($2+1) SOURCE_NAME . $3 ($4-1) ($4+1) TARGET_NAME +
-// Shared by the file route (fhx_sigtrack.inc: the pieces are tokens of a line of text) and the resident route (fhx_sigresident.inc:
+// Shared by the file route (fhx_sigtrack.inc: the pieces are tokens of a line of text) and the resident route (fhx_sigresident.hip:
 // the pieces are a row's identity and the %e text of its q), so that the two give the same bytes by construction: the grammar
 // beyond field 7 and its precedence, the length of a line, the DEFERRED marking, the round trip of a deferred score through
 // fhx::score::host_fields and the writer of the line exist here and nowhere else.

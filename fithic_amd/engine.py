@@ -149,7 +149,7 @@ class Engine:
         return self.ctx.get_array(_capi.A_FDR_COUNTS)
 
     def significant(self, fdr, names, strict=False, path=None):
-        """The FDR subset of this pass from its resident q (csrc/fhx_sigresident.inc), between run_pass / bh and next_pass:
+        """The FDR subset of this pass from its resident q (csrc/fhx_sigresident.hip), between run_pass / bh and next_pass:
         the mergefilter.Selection that mergefilter.select(file, fdr, strict) returns for the file this pass writes - same text,
         same n_lines (the header counted), same n_kept - without writing it.  `fdr` is text, as the shell passes it; `names` are
         the chromosome names the writer is given.  A q outside the grammar raises the ValueError mergefilter raises for that file,

@@ -4,7 +4,7 @@
   parent   the pass writes <prefix>.significances.txt.gz (fhx_write_significances_device: format + deflate + copy out + write),
            then fithic_amd.mergefilter.select reads it back (inflate + upload + newline scan + select + gather): wall time of
            both and select's stage_seconds
-  direct   Engine.significant on the resident q (csrc/fhx_sigresident.inc): wall time of the call and the host clocks the
+  direct   Engine.significant on the resident q (csrc/fhx_sigresident.hip): wall time of the call and the host clocks the
            library takes around its stages under FHX_TIMING (decide, rank scans, rows + ExpCC/bias, measure + format, copy out)
 
     python profiles/significant_time.py [--shape synth4m|C3] [--fdr 0.05] [--tmp DIR]

@@ -431,6 +431,35 @@ def test_split_lists_the_headers_chr1_and_orders_names_bytewise():
         assert t.n_kept == s.n_kept("chr10") + s.n_kept("chr2")
 
 
+@pytest.mark.parametrize("n", [257, 600])
+def test_the_subset_the_split_and_the_track_of_one_pass_agree(n):
+    """Engine.significant and Engine.split run the same kept-row steps (kept_extras, format_kept) over the kept rows in file order
+    and in name order: the cis lines of the one text, grouped by field 1, are byte for byte the subsets of the other.  257 loaded
+    rows are one full workgroup of sr_decide and one row; at 600 the kept rows themselves fill more than one workgroup of 256,
+    whose byte offset is no multiple of 16 (window_out's vector and bytewise paths), at another row in the split than in the
+    subset.  The track's kept count is the strict subset's."""
+    with Pass(n) as P:
+        assert (P.cols[0][:64] == 0).any() and (P.cols[0][:64] == 1).any()         # the chromosomes alternate row by row
+        for what, keep in (("every third row", np.arange(n) % 3 == 0), ("all", np.ones(n, bool))):
+            P.write_q(np.where(keep, KEEP, DROP))
+            subset = P.eng.significant("0.05", P.names)
+            s = P.split("0.05")
+            assert subset.n_kept == int((keep & P.emit).sum()) > 0 and subset.n_lines == s.n_lines, (n, what)
+            by_name = {}
+            for line in subset.subset_text().splitlines(keepends=True):
+                f = line.split(b"\t")
+                if f[0] == f[2]:
+                    by_name[f[0].decode()] = by_name.get(f[0].decode(), b"") + line
+            assert set(by_name) == {"chr1", "chr2"} and s.chromosomes == ["chr1", "chr2"], (n, what, sorted(by_name), s.chromosomes)
+            for name in s.chromosomes:
+                assert s.subset_text(name) == by_name[name], (n, what, name, "the split's subset is not the subset's lines")
+                assert s.n_kept(name) == by_name[name].count(b"\n"), (n, what, name)
+            assert P.track("0.05").n_kept == P.eng.significant("0.05", P.names, strict=True).n_kept, (n, what)
+            if n == 600 and what == "all":
+                second = sum(len(line) for line in subset.subset_text().splitlines(keepends=True)[:256])
+                assert subset.n_kept > 256 and second % 16 != 0, (subset.n_kept, second)      # the second workgroup's first byte
+
+
 def _trans_source():
     """the synthetic set and a third chromosome that only has trans rows (its first chromosome: listed, no cis row)"""
     base = _synth()
